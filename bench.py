@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- MSDF glyphs/s (64x64, fp32 tiles) on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--glyphs G]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--glyphs G] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no torchrun environment re-launches itself under torch.distributed.run with N ranks (one per GPU) and fails
@@ -17,6 +17,15 @@ A step = one pass of the hot path over one batch: on-device digestion of the HBM
 error-correction kernels -> G tiles in HBM. Inputs (flattened edge buffer, per-glyph transforms) are resident in HBM before the timed
 region; outputs stay in HBM. Scaling is weak: the global list is N rotated copies of the glyph list, cut into N contiguous shards of
 equal cost by msdfgen_amd.shard (rank r renders its own shard; no collective in the data path); value = all glyphs / max-over-ranks time.
+
+--dump-outputs DIR: after the timed steps, the tiles the last timed step wrote (float32, what GlyphBatch.generate hands its caller) go to
+DIR/tiles.npy (DIR/tiles_rank<r>.npy per rank when N > 1), a fixed, seeded sample of whole tiles that keeps all files within 64 MB, with the
+sampled glyph positions (float64) in DIR/tiles_index.npy (_rank<r>). All dumped values are finite: a texel the reference's overlapping
+combiner leaves at its -DBL_MAX start value maps to -inf in float32, in the library exactly as in the reference (every tile of this workload
+is pinned to it); the dump writes such texels as the float32 extreme of the same sign (NaN as 0) and counts them per tile in
+DIR/tiles_nonfinite.npy (-inf, +inf, NaN texels), so that no difference between two builds is lost. The inputs depend on the arguments
+only, so two builds run with the same arguments can be compared file for file. With --inprocess the sample also holds the 8-bit atlas cells of the same glyphs (atlas_cells.npy,
+as float32).
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus
   roofline      dominant pass = the distance field (HIP-event timed inside this process, algorithmic bytes per SURVEY.md 8d)
@@ -231,6 +240,34 @@ def profile_counters(args, w, h):
     return None
 
 
+DUMP_BYTES = 64*10**6
+
+
+def dump_sample(n, tile_bytes, share=1):
+    """Glyph positions dumped by --dump-outputs: all of them if they fit into 1/share of DUMP_BYTES (less a margin for .npy headers), else a
+    fixed, seeded, sorted sample of as many as fit. Per glyph: its tile(s), its position and its three non-finite counts (float64 each)."""
+    k = min(n, (DUMP_BYTES//share-4096)//(tile_bytes+32))
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(20240607).choice(n, k, replace=False))
+
+
+def finite_tiles(tiles):
+    """(tiles with -inf / +inf written as the float32 extreme of the same sign and NaN as 0, float64 [n, 3] counts of -inf / +inf / NaN texels per tile)."""
+    t = np.asarray(tiles, np.float32).reshape(len(tiles), -1)
+    counts = np.stack([np.isneginf(t).sum(1), np.isposinf(t).sum(1), np.isnan(t).sum(1)], 1).astype(np.float64)
+    big = np.finfo(np.float32).max
+    return np.nan_to_num(t, nan=0., posinf=big, neginf=-big).reshape(np.shape(tiles)), counts
+
+
+def dump_outputs(dirname, arrays):
+    """Writes {name: float32 / float64 array} as DIR/<name>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), (name, a.dtype)
+        np.save(os.path.join(dirname, name+".npy"), np.ascontiguousarray(a))
+
+
 def timed_steps(M, torch, dist, lib, gb, desc, out, cfg, w, h, steps, warmup, world, dev, stream):
     import ctypes as C
 
@@ -331,6 +368,11 @@ def inprocess(args):
         t2 = time.perf_counter()
         if rep >= args.warmup:
             t_float.append(t1-t0), t_bytes.append(t2-t1)
+    if args.dump_outputs:                                            # the last step's float tiles, and the 8-bit atlas cells of the same glyphs
+        pick = dump_sample(n, h*w*3*(4+4), 1)
+        cells = np.stack([atlas[(g//cols)*h:(g//cols+1)*h, (g % cols)*w:(g % cols+1)*w] for g in pick]) if len(pick) else np.zeros((0, h, w, 3), np.uint8)
+        ft, nonfinite = finite_tiles(tiles[pick])
+        dump_outputs(args.dump_outputs, {"tiles": ft, "tiles_nonfinite": nonfinite, "atlas_cells": cells.astype(np.float32), "tiles_index": pick.astype(np.float64)})
     f, b = float(np.median(t_float)), float(np.median(t_bytes))
     print(json.dumps({"metric": "MSDF glyphs/sec (64x64, fp32), end to end, one process driving the GPUs", "value": n/f, "unit": "glyphs/s", "n_gpus": args.gpus,
                       "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3*f, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
@@ -345,23 +387,21 @@ def inprocess(args):
 
 
 def streamed_end_to_end(M, batch, xfs, w, h, reps=7):
-    """SURVEY.md 8(d)'s metric as ONE pipelined call. (a) From REAL msdfgen::Shape objects: tests/shim/shim_check (a client of msdfgen's public headers linked
-    against the C++ shim; built in the authoring container, it travels to the GPU box) rebuilds the Shape objects of this workload and times
+    """SURVEY.md 8(d)'s metric as ONE pipelined call. (a) From REAL msdfgen::Shape objects: oracle/_ref/shim_check (a client of msdfgen's public headers linked
+    against the C++ shim; built by build() where msdfgen's sources exist, it travels with oracle/_ref/) rebuilds the Shape objects of this workload and times
     msdfgen_hip::generateMSDFBatch() -- host threads flatten chunk k+1 / k+2 into pinned staging while chunk k is uploaded, digested and rendered and chunk k-1
     travels back; the clock starts at `const Shape *const *` and stops when the caller's pinned bitmaps are complete. (b) msdfhip_generate_stream_csr from this
     process: the same pipeline fed from host CSR arrays (no Shape walk)."""
     import tempfile
     n = batch.n_glyphs
     res = {}
-    exe = os.path.join(ROOT, "tests", "shim", "shim_check")
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim_check")
     if os.path.exists(exe):
         with tempfile.NamedTemporaryFile(suffix=".bin", delete=False) as f:
             path = f.name
         try:
             batch.dump(path, xfs)
-            env = dict(os.environ)
-            env.setdefault("GPU_MAX_HW_QUEUES", "8")
-            r = subprocess.run([exe, "e2e", path, str(w), str(h), str(reps)], capture_output=True, text=True, timeout=300, env=env)
+            r = subprocess.run([exe, "e2e", path, str(w), str(h), str(reps)], capture_output=True, text=True, timeout=300)
             if r.returncode == 0 and r.stdout.strip():
                 d = json.loads(r.stdout.strip().splitlines()[-1])
                 res["from_shape_objects"] = {"float_tiles_glyphs_per_s": d["float_tiles_glyphs_per_s"], "uint8_atlas_glyphs_per_s": d["uint8_atlas_glyphs_per_s"],
@@ -395,10 +435,10 @@ def streamed_end_to_end(M, batch, xfs, w, h, reps=7):
 
 def flatten_ms(batch):
     """SURVEY 8(d) counts the HOST FLATTEN in the end-to-end metric: const msdfgen::Shape & -> CSR edge buffer, what the C++ shim does per call
-    (msdfgen_shim.cpp: flatten). Measured by the shim's own client (tests/shim/shim_check, built against the msdfgen headers in the authoring
-    container; it travels to the GPU box): real msdfgen::Shape objects built from this workload, flattened on 1 and on all usable threads."""
+    (msdfgen_shim.cpp: flatten). Measured by the shim's own client (oracle/_ref/shim_check, built against the msdfgen headers where they exist;
+    it travels with oracle/_ref/): real msdfgen::Shape objects built from this workload, flattened on 1 and on all usable threads."""
     import tempfile
-    exe = os.path.join(ROOT, "tests", "shim", "shim_check")
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim_check")
     if not os.path.exists(exe):
         return None
     gco, co = batch.glyph_contour_offsets.astype(np.int32), batch.contour_offsets.astype(np.int32)
@@ -517,7 +557,11 @@ def main():
     ap.add_argument("--strong-cut", default="contiguous", choices=["contiguous", "dealt"],
                     help="--strong: contiguous ranges of equal modelled cost, or glyphs in order of modelled cost dealt out to the ranks (every shard the same mix)")
     ap.add_argument("--inprocess", action="store_true", help="one process drives all --gpus devices through msdfhip_generate_sharded (end to end; prints its own JSON line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64, "
+                                                          "a fixed, seeded sample of whole tiles within 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.inprocess:
         return inprocess(args)
@@ -579,6 +623,12 @@ def main():
     cfg = M.MSDFGeneratorConfig(overlap_support=not args.simple_combiner)
 
     elapsed, dist_ms, ec_ms, launches = timed_steps(M, torch, dist, lib, gb, desc, out, cfg, w, h, args.steps, args.warmup, world, dev, stream)
+    if args.dump_outputs:                                            # outside the timed region: `out` holds what the last timed step wrote
+        pick = dump_sample(batch.n_glyphs, h*w*3*4, world)
+        sfx = "_rank%d" % rank if world > 1 else ""
+        tiles = out[torch.as_tensor(pick, dtype=torch.long, device=dev)].cpu().numpy() if len(pick) else np.zeros((0, h, w, 3), np.float32)
+        ft, nonfinite = finite_tiles(tiles)
+        dump_outputs(args.dump_outputs, {"tiles"+sfx: ft, "tiles_nonfinite"+sfx: nonfinite, "tiles_index"+sfx: pick.astype(np.float64)})
     per_rank = None
     if world > 1:
         cdev = "cpu" if args.same_device else dev
@@ -697,7 +747,7 @@ def main():
             "uint8_atlas_glyphs_per_s": src["uint8_atlas_glyphs_per_s"] if src else staged_u8, "float_tiles_glyphs_per_s": src["float_tiles_glyphs_per_s"] if src else staged_f32,
             "path": ("ONE pipelined call over real msdfgen::Shape objects, msdfgen_hip::generateMSDFBatch (flatten on the host threads || upload + digest || kernels || copy back, chunk by chunk); "
                      "wall clock of the call, median of %d" % src["reps"]) if src else
-                    "staged (flatten, then msdfhip_batch_create, then msdfhip_batch_generate_host): tests/shim/shim_check absent on this box, the streamed C++ entry was not timed",
+                    "staged (flatten, then msdfhip_batch_create, then msdfhip_batch_generate_host): oracle/_ref/shim_check absent on this machine, the streamed C++ entry was not timed",
             "staged": {"uint8_atlas_glyphs_per_s": staged_u8, "float_tiles_glyphs_per_s": staged_f32,
                        "ms": {"flatten": fl, "upload_and_digest": e2e["float_tiles"]["ms_upload_and_digest"], "uint8_generate_convert_copy_back": e2e["uint8_atlas"]["ms_generate_convert_and_copy_back"],
                               "float_generate_copy_back": e2e["float_tiles"]["ms_generate_and_copy_back"]},

@@ -121,7 +121,7 @@ class ShapeBatch:
                           cat(types, np.int32, (0,)), cat(colors, np.int32, (0,)), np.array(inv, np.uint8), list(names or []))
 
     def dump(self, path, xfs) -> None:
-        """The flat file tests/shim/shim_check reads to rebuild real msdfgen::Shape objects (`batch`, `e2e`, `flatten` modes): int32 nGlyphs, nContours,
+        """The flat file oracle/_ref/shim_check reads to rebuild real msdfgen::Shape objects (`batch`, `e2e`, `flatten` modes): int32 nGlyphs, nContours,
         nEdges; gco; co; f64 points[nEdges][8]; u8 types; u8 colors; f64 xfs[nGlyphs][6] (sx, sy, tx, ty, range lower, range upper); u8 inverse_y."""
         gco, co = self.glyph_contour_offsets.astype(np.int32), self.contour_offsets.astype(np.int32)
         with open(path, "wb") as f:

@@ -1,5 +1,5 @@
 """CLI-level drop-in: the reference's UNMODIFIED main.cpp built twice by integration/build_cli_dropin.sh -- once against
-msdfgen's own core (tests/cli/msdfgen_cpu) and once with INTEGRATION.md section 2 applied (tests/cli/msdfgen_hip: core/msdfgen.cpp and
+msdfgen's own core (oracle/_ref/cli/msdfgen_cpu) and once with INTEGRATION.md section 2 applied (oracle/_ref/cli/msdfgen_hip: core/msdfgen.cpp and
 core/msdf-error-correction.cpp guarded by integration/patch_msdfgen_for_hip.py, rasterization.cpp / render-sdf.cpp dropped, the HIP shim
 linked). Both run the same command lines; the -format fl32 outputs (raw floats, save-fl32.cpp:12-32) must be byte-identical.
 main.cpp:1233-1298 is the caller under test: generate* -> [distanceSignCorrection -> msdfErrorCorrection]."""
@@ -13,7 +13,8 @@ from conftest import load_npz
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-CPU, HIP = os.path.join(HERE, "cli", "msdfgen_cpu"), os.path.join(HERE, "cli", "msdfgen_hip")
+CLI = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "cli")
+CPU, HIP = os.path.join(CLI, "msdfgen_cpu"), os.path.join(CLI, "msdfgen_hip")
 
 TEARDROP = "{ 1471,0; 1149,0; 1021,333; 435,333; 314,0; 0,0; 571,1466; 884,1466; # }{ 926,580; 724,1124; 526,580; # }"          # README.md:214-218 style
 BLOBS = ("{ 0,0; (2,3; 5,3); 6,0; (4,-2; 1,-2); # } { 2,0.5; 4,0.5; 3,2; # } { 7,1; (8,3); 10,1; (8,-1); # } "
@@ -47,7 +48,7 @@ def run(binary, mode, desc, out, extra, size=(56, 48)):
 @pytest.mark.parametrize("shape", ["teardrop", "blobs", "a"])
 def test_reference_cli_with_and_without_the_hip_shim(tmp_path, shape):
     if not (os.path.exists(CPU) and os.path.exists(HIP)):
-        pytest.skip("tests/cli/ not built (integration/build_cli_dropin.sh needs the msdfgen sources)")
+        pytest.skip("oracle/_ref/cli/ not built (integration/build_cli_dropin.sh needs the msdfgen sources)")
     text = {"teardrop": TEARDROP, "blobs": BLOBS, "a": str(load_npz("shape_a.npz")["desc"])}[shape]
     desc = tmp_path/"shape.txt"
     desc.write_text(text)

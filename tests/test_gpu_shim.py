@@ -1,7 +1,7 @@
 """The C++ drop-in (msdfgen_amd/shim/msdfgen_shim.cpp): a client written against msdfgen's own headers (tests/shim/shim_check.cpp,
 after README.md:114-142) calls msdfgen::generateSDF/PSDF/MSDF/MTSDF with the reference's signatures and gets the HIP path.
-The client binary is built in the authoring container (needs the msdfgen headers + the reference's non-hot-path objects) and
-travels to the GPU box; the test is skipped where it does not exist."""
+The client binary is built by build() into oracle/_ref/shim_check where msdfgen's sources exist (it needs the msdfgen headers + the
+reference's non-hot-path objects) and travels with oracle/_ref/; the test is skipped where it does not exist."""
 import os
 import subprocess
 
@@ -13,13 +13,13 @@ from msdfgen_amd.shape import FlatShape
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-BIN = os.path.join(HERE, "shim", "shim_check")
+BIN = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "shim_check")
 
 
 @pytest.mark.parametrize("mode,ydown", [(1, 0), (2, 0), (3, 0), (4, 0), (3, 1)])
 def test_reference_client_through_cpp_shim(tmp_path, oracle, mode, ydown):
     if not os.path.exists(BIN):
-        pytest.skip("tests/shim/shim_check not built (needs the msdfgen headers)")
+        pytest.skip("oracle/_ref/shim_check not built (needs the msdfgen headers)")
     z = load_npz("shape_a.npz")
     s = FlatShape(z["contour_offsets"], z["points"], z["types"], z["colors"])
     desc = tmp_path/"a.txt"
@@ -40,7 +40,7 @@ def test_reference_client_through_cpp_shim(tmp_path, oracle, mode, ydown):
 def test_reference_client_scanline_flow_through_cpp_shim(tmp_path, oracle, mode, rule):
     """msdfgen::distanceSignCorrection / rasterize (core/rasterization.h:13-27) through the shim: main.cpp's -scanline flow."""
     if not os.path.exists(BIN):
-        pytest.skip("tests/shim/shim_check not built (needs the msdfgen headers)")
+        pytest.skip("oracle/_ref/shim_check not built (needs the msdfgen headers)")
     z = load_npz("shape_a.npz")
     s = FlatShape(z["contour_offsets"], z["points"], z["types"], z["colors"])
     desc = tmp_path/"a.txt"
@@ -67,7 +67,7 @@ def test_reference_client_scanline_flow_through_cpp_shim(tmp_path, oracle, mode,
 def test_reference_client_render_sdf_through_cpp_shim(tmp_path, oracle, mode):
     """msdfgen::renderSDF / simulate8bit (core/render-sdf.h:12-22) through the shim: a 2x preview of the generated field."""
     if not os.path.exists(BIN):
-        pytest.skip("tests/shim/shim_check not built (needs the msdfgen headers)")
+        pytest.skip("oracle/_ref/shim_check not built (needs the msdfgen headers)")
     z = load_npz("shape_a.npz")
     s = FlatShape(z["contour_offsets"], z["points"], z["types"], z["colors"])
     desc = tmp_path/"a.txt"
@@ -88,7 +88,7 @@ def test_reference_client_shapeless_error_correction_through_cpp_shim(tmp_path, 
     """msdfgen::msdfFastDistanceErrorCorrection / msdfFastEdgeErrorCorrection (core/msdf-error-correction.h:21-34) through the shim, all three
     overload families (SDFTransformation; Projection + Range; default and explicit minDeviationRatio) -- against the compiled reference."""
     if not os.path.exists(BIN):
-        pytest.skip("tests/shim/shim_check not built (needs the msdfgen headers)")
+        pytest.skip("oracle/_ref/shim_check not built (needs the msdfgen headers)")
     z = load_npz("shape_a.npz")
     s = FlatShape(z["contour_offsets"], z["points"], z["types"], z["colors"])
     desc = tmp_path/"a.txt"
@@ -113,7 +113,7 @@ def test_batch_entry_of_the_shim_equals_per_call_results(tmp_path, mode, size, c
     orientations, negative row strides) and an 8-bit atlas (pixelFloatToByte of the per-call floats; gutter bytes untouched) -- zero differing values.
     The 94 + 1 406 distinct glyphs: Basic Latin (Y-down flags as in the fixture) followed by DejaVu glyphs up to 543 edges / 43 contours."""
     if not os.path.exists(BIN):
-        pytest.skip("tests/shim/shim_check not built (needs the msdfgen headers)")
+        pytest.skip("oracle/_ref/shim_check not built (needs the msdfgen headers)")
     import json
     from msdfgen_amd.shape import ShapeBatch, autoframe
     z = load_npz("dejavu8192.npz")

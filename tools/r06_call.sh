@@ -3,7 +3,6 @@
 #   (traffic: HBM FETCH_SIZE / WRITE_SIZE of the distance pass per library variant, tools/traffic_ab.py -- the A/B that round 5 ran from one-off scripts)
 TAG=$1; shift
 mkdir -p gpurun_out
-export GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-8}
 for STEP in "$@"; do
   case "$STEP" in
     tests) timeout 900 python -m pytest tests -m gpu -q -x 2>&1 | grep -v "^  File \|dist-packages" | tail -40 > gpurun_out/${TAG}_gputests.log; tail -4 gpurun_out/${TAG}_gputests.log ;;

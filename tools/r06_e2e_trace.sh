@@ -1,5 +1,5 @@
 # Kernel + copy timeline of the last streamed end-to-end call (8-bit atlas): bash tools/r06_call.sh <tag> r06_e2e_trace.sh
-TAG=$1; REPO=$PWD; export TMPDIR=/tmp; export GPU_MAX_HW_QUEUES=8
+TAG=$1; REPO=$PWD; export TMPDIR=/tmp
 (cd /tmp && rm -rf /tmp/e2e_$TAG && timeout 200 rocprofv3 --kernel-trace --memory-copy-trace -d /tmp/e2e_$TAG -o e2e -- python $REPO/tools/e2e_stream.py 2 > /dev/null 2>&1)
 python - <<'PY' $(find /tmp/e2e_$1 -name "*.db" | head -1) | tee gpurun_out/${1}_e2e_timeline.txt
 import sqlite3, sys
