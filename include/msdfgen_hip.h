@@ -296,6 +296,18 @@ typedef struct MsdfHipPrepConfig {
 int msdfhip_batch_create_prepared(MsdfHipBatch **batch, int n_glyphs, const int32_t *glyph_contour_offsets, const int32_t *contour_offsets,
                                   const double *points, const uint8_t *types, const uint8_t *colors, const uint64_t *seeds,
                                   const MsdfHipPrepConfig *cfg);
+/* The streamed generator (msdfhip_generate_stream / _csr) over RAW outlines: every chunk is uploaded, prepared on the device (prep, seeds: as for
+ * msdfhip_batch_create_prepared), digested, rendered and copied back on its own stream, overlapped with the neighbouring chunks. The bytes of glyph g are
+ * those of msdfhip_batch_create_prepared with the same arrays, prep and seeds followed by msdfhip_batch_generate_host / _bytes_host, whatever the chunks.
+ * Source form: the colours `fill` writes are used only when prep->coloring == 0. CSR form: colors may be NULL (all WHITE).
+ * A NULL prep, a coloring outside 0..2 or a stencil with atlas output fail with MSDFHIP_ERR_INVALID before the device is touched. */
+int msdfhip_generate_stream_prepared(int device, int mode, int width, int height, int n_glyphs, const MsdfHipShapeSource *source,
+                                     const MsdfHipGlyph *glyphs, float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes,
+                                     uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep, const uint64_t *seeds);
+int msdfhip_generate_stream_csr_prepared(int device, int mode, int width, int height, int n_glyphs, const int32_t *glyph_contour_offsets,
+                                         const int32_t *contour_offsets, const double *points, const uint8_t *types, const uint8_t *colors,
+                                         const MsdfHipGlyph *glyphs, float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes,
+                                         uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep, const uint64_t *seeds);
 /* Diagnostics: after an error-correction pass, counts[0] = 1 if some glyph's candidate segment overflowed (those glyphs were redone by
  * the full per-texel pipeline), counts[1+g] = deferred distance checks pushed for glyph g. counts holds n_glyphs+1 entries. */
 int msdfhip_batch_candidate_counts(const MsdfHipBatch *batch, uint32_t *counts);

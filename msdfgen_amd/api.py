@@ -100,6 +100,19 @@ class MSDFGeneratorConfig(GeneratorConfig):
     _stage_limit: int = 0  # test hook: stop the stencil pipeline after stage k (see MsdfHipConfig.ec_stage_limit)
 
 
+@dataclass
+class PrepareConfig:
+    """Shape preparation of raw outlines on the device (msdfgen_hip.h, MsdfHipPrepConfig): Shape::normalize (core/Shape.cpp:65-92) and
+    edgeColoringSimple (coloring=1, core/edge-coloring.cpp:68-142) or edgeColoringInkTrap (coloring=2, :151-258); coloring=0 keeps the colours."""
+    normalize: bool = True
+    coloring: int = 1
+    angle_threshold: float = 3.0
+    seed: int = 0
+
+    def c_struct(self) -> _lib.PrepConfig:
+        return _lib.PrepConfig(int(bool(self.normalize)), int(self.coloring), float(self.angle_threshold), int(self.seed))
+
+
 def _c_config(config, y_orientation=None) -> _lib.Config:
     """y_orientation: the OUTPUT bitmap's orientation; the reference keeps the stencil's rows upward whatever it is
     (core/MSDFErrorCorrection.cpp:122,192,415), which is what MsdfHipConfig.stencil_y_down tells the device -- set on every path that
@@ -603,10 +616,12 @@ def generate_sharded(devices, shapes: ShapeBatch, mode, width, height, xfs, out=
 
 
 def generate_stream(shapes: ShapeBatch, mode, width, height, xfs, out=None, atlas=None, out_offsets=None, row_stride=None, config=None, stencil=None,
-                    y_orientation=Y_UPWARD, device=-1):
+                    y_orientation=Y_UPWARD, device=-1, prepare: Optional[PrepareConfig] = None, seeds=None):
     """msdfhip_generate_stream_csr: host CSR arrays in, host tiles (float32 `out`) or an 8-bit `atlas` out, as ONE pipelined call -- the glyph list is cut
     into chunks and chunk k+1's staging + upload + digest run under chunk k's kernels and chunk k-1's copy back (SURVEY.md 8d's end-to-end metric;
-    msdfgen_hip::generate*Batch() of the C++ shim is the same pipeline fed from msdfgen::Shape objects)."""
+    msdfgen_hip::generate*Batch() of the C++ shim is the same pipeline fed from msdfgen::Shape objects).
+    prepare: `shapes` are RAW outlines, prepared on the device chunk by chunk inside the pipeline (msdfhip_generate_stream_csr_prepared) -- the same
+    bytes as GlyphBatch.from_raw(shapes, normalize, coloring, angle_threshold, seeds=seeds, seed=seed) followed by generate(); `seeds`: one per glyph."""
     n = CHANNELS[mode]
     tile = width*height*n
     if out is None and atlas is None:
@@ -621,6 +636,17 @@ def generate_stream(shapes: ShapeBatch, mode, width, height, xfs, out=None, atla
     colors = np.ascontiguousarray(shapes.colors, np.uint8)
     if stencil is not None:
         assert stencil.dtype == np.uint8 and stencil.flags.c_contiguous and stencil.size >= shapes.n_glyphs*width*height
+    if prepare is not None:
+        pc = prepare.c_struct()
+        sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint64)
+        assert sd is None or sd.size == shapes.n_glyphs
+        _lib.check(_lib.load().msdfhip_generate_stream_csr_prepared(int(device), mode, width, height, shapes.n_glyphs, _lib.ptr(gco, _lib._ip), _lib.ptr(co, _lib._ip),
+                                                                    _lib.ptr(pts, _lib._dp), _lib.ptr(types, _lib._bp), _lib.ptr(colors, _lib._bp), d.ctypes.data,
+                                                                    out.ctypes.data if out is not None else None, out.size if out is not None else 0,
+                                                                    atlas.ctypes.data if atlas is not None else None, atlas.size if atlas is not None else 0,
+                                                                    stencil.ctypes.data if stencil is not None else None, C.byref(cfg), C.byref(pc),
+                                                                    sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None))
+        return out if out is not None else atlas
     _lib.check(_lib.load().msdfhip_generate_stream_csr(int(device), mode, width, height, shapes.n_glyphs, _lib.ptr(gco, _lib._ip), _lib.ptr(co, _lib._ip),
                                                        _lib.ptr(pts, _lib._dp), _lib.ptr(types, _lib._bp), _lib.ptr(colors, _lib._bp), d.ctypes.data,
                                                        out.ctypes.data if out is not None else None, out.size if out is not None else 0,

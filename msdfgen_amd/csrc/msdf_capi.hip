@@ -538,7 +538,8 @@ int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
     return MSDFHIP_OK;
 }
 
-// Upload of a few KB from pinned host memory by a kernel instead of an SDMA copy (see k_upload_words). bytes must be a multiple of 4.
+// Upload of a few KB from pinned host memory by a kernel instead of an SDMA copy (see k_upload_words; StreamFeeder::prepareChunk uses it the other way,
+// device words into pinned memory). bytes must be a multiple of 4.
 int uploadSmall(void *dst, const void *srcPinned, size_t bytes, hipStream_t stream) {
     if (bytes == 0)
         return MSDFHIP_OK;
@@ -1420,6 +1421,78 @@ int msdfhip_device_count(int *count) {
     return MSDFHIP_OK;
 }
 
+} // extern "C"
+
+namespace {
+
+// Host side of the preparation's sizes (the same arithmetic wherever raw outlines are prepared): co1 = the contour offsets after normalize, a prefix
+// of normalizedCount over the raw contour sizes; *bound2 = the upper bound of the coloured edge count (a contour of n1 < 3 edges may be split into 3*n1);
+// *longest = the longest normalized contour (it picks the colouring's LDS tier and says whether the `big` tables are needed).
+void prepOffsets(const int32_t *co, int nC, bool normalize, int32_t *co1, size_t *bound2, int *longest) {
+    size_t b2 = 0;
+    int lg = 0;
+    co1[0] = 0;
+    for (int c = 0; c < nC; ++c) {
+        const int n = co[c+1]-co[c];
+        const int n1 = normalize ? normalizedCount(n) : n;
+        co1[c+1] = co1[c]+n1;
+        b2 += n1 < 3 ? 3*(size_t) n1 : (size_t) n1;
+        lg = n1 > lg ? n1 : lg;
+    }
+    *bound2 = b2, *longest = lg;
+}
+
+// The device buffers of one preparation (every pointer the caller's: nothing is allocated here).
+struct PrepBuffers {
+    const int32_t *gco, *co, *co1;        // glyph -> contour offsets, raw contour offsets, contour offsets after normalize (prepOffsets)
+    EdgeArrays raw, norm, fin;            // raw edges (colors may be NULL = WHITE); normalized [co1[nC]]; coloured [bound2] (coloring != 0 only)
+    int32_t *cusp, *count, *co2;          // [nC+1] each: normalize's cusp flags; coloured edges per contour and their prefix (coloring != 0 only)
+    const unsigned long long *seeds;      // one per glyph, or NULL: cfg->seed for every glyph
+    ColourTables big;                     // the colouring's tables of contours beyond PREP_WAVE_MAX_EDGES (only when `longest` exceeds it)
+};
+
+// Shape preparation (row f3) as ONE queued sequence on `stream`: normalize (k_prep_normalize_flat + the cusp repair), then with coloring the coloured
+// counts, their prefix and the colouring wave. Never allocates, never waits: msdfhip_batch_create_prepared runs it on the null stream, the streamed
+// generator on each chunk's stream under the kernels of the chunks before it. With coloring the result is fin + co2, else norm + co1.
+int queuePreparation(const MsdfHipPrepConfig *cfg, int nGlyphs, int nC, int nE1, int longest, double crossThreshold, const PrepBuffers &pb, hipStream_t stream) {
+    if (nE1) {
+        HIPCHK(hipMemsetAsync(pb.cusp, 0, sizeof(int32_t)*(size_t) (nC+1), stream));
+        hipLaunchKernelGGL(k_prep_normalize_flat, dim3((nE1+255)/256), dim3(256), 0, stream, pb.raw, pb.co, pb.co1, nC, nE1, cfg->normalize ? 1 : 0, pb.norm, pb.cusp);
+        if (cfg->normalize)
+            hipLaunchKernelGGL(k_prep_normalize_cusps, dim3((nC+127)/128), dim3(128), 0, stream, pb.raw, pb.co, pb.co1, nC, pb.norm, (const int32_t *) pb.cusp);
+    }
+    if (cfg->coloring) {
+        if (nC)
+            hipLaunchKernelGGL(k_prep_count, dim3((nC+127)/128), dim3(128), 0, stream, pb.norm, pb.co1, nC, crossThreshold, pb.count);
+        hipLaunchKernelGGL(k_prep_offsets, dim3(1), dim3(256), 0, stream, (const int32_t *) pb.count, nC, pb.co2);
+        // one wavefront per glyph, lanes = edges / corners; the LDS tier of the launch from the longest contour (a contour beyond the tier uses `big`,
+        // which exists only past the large tier: the small tier is chosen only when no contour exceeds it)
+        const bool smallTier = longest <= PREP_WAVE_SMALL_EDGES && !tuning().prepLargeTier;
+        #define PREP_COLOUR(INK, TIER) hipLaunchKernelGGL((k_prep_colour_wave<INK, TIER>), dim3((unsigned) nGlyphs), dim3(WAVE), 0, stream, pb.norm, pb.gco, \
+                                                          pb.co1, (const int32_t *) pb.co2, nGlyphs, crossThreshold, pb.seeds, (unsigned long long) cfg->seed, pb.fin, pb.big)
+        if (nGlyphs && cfg->coloring == 1) {
+            if (smallTier) PREP_COLOUR(false, PREP_WAVE_SMALL_EDGES); else PREP_COLOUR(false, PREP_WAVE_MAX_EDGES);
+        } else if (nGlyphs) {
+            if (smallTier) PREP_COLOUR(true, PREP_WAVE_SMALL_EDGES); else PREP_COLOUR(true, PREP_WAVE_MAX_EDGES);
+        }
+        #undef PREP_COLOUR
+    }
+    HIPCHK(hipGetLastError());
+    return MSDFHIP_OK;
+}
+
+int checkPrepConfig(const MsdfHipPrepConfig *cfg, const char *who) {
+    if (!cfg)
+        return fail(MSDFHIP_ERR_INVALID, "%s: NULL preparation config", who);
+    if (cfg->coloring < 0 || cfg->coloring > 2)
+        return fail(MSDFHIP_ERR_INVALID, "%s: coloring %d (0 keep, 1 edgeColoringSimple, 2 edgeColoringInkTrap)", who, cfg->coloring);
+    return MSDFHIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
 int msdfhip_batch_create_prepared(MsdfHipBatch **batch, int n_glyphs, const int32_t *gco, const int32_t *co, const double *points, const uint8_t *types,
                                   const uint8_t *colors, const uint64_t *seeds, const MsdfHipPrepConfig *cfg) {
     if (!batch || n_glyphs < 0 || !gco || !co || !cfg)
@@ -1441,12 +1514,8 @@ int msdfhip_batch_create_prepared(MsdfHipBatch **batch, int n_glyphs, const int3
     // offsets after normalize are a host-side prefix over the raw contour sizes; the upper bound of the coloured size as well
     std::vector<int32_t> co1(nC+1, 0), co2(nC+1, 0);
     size_t bound2 = 0;
-    for (int c = 0; c < nC; ++c) {
-        const int n = co[c+1]-co[c];
-        const int n1 = cfg->normalize ? normalizedCount(n) : n;
-        co1[c+1] = co1[c]+n1;
-        bound2 += n1 < 3 ? 3*n1 : n1;
-    }
+    int longest = 0;
+    prepOffsets(co, nC, cfg->normalize != 0, co1.data(), &bound2, &longest);
     if (bound2 > 0x7fffffffull)
         return fail(MSDFHIP_ERR_INVALID, "too many edges");
     const int nE1 = co1[nC];
@@ -1457,13 +1526,15 @@ int msdfhip_batch_create_prepared(MsdfHipBatch **batch, int n_glyphs, const int3
         void release(void *p) { for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { ptrs.erase(ptrs.begin()+i); break; } }
     } dev;
     #define PREP_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(MSDFHIP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
-    int32_t *dGco = NULL, *dCo = NULL, *dCo1 = NULL, *dCo2 = NULL, *dCount = NULL;
+    int32_t *dGco = NULL, *dCo = NULL, *dCo1 = NULL, *dCo2 = NULL, *dCount = NULL, *dCusp = NULL;
     unsigned long long *dSeeds = NULL;
     EdgeArrays raw = { NULL, NULL, NULL }, norm = { NULL, NULL, NULL }, fin = { NULL, NULL, NULL };
+    ColourTables big = { NULL, NULL, NULL, NULL, NULL, NULL };
     const size_t eRaw = nE > 0 ? nE : 1, eNorm = nE1 > 0 ? nE1 : 1, eFin = bound2 > 0 ? bound2 : 1;
     PREP_CHK(dev.alloc((void **) &dGco, sizeof(int32_t)*(size_t) (n_glyphs+1)));
     PREP_CHK(dev.alloc((void **) &dCo, sizeof(int32_t)*(size_t) (nC+1)));
     PREP_CHK(dev.alloc((void **) &dCo1, sizeof(int32_t)*(size_t) (nC+1)));
+    PREP_CHK(dev.alloc((void **) &dCusp, sizeof(int32_t)*(size_t) (nC+1)));
     PREP_CHK(dev.alloc((void **) &raw.points, sizeof(double)*8*eRaw));
     PREP_CHK(dev.alloc((void **) &raw.types, eRaw));
     PREP_CHK(dev.alloc((void **) &norm.points, sizeof(double)*8*eNorm));
@@ -1480,36 +1551,18 @@ int msdfhip_batch_create_prepared(MsdfHipBatch **batch, int n_glyphs, const int3
             PREP_CHK(hipMemcpy(raw.colors, colors, (size_t) nE, hipMemcpyHostToDevice));
         }
     }
-    // Every pass below is queued without a host round trip; the coloured offsets come back once, at the end.
-    if (nE1) {
-        int32_t *dCusp = NULL;
-        PREP_CHK(dev.alloc((void **) &dCusp, sizeof(int32_t)*(size_t) (nC+1)));
-        PREP_CHK(hipMemsetAsync(dCusp, 0, sizeof(int32_t)*(size_t) (nC+1), 0));
-        hipLaunchKernelGGL(k_prep_normalize_flat, dim3((nE1+255)/256), dim3(256), 0, 0, raw, (const int32_t *) dCo, (const int32_t *) dCo1, nC, nE1, cfg->normalize ? 1 : 0, norm, dCusp);
-        if (cfg->normalize)
-            hipLaunchKernelGGL(k_prep_normalize_cusps, dim3((nC+127)/128), dim3(128), 0, 0, raw, (const int32_t *) dCo, (const int32_t *) dCo1, nC, norm, (const int32_t *) dCusp);
-    }
-    const int32_t *finalCo = co1.data();
-    int32_t *dFinalCo = dCo1;
+    const double crossThreshold = cfg->coloring ? sin(cfg->angle_threshold) : 0.;   // edge-coloring.cpp:69, taken by the host's libm like the reference's
     if (cfg->coloring) {
-        const double crossThreshold = sin(cfg->angle_threshold);  // edge-coloring.cpp:69, taken by the host's libm like the reference's
         PREP_CHK(dev.alloc((void **) &dCount, sizeof(int32_t)*(size_t) (nC+1)));
         PREP_CHK(dev.alloc((void **) &dCo2, sizeof(int32_t)*(size_t) (nC+1)));
         PREP_CHK(dev.alloc((void **) &fin.points, sizeof(double)*8*eFin));
         PREP_CHK(dev.alloc((void **) &fin.types, eFin));
         PREP_CHK(dev.alloc((void **) &fin.colors, eFin));
-        if (nC)
-            hipLaunchKernelGGL(k_prep_count, dim3((nC+127)/128), dim3(128), 0, 0, norm, (const int32_t *) dCo1, nC, crossThreshold, dCount);
-        hipLaunchKernelGGL(k_prep_offsets, dim3(1), dim3(256), 0, 0, (const int32_t *) dCount, nC, dCo2);
         if (seeds && n_glyphs) {
             PREP_CHK(dev.alloc((void **) &dSeeds, sizeof(unsigned long long)*(size_t) n_glyphs));
             PREP_CHK(hipMemcpy(dSeeds, seeds, sizeof(unsigned long long)*(size_t) n_glyphs, hipMemcpyHostToDevice));
         }
         // the colouring's per-contour tables live in LDS; a contour beyond PREP_WAVE_MAX_EDGES edges keeps them in global memory, indexed like the edges
-        ColourTables big = { NULL, NULL, NULL, NULL, NULL, NULL };
-        int longest = 0;
-        for (int c = 0; c < nC; ++c)
-            longest = co1[c+1]-co1[c] > longest ? co1[c+1]-co1[c] : longest;
         if (longest > PREP_WAVE_MAX_EDGES) {
             PREP_CHK(dev.alloc((void **) &big.cornerMask, sizeof(unsigned long long)*(eNorm/WAVE+(size_t) nC+2)));
             PREP_CHK(dev.alloc((void **) &big.splineColor, eNorm));
@@ -1520,22 +1573,20 @@ int msdfhip_batch_create_prepared(MsdfHipBatch **batch, int n_glyphs, const int3
                 PREP_CHK(dev.alloc((void **) &big.minor, eNorm));
             }
         }
-        // one wavefront per glyph, lanes = edges / corners; the LDS tier of the launch from the batch's longest contour (a contour beyond the tier uses `big`,
-        // which exists only past the large tier: the small tier is chosen only when no contour exceeds it)
-        const bool smallTier = longest <= PREP_WAVE_SMALL_EDGES && !tuning().prepLargeTier;
-        #define PREP_COLOUR(INK, TIER) hipLaunchKernelGGL((k_prep_colour_wave<INK, TIER>), dim3((unsigned) n_glyphs), dim3(WAVE), 0, 0, norm, (const int32_t *) dGco, \
-                                                          (const int32_t *) dCo1, (const int32_t *) dCo2, n_glyphs, crossThreshold, (const unsigned long long *) dSeeds, (unsigned long long) cfg->seed, fin, big)
-        if (n_glyphs && cfg->coloring == 1) {
-            if (smallTier) PREP_COLOUR(false, PREP_WAVE_SMALL_EDGES); else PREP_COLOUR(false, PREP_WAVE_MAX_EDGES);
-        } else if (n_glyphs) {
-            if (smallTier) PREP_COLOUR(true, PREP_WAVE_SMALL_EDGES); else PREP_COLOUR(true, PREP_WAVE_MAX_EDGES);
-        }
-        #undef PREP_COLOUR
+    } else
+        fin = norm;
+    // Every pass is queued without a host round trip; the coloured offsets come back once, at the end.
+    const PrepBuffers pb = { dGco, dCo, dCo1, raw, norm, fin, dCusp, dCount, dCo2, dSeeds, big };
+    rc = queuePreparation(cfg, n_glyphs, nC, nE1, longest, crossThreshold, pb, 0);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    const int32_t *finalCo = co1.data();
+    int32_t *dFinalCo = dCo1;
+    if (cfg->coloring) {
         PREP_CHK(hipMemcpy(co2.data(), dCo2, sizeof(int32_t)*(size_t) (nC+1), hipMemcpyDeviceToHost));   // in stream order after the kernels above
         finalCo = co2.data();
         dFinalCo = dCo2;
-    } else
-        fin = norm;
+    }
     PREP_CHK(hipGetLastError());
     PREP_CHK(hipDeviceSynchronize());
     #undef PREP_CHK
@@ -1861,6 +1912,7 @@ struct PipeSlot {
     size_t devInCap;
     hipEvent_t inputsUploaded;        // the chunk's upload has left pinnedIn
     bool inputsInFlight;
+    hipEvent_t prepCounted;           // streamed calls of raw outlines: the chunk's coloured contour offsets have reached pinnedIn (StreamFeeder::prepare)
 };
 
 // The slots of a pipeline in flight. Pipelines live in a process-wide pool per device (like the arenas of the single-shape calls):
@@ -1911,7 +1963,7 @@ struct PipeLease {
             PipeSlot &s = fresh->slot[k];
             s.stream = NULL, s.done = NULL, s.kernelsDone = NULL, s.distanceDone = NULL, s.pinnedOverflow = NULL, s.busy = false, s.dev = NULL, s.devCap = 0, s.pinnedGlyphs = NULL, s.pinnedGlyphCap = 0, s.viewCap = 0;
             s.pinnedTiles = NULL, s.pinnedTilesCap = 0, s.pendingFirst = 0, s.pendingCount = 0;
-            s.pinnedIn = NULL, s.pinnedInCap = 0, s.devIn = NULL, s.devInCap = 0, s.inputsUploaded = NULL, s.inputsInFlight = false;
+            s.pinnedIn = NULL, s.pinnedInCap = 0, s.devIn = NULL, s.devInCap = 0, s.inputsUploaded = NULL, s.inputsInFlight = false, s.prepCounted = NULL;
         }
         for (int k = 0; k < PIPE_SLOTS; ++k) {                   // a half-built pipe never reaches the pool
             hipError_t e = k == 0 ? hipStreamCreateWithFlags(&fresh->compute, hipStreamNonBlocking) : hipSuccess;
@@ -1930,6 +1982,8 @@ struct PipeLease {
             }
             if (e == hipSuccess)
                 e = hipEventCreateWithFlags(&fresh->slot[k].inputsUploaded, hipEventDisableTiming);
+            if (e == hipSuccess)
+                e = hipEventCreateWithFlags(&fresh->slot[k].prepCounted, hipEventDisableTiming);
             if (e != hipSuccess) {
                 (void) hipGetLastError();
                 destroyPipe(fresh);
@@ -2124,9 +2178,16 @@ struct StreamFeeder : ChunkFeeder {
     std::vector<std::shared_ptr<HostJob> > jobs;                 // flatten job of chunk k
     std::unique_ptr<std::atomic<int>[]> badType;                 // per chunk: a glyph whose fill produced an edge type outside 1..3 (-1: none); written by pool threads
     PipeSlot *slots;
+    // Raw outlines (msdfhip_generate_stream_prepared): every chunk is prepared on its own stream between its upload and its digest (queuePreparation),
+    // from the same staging the prepared form uses plus the host's normalized contour offsets (and the chunk's seeds) behind it.
+    const MsdfHipPrepConfig *prep;                               // NULL: the shapes are prepared already
+    const uint64_t *seeds;                                       // one per glyph of the whole list, or NULL (prep->seed)
+    double crossThreshold;                                       // sin(angle_threshold), by the host's libm (edge-coloring.cpp:69)
+    std::vector<char> mayHaveLong;                               // per chunk: a glyph whose normalized contours could exceed PREP_WAVE_MAX_EDGES (the `big` tables)
     enum { GRAIN = 32 };                                         // glyphs per flatten item
 
-    StreamFeeder(const MsdfHipShapeSource *source, int n) : src(source), nG(n), slots(NULL) { }
+    StreamFeeder(const MsdfHipShapeSource *source, int n, const MsdfHipPrepConfig *prepCfg = NULL, const uint64_t *glyphSeeds = NULL)
+        : src(source), nG(n), slots(NULL), prep(prepCfg), seeds(glyphSeeds), crossThreshold(prepCfg && prepCfg->coloring ? sin(prepCfg->angle_threshold) : 0.) { }
     ~StreamFeeder() { drain(); }
 
     // The flatten jobs run on the detached pool threads, capture `this`, call the caller's fill callbacks and write into the leased pipe's pinned staging:
@@ -2163,13 +2224,39 @@ struct StreamFeeder : ChunkFeeder {
         return MSDFHIP_OK;
     }
 
-    // layout of a chunk's inputs inside a slot's staging / device input area (offsets from the area's start)
-    struct Layout { size_t gco, co, points, types, colors, bytes; };
-    static Layout layout(size_t n, size_t nC, size_t nE) {
+    // layout of a chunk's inputs inside a slot's staging / device input area (offsets from the area's start); `bytes` are uploaded
+    struct Layout { size_t gco, co, points, types, colors, co1, seeds, bytes; };
+    Layout layout(size_t n, size_t nC, size_t nE) const {
         Carver c;
         Layout l;
         l.gco = c.take((n+1)*sizeof(int32_t)), l.co = c.take((nC+1)*sizeof(int32_t)), l.points = c.take((nE ? nE : 1)*8*sizeof(double));
-        l.types = c.take(nE ? nE : 1), l.colors = c.take(nE ? nE : 1), l.bytes = c.off;
+        l.types = c.take(nE ? nE : 1), l.colors = c.take(nE ? nE : 1);
+        l.co1 = prep ? c.take((nC+1)*sizeof(int32_t)) : 0;     // (raw outlines) contour offsets after normalize, from the host (prepOffsets)
+        l.seeds = prep && seeds ? c.take(n*sizeof(uint64_t)) : 0;
+        l.bytes = c.off;
+        return l;
+    }
+
+    // (raw outlines) the device-only part of a chunk's input area behind the uploaded part: the preparation's buffers, then the records + windings of
+    // the PREPARED edges. nE1 / nE2: normalized / coloured edge counts. begin() sizes the slots with their bounds (nE + 2 nC, nE + 4 nC: a raw contour of
+    // one edge becomes three, one of two edges at most six), a chunk carves its exact counts -- the same pieces in the same order, so never beyond.
+    struct PrepLayout { size_t cusp, count, co2, norm[3], fin[3], bigMask, bigSpline, bigEdgeLength, bigCornerLength, bigCornerIndex, bigMinor, recs, windings, bytes; };
+    PrepLayout prepLayout(size_t at, size_t nC, size_t nE1, size_t nE2, bool big) const {
+        Carver c;
+        c.off = (at+255)/256*256;
+        PrepLayout l = PrepLayout();
+        const size_t e1 = nE1 ? nE1 : 1, e2 = nE2 ? nE2 : 1;
+        l.cusp = c.take((nC+1)*sizeof(int32_t)), l.count = c.take((nC+1)*sizeof(int32_t)), l.co2 = c.take((nC+1)*sizeof(int32_t));
+        l.norm[0] = c.take(e1*8*sizeof(double)), l.norm[1] = c.take(e1), l.norm[2] = c.take(e1);
+        if (prep->coloring) {
+            l.fin[0] = c.take(e2*8*sizeof(double)), l.fin[1] = c.take(e2), l.fin[2] = c.take(e2);
+            if (big) {                                           // (msdfhip_batch_create_prepared's sizes)
+                l.bigMask = c.take(sizeof(unsigned long long)*(e1/WAVE+nC+2)), l.bigSpline = c.take(e1);
+                if (prep->coloring == 2)
+                    l.bigEdgeLength = c.take(sizeof(double)*e1), l.bigCornerLength = c.take(sizeof(double)*e1), l.bigCornerIndex = c.take(sizeof(int)*e1), l.bigMinor = c.take(e1);
+            }
+        }
+        l.recs = c.take(sizeof(EdgeRec)*(prep->coloring ? e2 : e1)), l.windings = c.take(nC ? nC : 1), l.bytes = c.off;
         return l;
     }
 
@@ -2213,20 +2300,29 @@ struct StreamFeeder : ChunkFeeder {
         slots = pipeSlots;
         chunkStart.clear(), chunkLen = lengths;
         int g = 0;
-        size_t needIn = 0, needC = 0, needE = 0;
+        size_t needIn = 0, needC = 0, needE = 0, prepPinned = 0, prepDev = 0;
+        mayHaveLong.assign(lengths.size(), 0);
         for (size_t ci = 0; ci < lengths.size(); g += lengths[ci], ++ci) {
             chunkStart.push_back(g);
             const size_t nC = (size_t) (contourBase[(size_t) g+lengths[ci]]-contourBase[(size_t) g]), nE = (size_t) (edgeBase[(size_t) g+lengths[ci]]-edgeBase[(size_t) g]);
-            if (nE > 0x7fffffffull/8 || nC > 0x7fffffffull/8)
+            if (nE > 0x7fffffffull/8 || nC > 0x7fffffffull/8 || (prep && nE+4*nC > 0x7fffffffull/8))
                 return fail(MSDFHIP_ERR_INVALID, "a pipeline chunk of %d glyphs holds %zu edges / %zu contours: beyond the 32-bit offsets of a batch", lengths[ci], nE, nC);
             const Layout l = layout((size_t) lengths[ci], nC, nE);
             needIn = l.bytes > needIn ? l.bytes : needIn, needC = nC > needC ? nC : needC, needE = nE > needE ? nE : needE;
+            if (prep) {                                          // + the coloured offsets coming back behind the staging; the preparation's buffers
+                for (int k = g; k < g+lengths[ci]; ++k)
+                    mayHaveLong[ci] |= (long long) hEdges[(size_t) k]+2LL*hContours[(size_t) k] > PREP_WAVE_MAX_EDGES;
+                const size_t pin = (l.bytes+255)/256*256+(nC+1)*sizeof(int32_t), dev = prepLayout(l.bytes, nC, nE+2*nC, nE+4*nC, mayHaveLong[ci] != 0).bytes;
+                prepPinned = pin > prepPinned ? pin : prepPinned, prepDev = dev > prepDev ? dev : prepDev;
+            }
         }
+        if (prep)
+            needIn = prepPinned;
         jobs.assign(lengths.size(), std::shared_ptr<HostJob>());
         badType.reset(new std::atomic<int>[lengths.size() ? lengths.size() : 1]);
         for (size_t ci = 0; ci < lengths.size(); ++ci)
             badType[ci].store(-1);
-        const size_t recBytes = (sizeof(EdgeRec)*(needE ? needE : 1)+255)/256*256, devNeed = needIn+recBytes+(needC ? needC : 1)+256;
+        const size_t recBytes = (sizeof(EdgeRec)*(needE ? needE : 1)+255)/256*256, devNeed = prep ? prepDev+256 : needIn+recBytes+(needC ? needC : 1)+256;
         for (int k = 0; k < PIPE_SLOTS; ++k) {                   // every slot can take the largest chunk (grown once, kept with the pooled pipe)
             PipeSlot &p = slots[k];
             if (p.pinnedInCap < needIn) {
@@ -2271,6 +2367,13 @@ struct StreamFeeder : ChunkFeeder {
         }
         const size_t nC = (size_t) (contourBase[(size_t) g0+n]-contourBase[(size_t) g0]), nE = (size_t) (edgeBase[(size_t) g0+n]-edgeBase[(size_t) g0]);
         const Layout l = layout((size_t) n, nC, nE);
+        size_t bound2 = 0;
+        int longest = 0;
+        if (prep) {                                              // the normalized offsets and the seeds travel with the chunk's upload
+            prepOffsets(reinterpret_cast<const int32_t *>(p.pinnedIn+l.co), (int) nC, prep->normalize != 0, reinterpret_cast<int32_t *>(p.pinnedIn+l.co1), &bound2, &longest);
+            if (seeds)
+                memcpy(p.pinnedIn+l.seeds, seeds+g0, sizeof(uint64_t)*(size_t) n);
+        }
         if (tuning().streamUploadByCopy)
             HIPCHK(hipMemcpyAsync(p.devIn, p.pinnedIn, l.bytes, hipMemcpyHostToDevice, stream));
         else {                                                   // (a kernel reading the pinned staging: never queues behind another chunk's copy back)
@@ -2291,6 +2394,11 @@ struct StreamFeeder : ChunkFeeder {
         v.dWindings = reinterpret_cast<int8_t *>(p.devIn+recOff+(sizeof(EdgeRec)*(nE ? nE : 1)+255)/256*256);
         v.hContours.assign(hContours.begin()+g0, hContours.begin()+g0+n);
         v.hEdges.assign(hEdges.begin()+g0, hEdges.begin()+g0+n);
+        if (prep) {
+            const int rcPrep = prepareChunk(p, l, n, (int) nC, bound2, longest, stream);
+            if (rcPrep != MSDFHIP_OK)
+                return rcPrep;
+        }
         int maxC = 0, maxE = 0;
         for (int g = 0; g < n; ++g) {
             maxC = v.hContours[(size_t) g] > maxC ? v.hContours[(size_t) g] : maxC;
@@ -2301,6 +2409,58 @@ struct StreamFeeder : ChunkFeeder {
         v.ecParamsAhead = false;
         v.serialClasses = !tuning().pipelineConcurrentClasses;
         return digest(&v, stream);
+    }
+
+    // (raw outlines) the chunk's preparation on its stream, behind its upload; then p.view is pointed at the prepared arrays. The per-glyph edge counts the
+    // launches are planned from are the PREPARED ones, and the colouring may split a contour in a way only the device knows: its contour offsets come back
+    // (one small copy + an event). runPipelineOnce calls this after the previous chunk's kernels are queued, so the device has work while the host waits.
+    int prepareChunk(PipeSlot &p, const Layout &l, int n, int nC, size_t bound2, int longest, hipStream_t stream) {
+        char *d = p.devIn;
+        const int32_t *hCo1 = reinterpret_cast<const int32_t *>(p.pinnedIn+l.co1), *hGco = reinterpret_cast<const int32_t *>(p.pinnedIn+l.gco);
+        const int nE1 = hCo1[nC];
+        const bool big = longest > PREP_WAVE_MAX_EDGES;
+        const PrepLayout pl = prepLayout(l.bytes, (size_t) nC, (size_t) nE1, bound2, big);
+        EdgeArrays raw = { reinterpret_cast<double *>(d+l.points), reinterpret_cast<uint8_t *>(d+l.types), reinterpret_cast<uint8_t *>(d+l.colors) };
+        EdgeArrays norm = { reinterpret_cast<double *>(d+pl.norm[0]), reinterpret_cast<uint8_t *>(d+pl.norm[1]), reinterpret_cast<uint8_t *>(d+pl.norm[2]) };
+        EdgeArrays fin = norm;
+        ColourTables tables = { NULL, NULL, NULL, NULL, NULL, NULL };
+        if (prep->coloring) {
+            fin.points = reinterpret_cast<double *>(d+pl.fin[0]), fin.types = reinterpret_cast<uint8_t *>(d+pl.fin[1]), fin.colors = reinterpret_cast<uint8_t *>(d+pl.fin[2]);
+            if (big) {
+                tables.cornerMask = reinterpret_cast<unsigned long long *>(d+pl.bigMask), tables.splineColor = reinterpret_cast<unsigned char *>(d+pl.bigSpline);
+                if (prep->coloring == 2) {
+                    tables.edgeLength = reinterpret_cast<double *>(d+pl.bigEdgeLength), tables.cornerLength = reinterpret_cast<double *>(d+pl.bigCornerLength);
+                    tables.cornerIndex = reinterpret_cast<int *>(d+pl.bigCornerIndex), tables.minor = reinterpret_cast<unsigned char *>(d+pl.bigMinor);
+                }
+            }
+        }
+        int32_t *dCo1 = reinterpret_cast<int32_t *>(d+l.co1), *dCo2 = reinterpret_cast<int32_t *>(d+pl.co2);
+        const PrepBuffers pb = { reinterpret_cast<const int32_t *>(d+l.gco), reinterpret_cast<const int32_t *>(d+l.co), dCo1, raw, norm, fin,
+                                 reinterpret_cast<int32_t *>(d+pl.cusp), reinterpret_cast<int32_t *>(d+pl.count), dCo2,
+                                 seeds ? reinterpret_cast<const unsigned long long *>(d+l.seeds) : NULL, tables };
+        int rc = queuePreparation(prep, n, nC, nE1, longest, crossThreshold, pb, stream);
+        if (rc != MSDFHIP_OK)
+            return rc;
+        const int32_t *hFinal = hCo1;                            // without colouring the host knows the final offsets already
+        if (prep->coloring) {
+            // the offsets come back by the word-copy kernel writing into the pinned staging rather than by a copy, which would share the copy engine with
+            // the earlier chunks' tiles (measured the same either way on 8 192 glyphs, tools/stream_raw_bench.py: the wait is the preparation itself)
+            int32_t *hCo2 = reinterpret_cast<int32_t *>(p.pinnedIn+(l.bytes+255)/256*256);
+            rc = uploadSmall(hCo2, dCo2, sizeof(int32_t)*(size_t) (nC+1), stream);
+            if (rc != MSDFHIP_OK)
+                return rc;
+            HIPCHK(hipEventRecord(p.prepCounted, stream));
+            HIPCHK(hipEventSynchronize(p.prepCounted));
+            hFinal = hCo2;
+        }
+        MsdfHipBatch &v = p.view;
+        v.nEdges = hFinal[nC];
+        v.dContourOffsets = prep->coloring ? dCo2 : dCo1;
+        v.dPoints = fin.points, v.dTypes = fin.types, v.dColors = fin.colors;
+        v.dRecs = reinterpret_cast<EdgeRec *>(d+pl.recs), v.dWindings = reinterpret_cast<int8_t *>(d+pl.windings);
+        for (int g = 0; g < n; ++g)
+            v.hEdges[(size_t) g] = hFinal[hGco[g+1]]-hFinal[hGco[g]];
+        return MSDFHIP_OK;
     }
 
     static_assert(PIPE_SLOTS >= 3, "StreamFeeder flattens two chunks ahead of the one being queued: it needs three staging areas");
@@ -2693,12 +2853,14 @@ int msdfhip_batch_generate_bytes_host(const MsdfHipBatch *b, int mode, int w, in
 // msdfhip_batch_create + msdfhip_batch_generate_host run one after the other: flatten all shapes (the caller), upload + digest all, then the chunk
 // pipeline. Here the glyph list is cut into the pipeline's chunks FIRST and every stage works chunk-wise: the host threads flatten chunk k+1 / k+2 from the
 // caller's shape objects straight into pinned staging while chunk k's upload, digest and kernels run and chunk k-1's tiles are copied back.
-int msdfhip_generate_stream(int device, int mode, int w, int h, int n_glyphs, const MsdfHipShapeSource *source, const MsdfHipGlyph *glyphs, float *out,
-                            size_t out_floats, uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg) {
+// prep != NULL (msdfhip_generate_stream_prepared): the source delivers RAW outlines, each chunk is prepared on the device on its own stream.
+static int generateStream(const char *who, int device, int mode, int w, int h, int n_glyphs, const MsdfHipShapeSource *source, const MsdfHipGlyph *glyphs,
+                          float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg,
+                          const MsdfHipPrepConfig *prep, const uint64_t *seeds) {
     if (!source || !source->count || !source->fill || n_glyphs < 0 || (!out) == (!atlas) || (n_glyphs > 0 && !glyphs))
-        return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_generate_stream (a shape source with count and fill, exactly one of out / atlas)");
+        return fail(MSDFHIP_ERR_INVALID, "bad arguments to %s (a shape source with count and fill, exactly one of out / atlas)", who);
     if (atlas && stencil)
-        return fail(MSDFHIP_ERR_INVALID, "msdfhip_generate_stream: a stencil buffer only goes with float output");
+        return fail(MSDFHIP_ERR_INVALID, "%s: a stencil buffer only goes with float output", who);
     if (n_glyphs == 0)
         return MSDFHIP_OK;
     if (device >= 0) {
@@ -2712,11 +2874,27 @@ int msdfhip_generate_stream(int device, int mode, int w, int h, int n_glyphs, co
     int rc = ensureDevice(device);
     if (rc != MSDFHIP_OK)
         return rc;
-    StreamFeeder feeder(source, n_glyphs);
+    StreamFeeder feeder(source, n_glyphs, prep, seeds);
     rc = feeder.count();
     if (rc != MSDFHIP_OK)
         return rc;
     return runPipeline(NULL, &feeder, currentDevice(), n_glyphs, mode, w, h, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg);
+}
+
+int msdfhip_generate_stream(int device, int mode, int w, int h, int n_glyphs, const MsdfHipShapeSource *source, const MsdfHipGlyph *glyphs, float *out,
+                            size_t out_floats, uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg) {
+    return generateStream("msdfhip_generate_stream", device, mode, w, h, n_glyphs, source, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg, NULL, NULL);
+}
+
+// Raw outlines in: the chunk pipeline above with the device's shape preparation (msdfhip_batch_create_prepared's sequence) between each chunk's upload and
+// its digest, on the chunk's stream.
+int msdfhip_generate_stream_prepared(int device, int mode, int w, int h, int n_glyphs, const MsdfHipShapeSource *source, const MsdfHipGlyph *glyphs, float *out,
+                                     size_t out_floats, uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg,
+                                     const MsdfHipPrepConfig *prep, const uint64_t *seeds) {
+    const int rc = checkPrepConfig(prep, "msdfhip_generate_stream_prepared");
+    if (rc != MSDFHIP_OK)
+        return rc;
+    return generateStream("msdfhip_generate_stream_prepared", device, mode, w, h, n_glyphs, source, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg, prep, seeds);
 }
 
 namespace {
@@ -2735,7 +2913,10 @@ struct CsrSource {                                               // a shape sour
             contourEnd[c-c0] = edgeBase+(s.co[c+1]-e0);
         memcpy(points, s.points+(size_t) e0*8, (size_t) nE*8*sizeof(double));
         memcpy(types, s.types+e0, (size_t) nE);
-        memcpy(colors, s.colors+e0, (size_t) nE);
+        if (s.colors)
+            memcpy(colors, s.colors+e0, (size_t) nE);
+        else
+            memset(colors, 7, (size_t) nE);                      // (raw outlines without colours: WHITE)
     }
 };
 }
@@ -2751,6 +2932,23 @@ int msdfhip_generate_stream_csr(int device, int mode, int w, int h, int n_glyphs
     CsrSource csr = { gco, co, points, types, colors };
     MsdfHipShapeSource source = { &csr, CsrSource::count, CsrSource::fill };
     return msdfhip_generate_stream(device, mode, w, h, n_glyphs, &source, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg);
+}
+
+int msdfhip_generate_stream_csr_prepared(int device, int mode, int w, int h, int n_glyphs, const int32_t *gco, const int32_t *co, const double *points,
+                                         const uint8_t *types, const uint8_t *colors, const MsdfHipGlyph *glyphs, float *out, size_t out_floats, uint8_t *atlas,
+                                         size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep, const uint64_t *seeds) {
+    int rc = checkPrepConfig(prep, "msdfhip_generate_stream_csr_prepared");
+    if (rc != MSDFHIP_OK)
+        return rc;
+    std::vector<int> hc, he;
+    int maxC = 0, maxE = 0;
+    rc = checkShapeArrays(n_glyphs, gco, co, points, types, colors, false, hc, he, maxC, maxE);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    CsrSource csr = { gco, co, points, types, colors };
+    MsdfHipShapeSource source = { &csr, CsrSource::count, CsrSource::fill };
+    return generateStream("msdfhip_generate_stream_csr_prepared", device, mode, w, h, n_glyphs, &source, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg,
+                          prep, seeds);
 }
 
 int msdfhip_set_host_threads(int threads) {
@@ -2984,6 +3182,8 @@ static void destroyPipe(Pipe *p) {
         hipFree(s.devIn);
         if (s.inputsUploaded)
             hipEventDestroy(s.inputsUploaded);
+        if (s.prepCounted)
+            hipEventDestroy(s.prepCounted);
         if (s.done)
             hipEventDestroy(s.done);
         if (s.kernelsDone)

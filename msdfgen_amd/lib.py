@@ -108,6 +108,10 @@ _PROTOS = {
     "msdfhip_generate_stream": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.POINTER(Config)]),
     "msdfhip_generate_stream_csr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _bp, _bp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp,
                                               C.POINTER(Config)]),
+    "msdfhip_generate_stream_prepared": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.POINTER(Config),
+                                                   C.POINTER(PrepConfig), C.POINTER(C.c_uint64)]),
+    "msdfhip_generate_stream_csr_prepared": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _bp, _bp, _vp, _vp, C.c_size_t, _vp, C.c_size_t,
+                                                       _vp, C.POINTER(Config), C.POINTER(PrepConfig), C.POINTER(C.c_uint64)]),
     "msdfhip_set_host_threads": (C.c_int, [C.c_int]),
     "msdfhip_single_call_fallbacks": (C.c_int, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_int]),
 }
