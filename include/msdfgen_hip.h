@@ -308,6 +308,28 @@ int msdfhip_generate_stream_csr_prepared(int device, int mode, int width, int he
                                          const int32_t *contour_offsets, const double *points, const uint8_t *types, const uint8_t *colors,
                                          const MsdfHipGlyph *glyphs, float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes,
                                          uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep, const uint64_t *seeds);
+/* Orientation around the preparation above, in the reference CLI's order:
+ *   orient_contours  1: Shape::orientContours (core/Shape.cpp:144-198) on the raw outline, before normalize (main.cpp:1105-1111, -windingpreprocess)
+ *   winding          after normalize, before the colouring (main.cpp:1131-1143): 0 keep, 1 reverse every contour (-reversewinding),
+ *                    2 reverse every contour when the true distance at a point outside Shape::getBounds is positive (-guesswinding)
+ * The _oriented entry points are their twins above plus `orient`; NULL means keep (what the twins do). Edge and contour counts do not change.
+ * orient_contours outside 0..1 or winding outside 0..2 fail with MSDFHIP_ERR_INVALID before the shape source is read or the device is touched. */
+typedef struct MsdfHipOrientConfig {
+    int32_t orient_contours;
+    int32_t winding;              /* 0 keep, 1 reverse, 2 guess */
+} MsdfHipOrientConfig;
+int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, const int32_t *glyph_contour_offsets, const int32_t *contour_offsets,
+                                           const double *points, const uint8_t *types, const uint8_t *colors, const uint64_t *seeds,
+                                           const MsdfHipPrepConfig *cfg, const MsdfHipOrientConfig *orient);
+int msdfhip_generate_stream_prepared_oriented(int device, int mode, int width, int height, int n_glyphs, const MsdfHipShapeSource *source,
+                                              const MsdfHipGlyph *glyphs, float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes,
+                                              uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep, const uint64_t *seeds,
+                                              const MsdfHipOrientConfig *orient);
+int msdfhip_generate_stream_csr_prepared_oriented(int device, int mode, int width, int height, int n_glyphs, const int32_t *glyph_contour_offsets,
+                                                  const int32_t *contour_offsets, const double *points, const uint8_t *types, const uint8_t *colors,
+                                                  const MsdfHipGlyph *glyphs, float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes,
+                                                  uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep, const uint64_t *seeds,
+                                                  const MsdfHipOrientConfig *orient);
 /* Diagnostics: after an error-correction pass, counts[0] = 1 if some glyph's candidate segment overflowed (those glyphs were redone by
  * the full per-texel pipeline), counts[1+g] = deferred distance checks pushed for glyph g. counts holds n_glyphs+1 entries. */
 int msdfhip_batch_candidate_counts(const MsdfHipBatch *batch, uint32_t *counts);

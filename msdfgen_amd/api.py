@@ -100,17 +100,27 @@ class MSDFGeneratorConfig(GeneratorConfig):
     _stage_limit: int = 0  # test hook: stop the stencil pipeline after stage k (see MsdfHipConfig.ec_stage_limit)
 
 
+WINDING_KEEP, WINDING_REVERSE, WINDING_GUESS = 0, 1, 2     # MsdfHipOrientConfig.winding: the reference CLI's -reversewinding / -guesswinding
+
+
 @dataclass
 class PrepareConfig:
-    """Shape preparation of raw outlines on the device (msdfgen_hip.h, MsdfHipPrepConfig): Shape::normalize (core/Shape.cpp:65-92) and
-    edgeColoringSimple (coloring=1, core/edge-coloring.cpp:68-142) or edgeColoringInkTrap (coloring=2, :151-258); coloring=0 keeps the colours."""
+    """Shape preparation of raw outlines on the device (msdfgen_hip.h, MsdfHipPrepConfig + MsdfHipOrientConfig), in the reference CLI's order:
+    Shape::orientContours (orient_contours, core/Shape.cpp:144-198), Shape::normalize (core/Shape.cpp:65-92), the winding step (winding: WINDING_KEEP,
+    WINDING_REVERSE every contour, or WINDING_GUESS from the true distance outside the bounds, main.cpp:1131-1143), then edgeColoringSimple
+    (coloring=1, core/edge-coloring.cpp:68-142) or edgeColoringInkTrap (coloring=2, :151-258); coloring=0 keeps the colours."""
     normalize: bool = True
     coloring: int = 1
     angle_threshold: float = 3.0
     seed: int = 0
+    orient_contours: bool = False
+    winding: int = WINDING_KEEP
 
     def c_struct(self) -> _lib.PrepConfig:
         return _lib.PrepConfig(int(bool(self.normalize)), int(self.coloring), float(self.angle_threshold), int(self.seed))
+
+    def c_orient(self) -> _lib.OrientConfig:
+        return _lib.OrientConfig(int(bool(self.orient_contours)), int(self.winding))
 
 
 def _c_config(config, y_orientation=None) -> _lib.Config:
@@ -355,9 +365,11 @@ class GlyphBatch:
         self._glyph_cache = {}
 
     @classmethod
-    def from_raw(cls, raw: ShapeBatch, normalize=True, coloring=1, angle_threshold=3.0, seeds=None, seed=0, device=None):
+    def from_raw(cls, raw: ShapeBatch, normalize=True, coloring=1, angle_threshold=3.0, seeds=None, seed=0, device=None, orient_contours=False,
+                 winding=WINDING_KEEP):
         """Uploads RAW outlines and prepares them on the device: Shape::normalize (core/Shape.cpp:65-92) and edgeColoringSimple
-        (coloring=1, core/edge-coloring.cpp:68-142) or edgeColoringInkTrap (coloring=2, :151-258) with (angle_threshold, seed; `seeds`: one per glyph). The prepared
+        (coloring=1, core/edge-coloring.cpp:68-142) or edgeColoringInkTrap (coloring=2, :151-258) with (angle_threshold, seed; `seeds`: one per glyph);
+        orient_contours: Shape::orientContours first; winding: WINDING_REVERSE / WINDING_GUESS after normalize (PrepareConfig). The prepared
         shapes are read back once into `.shapes` (they are small); the batch is digested and ready for generate()."""
         import torch
         if not torch.cuda.is_available():
@@ -374,10 +386,11 @@ class GlyphBatch:
         colors = np.ascontiguousarray(raw.colors, np.uint8)
         sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint64)
         cfg = _lib.PrepConfig(int(bool(normalize)), int(coloring), float(angle_threshold), int(seed))
+        orient = _lib.OrientConfig(int(bool(orient_contours)), int(winding))
         self._handle = C.c_void_p()
-        _lib.check(lib.msdfhip_batch_create_prepared(C.byref(self._handle), raw.n_glyphs, _lib.ptr(gco, _lib._ip), _lib.ptr(co, _lib._ip), _lib.ptr(pts, _lib._dp),
-                                                     _lib.ptr(types, _lib._bp), _lib.ptr(colors, _lib._bp),
-                                                     sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None, C.byref(cfg)))
+        _lib.check(lib.msdfhip_batch_create_prepared_oriented(C.byref(self._handle), raw.n_glyphs, _lib.ptr(gco, _lib._ip), _lib.ptr(co, _lib._ip),
+                                                              _lib.ptr(pts, _lib._dp), _lib.ptr(types, _lib._bp), _lib.ptr(colors, _lib._bp),
+                                                              sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None, C.byref(cfg), C.byref(orient)))
         ng, nc, ne, mc, me = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
         _lib.check(lib.msdfhip_batch_info(self._handle, C.byref(ng), C.byref(nc), C.byref(ne), C.byref(mc), C.byref(me)))
         co2 = np.zeros(nc.value+1, np.int32)
@@ -621,7 +634,8 @@ def generate_stream(shapes: ShapeBatch, mode, width, height, xfs, out=None, atla
     into chunks and chunk k+1's staging + upload + digest run under chunk k's kernels and chunk k-1's copy back (SURVEY.md 8d's end-to-end metric;
     msdfgen_hip::generate*Batch() of the C++ shim is the same pipeline fed from msdfgen::Shape objects).
     prepare: `shapes` are RAW outlines, prepared on the device chunk by chunk inside the pipeline (msdfhip_generate_stream_csr_prepared) -- the same
-    bytes as GlyphBatch.from_raw(shapes, normalize, coloring, angle_threshold, seeds=seeds, seed=seed) followed by generate(); `seeds`: one per glyph."""
+    bytes as GlyphBatch.from_raw(shapes, normalize, coloring, angle_threshold, seeds=seeds, seed=seed, orient_contours=orient_contours, winding=winding)
+    followed by generate(); `seeds`: one per glyph."""
     n = CHANNELS[mode]
     tile = width*height*n
     if out is None and atlas is None:
@@ -637,15 +651,14 @@ def generate_stream(shapes: ShapeBatch, mode, width, height, xfs, out=None, atla
     if stencil is not None:
         assert stencil.dtype == np.uint8 and stencil.flags.c_contiguous and stencil.size >= shapes.n_glyphs*width*height
     if prepare is not None:
-        pc = prepare.c_struct()
+        pc, po = prepare.c_struct(), prepare.c_orient()
         sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint64)
         assert sd is None or sd.size == shapes.n_glyphs
-        _lib.check(_lib.load().msdfhip_generate_stream_csr_prepared(int(device), mode, width, height, shapes.n_glyphs, _lib.ptr(gco, _lib._ip), _lib.ptr(co, _lib._ip),
-                                                                    _lib.ptr(pts, _lib._dp), _lib.ptr(types, _lib._bp), _lib.ptr(colors, _lib._bp), d.ctypes.data,
-                                                                    out.ctypes.data if out is not None else None, out.size if out is not None else 0,
-                                                                    atlas.ctypes.data if atlas is not None else None, atlas.size if atlas is not None else 0,
-                                                                    stencil.ctypes.data if stencil is not None else None, C.byref(cfg), C.byref(pc),
-                                                                    sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None))
+        _lib.check(_lib.load().msdfhip_generate_stream_csr_prepared_oriented(
+            int(device), mode, width, height, shapes.n_glyphs, _lib.ptr(gco, _lib._ip), _lib.ptr(co, _lib._ip), _lib.ptr(pts, _lib._dp), _lib.ptr(types, _lib._bp),
+            _lib.ptr(colors, _lib._bp), d.ctypes.data, out.ctypes.data if out is not None else None, out.size if out is not None else 0,
+            atlas.ctypes.data if atlas is not None else None, atlas.size if atlas is not None else 0, stencil.ctypes.data if stencil is not None else None,
+            C.byref(cfg), C.byref(pc), sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None, C.byref(po)))
         return out if out is not None else atlas
     _lib.check(_lib.load().msdfhip_generate_stream_csr(int(device), mode, width, height, shapes.n_glyphs, _lib.ptr(gco, _lib._ip), _lib.ptr(co, _lib._ip),
                                                        _lib.ptr(pts, _lib._dp), _lib.ptr(types, _lib._bp), _lib.ptr(colors, _lib._bp), d.ctypes.data,

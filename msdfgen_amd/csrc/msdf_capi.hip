@@ -1449,17 +1449,29 @@ struct PrepBuffers {
     int32_t *cusp, *count, *co2;          // [nC+1] each: normalize's cusp flags; coloured edges per contour and their prefix (coloring != 0 only)
     const unsigned long long *seeds;      // one per glyph, or NULL: cfg->seed for every glyph
     ColourTables big;                     // the colouring's tables of contours beyond PREP_WAVE_MAX_EDGES (only when `longest` exceeds it)
+    int32_t *votes;                       // [nC] orientContours' votes of glyphs beyond PREP_ORIENT_LDS_CONTOURS contours (orient_contours only)
+    double *hitX;                         // [3 nE] + hitTag: scanline hits beyond PREP_ORIENT_LDS_HITS (only when orientHitsBig: see prepOrientScratch)
+    int32_t *hitTag;
 };
 
-// Shape preparation (row f3) as ONE queued sequence on `stream`: normalize (k_prep_normalize_flat + the cusp repair), then with coloring the coloured
-// counts, their prefix and the colouring wave. Never allocates, never waits: msdfhip_batch_create_prepared runs it on the null stream, the streamed
+// Does a glyph of maxRawEdges raw edges need k_prep_orient's global hit scratch (3 hits per edge at most)?
+bool orientHitsBig(long long maxRawEdges) { return 3*maxRawEdges > PREP_ORIENT_LDS_HITS; }
+
+// Shape preparation (row f3) as ONE queued sequence on `stream`, in the reference CLI's order: orientContours on the raw edges (orient.orient_contours),
+// normalize (k_prep_normalize_flat + the cusp repair), the winding step on the normalized edges (orient.winding), then with coloring the coloured
+// counts, their prefix and the colouring wave. Orientation changes no count, so the offsets and bounds below do not depend on it. Never allocates, never waits: msdfhip_batch_create_prepared runs it on the null stream, the streamed
 // generator on each chunk's stream under the kernels of the chunks before it. With coloring the result is fin + co2, else norm + co1.
-int queuePreparation(const MsdfHipPrepConfig *cfg, int nGlyphs, int nC, int nE1, int longest, double crossThreshold, const PrepBuffers &pb, hipStream_t stream) {
+int queuePreparation(const MsdfHipPrepConfig *cfg, const MsdfHipOrientConfig &orient, int nGlyphs, int nC, int nE1, int longest, double crossThreshold,
+                      const PrepBuffers &pb, hipStream_t stream) {
+    if (nE1 && orient.orient_contours)                              // Shape::orientContours on the raw edges, in place (main.cpp:1105-1111)
+        hipLaunchKernelGGL(k_prep_orient, dim3((unsigned) nGlyphs), dim3(WAVE), 0, stream, pb.raw, pb.gco, pb.co, nGlyphs, pb.votes, pb.hitX, pb.hitTag);
     if (nE1) {
         HIPCHK(hipMemsetAsync(pb.cusp, 0, sizeof(int32_t)*(size_t) (nC+1), stream));
         hipLaunchKernelGGL(k_prep_normalize_flat, dim3((nE1+255)/256), dim3(256), 0, stream, pb.raw, pb.co, pb.co1, nC, nE1, cfg->normalize ? 1 : 0, pb.norm, pb.cusp);
         if (cfg->normalize)
             hipLaunchKernelGGL(k_prep_normalize_cusps, dim3((nC+127)/128), dim3(128), 0, stream, pb.raw, pb.co, pb.co1, nC, pb.norm, (const int32_t *) pb.cusp);
+        if (orient.winding)                                         // -reversewinding / -guesswinding on the normalized edges, in place (main.cpp:1131-1143)
+            hipLaunchKernelGGL(k_prep_winding, dim3((unsigned) nGlyphs), dim3(WAVE), 0, stream, pb.norm, pb.gco, pb.co1, nGlyphs, (int) orient.winding);
     }
     if (cfg->coloring) {
         if (nC)
@@ -1489,20 +1501,43 @@ int checkPrepConfig(const MsdfHipPrepConfig *cfg, const char *who) {
     return MSDFHIP_OK;
 }
 
+// NULL orient: keep (the v5 entry points). The checked value is returned in *out.
+int checkOrientConfig(const MsdfHipOrientConfig *orient, const char *who, MsdfHipOrientConfig *out) {
+    out->orient_contours = 0, out->winding = 0;
+    if (!orient)
+        return MSDFHIP_OK;
+    if (orient->orient_contours < 0 || orient->orient_contours > 1)
+        return fail(MSDFHIP_ERR_INVALID, "%s: orient_contours %d (0 or 1)", who, orient->orient_contours);
+    if (orient->winding < 0 || orient->winding > 2)
+        return fail(MSDFHIP_ERR_INVALID, "%s: winding %d (0 keep, 1 reverse, 2 guess)", who, orient->winding);
+    *out = *orient;
+    return MSDFHIP_OK;
+}
+
 } // namespace
 
 extern "C" {
 
 int msdfhip_batch_create_prepared(MsdfHipBatch **batch, int n_glyphs, const int32_t *gco, const int32_t *co, const double *points, const uint8_t *types,
                                   const uint8_t *colors, const uint64_t *seeds, const MsdfHipPrepConfig *cfg) {
+    return msdfhip_batch_create_prepared_oriented(batch, n_glyphs, gco, co, points, types, colors, seeds, cfg, NULL);
+}
+
+int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, const int32_t *gco, const int32_t *co, const double *points, const uint8_t *types,
+                                           const uint8_t *colors, const uint64_t *seeds, const MsdfHipPrepConfig *cfg, const MsdfHipOrientConfig *orientCfg) {
     if (!batch || n_glyphs < 0 || !gco || !co || !cfg)
         return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_batch_create_prepared");
     if (cfg->coloring < 0 || cfg->coloring > 2)
         return fail(MSDFHIP_ERR_INVALID, "coloring %d (0 keep, 1 edgeColoringSimple, 2 edgeColoringInkTrap)", cfg->coloring);
+    MsdfHipOrientConfig orient;
+    int rco = checkOrientConfig(orientCfg, "msdfhip_batch_create_prepared_oriented", &orient);
+    if (rco != MSDFHIP_OK)
+        return rco;
+    int maxRawEdges = 0;
     {
         std::vector<int> hc, he;
-        int mc = 0, me = 0;
-        int rcv = checkShapeArrays(n_glyphs, gco, co, points, types, colors, false, hc, he, mc, me);
+        int mc = 0;
+        int rcv = checkShapeArrays(n_glyphs, gco, co, points, types, colors, false, hc, he, mc, maxRawEdges);
         if (rcv != MSDFHIP_OK)
             return rcv;
     }
@@ -1526,7 +1561,8 @@ int msdfhip_batch_create_prepared(MsdfHipBatch **batch, int n_glyphs, const int3
         void release(void *p) { for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { ptrs.erase(ptrs.begin()+i); break; } }
     } dev;
     #define PREP_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(MSDFHIP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
-    int32_t *dGco = NULL, *dCo = NULL, *dCo1 = NULL, *dCo2 = NULL, *dCount = NULL, *dCusp = NULL;
+    int32_t *dGco = NULL, *dCo = NULL, *dCo1 = NULL, *dCo2 = NULL, *dCount = NULL, *dCusp = NULL, *dVotes = NULL, *dHitTag = NULL;
+    double *dHitX = NULL;
     unsigned long long *dSeeds = NULL;
     EdgeArrays raw = { NULL, NULL, NULL }, norm = { NULL, NULL, NULL }, fin = { NULL, NULL, NULL };
     ColourTables big = { NULL, NULL, NULL, NULL, NULL, NULL };
@@ -1575,9 +1611,16 @@ int msdfhip_batch_create_prepared(MsdfHipBatch **batch, int n_glyphs, const int3
         }
     } else
         fin = norm;
+    if (orient.orient_contours) {                                 // orientContours' scratch: votes of glyphs with many contours, hits beyond the LDS tier
+        PREP_CHK(dev.alloc((void **) &dVotes, sizeof(int32_t)*(size_t) (nC+1)));
+        if (orientHitsBig(maxRawEdges)) {
+            PREP_CHK(dev.alloc((void **) &dHitX, sizeof(double)*3*eRaw));
+            PREP_CHK(dev.alloc((void **) &dHitTag, sizeof(int32_t)*3*eRaw));
+        }
+    }
     // Every pass is queued without a host round trip; the coloured offsets come back once, at the end.
-    const PrepBuffers pb = { dGco, dCo, dCo1, raw, norm, fin, dCusp, dCount, dCo2, dSeeds, big };
-    rc = queuePreparation(cfg, n_glyphs, nC, nE1, longest, crossThreshold, pb, 0);
+    const PrepBuffers pb = { dGco, dCo, dCo1, raw, norm, fin, dCusp, dCount, dCo2, dSeeds, big, dVotes, dHitX, dHitTag };
+    rc = queuePreparation(cfg, orient, n_glyphs, nC, nE1, longest, crossThreshold, pb, 0);
     if (rc != MSDFHIP_OK)
         return rc;
     const int32_t *finalCo = co1.data();
@@ -2182,12 +2225,16 @@ struct StreamFeeder : ChunkFeeder {
     // from the same staging the prepared form uses plus the host's normalized contour offsets (and the chunk's seeds) behind it.
     const MsdfHipPrepConfig *prep;                               // NULL: the shapes are prepared already
     const uint64_t *seeds;                                       // one per glyph of the whole list, or NULL (prep->seed)
+    MsdfHipOrientConfig orient;                                  // orientation around the preparation (checked; all 0: keep)
     double crossThreshold;                                       // sin(angle_threshold), by the host's libm (edge-coloring.cpp:69)
     std::vector<char> mayHaveLong;                               // per chunk: a glyph whose normalized contours could exceed PREP_WAVE_MAX_EDGES (the `big` tables)
     enum { GRAIN = 32 };                                         // glyphs per flatten item
 
-    StreamFeeder(const MsdfHipShapeSource *source, int n, const MsdfHipPrepConfig *prepCfg = NULL, const uint64_t *glyphSeeds = NULL)
-        : src(source), nG(n), slots(NULL), prep(prepCfg), seeds(glyphSeeds), crossThreshold(prepCfg && prepCfg->coloring ? sin(prepCfg->angle_threshold) : 0.) { }
+    StreamFeeder(const MsdfHipShapeSource *source, int n, const MsdfHipPrepConfig *prepCfg = NULL, const uint64_t *glyphSeeds = NULL,
+                 const MsdfHipOrientConfig *orientCfg = NULL)
+        : src(source), nG(n), slots(NULL), prep(prepCfg), seeds(glyphSeeds), crossThreshold(prepCfg && prepCfg->coloring ? sin(prepCfg->angle_threshold) : 0.) {
+        orient.orient_contours = orientCfg ? orientCfg->orient_contours : 0, orient.winding = orientCfg ? orientCfg->winding : 0;
+    }
     ~StreamFeeder() { drain(); }
 
     // The flatten jobs run on the detached pool threads, capture `this`, call the caller's fill callbacks and write into the leased pipe's pinned staging:
@@ -2240,8 +2287,10 @@ struct StreamFeeder : ChunkFeeder {
     // (raw outlines) the device-only part of a chunk's input area behind the uploaded part: the preparation's buffers, then the records + windings of
     // the PREPARED edges. nE1 / nE2: normalized / coloured edge counts. begin() sizes the slots with their bounds (nE + 2 nC, nE + 4 nC: a raw contour of
     // one edge becomes three, one of two edges at most six), a chunk carves its exact counts -- the same pieces in the same order, so never beyond.
-    struct PrepLayout { size_t cusp, count, co2, norm[3], fin[3], bigMask, bigSpline, bigEdgeLength, bigCornerLength, bigCornerIndex, bigMinor, recs, windings, bytes; };
-    PrepLayout prepLayout(size_t at, size_t nC, size_t nE1, size_t nE2, bool big) const {
+    // With orient_contours: the votes (nC) and, when a glyph of the chunk can overflow k_prep_orient's LDS (hitsBig), 3 hits per raw edge (nE).
+    struct PrepLayout { size_t cusp, count, co2, norm[3], fin[3], bigMask, bigSpline, bigEdgeLength, bigCornerLength, bigCornerIndex, bigMinor, votes, hitX, hitTag,
+                        recs, windings, bytes; };
+    PrepLayout prepLayout(size_t at, size_t nC, size_t nE, size_t nE1, size_t nE2, bool big, bool hitsBig) const {
         Carver c;
         c.off = (at+255)/256*256;
         PrepLayout l = PrepLayout();
@@ -2255,6 +2304,11 @@ struct StreamFeeder : ChunkFeeder {
                 if (prep->coloring == 2)
                     l.bigEdgeLength = c.take(sizeof(double)*e1), l.bigCornerLength = c.take(sizeof(double)*e1), l.bigCornerIndex = c.take(sizeof(int)*e1), l.bigMinor = c.take(e1);
             }
+        }
+        if (orient.orient_contours) {
+            l.votes = c.take((nC+1)*sizeof(int32_t));
+            if (hitsBig)
+                l.hitX = c.take(3*(nE ? nE : 1)*sizeof(double)), l.hitTag = c.take(3*(nE ? nE : 1)*sizeof(int32_t));
         }
         l.recs = c.take(sizeof(EdgeRec)*(prep->coloring ? e2 : e1)), l.windings = c.take(nC ? nC : 1), l.bytes = c.off;
         return l;
@@ -2310,9 +2364,13 @@ struct StreamFeeder : ChunkFeeder {
             const Layout l = layout((size_t) lengths[ci], nC, nE);
             needIn = l.bytes > needIn ? l.bytes : needIn, needC = nC > needC ? nC : needC, needE = nE > needE ? nE : needE;
             if (prep) {                                          // + the coloured offsets coming back behind the staging; the preparation's buffers
-                for (int k = g; k < g+lengths[ci]; ++k)
+                int maxRaw = 0;
+                for (int k = g; k < g+lengths[ci]; ++k) {
                     mayHaveLong[ci] |= (long long) hEdges[(size_t) k]+2LL*hContours[(size_t) k] > PREP_WAVE_MAX_EDGES;
-                const size_t pin = (l.bytes+255)/256*256+(nC+1)*sizeof(int32_t), dev = prepLayout(l.bytes, nC, nE+2*nC, nE+4*nC, mayHaveLong[ci] != 0).bytes;
+                    maxRaw = hEdges[(size_t) k] > maxRaw ? hEdges[(size_t) k] : maxRaw;
+                }
+                const size_t pin = (l.bytes+255)/256*256+(nC+1)*sizeof(int32_t);
+                const size_t dev = prepLayout(l.bytes, nC, nE, nE+2*nC, nE+4*nC, mayHaveLong[ci] != 0, orientHitsBig(maxRaw)).bytes;
                 prepPinned = pin > prepPinned ? pin : prepPinned, prepDev = dev > prepDev ? dev : prepDev;
             }
         }
@@ -2419,7 +2477,11 @@ struct StreamFeeder : ChunkFeeder {
         const int32_t *hCo1 = reinterpret_cast<const int32_t *>(p.pinnedIn+l.co1), *hGco = reinterpret_cast<const int32_t *>(p.pinnedIn+l.gco);
         const int nE1 = hCo1[nC];
         const bool big = longest > PREP_WAVE_MAX_EDGES;
-        const PrepLayout pl = prepLayout(l.bytes, (size_t) nC, (size_t) nE1, bound2, big);
+        int maxRaw = 0;                                          // (p.view.hEdges: still the raw counts)
+        for (int g = 0; g < n; ++g)
+            maxRaw = p.view.hEdges[(size_t) g] > maxRaw ? p.view.hEdges[(size_t) g] : maxRaw;
+        const bool hitsBig = orient.orient_contours && orientHitsBig(maxRaw);
+        const PrepLayout pl = prepLayout(l.bytes, (size_t) nC, (size_t) reinterpret_cast<const int32_t *>(p.pinnedIn+l.co)[nC], (size_t) nE1, bound2, big, hitsBig);
         EdgeArrays raw = { reinterpret_cast<double *>(d+l.points), reinterpret_cast<uint8_t *>(d+l.types), reinterpret_cast<uint8_t *>(d+l.colors) };
         EdgeArrays norm = { reinterpret_cast<double *>(d+pl.norm[0]), reinterpret_cast<uint8_t *>(d+pl.norm[1]), reinterpret_cast<uint8_t *>(d+pl.norm[2]) };
         EdgeArrays fin = norm;
@@ -2437,8 +2499,10 @@ struct StreamFeeder : ChunkFeeder {
         int32_t *dCo1 = reinterpret_cast<int32_t *>(d+l.co1), *dCo2 = reinterpret_cast<int32_t *>(d+pl.co2);
         const PrepBuffers pb = { reinterpret_cast<const int32_t *>(d+l.gco), reinterpret_cast<const int32_t *>(d+l.co), dCo1, raw, norm, fin,
                                  reinterpret_cast<int32_t *>(d+pl.cusp), reinterpret_cast<int32_t *>(d+pl.count), dCo2,
-                                 seeds ? reinterpret_cast<const unsigned long long *>(d+l.seeds) : NULL, tables };
-        int rc = queuePreparation(prep, n, nC, nE1, longest, crossThreshold, pb, stream);
+                                 seeds ? reinterpret_cast<const unsigned long long *>(d+l.seeds) : NULL, tables,
+                                 orient.orient_contours ? reinterpret_cast<int32_t *>(d+pl.votes) : NULL,
+                                 hitsBig ? reinterpret_cast<double *>(d+pl.hitX) : NULL, hitsBig ? reinterpret_cast<int32_t *>(d+pl.hitTag) : NULL };
+        int rc = queuePreparation(prep, orient, n, nC, nE1, longest, crossThreshold, pb, stream);
         if (rc != MSDFHIP_OK)
             return rc;
         const int32_t *hFinal = hCo1;                            // without colouring the host knows the final offsets already
@@ -2856,7 +2920,7 @@ int msdfhip_batch_generate_bytes_host(const MsdfHipBatch *b, int mode, int w, in
 // prep != NULL (msdfhip_generate_stream_prepared): the source delivers RAW outlines, each chunk is prepared on the device on its own stream.
 static int generateStream(const char *who, int device, int mode, int w, int h, int n_glyphs, const MsdfHipShapeSource *source, const MsdfHipGlyph *glyphs,
                           float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg,
-                          const MsdfHipPrepConfig *prep, const uint64_t *seeds) {
+                          const MsdfHipPrepConfig *prep, const uint64_t *seeds, const MsdfHipOrientConfig *orient = NULL) {
     if (!source || !source->count || !source->fill || n_glyphs < 0 || (!out) == (!atlas) || (n_glyphs > 0 && !glyphs))
         return fail(MSDFHIP_ERR_INVALID, "bad arguments to %s (a shape source with count and fill, exactly one of out / atlas)", who);
     if (atlas && stencil)
@@ -2874,7 +2938,7 @@ static int generateStream(const char *who, int device, int mode, int w, int h, i
     int rc = ensureDevice(device);
     if (rc != MSDFHIP_OK)
         return rc;
-    StreamFeeder feeder(source, n_glyphs, prep, seeds);
+    StreamFeeder feeder(source, n_glyphs, prep, seeds, orient);
     rc = feeder.count();
     if (rc != MSDFHIP_OK)
         return rc;
@@ -2891,10 +2955,22 @@ int msdfhip_generate_stream(int device, int mode, int w, int h, int n_glyphs, co
 int msdfhip_generate_stream_prepared(int device, int mode, int w, int h, int n_glyphs, const MsdfHipShapeSource *source, const MsdfHipGlyph *glyphs, float *out,
                                      size_t out_floats, uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg,
                                      const MsdfHipPrepConfig *prep, const uint64_t *seeds) {
-    const int rc = checkPrepConfig(prep, "msdfhip_generate_stream_prepared");
+    return msdfhip_generate_stream_prepared_oriented(device, mode, w, h, n_glyphs, source, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg, prep, seeds, NULL);
+}
+
+// + orientation around the preparation (orient NULL: keep); checked before the source is read.
+int msdfhip_generate_stream_prepared_oriented(int device, int mode, int w, int h, int n_glyphs, const MsdfHipShapeSource *source, const MsdfHipGlyph *glyphs,
+                                              float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg,
+                                              const MsdfHipPrepConfig *prep, const uint64_t *seeds, const MsdfHipOrientConfig *orient) {
+    int rc = checkPrepConfig(prep, "msdfhip_generate_stream_prepared");
     if (rc != MSDFHIP_OK)
         return rc;
-    return generateStream("msdfhip_generate_stream_prepared", device, mode, w, h, n_glyphs, source, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg, prep, seeds);
+    MsdfHipOrientConfig o;
+    rc = checkOrientConfig(orient, "msdfhip_generate_stream_prepared_oriented", &o);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    return generateStream("msdfhip_generate_stream_prepared", device, mode, w, h, n_glyphs, source, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg, prep, seeds,
+                          &o);
 }
 
 namespace {
@@ -2937,7 +3013,19 @@ int msdfhip_generate_stream_csr(int device, int mode, int w, int h, int n_glyphs
 int msdfhip_generate_stream_csr_prepared(int device, int mode, int w, int h, int n_glyphs, const int32_t *gco, const int32_t *co, const double *points,
                                          const uint8_t *types, const uint8_t *colors, const MsdfHipGlyph *glyphs, float *out, size_t out_floats, uint8_t *atlas,
                                          size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep, const uint64_t *seeds) {
+    return msdfhip_generate_stream_csr_prepared_oriented(device, mode, w, h, n_glyphs, gco, co, points, types, colors, glyphs, out, out_floats, atlas, atlas_bytes,
+                                                         stencil, cfg, prep, seeds, NULL);
+}
+
+int msdfhip_generate_stream_csr_prepared_oriented(int device, int mode, int w, int h, int n_glyphs, const int32_t *gco, const int32_t *co, const double *points,
+                                                  const uint8_t *types, const uint8_t *colors, const MsdfHipGlyph *glyphs, float *out, size_t out_floats,
+                                                  uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep,
+                                                  const uint64_t *seeds, const MsdfHipOrientConfig *orient) {
     int rc = checkPrepConfig(prep, "msdfhip_generate_stream_csr_prepared");
+    if (rc != MSDFHIP_OK)
+        return rc;
+    MsdfHipOrientConfig o;
+    rc = checkOrientConfig(orient, "msdfhip_generate_stream_csr_prepared_oriented", &o);
     if (rc != MSDFHIP_OK)
         return rc;
     std::vector<int> hc, he;
@@ -2948,7 +3036,7 @@ int msdfhip_generate_stream_csr_prepared(int device, int mode, int w, int h, int
     CsrSource csr = { gco, co, points, types, colors };
     MsdfHipShapeSource source = { &csr, CsrSource::count, CsrSource::fill };
     return generateStream("msdfhip_generate_stream_csr_prepared", device, mode, w, h, n_glyphs, &source, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg,
-                          prep, seeds);
+                          prep, seeds, &o);
 }
 
 int msdfhip_set_host_threads(int threads) {

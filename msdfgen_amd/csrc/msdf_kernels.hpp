@@ -2246,6 +2246,41 @@ k_prep_colour_wave(EdgeArrays norm, const int32_t *gco, const int32_t *co1, cons
     }
 }
 
+// Shape::orientContours (msdf_shapeprep.hpp: orientGlyphWave), one wavefront per glyph, on the RAW edges in place -- queued before k_prep_normalize_flat.
+// Hits and votes in LDS; a glyph of more than PREP_ORIENT_LDS_CONTOURS contours votes in `votes` (one int per contour), the hits of a glyph beyond
+// PREP_ORIENT_LDS_HITS go to bigX / bigTag (3 per raw edge, indexed like the edges; NULL when no glyph of the launch has more than PREP_ORIENT_LDS_HITS/3
+// edges: the host knows the counts).
+__global__ void __launch_bounds__(WAVE)
+k_prep_orient(EdgeArrays raw, const int32_t *gco, const int32_t *co, int nGlyphs, int32_t *votes, double *bigX, int32_t *bigTag) {
+    __shared__ double hitX[PREP_ORIENT_LDS_HITS];
+    __shared__ int hitTag[PREP_ORIENT_LDS_HITS];
+    __shared__ int ldsVotes[PREP_ORIENT_LDS_CONTOURS];
+    __shared__ int count;
+    const int g = blockIdx.x;
+    if (g >= nGlyphs)
+        return;
+    WaveCtx ctx;
+    ctx.lane = threadIdx.x;
+    const int c0 = gco[g], c1 = gco[g+1];
+    const size_t h0 = 3*(size_t) co[c0];
+    const OrientHits hits = { hitX, hitTag, bigX ? bigX+h0 : NULL, bigTag ? bigTag+h0 : NULL };
+    orientGlyphWave(ctx, raw, co, c0, c1, c1-c0 <= PREP_ORIENT_LDS_CONTOURS ? ldsVotes : votes+c0, &count, hits);
+}
+
+// The CLI's -reversewinding (mode 1) / -guesswinding (mode 2) on the NORMALIZED edges in place (msdf_shapeprep.hpp: windingGlyphWave), one wavefront per
+// glyph -- queued after normalize, before the colouring.
+__global__ void __launch_bounds__(WAVE) k_prep_winding(EdgeArrays norm, const int32_t *gco, const int32_t *co1, int nGlyphs, int mode) {
+    __shared__ double lo[2*WAVE], hi[2*WAVE], d[WAVE], dot[WAVE];
+    __shared__ int idx[WAVE];
+    const int g = blockIdx.x;
+    if (g >= nGlyphs)
+        return;
+    WaveCtx ctx;
+    ctx.lane = threadIdx.x;
+    const WindingScratch s = { lo, hi, d, dot, idx };
+    windingGlyphWave(ctx, norm, co1, gco[g], gco[g+1], mode, s);
+}
+
 // ------------------------------------------------------------------------------------------- 8-bit atlas output (row f2)
 
 // pixelFloatToByte (core/pixel-conversion.hpp:8-10): byte(~int(255.5f-255.f*clamp(x))), fp32 arithmetic, clamp(NaN) = 0.

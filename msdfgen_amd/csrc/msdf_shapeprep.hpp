@@ -15,6 +15,8 @@
 #pragma once
 
 #include "msdf_device.hpp"
+#include "msdf_prep.hpp"
+#include "msdf_scanline.hpp"
 
 namespace msdfhip {
 
@@ -655,6 +657,311 @@ MSDF_HD void colourContourWave(const Ctx &ctx, const ColourTables &t, const Edge
         });
     }
     ctx.sync();                                                                       // the tables are the next contour's
+}
+
+// ------------------------------------------------------------------------------------------- orientation (Shape::orientContours, the CLI's winding modes)
+//
+// Two optional steps around normalize: Shape::orientContours on the RAW edges before it (core/Shape.cpp:144-198; main.cpp:1105-1111), and the CLI's
+// -reversewinding / -guesswinding on the NORMALIZED edges after it, before the colouring (main.cpp:1131-1143). Both are one wavefront per glyph
+// (k_prep_orient, k_prep_winding) and end in Contour::reverse in place. Orientation must come first: splitInThirds and the deconvergence depend on
+// edge direction, so reversing before and after normalize do not give the same bits.
+//
+// orientContours, restated for lanes = edges. The reference sorts a scanline's hits by x, zeroes the direction of every hit whose x equals its
+// neighbour's, and adds 2*((j&1)^(direction > 0))-1 to the vote of the hit's contour for the hit at sorted position j. Only a hit without an equal
+// partner keeps a direction, and its position is then the number of hits with a strictly smaller x: so the hits are stored in any order (an atomic
+// slot counter), every lane ranks its hits by counting, and the integer votes are added with atomics -- any order gives the same sums. Contours still
+// cast their scanlines in contour order, one at a time: a contour whose vote is nonzero by then casts none (the reference's serial skip rule).
+
+enum { PREP_ORIENT_LDS_HITS = 1024, PREP_ORIENT_LDS_CONTOURS = 256 };   // k_prep_orient's LDS tier; beyond it: global scratch (one int32 per contour, 3 hits per edge)
+
+MSDF_HD int prepAtomicAdd(int *p, int v) {                                            // relaxed, device scope (the votes may live in global memory)
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    const int old = *p;
+    *p = old+v;
+    return old;
+#endif
+}
+MSDF_HD int prepAtomicLoad(const int *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    return *p;
+#endif
+}
+MSDF_HD void prepAtomicStore(int *p, int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    *p = v;
+#endif
+}
+
+MSDF_HD PrepEdge reversedEdge(PrepEdge e) {                                           // edge-segments.cpp:451-470
+    const V2 p0 = e.p[0];
+    e.p[0] = e.p[e.type], e.p[e.type] = p0;
+    if (e.type == 3) {
+        const V2 p1 = e.p[1];
+        e.p[1] = e.p[2], e.p[2] = p1;
+    }
+    return e;
+}
+
+// storeEdge for an array whose colours may be absent (raw outlines without colours: WHITE, nothing to move)
+MSDF_HD void storeEdgeKeepColour(const EdgeArrays &a, int e, const PrepEdge &v) {
+    if (a.colors) {
+        storeEdge(a, e, v);
+        return;
+    }
+    for (int i = 0; i < 4; ++i) {
+        a.points[8*(size_t) e+2*i] = i <= v.type ? v.p[i].x : 0.;
+        a.points[8*(size_t) e+2*i+1] = i <= v.type ? v.p[i].y : 0.;
+    }
+    a.types[e] = (uint8_t) v.type;
+}
+
+// Contour::reverse (core/Contour.cpp:83-88) of the edges [b, b+n) in place: lanes = the pairs (k, n-1-k), each edge reversed; colours travel with their edges.
+template <class Ctx>
+MSDF_HD void reverseContourWave(const Ctx &ctx, const EdgeArrays &a, int b, int n) {
+    const int pairs = (n+1)/2;
+    for (int base = 0; base < pairs; base += PREP_WAVE) {
+        ctx.lanes([&](int lane) {
+            const int k = base+lane, m = n-1-k;
+            if (k < pairs) {
+                const PrepEdge ek = loadEdge(a, b+k), em = loadEdge(a, b+m);
+                storeEdgeKeepColour(a, b+k, reversedEdge(em));
+                if (m != k)
+                    storeEdgeKeepColour(a, b+m, reversedEdge(ek));
+            }
+        });
+    }
+    ctx.sync();
+}
+
+MSDF_HD RawEdge rawOf(const PrepEdge &e) {
+    RawEdge r;
+    for (int i = 0; i < 4; ++i)
+        r.p[i] = e.p[i];
+    r.type = e.type, r.color = e.color;
+    return r;
+}
+
+// The last contour of [c0, c1) whose first edge is at or before e (skips empty contours).
+MSDF_HD int contourOfEdge(const int32_t *co, int c0, int c1, int e) {
+    int lo = c0, hi = c1-1;
+    while (lo < hi) {
+        const int mid = (lo+hi+1)>>1;
+        if (co[mid] <= e)
+            lo = mid;
+        else
+            hi = mid-1;
+    }
+    return lo;
+}
+
+// Where a glyph's scanline hits go: the first PREP_ORIENT_LDS_HITS in LDS, the rest (a glyph of more than PREP_ORIENT_LDS_HITS/3 edges only) in global
+// scratch of 3 hits per edge. tag = (contour within the glyph) << 1 | (direction > 0).
+struct OrientHits {
+    double *x;
+    int *tag;
+    double *bigX;                 // NULL when the glyph cannot overflow LDS
+    int *bigTag;
+    MSDF_HD void put(int k, double v, int t) const {
+        if (k < PREP_ORIENT_LDS_HITS)
+            x[k] = v, tag[k] = t;
+        else if (bigX)
+            bigX[k-PREP_ORIENT_LDS_HITS] = v, bigTag[k-PREP_ORIENT_LDS_HITS] = t;
+    }
+    MSDF_HD double getX(int k) const { return k < PREP_ORIENT_LDS_HITS ? x[k] : bigX[k-PREP_ORIENT_LDS_HITS]; }
+    MSDF_HD int getTag(int k) const { return k < PREP_ORIENT_LDS_HITS ? tag[k] : bigTag[k-PREP_ORIENT_LDS_HITS]; }
+};
+
+// y of contour [b, b+n)'s scanline (Shape.cpp:161-168): the first point(1).y that differs from y0 = point(0).y of the first edge, else the first such
+// point(ratio).y; y = mix(y0, y1, ratio). The first differing edge is found 64 edges at a time by ballot, then evaluated by the whole wavefront.
+template <class Ctx>
+MSDF_HD double orientScanY(const Ctx &ctx, const EdgeArrays &raw, int b, int n) {
+    const double ratio = 0x1.3c6ef372fe95p-1;                                          // .5*(sqrt(5)-1), rounded once like the reference's
+    const double y0 = edgePoint(loadEdge(raw, b), 0).y;
+    for (int pass = 0; pass < 2; ++pass) {
+        const double t = pass ? ratio : 1.;
+        for (int base = 0; base < n; base += PREP_WAVE) {
+            const unsigned long long mask = ctx.ballot([&](int lane) { return base+lane < n && edgePoint(loadEdge(raw, b+base+lane), t).y != y0; });
+            if (mask) {
+                const double y1 = edgePoint(loadEdge(raw, b+base+__builtin_ctzll(mask)), t).y;
+                return (1.-ratio)*y0+ratio*y1;                                        // mix, arithmetics.hpp:27-31
+            }
+        }
+    }
+    return (1.-ratio)*y0+ratio*y0;
+}
+
+// Shape::orientContours of the glyph whose contours are [c0, c1) (offsets co into `raw`), in place. votes: one int per contour of the glyph (LDS or
+// global); count: one int (LDS). Contours with a negative vote are reversed at the end.
+template <class Ctx>
+MSDF_HD void orientGlyphWave(const Ctx &ctx, const EdgeArrays &raw, const int32_t *co, int c0, int c1, int *votes, int *count, const OrientHits &hits) {
+    const int nc = c1-c0, e0 = co[c0], e1 = co[c1];
+    ctx.lanes([&](int lane) {
+        for (int i = lane; i < nc; i += PREP_WAVE)
+            prepAtomicStore(votes+i, 0);
+    });
+    ctx.sync();
+    for (int i = 0; i < nc; ++i) {
+        const int b = co[c0+i], n = co[c0+i+1]-b;
+        if (!n || prepAtomicLoad(votes+i))
+            continue;
+        const double y = orientScanY(ctx, raw, b, n);
+        ctx.leader([&]() { *count = 0; });
+        ctx.sync();
+        for (int base = e0; base < e1; base += PREP_WAVE) {                              // lanes = edges: EdgeSegment::scanlineIntersections (Shape.cpp:172-180)
+            ctx.lanes([&](int lane) {
+                const int e = base+lane;
+                if (e < e1) {
+                    const int c = contourOfEdge(co, c0, c1, e);
+                    const RawEdge r = rawOf(loadEdge(raw, e));
+                    EdgeRec rec;
+                    buildRecord(rec, r, r, r, c);                                     // (only the control points and ab / br / as are read)
+                    double x[3];
+                    int dy[3];
+                    const int m = scanlineIntersections(rec, x, dy, y);
+                    MSDF_UNROLL
+                    for (int k = 0; k < 3; ++k)                              // (a constant trip count keeps x / dy in registers)
+                        if (k < m)
+                            hits.put(prepAtomicAdd(count, 1), x[k], (c-c0)<<1|(dy[k] > 0));
+                }
+            });
+        }
+        ctx.sync();
+        const int total = *count;
+        ctx.lanes([&](int lane) {                                                     // lanes = hits: sorted position by counting (Shape.cpp:182-190)
+            for (int h = lane; h < total; h += PREP_WAVE) {
+                const double x = hits.getX(h);
+                int rank = 0;
+                bool tie = false;
+                for (int k = 0; k < total; ++k) {
+                    const double xk = hits.getX(k);
+                    rank += xk < x;
+                    tie = tie || (k != h && xk == x);
+                }
+                if (!tie) {
+                    const int tag = hits.getTag(h);
+                    prepAtomicAdd(votes+(tag>>1), 2*((rank&1)^(tag&1))-1);
+                }
+            }
+        });
+        ctx.sync();
+    }
+    for (int i = 0; i < nc; ++i)                                                      // Shape.cpp:194-197
+        if (prepAtomicLoad(votes+i) < 0)
+            reverseContourWave(ctx, raw, co[c0+i], co[c0+i+1]-co[c0+i]);
+}
+
+// Edge bounds (edge-segments.cpp:405-449) into lo / hi, pointBounds' comparisons.
+MSDF_HD void boundPoint(V2 p, V2 &lo, V2 &hi) {
+    if (p.x < lo.x) lo.x = p.x;
+    if (p.y < lo.y) lo.y = p.y;
+    if (p.x > hi.x) hi.x = p.x;
+    if (p.y > hi.y) hi.y = p.y;
+}
+
+MSDF_HD void edgeBound(const PrepEdge &e, V2 &lo, V2 &hi) {
+    const V2 *p = e.p;
+    boundPoint(p[0], lo, hi);
+    boundPoint(p[e.type], lo, hi);
+    if (e.type == 2) {
+        const V2 bot = (p[1]-p[0])-(p[2]-p[1]);
+        if (bot.x) {
+            const double param = (p[1].x-p[0].x)/bot.x;
+            if (param > 0 && param < 1)
+                boundPoint(edgePoint(e, param), lo, hi);
+        }
+        if (bot.y) {
+            const double param = (p[1].y-p[0].y)/bot.y;
+            if (param > 0 && param < 1)
+                boundPoint(edgePoint(e, param), lo, hi);
+        }
+    } else if (e.type == 3) {
+        const V2 a0 = p[1]-p[0];
+        const V2 a1 = 2*(p[2]-p[1]-a0);
+        const V2 a2 = p[3]-3*p[2]+3*p[1]-p[0];
+        double params[2];
+        int solutions = solveQuadratic(params, a2.x, a1.x, a0.x);
+        MSDF_UNROLL
+        for (int i = 0; i < 2; ++i)
+            if (i < solutions && params[i] > 0 && params[i] < 1)
+                boundPoint(edgePoint(e, params[i]), lo, hi);
+        solutions = solveQuadratic(params, a2.y, a1.y, a0.y);
+        MSDF_UNROLL
+        for (int i = 0; i < 2; ++i)
+            if (i < solutions && params[i] > 0 && params[i] < 1)
+                boundPoint(edgePoint(e, params[i]), lo, hi);
+    }
+}
+
+// Per-lane partials of the winding guess, exchanged through memory the wavefront shares (64 entries each).
+struct WindingScratch {
+    double *lo, *hi;              // [2*64]: x, y
+    double *d, *dot;              // [64]: the lane's nearest edge (SignedDistance)
+    int *idx;                     // [64]: its visit index
+};
+
+// The CLI's winding step on the NORMALIZED glyph [c0, c1) (offsets co into `norm`), in place: mode 1 reverses every contour; mode 2 (-guesswinding)
+// takes Shape::getBounds b (Shape.cpp:104-115) and reverses every contour when SimpleTrueShapeDistanceFinder::oneShotDistance at
+// (b.l-(b.r-b.l)-1, b.b-(b.t-b.b)-1) is > 0 (main.cpp:1131-1143). Lanes = edges for both: min / max of the lanes' bounds (order-free but for the sign of a
+// zero, which the query point does not depend on), and the nearest edge by SignedDistance < with the reference's visit order breaking exact ties
+// (sdReplaces: a total order, so the wavefront's winner is the reference's). Returns whether the glyph was reversed.
+template <class Ctx>
+MSDF_HD bool windingGlyphWave(const Ctx &ctx, const EdgeArrays &norm, const int32_t *co, int c0, int c1, int mode, const WindingScratch &s) {
+    const int e0 = co[c0], e1 = co[c1];
+    if (e0 == e1)
+        return false;                                                                 // nothing to reverse (an empty glyph's distance is -DBL_MAX anyway)
+    bool reverse = mode == 1;
+    if (mode == 2) {
+        ctx.lanes([&](int lane) {
+            V2 lo = mk(1e240, 1e240), hi = mk(-1e240, -1e240);                        // Shape::getBounds' LARGE_VALUE
+            for (int e = e0+lane; e < e1; e += PREP_WAVE)
+                edgeBound(loadEdge(norm, e), lo, hi);
+            s.lo[2*lane] = lo.x, s.lo[2*lane+1] = lo.y, s.hi[2*lane] = hi.x, s.hi[2*lane+1] = hi.y;
+        });
+        ctx.sync();
+        V2 lo = mk(1e240, 1e240), hi = mk(-1e240, -1e240);
+        for (int k = 0; k < PREP_WAVE; ++k) {
+            lo = mk(s.lo[2*k] < lo.x ? s.lo[2*k] : lo.x, s.lo[2*k+1] < lo.y ? s.lo[2*k+1] : lo.y);
+            hi = mk(s.hi[2*k] > hi.x ? s.hi[2*k] : hi.x, s.hi[2*k+1] > hi.y ? s.hi[2*k+1] : hi.y);
+        }
+        const V2 o = mk(lo.x-(hi.x-lo.x)-1, lo.y-(hi.y-lo.y)-1);
+        ctx.sync();
+        ctx.lanes([&](int lane) {
+            Selector<1> sel;
+            selInit(sel);
+            for (int e = e0+lane; e < e1; e += PREP_WAVE) {
+                const int c = contourOfEdge(co, c0, c1, e), b = co[c], n = co[c+1]-b;
+                const RawEdge r = rawOf(loadEdge(norm, e));
+                EdgeRec rec;
+                buildRecord(rec, r, r, r, c);                                         // (the true distance reads nothing of the neighbours)
+                double param;
+                const SD sd = signedDistance(rec, o, param);
+                const int idx = b+(e == b+n-1 ? 0 : e-b+1);                           // visit order: last edge first (ShapeDistanceFinder.hpp:45-57)
+                if (sdReplaces(sd, idx, sel.m, sel.idx[0]))
+                    sel.m = sd, sel.idx[0] = idx;
+            }
+            s.d[lane] = sel.m.d, s.dot[lane] = sel.m.dot, s.idx[lane] = sel.idx[0];
+        });
+        ctx.sync();
+        SD best = { s.d[0], s.dot[0] };
+        int bestIdx = s.idx[0];
+        for (int k = 1; k < PREP_WAVE; ++k) {
+            const SD sd = { s.d[k], s.dot[k] };
+            if (sdReplaces(sd, s.idx[k], best, bestIdx))
+                best = sd, bestIdx = s.idx[k];
+        }
+        ctx.sync();
+        reverse = best.d > 0;
+    }
+    if (reverse)
+        for (int c = c0; c < c1; ++c)
+            reverseContourWave(ctx, norm, co[c], co[c+1]-co[c]);
+    return reverse;
 }
 
 } // namespace msdfhip

@@ -40,6 +40,11 @@ class PrepConfig(C.Structure):
     _fields_ = [("normalize", C.c_int32), ("coloring", C.c_int32), ("angle_threshold", C.c_double), ("seed", C.c_uint64)]
 
 
+class OrientConfig(C.Structure):
+    """MsdfHipOrientConfig."""
+    _fields_ = [("orient_contours", C.c_int32), ("winding", C.c_int32)]
+
+
 class Glyph(C.Structure):
     """MsdfHipGlyph."""
     _fields_ = [("xf", C.c_double*6), ("out_offset", C.c_int64), ("row_stride", C.c_int32), ("flip", C.c_int32)]
@@ -71,6 +76,8 @@ _PROTOS = {
     "msdfhip_batch_create": (C.c_int, [C.POINTER(_vp), C.c_int, _ip, _ip, _dp, _bp, _bp]),
     "msdfhip_batch_create_device": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msdfhip_batch_create_prepared": (C.c_int, [C.POINTER(_vp), C.c_int, _ip, _ip, _dp, _bp, _bp, C.POINTER(C.c_uint64), C.POINTER(PrepConfig)]),
+    "msdfhip_batch_create_prepared_oriented": (C.c_int, [C.POINTER(_vp), C.c_int, _ip, _ip, _dp, _bp, _bp, C.POINTER(C.c_uint64), C.POINTER(PrepConfig),
+                                                         C.POINTER(OrientConfig)]),
     "msdfhip_batch_candidate_counts": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "msdfhip_batch_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "msdfhip_batch_download": (C.c_int, [_vp, _ip, _dp, _bp, _bp]),
@@ -112,6 +119,11 @@ _PROTOS = {
                                                    C.POINTER(PrepConfig), C.POINTER(C.c_uint64)]),
     "msdfhip_generate_stream_csr_prepared": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _bp, _bp, _vp, _vp, C.c_size_t, _vp, C.c_size_t,
                                                        _vp, C.POINTER(Config), C.POINTER(PrepConfig), C.POINTER(C.c_uint64)]),
+    "msdfhip_generate_stream_prepared_oriented": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp,
+                                                            C.POINTER(Config), C.POINTER(PrepConfig), C.POINTER(C.c_uint64), C.POINTER(OrientConfig)]),
+    "msdfhip_generate_stream_csr_prepared_oriented": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _bp, _bp, _vp, _vp, C.c_size_t, _vp,
+                                                                C.c_size_t, _vp, C.POINTER(Config), C.POINTER(PrepConfig), C.POINTER(C.c_uint64),
+                                                                C.POINTER(OrientConfig)]),
     "msdfhip_set_host_threads": (C.c_int, [C.c_int]),
     "msdfhip_single_call_fallbacks": (C.c_int, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_int]),
 }

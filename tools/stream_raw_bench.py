@@ -5,8 +5,11 @@ One process, the 8 192 DejaVu glyphs of tests/golden/dejavu8192.npz, MSDF at 48x
                    chunk on the device, inside the pipeline
     (c) cpu+a      the compiled reference's Shape::normalize + edgeColoringSimple on the host (oracle/_ref/libmsdfgen_ref.so through oracle.pyoracle.Ref,
                    a thread pool of --threads, as bench.py's CPU baseline), then (a)
+    (d) raw+orient (b) with orient_contours=1, winding=guess: k_prep_orient before normalize, k_prep_winding after it
+    (e) cpu-orient+a  (c) with the reference's orientContours before normalize and the -guesswinding step after it (tests/orientcases.py), then (a)
 Every (size, output, variant) is warmed up first; the timed calls are interleaved round-robin, --reps of each; median / min / max per cell.
 (b)'s bytes are checked against (a)'s once per cell (the fixture's shapes are what the reference's preparation gives the wiped set).
+--perturb: the raw variants stream the outlines with every contour of every 3rd glyph and one contour of every 5th reversed (orientcases.perturbed).
     python tools/stream_raw_bench.py [--reps 9] [--out profiles/NAME_stream_raw.jsonl]
     python tools/stream_raw_bench.py --only raw --reps 3 --sizes 48 --outputs uint8      (one variant alone: for rocprofv3 runs)"""
 import argparse
@@ -40,22 +43,35 @@ def cpu_prepare(ref, raw, pool):
     return ShapeBatch.from_shapes([FlatShape(f.contour_offsets, f.points, f.types, f.colors) for f in fas])
 
 
+def cpu_prepare_oriented(ref, raw, pool):
+    """(e)'s host preparation: orientContours, normalize, the winding guess, edgeColoringSimple(3.0, seed 0) -- the reference's, glyph by glyph."""
+    import orientcases as OC
+    fas = list(pool.map(lambda g: OC.ref_prepare(ref, raw.shape(g), True, 2, True, 1, 3.0, 0), range(raw.n_glyphs), chunksize=64))
+    return ShapeBatch.from_shapes(fas)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--sizes", default="48,64")
     ap.add_argument("--outputs", default="uint8,float")
-    ap.add_argument("--only", choices=("prepared", "raw", "cpu+a"), default=None)
+    ap.add_argument("--only", choices=("prepared", "raw", "cpu+a", "raw+orient", "cpu-orient+a"), default=None)
+    ap.add_argument("--perturb", action="store_true")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--out", default=None, help="jsonl file (one line per cell)")
     args = ap.parse_args()
     M.init(0)
     prepared, raw, xfs = load_sets()
     n = raw.n_glyphs
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    if args.perturb:
+        import orientcases as OC
+        raw = OC.perturbed(raw)
     prep = M.PrepareConfig(True, 1, 3.0, 0)
-    variants = [args.only] if args.only else ["prepared", "raw", "cpu+a"]
+    prep_orient = M.PrepareConfig(True, 1, 3.0, 0, orient_contours=True, winding=M.WINDING_GUESS)
+    variants = [args.only] if args.only else ["prepared", "raw", "cpu+a", "raw+orient", "cpu-orient+a"]
     ref, pool, cpu_impl = None, None, None
-    if "cpu+a" in variants:
+    if "cpu+a" in variants or "cpu-orient+a" in variants:
         from oracle.pyoracle import Ref, Oracle
         ref = Ref() if Ref.available() else Oracle()
         cpu_impl = "compiled reference (oracle/_ref/libmsdfgen_ref.so)" if isinstance(ref, Ref) else "oracle C port (reference not built)"
@@ -80,8 +96,12 @@ def main():
                     stream(prepared)
                 elif v == "raw":
                     stream(raw, prepare=prep)
-                else:
+                elif v == "raw+orient":
+                    stream(raw, prepare=prep_orient)
+                elif v == "cpu+a":
                     stream(cpu_prepare(ref, raw, pool))
+                else:
+                    stream(cpu_prepare_oriented(ref, raw, pool))
 
             for v in variants:                                       # warm-up: pools, pipes, staging grown, kernels loaded
                 run(v)
@@ -103,14 +123,14 @@ def main():
                 t = np.array(times[v])
                 line = {"tool": "stream_raw_bench", "glyphs": n, "size": size, "output": output, "variant": v, "reps": args.reps,
                         "median_ms": round(float(np.median(t)), 3), "min_ms": round(float(t.min()), 3), "max_ms": round(float(t.max()), 3),
-                        "glyphs_per_s": round(n/float(np.median(t))*1e3), "raw_equals_prepared": same, **env}
-                if v == "cpu+a":
+                        "glyphs_per_s": round(n/float(np.median(t))*1e3), "raw_equals_prepared": same, "perturbed": args.perturb, **env}
+                if v in ("cpu+a", "cpu-orient+a"):
                     line["cpu_prepare"] = "%s, %d threads" % (cpu_impl, args.threads)
                 lines.append(line)
                 print(json.dumps(line), flush=True)
             if args.only is None:
                 a, b = np.median(times["prepared"]), np.median(times["raw"])
-                print("# %dx%d %s: raw / prepared = %.3f" % (size, size, output, b/a), flush=True)
+                print("# %dx%d %s: raw / prepared = %.3f, raw+orient - raw = %.3f ms" % (size, size, output, b/a, np.median(times["raw+orient"])-b), flush=True)
     if pool:
         pool.shutdown()
     if args.out:
