@@ -66,13 +66,8 @@ struct Tuning {
     int qpEdgeCost, qpMaxEdges, qpMinCount, qpWideMaxEdges;
     float qpWideLoad, qpWideMeanCount;
     size_t signCap;                  // MSDFHIP_SIGN_CAP            row-list capacity of the sign pass
-    bool pipelineUniform;            // MSDFHIP_PIPELINE_UNIFORM    equal pipeline chunks (no half chunks at the ends)
-    char pipelineLengths[128];       // MSDFHIP_PIPELINE_LENGTHS    experiment: explicit chunk lengths "512,1024,..." (the last one repeats)
     bool pipelineTrace;              // MSDFHIP_PIPELINE_TRACE      host-output pipeline prints per chunk when its kernels / its copy back finished (stderr)
     int microbatch;                  // MSDFHIP_MICROBATCH          0 / 1 disables the grouping of concurrent single-shape calls; N caps the group
-    int sidePriority;                // MSDFHIP_SIDE_PRIORITY       queue priority of the side-class streams: low (-1, default) / none (0) / high (+1) / one (-2) / rest (-3)
-    bool noClassSort;                // MSDFHIP_NO_CLASS_SORT       glyph classes in batch order instead of heaviest first (A/B)
-    bool noEcAhead;                  // MSDFHIP_NO_EC_AHEAD         k_ec_params behind the distance pass, as before round 6 (A/B)
     int queryStatic;                 // MSDFHIP_QUERY_STATIC        2: first ticket dealt, the others from eight counters; 0: k_ec_query draws its tickets from an atomic counter (rounds 2-5) instead of the static serpentine deal
     int queryGridSteps;              // MSDFHIP_QUERY_GRID          grid form of the distance checks: edges a lane may walk per item (0 = off: the two older forms only)
     int queryBatch;                  // MSDFHIP_QUERY_BATCH         cooperative distance checks a wavefront of k_ec_query takes per ticket (default 1: more only lengthens the tail)
@@ -87,13 +82,6 @@ struct Tuning {
     int smallMaxEdges;               // MSDFHIP_SMALL_MAX_EDGES     glyphs of the LDS-scratch class have at most this many edges (128)
     int ldsClassTpw;                 // MSDFHIP_LDS_CLASS_TPW       tiles per wavefront of the LDS-scratch class: 4 (default; 1 in short launches) or always 1
     int pipelineDepth;               // MSDFHIP_PIPELINE_DEPTH      chunks of the host-output pipeline whose kernels may run at the same time (2; at most PIPE_SLOTS-1)
-    bool pipelineConcurrentClasses;  // MSDFHIP_PIPELINE_CLASSES=concurrent: a chunk's glyph classes on side streams (default: one after the other on the chunk's stream)
-    bool pipelineNoAhead;            // MSDFHIP_PIPELINE_NO_AHEAD    A/B: a chunk's class lists and correction constants inside its launch chain, as before round 5
-    bool streamUploadByCopy;         // MSDFHIP_STREAM_UPLOAD=copy: the streamed generator uploads a chunk's inputs with hipMemcpyAsync instead of the upload kernel (A/B)
-    bool pipelineGateDistance;       // MSDFHIP_PIPELINE_GATE=distance|kernels: chunk k+depth takes its turn when chunk k's DISTANCE PASS is done (its correction pass then runs under the
-                                     //                              next chunk's distance pass) or when all its kernels are
-    bool pipelineOverflowPass;       // MSDFHIP_PIPELINE_OVERFLOW_PASS  A/B: every chunk of the host-output pipeline launches the per-texel overflow pass (round 4) instead of mirroring the count
-    bool queueMemset;                // MSDFHIP_QUEUE_MEMSET        A/B: zero the persistent launch's work queue with a memset in front of every launch (round 4) instead of by the launch itself
     bool prepLargeTier;              // MSDFHIP_PREP_LARGE_TIER     tests: the colouring kernel always with its 2 048-edge LDS tables (default: 256-edge tier when no contour is longer)
     int hostThreads;                 // MSDFHIP_HOST_THREADS        host threads of the streamed generator's flatten pool (0 = the usable cores, at most 32); read when the pool is created
     long singleSpinLimit;            // MSDFHIP_SINGLE_SPIN_LIMIT   tests: iterations k_single_call's grid barrier waits before it gives up (0 = scaled with the shape)
@@ -121,18 +109,11 @@ void readTuning() {
     if (env)
         sscanf(env, "%d,%d,%d,%d,%f,%f", &t.qpEdgeCost, &t.qpMaxEdges, &t.qpMinCount, &t.qpWideMaxEdges, &t.qpWideLoad, &t.qpWideMeanCount);
     t.signCap = (env = getenv("MSDFHIP_SIGN_CAP")) ? (size_t) atol(env) : (size_t) 192;
-    t.pipelineUniform = getenv("MSDFHIP_PIPELINE_UNIFORM") != NULL;
     t.pipelineTrace = getenv("MSDFHIP_PIPELINE_TRACE") != NULL;
-    t.pipelineLengths[0] = 0;
-    if ((env = getenv("MSDFHIP_PIPELINE_LENGTHS")))
-        snprintf(t.pipelineLengths, sizeof(t.pipelineLengths), "%s", env);
     t.microbatch = (env = getenv("MSDFHIP_MICROBATCH")) ? atoi(env) : 256;
     if (t.microbatch < 1)
         t.microbatch = 1;
     t.devices[0] = 0;
-    t.sidePriority = (env = getenv("MSDFHIP_SIDE_PRIORITY")) ? (env[0] == 'l' ? -1 : env[0] == 'h' ? 1 : env[0] == 'o' ? -2 : env[0] == 'r' ? -3 : 0) : -1;
-    t.noClassSort = getenv("MSDFHIP_NO_CLASS_SORT") != NULL;
-    t.noEcAhead = getenv("MSDFHIP_NO_EC_AHEAD") != NULL;
     t.queryStatic = (env = getenv("MSDFHIP_QUERY_STATIC")) ? atoi(env) : 2;
     t.queryGridSteps = (env = getenv("MSDFHIP_QUERY_GRID")) ? atoi(env) : 16;
     t.queryBatch = (env = getenv("MSDFHIP_QUERY_BATCH")) && atoi(env) > 0 ? atoi(env) : 1;
@@ -150,13 +131,7 @@ void readTuning() {
     t.smallMaxEdges = (env = getenv("MSDFHIP_SMALL_MAX_EDGES")) && atoi(env) > 0 ? atoi(env) : 128;
     t.ldsClassTpw = (env = getenv("MSDFHIP_LDS_CLASS_TPW")) && atoi(env) == 1 ? 1 : 4;
     t.pipelineDepth = (env = getenv("MSDFHIP_PIPELINE_DEPTH")) && atoi(env) >= 1 && atoi(env) <= 3 ? atoi(env) : 2;
-    t.pipelineConcurrentClasses = (env = getenv("MSDFHIP_PIPELINE_CLASSES")) && env[0] == 'c';
-    t.pipelineNoAhead = getenv("MSDFHIP_PIPELINE_NO_AHEAD") != NULL;
-    t.streamUploadByCopy = (env = getenv("MSDFHIP_STREAM_UPLOAD")) && env[0] == 'c';
     t.prepLargeTier = getenv("MSDFHIP_PREP_LARGE_TIER") != NULL;
-    t.queueMemset = getenv("MSDFHIP_QUEUE_MEMSET") != NULL;
-    t.pipelineOverflowPass = getenv("MSDFHIP_PIPELINE_OVERFLOW_PASS") != NULL;
-    t.pipelineGateDistance = (env = getenv("MSDFHIP_PIPELINE_GATE")) ? env[0] == 'd' : false;
     t.hostThreads = (env = getenv("MSDFHIP_HOST_THREADS")) && atoi(env) > 0 ? atoi(env) : 0;
     t.singleSpinLimit = (env = getenv("MSDFHIP_SINGLE_SPIN_LIMIT")) && atol(env) > 0 ? atol(env) : 0;
     t.singleVerbose = getenv("MSDFHIP_SINGLE_VERBOSE") != NULL;
@@ -512,8 +487,6 @@ int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
             // Launches on one batch are ordered by the caller (they share the batch's workspaces).
             std::lock_guard<std::mutex> lock(b->scratchMutex);
             queue += b->queueParity ? 16 : 0;                    // (the kernel finds the other set at `queue ^ 64 bytes`)
-            if (tuning().queueMemset)                            // (A/B: round 4's memset in front of the launch)
-                HIPCHK(hipMemsetAsync(queue, 0, 8*sizeof(unsigned), stream));
             args.gres = gres, args.gresStride = stride, args.workQueue = queue, args.workItems = (unsigned) blocks;
             launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) chunk, plan.bytes, stream, args);
             HIPCHK(hipGetLastError());
@@ -619,7 +592,7 @@ int ensureBuckets(const MsdfHipBatch *b, int limit, hipStream_t stream) {
             order[at++] = g;
     // Heaviest glyphs first inside each class (longest-processing-time order: a launch is ~26 rounds of workgroups, its tail is the last round's
     // heaviest glyph; the output does not depend on the order -- a glyph writes its own tiles).
-    if (!tuning().noClassSort) {
+    {
         const int *hE = b->hEdges.data(), *hC = b->hContours.data();
         auto heavier = [hE, hC](int x, int y) { return (long long) hE[x]*(hC[x] > 1 ? hC[x] : 1) > (long long) hE[y]*(hC[y] > 1 ? hC[y] : 1); };
         std::stable_sort(order, order+nOne, heavier);
@@ -656,7 +629,7 @@ int ensureEcOrder(const MsdfHipBatch *b, const int **order, hipStream_t stream) 
         return MSDFHIP_OK;
     }
     b->ecOrderTried = true;
-    if (tuning().noClassSort || b->serialClasses || b->bucketExternal || b->nGlyphs < 256 || b->hEdges.size() != (size_t) b->nGlyphs ||
+    if (b->serialClasses || b->bucketExternal || b->nGlyphs < 256 || b->hEdges.size() != (size_t) b->nGlyphs ||
         b->hContours.size() != (size_t) b->nGlyphs)
         return MSDFHIP_OK;
     const size_t bytes = sizeof(int)*(size_t) b->nGlyphs;
@@ -703,11 +676,9 @@ int ensureSideStreams(const MsdfHipBatch *b) {
     (void) hipDeviceGetStreamPriorityRange(&least, &greatest);
     for (int k = 0; k < 2; ++k) {
         // The two side classes run at LOW queue priority: the long LDS-class launch on the caller's stream gets the slots first and the side
-        // classes fill what it leaves, its tail included (distance pass 3.93 -> 3.80-3.88 ms; high: 4.01). MSDFHIP_SIDE_PRIORITY=none|low|high|one|rest.
-        const int which = tuning().sidePriority;                    // -1 both low, +1 both high, -2 only the one-contour class low, -3 only the global-scratch class low
-        const int prio = (which == -1 || (which == -2 && k == 1) || (which == -3 && k == 0)) ? least : which > 0 ? greatest : 0;
-        if (prio != 0)
-            HIPCHK(hipStreamCreateWithPriority(&b->sideStream[k], hipStreamNonBlocking, prio));
+        // classes fill what it leaves, its tail included (distance pass 3.93 -> 3.80-3.88 ms; high: 4.01).
+        if (least != 0)
+            HIPCHK(hipStreamCreateWithPriority(&b->sideStream[k], hipStreamNonBlocking, least));
         else
             HIPCHK(hipStreamCreateWithFlags(&b->sideStream[k], hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&b->joinEvent[k], hipEventDisableTiming));
@@ -1782,7 +1753,7 @@ int msdfhip_batch_generate(const MsdfHipBatch *b, int mode, int w, int h, const 
     float *stageA = stages ? dScratch : NULL, *stageB = stages == 2 ? dScratch+tileFloats : NULL;
     float *dst = stages ? stageA : dOut;
     EcAheadRequest ahead = { channelsOf(mode), w, h, dGlyphs, cfg };
-    b->ecAheadWanted = correct && !b->ecParamsAhead && !tuning().noEcAhead ? &ahead : NULL;
+    b->ecAheadWanted = correct && !b->ecParamsAhead ? &ahead : NULL;
     switch (mode) {
         case 1: rc = dispatchDistance<1>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream); break;
         case 2: rc = dispatchDistance<2>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream); break;
@@ -2056,7 +2027,7 @@ static void sliceBatch(const MsdfHipBatch *b, MsdfHipBatch &v, int g0, int n) {
     v.maxContours = maxC, v.maxEdges = maxE;
     v.bucketLimit = -1;                                          // the class lists are per glyph range
     v.ecParamsAhead = false;
-    v.serialClasses = !tuning().pipelineConcurrentClasses;       // pipeline chunks overlap each other; side streams per chunk only alias the few hardware queues
+    v.serialClasses = true;                                      // pipeline chunks overlap each other; side streams per chunk only alias the few hardware queues
 }
 
 static int fetchGlyphCounts(const MsdfHipBatch *b) {             // device-array batches: the per-glyph counts are read back once
@@ -2432,13 +2403,10 @@ struct StreamFeeder : ChunkFeeder {
             if (seeds)
                 memcpy(p.pinnedIn+l.seeds, seeds+g0, sizeof(uint64_t)*(size_t) n);
         }
-        if (tuning().streamUploadByCopy)
-            HIPCHK(hipMemcpyAsync(p.devIn, p.pinnedIn, l.bytes, hipMemcpyHostToDevice, stream));
-        else {                                                   // (a kernel reading the pinned staging: never queues behind another chunk's copy back)
-            const int rcUp = uploadSmall(p.devIn, p.pinnedIn, (l.bytes+15)/16*16, stream);
-            if (rcUp != MSDFHIP_OK)
-                return rcUp;
-        }
+        // (a kernel reading the pinned staging: never queues behind another chunk's copy back)
+        const int rcUp = uploadSmall(p.devIn, p.pinnedIn, (l.bytes+15)/16*16, stream);
+        if (rcUp != MSDFHIP_OK)
+            return rcUp;
         HIPCHK(hipEventRecord(p.inputsUploaded, stream));
         p.inputsInFlight = true;
         MsdfHipBatch &v = p.view;
@@ -2465,7 +2433,7 @@ struct StreamFeeder : ChunkFeeder {
         v.maxContours = maxC, v.maxEdges = maxE;
         v.bucketLimit = -1;
         v.ecParamsAhead = false;
-        v.serialClasses = !tuning().pipelineConcurrentClasses;
+        v.serialClasses = true;
         return digest(&v, stream);
     }
 
@@ -2661,7 +2629,7 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
         int rem = nG;
         const int unit = out ? (chunk/2 >= 64 ? chunk/2/64*64 : chunk) : chunk;     // the schedule's full chunk (the slots are sized for `chunk` either way)
         const int first = out ? (unit/2 >= 64 ? unit/2/64*64 : unit) : (unit*3/8 >= 64 ? unit*3/8/64*64 : unit);
-        if (nG >= 2*chunk && first < unit && !tuning().pipelineUniform) {
+        if (nG >= 2*chunk && first < unit) {
             lengths.push_back(first);
             for (rem -= first; rem > unit+unit/2; rem -= unit)
                 lengths.push_back(unit);
@@ -2685,19 +2653,6 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
     }
     if (lengths.size() > 1)
         hintHwQueuesOnce();
-    if (tuning().pipelineLengths[0]) {                           // experiment knob: explicit schedule, capped by the slots' capacity
-        lengths.clear();
-        int rem = nG, last = chunk;
-        for (const char *q = tuning().pipelineLengths; rem > 0; ) {
-            char *end = NULL;
-            const long v = *q ? strtol(q, &end, 10) : 0;
-            if (end && end != q)
-                last = (int) (v < 64 ? 64 : v > chunk ? chunk : v), q = *end == ',' ? end+1 : end;
-            const int take = last < rem ? last : rem;
-            lengths.push_back(take);
-            rem -= take;
-        }
-    }
     // MSDFHIP_PIPELINE_TRACE: timed events per chunk (kernels enqueued / finished, copy finished) relative to the first enqueue
     struct TraceEvents { hipEvent_t start, kernels, copied; long long hostEnqueued; };
     std::vector<TraceEvents> trace;
@@ -2803,13 +2758,11 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
         }
         // Everything up to here -- the chunk's inputs (streamed calls: upload + digest), its descriptors -- and the two preparations below do not depend on
         // the chunks before it: they are queued AHEAD of the chunk's turn on the device and run under the earlier chunks' kernels.
-        if (!tuning().pipelineNoAhead) {
-            rc = prepareAhead(&p.view, mode, w, h, dGlyphs, cfg, compute);
-            if (rc != MSDFHIP_OK)
-                break;
-        }
+        rc = prepareAhead(&p.view, mode, w, h, dGlyphs, cfg, compute);
+        if (rc != MSDFHIP_OK)
+            break;
         if (ci >= (size_t) depth)                                // at most `depth` (two) chunks' kernels at a time, in order: chunk k starts when chunk k-depth's KERNELS are done
-            HIPCHK(hipStreamWaitEvent(compute, tuning().pipelineGateDistance ? pipe[(slot+PIPE_SLOTS-depth)%PIPE_SLOTS].distanceDone : pipe[(slot+PIPE_SLOTS-depth)%PIPE_SLOTS].kernelsDone, 0));
+            HIPCHK(hipStreamWaitEvent(compute, pipe[(slot+PIPE_SLOTS-depth)%PIPE_SLOTS].kernelsDone, 0));
         p.view.afterDistance = p.distanceDone;
         p.pinnedOverflow[0] = 0;                                 // (the slot's previous chunk is done: nothing on the device writes it any more)
         p.view.overflowOut = mirrorOverflow ? p.pinnedOverflow : NULL, p.view.overflowMirrored = false;
@@ -2881,8 +2834,7 @@ static std::atomic<unsigned long long> gPipelineOverflowReruns(0);
 static int runPipeline(const MsdfHipBatch *b, ChunkFeeder *feeder, int device, int nGlyphs, int mode, int w, int h, const MsdfHipGlyph *glyphs, float *out, size_t outFloats,
                        uint8_t *atlas, size_t atlasBytes, uint8_t *stencil, const MsdfHipConfig *cfg) {
     bool overflowed = false;
-    const bool mirror = !tuning().pipelineOverflowPass;
-    int rc = runPipelineOnce(b, feeder, device, nGlyphs, mode, w, h, glyphs, out, outFloats, atlas, atlasBytes, stencil, cfg, mirror, &overflowed);
+    int rc = runPipelineOnce(b, feeder, device, nGlyphs, mode, w, h, glyphs, out, outFloats, atlas, atlasBytes, stencil, cfg, true, &overflowed);
     if (rc == MSDFHIP_OK && overflowed) {                        // some glyph's candidate segment overflowed: the whole call again, every chunk with the overflow pass
         ++gPipelineOverflowReruns;
         rc = runPipelineOnce(b, feeder, device, nGlyphs, mode, w, h, glyphs, out, outFloats, atlas, atlasBytes, stencil, cfg, false, &overflowed);
@@ -4211,8 +4163,6 @@ int msdfhip_front_door_devices(int *out, int cap) {
 }
 
 int msdfhip_reload_tuning(void) {
-    // Knobs consumed when a resource is CREATED (MSDFHIP_SIDE_PRIORITY: a batch's side streams; pooled pipeline slots) apply to resources created
-    // after the reload; msdfhip_trim() drops the pooled ones.
     {
         std::lock_guard<std::mutex> lock(gTuningMutex);
         readTuning();

@@ -32,19 +32,13 @@
 #define MSDF_UNIFORM(x) (x)
 #endif
 
-#if defined(MSDF_NO_UNLIKELY)
-#define MSDF_UNLIKELY(x) (x)
-#else
-#define MSDF_UNLIKELY(x) __builtin_expect(!!(x), 0)
-#endif   // a cold path: the register allocator places its spill code by block frequency
+#define MSDF_UNLIKELY(x) __builtin_expect(!!(x), 0)   // a cold path: the register allocator places its spill code by block frequency
 
 namespace msdfhip {
 
 // Wave vote: does ANY lane of the wavefront need this? Used where skipping work is exact whenever no lane needs it and evaluating more is
 // harmless (the walk of k_distance is wave-uniform: every lane looks at the same edge / contour).
-#if defined(MSDF_NO_DYNAMIC_CULL)
-#define MSDF_WAVE_ANY(pred) (true)
-#elif defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
 #define MSDF_WAVE_ANY(pred) (__any((int) (pred)) != 0)
 #else
 #define MSDF_WAVE_ANY(pred) (pred)                   // host walk: one "lane" at a time, i.e. the most aggressive skipping
@@ -135,7 +129,7 @@ MSDF_HD double cross(V2 a, V2 b) { return a.x*b.y-a.y*b.x; }
 // is the identity and the patch never applies: the SAME seven FMAs without them yield the same bits with 10 instead of 18 instructions.
 // The wavefront takes the compiler's sqrt whenever any lane is outside that range (a texel exactly on a control point: x = 0).
 // msdfhip_debug_sqrt_mismatches compares the two on the device (tests/test_gpu_parity.py).
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MSDF_NO_LEAN_SQRT)
+#if defined(__HIP_DEVICE_COMPILE__)
 __device__ inline double leanSqrtCore(double x) {
     const double y = __builtin_amdgcn_rsq(x);
     double g = x*y;
@@ -202,13 +196,8 @@ MSDF_HD double dmax(double a, double b) { return a < b ? b : a; }
 // For the CONSERVATIVE tests only (tile cull, per-texel relevance: they decide what is evaluated, never a value): the hardware's
 // v_max_f64 / v_min_f64 -- one instruction where the reference-exact dmax / dmin (b < a ? b : a, whose NaN and signed-zero behaviour
 // differs from IEEE maxNum) costs a compare and two selects.
-#if defined(MSDF_EXACT_MINMAX_EVERYWHERE)
-MSDF_HD double cmax(double a, double b) { return dmax(a, b); }
-MSDF_HD double cmin(double a, double b) { return dmin(a, b); }
-#else
 MSDF_HD double cmax(double a, double b) { return __builtin_fmax(a, b); }
 MSDF_HD double cmin(double a, double b) { return __builtin_fmin(a, b); }
-#endif
 MSDF_HD double median(double a, double b, double c) { return dmax(dmin(a, b), dmin(dmax(a, b), c)); }
 MSDF_HD float fmin_(float a, float b) { return b < a ? b : a; }
 MSDF_HD float fmax_(float a, float b) { return a < b ? b : a; }
@@ -581,11 +570,6 @@ template <class Rec> MSDF_HD SD sdCubic(const Rec &e, V2 o, double &param) {    
 }
 
 template <class Rec> MSDF_HD SD signedDistance(const Rec &e, V2 o, double &param) {
-#if defined(MSDF_ONLY_TYPE)
-    if (MSDF_ONLY_TYPE == 1) return sdLinear(e, o, param);
-    if (MSDF_ONLY_TYPE == 2) return sdQuadratic(e, o, param);
-    if (MSDF_ONLY_TYPE == 3) return sdCubic(e, o, param);
-#endif
     if (e.Type() == 1)
         return sdLinear(e, o, param);
     if (e.Type() == 2)
@@ -647,24 +631,13 @@ MSDF_HD void pbInit(PB &b) {             // edge-selectors.cpp:54 followed by re
 // the tie-break dot is never negative), so a stored minimum is never -DBL_MAX again.
 MSDF_HD bool pbHasNear(const PB &b) { return b.td != -DBL_MAX; }
 
-MSDF_HD void pbAddPerp(PB &b, double d) {                                    // edge-selectors.cpp:89-94
-    if (d <= 0 && d > b.neg)
-        b.neg = d;
-    if (d >= 0 && d < b.pos)
-        b.pos = d;
-}
-// ... for a channel the edge may or may not carry (on: wave-uniform in k_distance). Folded into the conditions, the channel test is a scalar
-// AND on the compare masks; as "if (on) pbAddPerp()" the compiler selected twice (new value, then channel).
+// edge-selectors.cpp:89-94 for a channel the edge may or may not carry (on: wave-uniform in k_distance). Folded into the conditions, the channel
+// test is a scalar AND on the compare masks; as "if (on) addPerp()" the compiler selected twice (new value, then channel).
 MSDF_HD void pbAddPerpIf(PB &b, double d, bool on) {
-#if defined(MSDF_NO_DIET_PERPMASK)
-    if (on)
-        pbAddPerp(b, d);
-#else
     if (on & (d <= 0) & (d > b.neg))
         b.neg = d;
     if (on & (d >= 0) & (d < b.pos))
         b.pos = d;
-#endif
 }
 
 MSDF_HD void pbMerge(PB &b, const PB &o) {                                   // edge-selectors.cpp:96-106
@@ -679,9 +652,6 @@ MSDF_HD void pbMerge(PB &b, const PB &o) {                                   // 
 
 // pbMerge for the wave-uniform walk of k_distance: the three selects of the minimum only when some lane's contour is nearer.
 MSDF_HD void pbMergeWave(PB &b, const PB &o) {
-#if defined(MSDF_NO_DIET_MERGE)
-    pbMerge(b, o);
-#else
     SD a = { o.td, o.tdot }, c = { b.td, b.tdot };
     const bool less = sdLess(a, c);
     if (MSDF_WAVE_ANY(less)) {
@@ -692,7 +662,6 @@ MSDF_HD void pbMergeWave(PB &b, const PB &o) {
         b.neg = o.neg;
     if (o.pos < b.pos)
         b.pos = o.pos;
-#endif
 }
 
 MSDF_HD double pbCompute(const PB &b) {                                      // edge-selectors.cpp:108-117
@@ -748,15 +717,11 @@ MSDF_HD bool sdReplaces(SD sd, int idx, SD cur, int curIdx) {
 // tie-break (three more compares) is evaluated only when SOME lane has an exact tie (edges meeting in a corner point, seen from a texel
 // beyond it).
 MSDF_HD bool sdReplacesWave(SD sd, int idx, SD cur, int curIdx) {
-#if defined(MSDF_NO_DIET_TIES)
-    return sdReplaces(sd, idx, cur, curIdx);
-#else
     const double a = fabs(sd.d), b = fabs(cur.d);
     bool r = a < b;
     if (MSDF_WAVE_ANY(a == b))
         r = r || (a == b && (sd.dot < cur.dot || (sd.dot == cur.dot && idx < curIdx)));
     return r;
-#endif
 }
 
 // addEdge: edge-selectors.cpp:19-29 (true), :129-160 (perpendicular), :174-227 (multi)
@@ -829,16 +794,6 @@ MSDF_HD bool selEdgeRelevantBox(const Selector<SEL> &s, const Rec &e, V2 o, doub
         if (!mask)
             return false;
         bound2 = 0;
-#if defined(MSDF_NO_DIET_BOUND)
-        for (int i = 0; i < (int) SelTraits<SEL>::NPB; ++i)
-            if (mask&(1<<i))
-                bound2 = cmax(bound2, s.c[i].td*s.c[i].td);
-#elif defined(MSDF_NO_DIET_BOUNDMAX)
-        // a channel the edge does not carry contributes (td*0)*td = +0 (also for td = -DBL_MAX): the wave-uniform channel bit becomes a scalar
-        // factor of the product instead of two selects per channel
-        for (int i = 0; i < (int) SelTraits<SEL>::NPB; ++i)
-            bound2 = cmax(bound2, (s.c[i].td*((mask&(1<<i)) ? 1. : 0.))*s.c[i].td);
-#else
         // max over the carried channels of td^2 == (max of |td|)^2: rounding is monotonic, so squaring the maximum once yields the very value the
         // maximum of the squares had (round 6, tools/isa_bbcount.py: this test is 10 % of the kernel's VALU instructions; 7 instead of 10 of them
         // build the bound). The channel bit stays a scalar factor (|td|*0 = +0, also for td = -DBL_MAX); the absolute value is an operand modifier.
@@ -846,7 +801,6 @@ MSDF_HD bool selEdgeRelevantBox(const Selector<SEL> &s, const Rec &e, V2 o, doub
         for (int i = 0; i < (int) SelTraits<SEL>::NPB; ++i)
             t = cmax(t, fabs(s.c[i].td)*((mask&(1<<i)) ? 1. : 0.));
         bound2 = t*t;
-#endif
     }
     bound2 *= 1+1e-9;                                // (-DBL_MAX)^2 = inf: nothing is skipped until a channel has a candidate
     const double dx = cmax(cmax(e.Lo().x-o.x, o.x-e.Hi().x), 0.);
@@ -1150,18 +1104,7 @@ MSDF_HD void shapeDistanceOverlap(const EdgeRec *rec, const Edges &edges, const 
                     res[(c*NCH+ch)*rstride] = d[ch];
                 const double m = resolve<SEL>(d);
                 const int w = windings[c];
-#if !defined(MSDF_DIET_FIRSTCONTOUR)
-                selMerge(acc, sel);
-#else                                                 // measured: +31 spilled VGPRs in <3,true,false> (the branch keeps both paths live); off
-                // merge(initial state, sel) == sel, field by field (edge-selectors.cpp:96-106 against :54: any minimum beats -DBL_MAX, an
-                // untouched channel IS the initial state): the first contour's selector is copied instead of merged
-                if (c == 0) {
-                    acc.m = sel.m;
-                    for (int i = 0; i < (int) SelTraits<SEL>::NPB; ++i)
-                        acc.c[i] = sel.c[i];
-                } else
-                    selMerge(acc, sel);
-#endif
+                selMerge(acc, sel);                           // (copying the first contour's selector instead: measured +31 spilled VGPRs in <3,true,false>, the branch keeps both paths live)
                 if (w > 0 && m >= 0) {
                     if (!nInner)
                         firstInner = c;
@@ -1196,11 +1139,6 @@ MSDF_HD void shapeDistanceOverlap(const EdgeRec *rec, const Edges &edges, const 
     else
         for (int ch = 0; ch < NCH; ++ch)
             shapeD[ch] = parked[ch];
-#if defined(MSDF_ABLATE_EPILOGUE)                                   // measurement only: what the combiner's selection loops over the stored distances cost
-    for (int ch = 0; ch < NCH; ++ch)
-        out[ch] = shapeD[ch]+(double) (nInner+nOuter+firstInner+firstOuter);
-    return;
-#endif
     combinerEpilogue<SEL>(edges, windings, C, res, rstride, nInner, nOuter, firstInner, firstOuter, second, shapeD, parked, out);
 }
 
@@ -1297,11 +1235,6 @@ MSDF_HD void shapeDistanceOverlapSplit(const EdgeRec *rec, const Edges &edges, c
         for (int ch = 0; ch < NCH; ++ch)
             shapeD[ch] = parked[ch];
     }
-#if defined(MSDF_ABLATE_EPILOGUE)
-    for (int ch = 0; ch < NCH; ++ch)
-        out[ch] = shapeD[ch]+(double) (nInner+nOuter+firstInner+firstOuter);
-    return;
-#endif
     combinerEpilogue<SEL>(edges, windings, C, res, rstride, nInner, nOuter, firstInner, firstOuter, second, shapeD, parked, out);
 }
 

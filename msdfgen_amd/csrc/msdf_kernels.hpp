@@ -65,20 +65,14 @@ struct WaveCtx {
 };
 
 enum { PREP_WINDING_LDS_EDGES = 768 };                              // edges whose point(0) a winding wavefront parks in LDS at a time (12 KB; contours beyond: contourWindingsWave)
-#ifndef MSDF_PREP_ABLATE
-#define MSDF_PREP_ABLATE 0                                          // measurement builds only: 1 no windings, 3 no records (2, no contour search, hangs: a wrong contour makes visitToEdge loop)
-#endif
 // The first edgeBlocks workgroups digest one edge per thread; the workgroups after them compute the contour windings (k_windings' job, folded
-// into the same launch: the single-shape entry points are launch-latency bound): a lane per contour, except that contours of at least
-// PREP_WINDING_WAVE_MIN_EDGES edges -- whose serial walk by one lane would be the tail of the whole launch -- are taken by their wavefront together,
-// lanes = edges (contourWindingsWave). (All of a wavefront's 64 contours that way was measured SLOWER than a lane each: 0.154 vs 0.097 ms on the bench
-// workload -- ten rounds of loads and ~600 ordered additions per wavefront where most contours have ten edges.) blockDim.x = 256.
+// into the same launch: the single-shape entry points are launch-latency bound), a group of contours whose edges fit the wavefront's LDS area
+// at a time (below); a contour beyond that area is taken by its wavefront together, lanes = edges (contourWindingsWave). (All of a wavefront's
+// 64 contours that way was measured SLOWER than a lane each: 0.154 vs 0.097 ms on the bench workload -- ten rounds of loads and ~600 ordered
+// additions per wavefront where most contours have ten edges.) blockDim.x = 256.
 __global__ void k_prep_records(EdgeRec *recs, int nEdges, int nContours, const int32_t *contourOffsets,
                                const double *points, const uint8_t *types, const uint8_t *colors, int8_t *windings, int edgeBlocks) {
     if ((int) blockIdx.x >= edgeBlocks) {
-#if MSDF_PREP_ABLATE == 1                                            // measurement only: no windings
-        return;
-#endif
         __shared__ double terms[4][64];
         const int wave = threadIdx.x>>6, lane = threadIdx.x&63;
         const int cBegin = ((int) blockIdx.x-edgeBlocks)*256+64*wave;
@@ -86,12 +80,7 @@ __global__ void k_prep_records(EdgeRec *recs, int nEdges, int nContours, const i
             return;
         const int c = cBegin+lane;
         const int cb = c < nContours ? contourOffsets[c] : 0, ce = c < nContours ? contourOffsets[c+1] : 0;
-#if !defined(MSDF_PREP_LANE_WINDINGS)
         const bool isLong = c < nContours && ce-cb > PREP_WINDING_LDS_EDGES;    // (beyond the LDS area: contourWindingsWave, a wavefront per contour, as before)
-#else
-        const bool isLong = c < nContours && ce-cb >= PREP_WINDING_WAVE_MIN_EDGES;
-#endif
-#if !defined(MSDF_PREP_LANE_WINDINGS)
         // Round 6: a lane per contour made one DEPENDENT, first-touch memory round trip per edge -- up to 47 of them, 0.073 of the digest's 0.114 ms with
         // the edge workgroups long gone (variants/pab1: the launch without windings). Now in two steps per group of consecutive contours whose edges fit the
         // wavefront's LDS area: lanes = EDGES load the rows (coalesced, independent) and park point(0) of every edge (edge-segments.cpp:108-119, the
@@ -140,10 +129,6 @@ __global__ void k_prep_records(EdgeRec *recs, int nEdges, int nContours, const i
             sync.sync();
             done += count;
         }
-#else
-        if (c < nContours && !isLong)
-            windings[c] = (int8_t) contourWinding(c, contourOffsets, points, types, colors);
-#endif
         unsigned long long longMask = __ballot(isLong);
         WaveCtx ctx;
         ctx.lane = lane;
@@ -158,9 +143,6 @@ __global__ void k_prep_records(EdgeRec *recs, int nEdges, int nContours, const i
     if (slot >= nEdges)
         return;
     int lo = 0, hi = nContours-1;               // last contour c with contourOffsets[c] <= slot (skips empty contours)
-#if MSDF_PREP_ABLATE == 3                                            // measurement only: no records
-    return;
-#endif
     while (lo < hi) {
         int mid = (lo+hi+1)>>1;
         if (contourOffsets[mid] <= slot)
@@ -447,14 +429,10 @@ __device__ inline void selAddContour(Selector<SEL> &sel, const EdgeRec *rec, con
         // 6.28 ms per step; a batch lands in 380 cycles on average, 4 % of a wavefront's life. It also cannot be made safe in C++: the
         // dummy destination of an unwaited s_load may be copied or spilled by the register allocator and its register reused while the
         // load is still in flight. Gone.)
-#if defined(MSDF_ONE_STAGE_RELEVANCE)                               // A/B only
-        const bool relevant = MSDF_WAVE_ANY(selEdgeRelevant(sel, r, o));
-#else
         double bound2;
         bool relevant = MSDF_WAVE_ANY(selEdgeRelevantBox(sel, r, o, bound2));      // some lane within reach of the control box: evaluate, whatever the wedges say
         if (SEL >= 2 && !relevant)
             relevant = MSDF_WAVE_ANY(selEdgeRelevantWedges<SEL>(r, o, bound2));
-#endif
 #if defined(MSDF_PROFILE_WAITS)
         MSDF_STAMP(t2);
         edges.prof[6] += t2-t1;
@@ -520,9 +498,6 @@ __device__ inline void selAddContour(Selector<SEL> &sel, const EdgeRec *rec, con
 // order, so the result does not depend on how the contour's edges were dealt (the same argument, and the same function, as the team of k_single_call).
 // All S lanes of a candidate hold identical values afterwards and take identical branches; xor-shuffles below S never leave the (aligned) group, so
 // divergence BETWEEN candidates (second walks of the combiner) cannot make a lane read an inactive one.
-#ifndef MSDF_QGRID_ABLATE
-#define MSDF_QGRID_ABLATE 0                                         // measurement builds only (profiles/r06_ab_notes.md 12): 1 loads without evaluation, 2 one record for all lanes, 3 no items, 4 no distance query, 5 no loads / evaluation, 6 no shuffles either, 7 grid items only, 8 all but the grid items, 9 cooperative items without their query, 10 cooperative rounds without loads / evaluation
-#endif
 struct EdgesGrid {
     const int32_t *coff;
     int slice, S;
@@ -534,24 +509,13 @@ __device__ inline void selAddContour(Selector<2> &sel, const EdgeRec *rec, const
     Selector<2> mine;
     selInit(mine);
     const int e = MSDF_UNIFORM(edges.end(c));
-#if MSDF_QGRID_ABLATE >= 5                                          // measurement only: no loads, no evaluation (6: no shuffles either)
-    mine.c[0].td = o.x, mine.c[0].tdot = o.y+e;
-#endif
     MSDF_NOUNROLL
-    for (int i = MSDF_UNIFORM(edges.begin(c))+edges.slice; i < (MSDF_QGRID_ABLATE >= 5 ? 0 : e); i += edges.S) {
-#if MSDF_QGRID_ABLATE == 2                                          // measurement only: every lane evaluates the contour's first record (loads coalesce and hit)
-        const EdgeRegs r = loadEdgeRegs(rec+MSDF_UNIFORM(edges.begin(c)), i);
-#else
+    for (int i = MSDF_UNIFORM(edges.begin(c))+edges.slice; i < e; i += edges.S) {
         const EdgeRegs r = loadEdgeRegs(rec+i, i);
-#endif
-#if MSDF_QGRID_ABLATE == 1                                          // measurement only: the loads without the evaluation
-        mine.c[0].neg += r.r0[0]+r.r1[1]+r.e0[2]+r.e1[3]+r.e2[4];
-#else
         selAddEdge(mine, r, i, o);
-#endif
     }
     MSDF_NOUNROLL
-    for (int off = 1; off < (MSDF_QGRID_ABLATE == 6 ? 1 : edges.S); off <<= 1) {
+    for (int off = 1; off < edges.S; off <<= 1) {
         Selector<2> other;
         selInit(other);
         PB &m = mine.c[0], &t = other.c[0];
@@ -572,9 +536,6 @@ struct PsdfQueryGrid {                                              // PsdfQuery
     double *res;
     __device__ double operator()(V2 q) const {
         double out[1];
-#if MSDF_QGRID_ABLATE == 4                                          // measurement only: candidate, texels, interpolation, stores -- no distance query
-        return q.x+q.y;
-#endif
         EdgesGrid edges;
         edges.coff = coff, edges.slice = slice, edges.S = S;
         if (OVERLAP)
@@ -744,10 +705,6 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
         // The bounds U[ch] are per contour for the overlapping combiner (one selector per contour, every contour's own distance is
         // needed) and over the whole shape for the simple combiner (a single selector).
         double U[3] = { DBL_MAX, DBL_MAX, DBL_MAX };
-#if defined(MSDF_ABLATE_PHASE1)                                     // measurement only (with MSDF_ABLATE_PHASE2): launch + header loads + stores
-        for (int c = col; c < C; c += ROW)
-            cstart[c] = 0;
-#else
         const int nE = knownEdges >= 0 ? knownEdges : coff[C]-e0;
 #if defined(MSDF_PROFILE_WAITS)
         unsigned long long pHdr;
@@ -815,11 +772,7 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
                     for (int ch = 0; ch < (SEL <= 2 ? 1 : 3); ++ch)
                         if ((mask>>ch)&1)
                             umax = dmax(umax, OVERLAP ? (double) __int_as_float((int) bounds[(size_t) c*3+ch]) : U[ch]);
-#if defined(MSDF_NO_TILE_CULL)
-                    keep = true;
-#else
                     keep = cullEdgeSurvives<(SEL >= 2)>(rec[i], tc, tr, umax);
-#endif
                 }
             }
             // key = (contour segment within the 16-lane row | distance | slot): contours stay grouped, nearest first inside each. The
@@ -849,7 +802,6 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
         for (int c = col; c < C; c += ROW)                          // empty contours at the end
             if (coff[c]-e0 == nE)
                 cstart[c] = nSurv;
-#endif
         if (col == 0)
             cstart[C] = nSurv;
     }
@@ -895,9 +847,6 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
             continue;
         const V2 p = fastXf ? mk(divExact(x+.5, t.sx, rsx)-t.tx, divExact(y+.5, t.sy, rsy)-t.ty)
                             : unproject(t, mk(x+.5, y+.5));         // msdfgen.cpp:68 (coord/scale-translate, correctly rounded either way)
-#if defined(MSDF_LAZY_RECORDS)                                      // A/B only: compiler-placed field loads, one dependent round trip each
-        EdgesCulled edges;
-#else
         EdgesCulledPacked edges;
         edges.total = MSDF_UNIFORM(cstarts[(size_t) q*(C+1)+C]);
 #if defined(MSDF_PROFILE_WAITS)
@@ -905,35 +854,23 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
             edges.prof[i] = 0;
         MSDF_STAMP(tTile0);
 #endif
-#endif
         edges.cstart = cstarts+(size_t) q*(C+1);
         edges.list = lists+(size_t) q*maxEdges;
-#if !defined(MSDF_LAZY_RECORDS)
         edges.first = teamRank, edges.step = TEAM;
-#endif
         TeamExchange<TEAM> team;
         team.x = teamXchg, team.lane = lane, team.rank = teamRank;
         double d[NCH];
-#if defined(MSDF_ABLATE_PHASE2)                                     // measurement only: what phase 1 + the launch cost alone
-        for (int ch = 0; ch < NCH; ++ch)
-            d[ch] = (double) edges.cstart[C];
-#else
         if (OVERLAP) {
-#if defined(MSDF_LAZY_RECORDS) || defined(MSDF_ONE_PASS_LOOP)    // A/B: the single rolled pass loop of rounds 2-5
-            shapeDistanceOverlap<SEL>(rec, edges, wind, C, p, res+lane, WAVE, d);
-#else
             EdgesCulled cold;                                       // the rare second walks: the same survivor lists, record fields loaded where they are used
             cold.cstart = edges.cstart, cold.list = edges.list;
             if (TEAM > 1)
                 shapeDistanceOverlapSplit<SEL>(rec, edges, cold, wind, C, p, res+lane, WAVE, d, team);
             else
                 shapeDistanceOverlapSplit<SEL>(rec, edges, cold, wind, C, p, res+lane, WAVE, d);
-#endif
         } else if (TEAM > 1)
             shapeDistanceSimple<SEL>(rec, edges, C, p, d, team);
         else
             shapeDistanceSimple<SEL>(rec, edges, C, p, d);
-#endif
         if (TEAM > 1 && teamRank != 0)
             continue;                                               // a helper: the leader holds the tile's distances and stores them
         // The texel's coordinates are derived AGAIN from the lane index here, through a copy the compiler cannot see through: kept live across the walk,
@@ -947,15 +884,11 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
         float *px = toScratch ? dst+(((size_t) wk.g*height+yn)*width+xo)*NCH
                               : dst+gd.out_offset+(ptrdiff_t) gd.row_stride*yn+(ptrdiff_t) NCH*xo;
         for (int ch = 0; ch < NCH; ++ch) {
-#if !defined(MSDF_PLAIN_TILE_STORES)
             // streaming (nontemporal) stores: 400 MB of tiles per pass otherwise push the 128-VGPR kernels' scratch lines out of L2 (round 5, A/B: the pass's
             // FETCH_SIZE 361 -> 160 MB, WRITE_SIZE 2.98 -> 2.80 GB, step 5.47 -> 5.39 ms)
             __builtin_nontemporal_store(mapDistance(t, d[ch]), &px[ch]);   // msdfgen.cpp:20-48
-#else
-            px[ch] = mapDistance(t, d[ch]);
-#endif
         }
-#if defined(MSDF_PROFILE_WAITS) && !defined(MSDF_LAZY_RECORDS)
+#if defined(MSDF_PROFILE_WAITS)
         {
             MSDF_STAMP(tTile1);
             edges.prof[13] += tTile1-tTile0;                        // whole tile: prologue + distance + stores
@@ -1064,12 +997,8 @@ __device__ inline void selAddContour(Selector<2> &sel, const EdgeRec *rec, const
                 if (i < edges.nE) {
                     Selector<2> mine;
                     selInit(mine);
-#if MSDF_QGRID_ABLATE != 10                                         // (10, measurement only: cooperative rounds without loads / evaluation)
                     const EdgeRegs r = loadEdgeRegs(rec+i, i);
                     selAddEdge(mine, r, i, o);
-#else
-                    mine.c[0].td = o.x+i, mine.c[0].tdot = o.y;
-#endif
                     edges.slots[i] = mine.c[0];
                 }
             }
@@ -1115,12 +1044,8 @@ __device__ inline void selAddContour(Selector<2> &sel, const EdgeRec *rec, const
         selInit(mine);
         const int i = base+edges.lane;
         if (i < e) {
-#if MSDF_QGRID_ABLATE != 10
             const EdgeRegs r = loadEdgeRegs(rec+i, i);
             selAddEdge(mine, r, i, o);
-#else
-            mine.c[0].td = o.x+i, mine.c[0].tdot = o.y;
-#endif
         }
         PB &m = mine.c[0];
         MSDF_UNROLL
@@ -1161,9 +1086,6 @@ struct PsdfQueryCooperative {                                       // same quer
         for (int i = 0; i < 16; ++i)
             edges.prof[i] = 0;
         const unsigned long long qq0 = qNow();
-#endif
-#if MSDF_QGRID_ABLATE == 9                                          // measurement only: cooperative items without their distance query
-        return q.x+q.y;
 #endif
         if (slots)
             waveSync();                                             // the previous query's slot reads are done
@@ -1371,11 +1293,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     const int x = tx*TILE+lx, yn = ty*TILE+ly;
     const bool inside = x < width && yn < height;
     int st = 0;
-#if defined(MSDF_EC_ABLATE) && MSDF_EC_ABLATE == 1                          // measurement only: halo load + store, no classification
-    const bool classify = false;
-#else
     const bool classify = inside;
-#endif
     Neighbourhood nb;
     nb.valid = 0;
     if (classify) {
@@ -1421,11 +1339,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     waveSync();
 
     // ---- phase B (lane = queued pair): protectEdges' edgeBetweenTexels tests, densely; a hit protects the owning texel
-#if defined(MSDF_EC_ABLATE) && MSDF_EC_ABLATE <= 2
-    const int nProtect = 0;
-#else
     const int nProtect = itemCount[1];
-#endif
     for (int base = 0; base < nProtect; base += WAVE) {
         const int it = base+lane;
         if (it >= nProtect)
@@ -1440,11 +1354,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     waveSync();
 
     // ---- phase C (lane = queued test): stage 2, densely; verdicts are OR-ed into the owning texel's word
-#if defined(MSDF_EC_ABLATE) && MSDF_EC_ABLATE <= 3
-    const int nItems = 0;
-#else
     const int nItems = itemCount[0];
-#endif
     for (int base = 0; base < nItems; base += WAVE) {
         const int it = base+lane;
         if (it >= nItems)
@@ -1807,18 +1717,6 @@ k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const i
         const bool qChunk = ecQueryListedFirst(count, nE, C, lpcMaxContours);
 #endif
         const int gridS = ecQueryGridSlices(count, nE, C, lpcMaxContours);
-#if MSDF_QGRID_ABLATE == 3                                          // measurement only: ticket, lookup and glyph state of every item, nothing else
-        if (count != 0xffffffffu)
-            continue;
-#endif
-#if MSDF_QGRID_ABLATE == 7                                          // measurement only: the grid items alone (no cooperative, no lane-per-candidate items)
-        if (!gridS)
-            continue;
-#endif
-#if MSDF_QGRID_ABLATE == 8                                          // measurement only: without the grid items
-        if (gridS)
-            continue;
-#endif
         if (gridS) {                                                // lanes = (candidate, slice): 64 / gridS candidates per item
             PsdfQueryGrid<OVERLAP, WindingMasks> query;
             query.rec = batch.recs+coff[0], query.coff = coff, query.windings = wind, query.C = C, query.res = smemLds+threadIdx.x;

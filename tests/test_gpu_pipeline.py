@@ -357,7 +357,7 @@ def test_candidate_overflow_in_a_pipeline_chunk_reruns_the_call(glyphs):
     chunk's candidate-overflow count into pinned memory and a call that had one is run again with the pass (msdfhip_pipeline_overflow_reruns). Overlapping
     strokes rendered WITHOUT overlap support under ALWAYS_CHECK_DISTANCE overflow their candidate segments (tests/test_gpu_parity.py:
     test_candidate_segment_overflow_is_handled_per_glyph): mixed into ordinary glyphs, through packed float tiles, the 8-bit atlas and the streamed generator
-    -- bytes must equal the device batch (whose correction always launches the pass), with and without the mirror."""
+    -- bytes must equal the device batch (whose correction always launches the pass), through the rerun that launches it in every chunk."""
     from msdfgen_amd import synth
     from msdfgen_amd.shape import autoframe
     sub, xfs, want48 = glyphs
@@ -397,16 +397,6 @@ def test_candidate_overflow_in_a_pipeline_chunk_reruns_the_call(glyphs):
     finally:
         lib.msdfhip_set_pipeline_chunk(0)
         hb.close()
-    # the round-4 form (every chunk launches the pass) gives the same bytes
-    import os
-    os.environ["MSDFHIP_PIPELINE_OVERFLOW_PASS"] = "1"
-    lib.msdfhip_reload_tuning()
-    try:
-        got = M.generate_stream(mix, M.MODE_MSDF, 48, 48, mxf, config=c)
-        assert (bits(got) == bits(want)).all() and lib.msdfhip_pipeline_overflow_reruns(1) == 0
-    finally:
-        del os.environ["MSDFHIP_PIPELINE_OVERFLOW_PASS"]
-        lib.msdfhip_reload_tuning()
 
 
 def test_automatic_chunk_schedules_at_full_tile_size():
