@@ -322,7 +322,11 @@ template <int N>
 MSDF_HD double sdfErrorOfLine(const EdgeRec *rec, int nE, const float *px, int w, int h, double sx, double sy, double tx, double ty, bool yDown,
                               int row, int subRow, int scanlinesPerRow, int fillRule, StridedList &refList, StridedList &sdfList) {
     const double subRowSize = 1./scanlinesPerRow;
-    const double xFrom = .5/sx-tx, xTo = (w-.5)/sx-tx;
+    double xFrom = .5/sx-tx, xTo = (w-.5)/sx-tx;
+    if (xFrom > xTo) {                                          // a negative x scale: Scanline::overlap never ends on a reversed interval (its first
+        const double x = xFrom;                                 // loop waits for xTo to pass xFrom); the row is measured over the same texel
+        xFrom = xTo, xTo = x;                                   // centres in ascending order instead
+    }
     const double overlapFactor = 1/(xTo-xFrom);
     const double bt = (subRow+.5)*subRowSize;
     const double y = (row+bt+.5)/sy-ty;

@@ -2176,6 +2176,10 @@ double orc_estimate_sdf_error(const orc_shape *shape, const float *px, int w, in
     double subRowSize = 1./scanlinesPerRow;
     double xFrom = .5/sx-tx;
     double xTo = (w-.5)/sx-tx;
+    if (xFrom > xTo) {          /* negative x scale: the reference never returns (Scanline.cpp:33 waits for xTo to pass xFrom); ascending order instead */
+        double x = xFrom;
+        xFrom = xTo, xTo = x;
+    }
     double overlapFactor = 1/(xTo-xFrom);
     double error = 0;
     int nE = shape->contour_offsets[shape->n_contours];

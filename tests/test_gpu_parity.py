@@ -214,6 +214,17 @@ def test_fuzz_sweep_single_calls_vs_oracle():
     assert r["shapes"] >= 300 and r["max_abs_delta"] <= TOL and r["values_differing_bitwise"] <= r["values_compared"]*1e-6, r
 
 
+def test_fuzz_sweep_framings_vs_oracle():
+    """The same generator under the framings of tests/xformcases.py instead of autoframe (mirrored, anisotropic, zoomed, off-tile, odd ranges, all-ones
+    scale significands, far-off coordinates, tiny bitmaps), batched and Y up or down at random per group."""
+    import fuzzlib
+    import xformcases
+    r = fuzzlib.run(1500, 421, deadline_s=60, framing=xformcases.FAMILIES)
+    print(r)
+    assert r["shapes"] >= 300 and r["max_abs_delta"] <= TOL and r["values_differing_bitwise"] <= r["values_compared"]*1e-6, r
+    assert len(r["framings"]) >= 8, r
+
+
 def test_degenerate_and_empty_inputs(oracle):
     empty = FlatShape(np.zeros(1, np.int32), np.zeros((0, 8)), np.zeros(0, np.int32), np.zeros(0, np.int32))
     xf = np.array([10., 10., .1, .1, -.2, .2])
