@@ -256,7 +256,6 @@ struct ScopedTimer {
 
 } // namespace
 
-struct EcAheadRequest { int channels, w, h; const MsdfHipGlyph *dGlyphs; const MsdfHipConfig *cfg; };
 struct MsdfHipBatch {
     int device;                       // the HIP device the batch lives on; every call on the batch binds the calling thread to it
     int nGlyphs, nContours, nEdges, maxContours, maxEdges;
@@ -289,25 +288,28 @@ struct MsdfHipBatch {
     mutable int nHuge, restMaxC, restMaxE;   // glyphs whose survivor lists exceed a CU's LDS (list-free kernel, last in dBucket); maxima of the class before them
     mutable float restShare;          // the global-scratch class's share of the batch's modelled cost (glyphCost): sizes its persistent launch
     bool serialClasses;               // launch the glyph classes one after the other on the caller's stream (host-output pipeline: its chunks overlap instead)
-    unsigned *overflowOut;            // single-shape host calls: where k_ec_query mirrors the candidate-overflow count (then no k_ec_slow launch)
-    mutable bool overflowMirrored;    // set by the correction launch when it did so
     mutable int *hEcOrder;            // (pinned host copy the list below is uploaded from)
     mutable hipEvent_t ecOrderReady;  // (recorded behind that upload)
     mutable int *dEcOrder;            // glyph indices heaviest first (k_ec_scan / k_ec_query), built on first use; NULL: batch order
     mutable bool ecOrderTried;
-    mutable const struct EcAheadRequest *ecAheadWanted;   // msdfhip_batch_generate: the coming correction pass's k_ec_params may run NEXT TO the distance pass -- dispatchDistance queues it on a side stream behind the fork and clears this
-    mutable bool ecParamsAhead;       // k_ec_params of the coming correction pass was launched ahead of the distance pass (prepareAhead): launchEc skips it
-    mutable hipEvent_t afterDistance; // host-output pipeline: recorded on the call's stream between the distance pass and what follows it (NULL: not wanted)
     int glyphCap;                     // per-glyph work buffers are sized for max(nGlyphs, glyphCap) glyphs (views of the host-output pipeline)
     mutable hipStream_t sideStream[2];   // the three glyph classes of the distance pass run concurrently: two of them on these (fork / join by events)
     mutable hipEvent_t forkEvent, joinEvent[2];
     MsdfHipBatch() : device(0), nGlyphs(0), nContours(0), nEdges(0), maxContours(0), maxEdges(0), ownsInputs(false), dGlyphContourOffsets(NULL),
                      dContourOffsets(NULL), dPoints(NULL), dTypes(NULL), dColors(NULL), dRecs(NULL), dWindings(NULL), dScratch(NULL), scratchFloats(0),
                      dDeferred(NULL), dEcParams(NULL), dGres(NULL), dWorkQueue(NULL), queueParity(0), gresBytes(0), gresExternal(false), deferredCap(0), bucketLimit(-1), dBucket(NULL), hBucket(NULL), bucketExternal(false), bucketUploaded(false), nOne(0), nSmall(0),
-                     smallMaxC(0), smallMaxE(0), oneMaxE(0), nHuge(0), restMaxC(0), restMaxE(0), restShare(1.f), serialClasses(false), overflowOut(NULL), overflowMirrored(false), hEcOrder(NULL), ecOrderReady(NULL), dEcOrder(NULL), ecOrderTried(false), ecAheadWanted(NULL), ecParamsAhead(false), afterDistance(NULL), glyphCap(0), forkEvent(NULL) { sideStream[0] = sideStream[1] = NULL, joinEvent[0] = joinEvent[1] = NULL; }
+                     smallMaxC(0), smallMaxE(0), oneMaxE(0), nHuge(0), restMaxC(0), restMaxE(0), restShare(1.f), serialClasses(false), hEcOrder(NULL), ecOrderReady(NULL), dEcOrder(NULL), ecOrderTried(false), glyphCap(0), forkEvent(NULL) { sideStream[0] = sideStream[1] = NULL, joinEvent[0] = joinEvent[1] = NULL; }
 };
 
 namespace {
+
+// What one generate call passes down its launch chain. Each caller builds it on its stack: nothing of a call, failed or not, stays on the batch.
+struct GenerateCall {
+    bool ecParamsQueued = false;      // k_ec_params of THIS request is already queued on the call's stream (prepareAhead, or next to the distance pass): launchEc skips it
+    hipEvent_t afterDistance = NULL;  // host-output pipeline: recorded on the call's stream between the distance pass and what follows it (NULL: not wanted)
+    unsigned *overflowOut = NULL;     // pipeline chunks, single-shape calls: where k_ec_query mirrors the candidate-overflow count (then no k_ec_slow launch)
+    bool overflowMirrored = false;    // out: the correction pass did so
+};
 
 BatchView viewOf(const MsdfHipBatch *b) {
     BatchView v;
@@ -739,9 +741,12 @@ int overlapClassLimit(int nch) {
     return limitAll;
 }
 
-int runCorrectionAhead(const MsdfHipBatch *b, const EcAheadRequest &req, hipStream_t stream);   // (below: runCorrection(..., paramsOnly))
+int runCorrection(const MsdfHipBatch *b, int channels, int w, int h, const MsdfHipGlyph *dGlyphs, const float *src, float *out, uint8_t *stencil,
+                  const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call, bool paramsOnly = false);   // (below)
+// ecAhead: the config of the coming correction pass, whose k_ec_params may run next to the distance pass (NULL: not wanted); call.ecParamsQueued says whether it did.
 template <int SEL>
-int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, float *dst, int toScratch, bool overlap, hipStream_t stream) {
+int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, float *dst, int toScratch, bool overlap, hipStream_t stream,
+                     const MsdfHipConfig *ecAhead, GenerateCall &call) {
     // A glyph whose survivor lists exceed a CU's LDS takes the list-free kernel (the reference cannot fail on a large shape; neither may this) --
     // alone: in a batch, the OTHER glyphs keep the culled kernels (ensureBuckets puts the oversized ones last in the class list; maxE / maxC below
     // are the maxima of the rest). Round 3 sent the whole batch through the list-free kernel with it.
@@ -844,12 +849,11 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
     }
     // (an error between fork and join must not leave side-stream kernels unordered with the caller's stream: the launches only set rc,
     // the join below always runs)
-    if (b->ecAheadWanted && sOne != stream) {
+    int aheadRc = MSDFHIP_OK;
+    if (ecAhead && sOne != stream) {
         // the correction pass's per-glyph constants (k_ec_params: 17 us + a dependent launch behind the join, round 6 timeline) depend on nothing the distance
         // pass writes: ahead of the one-contour class on its side stream
-        const EcAheadRequest *req = b->ecAheadWanted;
-        b->ecAheadWanted = NULL;
-        rc = runCorrectionAhead(b, *req, sOne);
+        aheadRc = runCorrection(b, SelTraits<SEL>::NCH, w, h, dGlyphs, NULL, NULL, NULL, *ecAhead, sOne, call, true);
     }
     if (nRest > 0) {                                             // first: few, heavy glyphs -- the longest tail
         LdsPlan rest = plan;                                     // sized for the batch's largest glyph
@@ -898,6 +902,7 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
             e = hipStreamWaitEvent(stream, b->joinEvent[1], 0);
         joinError = e != hipSuccess ? e : joinError;
     }
+    rc = aheadRc != MSDFHIP_OK ? aheadRc : rc;                   // (queued before the classes: its error is the call's first)
     if (joinError != hipSuccess) {                               // could not order the streams by events: fall back to waiting for them here
         (void) hipGetLastError();
         if (sRest != stream)
@@ -960,9 +965,10 @@ unsigned queryResidentBlocks(int device, size_t lds) {
 
 template <int N, bool OVERLAP, bool GRES>
 int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, const float *src, float *out, uint8_t *stencil,
-             const MsdfHipConfig &cfg, hipStream_t stream, bool paramsOnly = false) {
-    // paramsOnly (prepareAhead): only what does not depend on the distance field -- the work buffers and k_ec_params (per-glyph constants, corner texels,
-    // zeroed candidate header) -- so that it is off the launch chain that follows the distance pass; the full call then skips that launch.
+             const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call, bool paramsOnly) {
+    // paramsOnly (prepareAhead, dispatchDistance): only what does not depend on the distance field -- the work buffers and k_ec_params (per-glyph constants,
+    // corner texels, zeroed candidate header) -- so that it is off the launch chain that follows the distance pass; call.ecParamsQueued says whether it
+    // launched k_ec_params, and the full pass then skips that launch.
     const int tilesX = (w+TILE-1)/TILE, tilesY = (h+TILE-1)/TILE, tiles = tilesX*tilesY;
     const unsigned blocks = (unsigned) b->nGlyphs*(unsigned) tiles;
     const size_t allTexels = (size_t) b->nGlyphs*w*h;
@@ -1067,7 +1073,7 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         if (resident && queryBlocks > resident)
             queryBlocks = resident;
     }
-    if (paramsOnly || !b->ecParamsAhead)                         // (the ahead call ALWAYS launches it: a flag left over from a failed call cannot make both calls skip it)
+    if (!call.ecParamsQueued)
         hipLaunchKernelGGL(k_ec_params, dim3((unsigned) b->nGlyphs), dim3(WAVE), 0, stream, b->dEcParams, viewOf(b), dGlyphs, cfg,
                            reinterpret_cast<unsigned *>(deferred), corners, offsets+ecSizesAt(b->nGlyphs));   // also zeroes the candidate header
     const int *ecOrder = NULL;                                   // glyphs heaviest first for the distance checks' work list (NULL: batch order)
@@ -1076,19 +1082,18 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         return rc;
     if (paramsOnly) {
         HIPCHK(hipGetLastError());
-        b->ecParamsAhead = true;
+        call.ecParamsQueued = true;
         return MSDFHIP_OK;
     }
-    b->ecParamsAhead = false;
     hipLaunchKernelGGL((k_ec_fast<N>), dim3(blocks), dim3(WAVE), fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
                        (const EcGlyphParams *) b->dEcParams, deferred, seg, b->maxEdges, (const int *) corners);
     hipLaunchKernelGGL(k_ec_scan, dim3(1), dim3(1024), 0, stream, b->nGlyphs, reinterpret_cast<const unsigned *>(deferred), seg, offsets, lpcMaxContours, ecOrder);
     hipLaunchKernelGGL((k_ec_query<N, OVERLAP>), dim3(queryBlocks), dim3(WAVE), queryLds, stream, b->nGlyphs, b->dGlyphContourOffsets, b->dContourOffsets,
                        (const EdgeRec *) viewOf(b).recs, viewOf(b).windings, dGlyphs, w, h, src, out, stencil, cfg,
                        (const EcGlyphParams *) b->dEcParams, (const EcCandidate *) deferred, seg, (const int *) offsets, offsets+2*(size_t) b->nGlyphs+2, tuning().queryBatch, slotCap, slotOffset, lpcMaxContours,
-                       b->overflowOut, ecOrder, staticDeal ? (tuning().queryStatic == 2 ? 5 : 1) : 0);
-    if (b->overflowOut)
-        b->overflowMirrored = true;                              // the caller looks at the count after its copy back and reruns with the pass below if needed
+                       call.overflowOut, ecOrder, staticDeal ? (tuning().queryStatic == 2 ? 5 : 1) : 0);
+    if (call.overflowOut)
+        call.overflowMirrored = true;                            // the caller looks at the count after its copy back and reruns with the pass below if needed
     else
         hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(slowGrid), dim3(WAVE), slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
                            (const EcCandidate *) deferred, seg, 1, gres, gresStride);
@@ -1098,12 +1103,12 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
 
 template <int N>
 int dispatchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, const float *src, float *out, uint8_t *stencil,
-               const MsdfHipConfig &cfg, hipStream_t stream, bool paramsOnly = false) {
+               const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call, bool paramsOnly) {
     if (!cfg.overlap_support)
-        return launchEc<N, false, false>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, paramsOnly);
+        return launchEc<N, false, false>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly);
     const bool globalRes = (size_t) b->maxContours*WAVE*sizeof(double) > 96*1024;
-    return globalRes ? launchEc<N, true, true>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, paramsOnly)
-                     : launchEc<N, true, false>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, paramsOnly);
+    return globalRes ? launchEc<N, true, true>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly)
+                     : launchEc<N, true, false>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly);
 }
 
 int checkConfig(const MsdfHipConfig *cfg) {
@@ -1130,19 +1135,16 @@ int ensureScratch(const MsdfHipBatch *b, size_t floats, float **out) {
 
 // Error correction only: src (packed pre-correction tiles) -> out.
 int runCorrection(const MsdfHipBatch *b, int channels, int w, int h, const MsdfHipGlyph *dGlyphs, const float *src, float *out, uint8_t *stencil,
-                  const MsdfHipConfig &cfg, hipStream_t stream, bool paramsOnly = false) {
-    return channels == 3 ? dispatchEc<3>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, paramsOnly) : dispatchEc<4>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, paramsOnly);
-}
-
-int runCorrectionAhead(const MsdfHipBatch *b, const EcAheadRequest &req, hipStream_t stream) {
-    return runCorrection(b, req.channels, req.w, req.h, req.dGlyphs, NULL, NULL, NULL, *req.cfg, stream, true);
+                  const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call, bool paramsOnly) {
+    return channels == 3 ? dispatchEc<3>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly)
+                         : dispatchEc<4>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly);
 }
 
 // What a generate call on `b` will need that does NOT depend on other work of the device: the class lists of the overlapping combiner and the correction
 // pass's per-glyph constants. The host-output pipeline queues these on a chunk's stream BEFORE the chunk waits for its turn on the device -- a small
 // kernel launched between two chunks' large ones waits 0.1-0.4 ms for wavefront slots, and every such launch in a chunk's chain delays the whole chunk
 // (rocprofv3 timeline of the pipeline, profiles/r05_ab_notes.md).
-int prepareAhead(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGlyph *dGlyphs, const MsdfHipConfig *cfg, hipStream_t stream) {
+int prepareAhead(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGlyph *dGlyphs, const MsdfHipConfig *cfg, hipStream_t stream, GenerateCall &call) {
     if (b->nGlyphs == 0 || w == 0 || h == 0)
         return MSDFHIP_OK;
     const int nch = channelsOf(mode), tilesAll = ((w+TILE-1)/TILE)*((h+TILE-1)/TILE);
@@ -1154,7 +1156,7 @@ int prepareAhead(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGly
         rc = ensureBuckets(b, limit < 1 ? 1 : limit, stream);
     }
     if (rc == MSDFHIP_OK && mode >= 3 && cfg->ec_mode != MSDFHIP_EC_DISABLED)
-        rc = runCorrection(b, nch, w, h, dGlyphs, NULL, NULL, NULL, *cfg, stream, true);
+        rc = runCorrection(b, nch, w, h, dGlyphs, NULL, NULL, NULL, *cfg, stream, call, true);
     return rc;
 }
 
@@ -1726,19 +1728,12 @@ int msdfhip_batch_windings(const MsdfHipBatch *b, int32_t *windings) {
     return MSDFHIP_OK;
 }
 
-int msdfhip_batch_generate(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGlyph *dGlyphs, float *dOut, uint8_t *dStencil,
-                           float *dScratch, const MsdfHipConfig *cfg, void *streamPtr) {
-    if (!b || mode < 1 || mode > 4 || w < 0 || h < 0 || !dGlyphs || !dOut)
-        return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_batch_generate");
-    int rc = checkConfig(cfg);
-    if (rc != MSDFHIP_OK)
-        return rc;
-    rc = ensureDevice(b->device);
-    if (rc != MSDFHIP_OK)
-        return rc;
+// One generate call on b (arguments checked, device bound): distance pass -> sign correction -> error correction.
+static int runGenerate(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGlyph *dGlyphs, float *dOut, uint8_t *dStencil, float *dScratch,
+                       const MsdfHipConfig *cfg, hipStream_t stream, GenerateCall &call) {
     if (b->nGlyphs == 0 || w == 0 || h == 0)
         return MSDFHIP_OK;                                       // zero-size bitmap: no-op, like the reference loops
-    hipStream_t stream = (hipStream_t) streamPtr;
+    int rc = MSDFHIP_OK;
     const bool overlap = cfg->overlap_support != 0;
     const bool correct = mode >= 3 && cfg->ec_mode != MSDFHIP_EC_DISABLED; // msdf-error-correction.cpp:13-14
     const bool signPass = cfg->sign_correction != 0;                       // main.cpp:1281-1298: generate -> sign correction -> error correction
@@ -1752,17 +1747,15 @@ int msdfhip_batch_generate(const MsdfHipBatch *b, int mode, int w, int h, const 
     }
     float *stageA = stages ? dScratch : NULL, *stageB = stages == 2 ? dScratch+tileFloats : NULL;
     float *dst = stages ? stageA : dOut;
-    EcAheadRequest ahead = { channelsOf(mode), w, h, dGlyphs, cfg };
-    b->ecAheadWanted = correct && !b->ecParamsAhead ? &ahead : NULL;
+    const MsdfHipConfig *ecAhead = correct && !call.ecParamsQueued ? cfg : NULL;   // (taken only where the distance pass forks its classes onto side streams)
     switch (mode) {
-        case 1: rc = dispatchDistance<1>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream); break;
-        case 2: rc = dispatchDistance<2>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream); break;
-        case 3: rc = dispatchDistance<3>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream); break;
-        default: rc = dispatchDistance<4>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream); break;
+        case 1: rc = dispatchDistance<1>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream, ecAhead, call); break;
+        case 2: rc = dispatchDistance<2>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream, ecAhead, call); break;
+        case 3: rc = dispatchDistance<3>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream, ecAhead, call); break;
+        default: rc = dispatchDistance<4>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream, ecAhead, call); break;
     }
-    b->ecAheadWanted = NULL;                                     // (not taken: no side stream in this launch -- the correction pass launches k_ec_params itself)
-    if (rc == MSDFHIP_OK && b->afterDistance)
-        HIPCHK(hipEventRecord(b->afterDistance, stream));
+    if (rc == MSDFHIP_OK && call.afterDistance)
+        HIPCHK(hipEventRecord(call.afterDistance, stream));
     if (rc != MSDFHIP_OK || !stages)
         return rc;
     const float *ecSrc = stageA;
@@ -1772,7 +1765,21 @@ int msdfhip_batch_generate(const MsdfHipBatch *b, int mode, int w, int h, const 
             return rc;
         ecSrc = stageB;
     }
-    return runCorrection(b, channelsOf(mode), w, h, dGlyphs, ecSrc, dOut, dStencil, *cfg, stream);
+    return runCorrection(b, channelsOf(mode), w, h, dGlyphs, ecSrc, dOut, dStencil, *cfg, stream, call);
+}
+
+int msdfhip_batch_generate(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGlyph *dGlyphs, float *dOut, uint8_t *dStencil,
+                           float *dScratch, const MsdfHipConfig *cfg, void *streamPtr) {
+    if (!b || mode < 1 || mode > 4 || w < 0 || h < 0 || !dGlyphs || !dOut)
+        return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_batch_generate");
+    int rc = checkConfig(cfg);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    rc = ensureDevice(b->device);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    GenerateCall call;
+    return runGenerate(b, mode, w, h, dGlyphs, dOut, dStencil, dScratch, cfg, (hipStream_t) streamPtr, call);
 }
 
 int msdfhip_tiles_to_bytes(const float *dTiles, int nGlyphs, int w, int h, int channels, const MsdfHipGlyph *dGlyphs, uint8_t *dAtlas, void *streamPtr) {
@@ -1934,7 +1941,6 @@ struct PipeSlot {
 // device / pinned allocations every time; the pool is bounded by the peak number of concurrent host-output calls.
 struct Pipe {
     int device;
-    hipStream_t compute;              // (unused: one stream for all chunks' kernels was measured slower, see runPipeline)
     PipeSlot slot[PIPE_SLOTS];
 };
 
@@ -1950,8 +1956,6 @@ struct PipeLease {
         if (p) {
             // Whatever exit the call took (an error return may leave copies into caller memory / kernels in flight on the slots' streams):
             // nothing of this call is pending when the next caller takes the pipe. Idle streams answer at once.
-            if (p->compute)
-                (void) hipStreamSynchronize(p->compute);
             for (int k = 0; k < PIPE_SLOTS; ++k)
                 if (p->slot[k].stream)
                     (void) hipStreamSynchronize(p->slot[k].stream);
@@ -1972,7 +1976,6 @@ struct PipeLease {
         }
         Pipe *fresh = new Pipe();
         fresh->device = device;
-        fresh->compute = NULL;
         for (int k = 0; k < PIPE_SLOTS; ++k) {
             PipeSlot &s = fresh->slot[k];
             s.stream = NULL, s.done = NULL, s.kernelsDone = NULL, s.distanceDone = NULL, s.pinnedOverflow = NULL, s.busy = false, s.dev = NULL, s.devCap = 0, s.pinnedGlyphs = NULL, s.pinnedGlyphCap = 0, s.viewCap = 0;
@@ -1980,9 +1983,7 @@ struct PipeLease {
             s.pinnedIn = NULL, s.pinnedInCap = 0, s.devIn = NULL, s.devInCap = 0, s.inputsUploaded = NULL, s.inputsInFlight = false, s.prepCounted = NULL;
         }
         for (int k = 0; k < PIPE_SLOTS; ++k) {                   // a half-built pipe never reaches the pool
-            hipError_t e = k == 0 ? hipStreamCreateWithFlags(&fresh->compute, hipStreamNonBlocking) : hipSuccess;
-            if (e == hipSuccess)
-                e = hipStreamCreateWithFlags(&fresh->slot[k].stream, hipStreamNonBlocking);
+            hipError_t e = hipStreamCreateWithFlags(&fresh->slot[k].stream, hipStreamNonBlocking);
             if (e == hipSuccess)
                 e = hipEventCreateWithFlags(&fresh->slot[k].done, hipEventDisableTiming);
             if (e == hipSuccess)
@@ -2026,7 +2027,6 @@ static void sliceBatch(const MsdfHipBatch *b, MsdfHipBatch &v, int g0, int n) {
     }
     v.maxContours = maxC, v.maxEdges = maxE;
     v.bucketLimit = -1;                                          // the class lists are per glyph range
-    v.ecParamsAhead = false;
     v.serialClasses = true;                                      // pipeline chunks overlap each other; side streams per chunk only alias the few hardware queues
 }
 
@@ -2432,7 +2432,6 @@ struct StreamFeeder : ChunkFeeder {
         }
         v.maxContours = maxC, v.maxEdges = maxE;
         v.bucketLimit = -1;
-        v.ecParamsAhead = false;
         v.serialClasses = true;
         return digest(&v, stream);
     }
@@ -2557,13 +2556,8 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
         feeder = &resident;
     struct FeederDrain {                                         // declared after the lease: runs BEFORE the pipe goes back to the pool, on every exit (HIPCHK returns included)
         ChunkFeeder *f;
-        PipeSlot *slots;
-        ~FeederDrain() {
-            f->drain();
-            for (int k = 0; slots && k < PIPE_SLOTS; ++k)
-                slots[k].view.ecParamsAhead = false;             // (a call that failed between prepareAhead and its correction pass must not leave the flag to the pipe's next user)
-        }
-    } drainGuard = { feeder, lease.p->slot };
+        ~FeederDrain() { f->drain(); }
+    } drainGuard = { feeder };
     PipeSlot *pipe = lease.p->slot;
     const size_t texels = (size_t) w*h, tile = texels*N;         // floats per tile; also bytes per 8-bit tile
     const size_t total = out ? outFloats : atlasBytes, elem = out ? sizeof(float) : 1;
@@ -2758,15 +2752,16 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
         }
         // Everything up to here -- the chunk's inputs (streamed calls: upload + digest), its descriptors -- and the two preparations below do not depend on
         // the chunks before it: they are queued AHEAD of the chunk's turn on the device and run under the earlier chunks' kernels.
-        rc = prepareAhead(&p.view, mode, w, h, dGlyphs, cfg, compute);
+        GenerateCall call;
+        call.afterDistance = p.distanceDone;
+        call.overflowOut = mirrorOverflow ? p.pinnedOverflow : NULL;
+        rc = prepareAhead(&p.view, mode, w, h, dGlyphs, cfg, compute, call);
         if (rc != MSDFHIP_OK)
             break;
         if (ci >= (size_t) depth)                                // at most `depth` (two) chunks' kernels at a time, in order: chunk k starts when chunk k-depth's KERNELS are done
             HIPCHK(hipStreamWaitEvent(compute, pipe[(slot+PIPE_SLOTS-depth)%PIPE_SLOTS].kernelsDone, 0));
-        p.view.afterDistance = p.distanceDone;
         p.pinnedOverflow[0] = 0;                                 // (the slot's previous chunk is done: nothing on the device writes it any more)
-        p.view.overflowOut = mirrorOverflow ? p.pinnedOverflow : NULL, p.view.overflowMirrored = false;
-        rc = msdfhip_batch_generate(&p.view, mode, w, h, dGlyphs, dTiles, dStencil, NULL, cfg, compute);
+        rc = runGenerate(&p.view, mode, w, h, dGlyphs, dTiles, dStencil, NULL, cfg, compute, call);
         if (rc != MSDFHIP_OK)
             break;
         const char *dResult = reinterpret_cast<const char *>(dTiles);
@@ -2807,7 +2802,6 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
             rc = fail(MSDFHIP_ERR_HIP, "host-output pipeline: %s", hipGetErrorString(e));
         if (mirrorOverflow && e == hipSuccess && p.pinnedOverflow[0] != 0)
             *overflowed = true;
-        p.view.overflowOut = NULL;
         if (rc == MSDFHIP_OK && p.pendingCount)
             scatterPending(p, glyphs, dstBytes, elem, w, h, N);
         p.pendingCount = 0;
@@ -3202,8 +3196,6 @@ static int arenaReserve(ThreadArena &a, size_t devBytes, size_t pinnedBytes) {
 
 static void destroyPipe(Pipe *p) {
     (void) hipSetDevice(p->device);
-    if (p->compute)
-        (void) hipStreamSynchronize(p->compute);
     for (int k = 0; k < PIPE_SLOTS; ++k) {
         PipeSlot &s = p->slot[k];
         if (s.stream)
@@ -3235,8 +3227,6 @@ static void destroyPipe(Pipe *p) {
         if (s.stream)
             hipStreamDestroy(s.stream);
     }
-    if (p->compute)
-        hipStreamDestroy(p->compute);
     (void) hipGetLastError();
     delete p;
 }
@@ -3560,7 +3550,7 @@ static int runGroup(ShapeCall *const *calls, int n) {
     const MsdfHipGlyph *dGlyph = reinterpret_cast<const MsdfHipGlyph *>(a.dev+hGlyph);
     float *dOut = reinterpret_cast<float *>(a.dev+hOut);
     uint8_t *dStencil = anyStencil ? reinterpret_cast<uint8_t *>(a.dev+hStencil) : NULL;
-    b.overflowOut = reinterpret_cast<unsigned *>(a.dev+hStatus);
+    unsigned *overflowOut = reinterpret_cast<unsigned *>(a.dev+hStatus);   // where k_ec_query mirrors the candidate-overflow count (NULL: rerun with the overflow pass)
 
     // ---- one launch for the whole call (msdf_single.hpp) where it applies: ONE shape, a generate*() call without the scanline pass, a bitmap of
     // at most 256 tiles, lists / correction scratch within 64 KB of LDS. A candidate overflow (pathological inputs) reruns the batched sequence below.
@@ -3695,29 +3685,31 @@ static int runGroup(ShapeCall *const *calls, int n) {
     }
     rc = fusedDone ? MSDFHIP_OK : digest(&b, a.stream);
     for (int attempt = 0; !fusedDone && rc == MSDFHIP_OK && attempt < 2; ++attempt) {
-        b.overflowMirrored = false;
+        GenerateCall call;
+        call.overflowOut = overflowOut;
         if (op == OP_ERROR_CORRECTION)
-            rc = runCorrection(&b, channels, w, h, dGlyph, reinterpret_cast<const float *>(a.dev+hSrc), dOut, dStencil, *cfg, a.stream);
+            rc = runCorrection(&b, channels, w, h, dGlyph, reinterpret_cast<const float *>(a.dev+hSrc), dOut, dStencil, *cfg, a.stream, call);
         else if (op == OP_SIGN_CORRECTION)
             rc = runSignCorrection(&b, channels, w, h, dGlyph, reinterpret_cast<const float *>(a.dev+hSrc), dOut, 0, cfg->sdf_zero_value, cfg->fill_rule, a.stream);
         else if (op == OP_RASTERIZE)
             rc = runSignCorrection(&b, 1, w, h, dGlyph, NULL, dOut, 0, 0.f, cfg->fill_rule, a.stream);
         else
-            rc = msdfhip_batch_generate(&b, mode, w, h, dGlyph, dOut, dStencil, stages ? reinterpret_cast<float *>(a.dev+dScratch) : NULL, cfg, a.stream);
+            rc = runGenerate(&b, mode, w, h, dGlyph, dOut, dStencil, stages ? reinterpret_cast<float *>(a.dev+dScratch) : NULL, cfg, a.stream, call);
         if (rc != MSDFHIP_OK)
             break;
         HIPCHK(hipMemcpyAsync(a.pinned+hStatus, a.dev+hStatus, 256+(anyStencil ? resultBytes : n*tileBytes), hipMemcpyDeviceToHost, a.stream));
         HIPCHK(waitStream(a.stream));
-        if (!(b.overflowMirrored && *reinterpret_cast<const unsigned *>(a.pinned+hStatus) != 0))
+        if (!(call.overflowMirrored && *reinterpret_cast<const unsigned *>(a.pinned+hStatus) != 0))
             break;
         // a glyph's candidate segment overflowed (more than 1/16 of its texels needed a distance check): once more, with the per-texel
         // overflow pass in the launch sequence. Pathological inputs only.
-        b.overflowOut = NULL;
+        overflowOut = NULL;
         if (bitmapIsInput)
             break;                                               // (in-place correction of a caller bitmap: the input copy on the device is intact, rerun below)
     }
-    if (rc == MSDFHIP_OK && b.overflowOut == NULL && bitmapIsInput) {
-        rc = runCorrection(&b, channels, w, h, dGlyph, reinterpret_cast<const float *>(a.dev+hSrc), dOut, dStencil, *cfg, a.stream);
+    if (rc == MSDFHIP_OK && overflowOut == NULL && bitmapIsInput) {
+        GenerateCall call;
+        rc = runCorrection(&b, channels, w, h, dGlyph, reinterpret_cast<const float *>(a.dev+hSrc), dOut, dStencil, *cfg, a.stream, call);
         if (rc == MSDFHIP_OK) {
             HIPCHK(hipMemcpyAsync(a.pinned+hStatus, a.dev+hStatus, 256+(anyStencil ? resultBytes : n*tileBytes), hipMemcpyDeviceToHost, a.stream));
             HIPCHK(waitStream(a.stream));

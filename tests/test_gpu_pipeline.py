@@ -196,6 +196,21 @@ def test_batch_remembers_its_device(glyphs):
         M.HostBatch(sub.select([0]), device=64)
 
 
+def test_failed_generate_leaves_nothing_to_the_next_call(glyphs):
+    """A call that fails after its distance pass queued the correction pass's k_ec_params on a side stream (1 500 glyphs fork the glyph classes),
+    here at the sign pass's fill-rule check, must not change what the next call on the same resident batch computes: its per-glyph
+    constants come from its own request.  Same bitmap size in both calls, so every buffer region is in bounds whatever the failed call left."""
+    sub, xfs, want = glyphs
+    other = np.array(xfs, np.float64, copy=True)
+    other[:, :2] *= .9
+    other[:, 2:4] += .25
+    gb = M.GlyphBatch(sub)
+    with pytest.raises(M.MsdfHipError):
+        gb.generate(M.MODE_MSDF, 48, 48, other, scanline_pass=True, fill_rule=7)
+    got = gb.generate(M.MODE_MSDF, 48, 48, xfs).cpu().numpy()
+    assert (bits(got) == bits(want)).all()
+
+
 def test_device_memory_stays_flat_over_many_calls(glyphs):
     """Long-running callers: single-shape calls mixing few- and many-contour shapes, and fresh worker threads for every
     round (msdf-atlas-gen spawns a new team per Workload::finish()), must not grow device or pinned memory."""
