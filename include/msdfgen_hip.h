@@ -404,6 +404,49 @@ int msdfhip_debug_single_call_phases(double *out8, int reset);
  * (core/msdfgen.cpp:78-106 cannot fail); these counters only say how often the slow road was taken since the last reset. Any pointer may be NULL. */
 int msdfhip_single_call_fallbacks(unsigned long long *barrier_timeouts, unsigned long long *lost_flags, unsigned long long *refused, int reset);
 
+/* Which launch route the batched passes took (tests: the routes depend on the size of a launch and on the MSDFHIP_* knobs). One relaxed counter per
+ * launch site, bumped on the host when the launch is issued; a one-glyph batch beyond the small route counts in the class of its glyph.
+ * Distance pass (dispatchDistance):
+ *   0 SMALL_SIMPLE      small launch (<= MSDFHIP_SMALL_LAUNCH_TILES tiles), one tile per wavefront, simple combiner (also its one-contour part)
+ *   1 SMALL_OVERLAP     small launch, overlapping combiner, combiner scratch in the global workspace
+ *   2 ONE_QUAD          one-contour class, four tiles per wavefront
+ *   3 ONE_SINGLE        one-contour class, one tile per wavefront (short launch)
+ *   4 LDS_QUAD          LDS-scratch class, four tiles per wavefront
+ *   5 LDS_SINGLE        LDS-scratch class, one tile per wavefront (short launch or MSDFHIP_LDS_CLASS_TPW=1)
+ *   6 GLOBAL_DIRECT     global-scratch class, one workgroup per tile (chunked by workspace)
+ *   7 GLOBAL_PERSISTENT global-scratch class, persistent workgroups drawing tiles from a work queue
+ *   8 FULL_SIMPLE       the whole batch (or all but its oversized glyphs) through the four-tile simple-combiner plan, outside the small route
+ *   9 UNCULLED          the list-free kernel (glyphs whose survivor lists exceed a CU's LDS)
+ * Error correction (launchEc):
+ *  10 EC_QUERY_HEAVIEST k_ec_query over the heaviest-first work list (batches of >= 256 glyphs)
+ *  11 EC_QUERY_BATCH    k_ec_query in batch order
+ *  12 EC_WIDE_SLOTS     the launch took the wide slot cap (up to 1 024 edges; batches of < 256 glyphs)
+ *  13 EC_SLOW_ALL       k_ec_slow over every texel (more contours than k_ec_query's LDS scratch holds)
+ * Sign pass (launchSign):
+ *  14 SIGN_WHOLE_ROWS   a wavefront takes whole tile rows (span == tiles per row)
+ *  15 SIGN_SPLIT        tile rows split between wavefronts
+ *  16 SIGN_CHUNKED      the row lists hold fewer than 3 x the largest glyph's edges: edges walked in chunks
+ * Writes min(cap, MSDFHIP_ROUTE_COUNT) counters to `out` and returns that number; reset != 0 zeroes all of them after reading. Diagnostics. */
+#define MSDFHIP_ROUTE_DIST_SMALL_SIMPLE      0
+#define MSDFHIP_ROUTE_DIST_SMALL_OVERLAP     1
+#define MSDFHIP_ROUTE_DIST_ONE_QUAD          2
+#define MSDFHIP_ROUTE_DIST_ONE_SINGLE        3
+#define MSDFHIP_ROUTE_DIST_LDS_QUAD          4
+#define MSDFHIP_ROUTE_DIST_LDS_SINGLE        5
+#define MSDFHIP_ROUTE_DIST_GLOBAL_DIRECT     6
+#define MSDFHIP_ROUTE_DIST_GLOBAL_PERSISTENT 7
+#define MSDFHIP_ROUTE_DIST_FULL_SIMPLE       8
+#define MSDFHIP_ROUTE_DIST_UNCULLED          9
+#define MSDFHIP_ROUTE_EC_QUERY_HEAVIEST     10
+#define MSDFHIP_ROUTE_EC_QUERY_BATCH        11
+#define MSDFHIP_ROUTE_EC_WIDE_SLOTS         12
+#define MSDFHIP_ROUTE_EC_SLOW_ALL           13
+#define MSDFHIP_ROUTE_SIGN_WHOLE_ROWS       14
+#define MSDFHIP_ROUTE_SIGN_SPLIT            15
+#define MSDFHIP_ROUTE_SIGN_CHUNKED          16
+#define MSDFHIP_ROUTE_COUNT                 17
+int msdfhip_debug_route_counts(unsigned long long *out, int cap, int reset);
+
 #ifdef __cplusplus
 }
 #endif

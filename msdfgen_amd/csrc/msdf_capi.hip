@@ -109,6 +109,8 @@ void readTuning() {
     if (env)
         sscanf(env, "%d,%d,%d,%d,%f,%f", &t.qpEdgeCost, &t.qpMaxEdges, &t.qpMinCount, &t.qpWideMaxEdges, &t.qpWideLoad, &t.qpWideMeanCount);
     t.signCap = (env = getenv("MSDFHIP_SIGN_CAP")) ? (size_t) atol(env) : (size_t) 192;
+    if (t.signCap < 3)                                           // one edge's intersections per row: below, the sign pass's chunks would hold no edge
+        t.signCap = 3;
     t.pipelineTrace = getenv("MSDFHIP_PIPELINE_TRACE") != NULL;
     t.microbatch = (env = getenv("MSDFHIP_MICROBATCH")) ? atoi(env) : 256;
     if (t.microbatch < 1)
@@ -149,6 +151,12 @@ const Tuning &tuning() {
     }
     return *t;
 }
+
+// Which launch route the batched passes took (msdfhip_debug_route_counts; indices MSDFHIP_ROUTE_* of msdfgen_hip.h): bumped on the host at each launch site
+// once the launch is issued, per launch site rather than per kernel instance (the small overlapping route and the direct global-scratch class share one).
+std::atomic<unsigned long long> gRouteCounts[MSDFHIP_ROUTE_COUNT];
+
+inline void countRoute(int route) { gRouteCounts[route].fetch_add(1, std::memory_order_relaxed); }
 
 #define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (void) hipGetLastError(); return fail(MSDFHIP_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
 
@@ -441,8 +449,10 @@ void launchDistanceKernel(unsigned grid, size_t lds, hipStream_t stream, const D
 
 template <int SEL, bool OVERLAP, bool GRES, int TPW_ = (GRES ? 1 : (int) QUAD)>
 int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, float *dst, int toScratch, const LdsPlan &plan, hipStream_t stream,
-                   const int *dGlyphMap = NULL, int nMapped = 0, size_t shareGrid = 0) {
+                   const int *dGlyphMap = NULL, int nMapped = 0, size_t shareGrid = 0, bool *persistent = NULL) {
     const int tilesX = (w+TILE-1)/TILE, tilesY = (h+TILE-1)/TILE, tiles = tilesX*tilesY;
+    if (persistent)
+        *persistent = false;
     const int nG = dGlyphMap ? nMapped : b->nGlyphs;
     if (nG == 0)
         return MSDFHIP_OK;
@@ -493,6 +503,8 @@ int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
             launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) chunk, plan.bytes, stream, args);
             HIPCHK(hipGetLastError());
             b->queueParity ^= 1u;
+            if (persistent)
+                *persistent = true;
             return MSDFHIP_OK;
         }
         chunk = GRES_WORKSPACE_CAP/plan.resBytes;
@@ -728,7 +740,15 @@ int launchUnculled(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
     hipLaunchKernelGGL((k_distance_unculled<SEL, OVERLAP>), dim3((unsigned) groups), dim3(WAVE), 0, stream, v.nGlyphs, v.glyphContourOffsets, v.contourOffsets, v.recs,
                        v.windings, dGlyphs, w, h, tilesX, tiles, dst, toScratch, gres, resBytes/sizeof(double), counter, (unsigned) items, dGlyphMap);
     HIPCHK(hipGetLastError());
+    countRoute(MSDFHIP_ROUTE_DIST_UNCULLED);
     return MSDFHIP_OK;
+}
+
+// rc of a launch, counted under `route` when it was issued (msdfhip_debug_route_counts)
+int counted(int rc, int route) {
+    if (rc == MSDFHIP_OK)
+        countRoute(route);
+    return rc;
 }
 
 // Contours up to which a glyph's combiner scratch fits the per-wavefront LDS budget next to the lists of a smallMaxEdges glyph (the LDS class's bound).
@@ -791,27 +811,30 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
     single.resBytes = overlap ? (size_t) maxC*SelTraits<SEL>::NCH*WAVE*sizeof(double) : 0;
     if (!overlap || maxC <= 1) {
         if (smallLaunch)
-            return launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, single, stream);
+            return counted(launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, single, stream), MSDFHIP_ROUTE_DIST_SMALL_SIMPLE);
         if (overlap) {
             rc = planLds(b, SelTraits<SEL>::NCH, false, plan, maxC, maxE);
             if (rc != MSDFHIP_OK)
                 return rc;
         }
         if (!hugeBatch)
-            return launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream);
-        rc = nCulled > 0 ? launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream, b->dBucket, nCulled) : MSDFHIP_OK;
+            return counted(launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream), MSDFHIP_ROUTE_DIST_FULL_SIMPLE);
+        rc = nCulled > 0 ? counted(launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream, b->dBucket, nCulled), MSDFHIP_ROUTE_DIST_FULL_SIMPLE)
+                         : MSDFHIP_OK;
         if (rc == MSDFHIP_OK)                                    // (the oversized glyphs after the others on the same stream: they share the batch's workspace)
             rc = overlap && b->maxContours > 1 ? launchUnculled<SEL, true>(b, dGlyphs, w, h, dst, toScratch, stream, b->dBucket+nCulled, nHuge)
                                                : launchUnculled<SEL, false>(b, dGlyphs, w, h, dst, toScratch, stream, b->dBucket+nCulled, nHuge);
         return rc;
     }
     if (smallLaunch && b->nGlyphs == 1)
-        return launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, single, stream);
+        return counted(launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, single, stream), MSDFHIP_ROUTE_DIST_SMALL_OVERLAP);
     const int limit = limitAll;
+    bool persistent = false;                                     // (whether a global-scratch launch went persistent: route counters only)
     if (b->nGlyphs == 1) {                                       // the class is known, no index map
         if (maxC <= limit && maxE <= smallMaxEdges && !plan.globalRes)
-            return launchDistance<SEL, true, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream);
-        return launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, single, stream);
+            return counted(launchDistance<SEL, true, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream), MSDFHIP_ROUTE_DIST_LDS_QUAD);
+        rc = launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, NULL, 0, 0, &persistent);
+        return counted(rc, persistent ? MSDFHIP_ROUTE_DIST_GLOBAL_PERSISTENT : MSDFHIP_ROUTE_DIST_GLOBAL_DIRECT);
     }
     rc = ensureBuckets(b, limit < 1 ? 1 : limit, stream);
     if (rc != MSDFHIP_OK)
@@ -819,12 +842,13 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
     const int nRest = nCulled-b->nOne-b->nSmall;
     if (smallLaunch) {
         if (b->nOne > 0) {
-            rc = launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, b->dBucket, b->nOne);
+            rc = counted(launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, b->dBucket, b->nOne), MSDFHIP_ROUTE_DIST_SMALL_SIMPLE);
             if (rc != MSDFHIP_OK)
                 return rc;
         }
         if (b->nGlyphs > b->nOne)
-            return launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, b->dBucket+b->nOne, b->nGlyphs-b->nOne);
+            return counted(launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, b->dBucket+b->nOne, b->nGlyphs-b->nOne),
+                           MSDFHIP_ROUTE_DIST_SMALL_OVERLAP);
         return MSDFHIP_OK;
     }
     // The classes are disjoint sets of glyphs: their launches run CONCURRENTLY (the long LDS-class launch on the caller's stream, the other
@@ -865,7 +889,8 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
             shareGrid = (size_t) ((double) slots*b->restShare*tuning().shareGridFactor);
             shareGrid = shareGrid < 256 ? 256 : shareGrid;
         }
-        rc = launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, rest, sRest, b->dBucket+b->nOne+b->nSmall, nRest, shareGrid);
+        rc = launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, rest, sRest, b->dBucket+b->nOne+b->nSmall, nRest, shareGrid, &persistent);
+        rc = counted(rc, persistent ? MSDFHIP_ROUTE_DIST_GLOBAL_PERSISTENT : MSDFHIP_ROUTE_DIST_GLOBAL_DIRECT);
     }
     if (rc == MSDFHIP_OK && b->nSmall > 0) {
         // A launch of few rounds of wavefronts (a shard of an atlas: BASELINE config 4 over 8 GPUs leaves 1 024 glyphs per device) ends when its
@@ -875,8 +900,10 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
         LdsPlan small;
         rc = planLds(b, SelTraits<SEL>::NCH, true, small, b->smallMaxC, b->smallMaxE, shortLaunch ? 1 : (int) QUAD);
         if (rc == MSDFHIP_OK)
-            rc = shortLaunch ? launchDistance<SEL, true, false, 1>(b, dGlyphs, w, h, dst, toScratch, small, stream, b->dBucket+b->nOne, b->nSmall)
-                             : launchDistance<SEL, true, false>(b, dGlyphs, w, h, dst, toScratch, small, stream, b->dBucket+b->nOne, b->nSmall);
+            rc = shortLaunch ? counted(launchDistance<SEL, true, false, 1>(b, dGlyphs, w, h, dst, toScratch, small, stream, b->dBucket+b->nOne, b->nSmall),
+                                       MSDFHIP_ROUTE_DIST_LDS_SINGLE)
+                             : counted(launchDistance<SEL, true, false>(b, dGlyphs, w, h, dst, toScratch, small, stream, b->dBucket+b->nOne, b->nSmall),
+                                       MSDFHIP_ROUTE_DIST_LDS_QUAD);
     }
     if (rc == MSDFHIP_OK && b->nOne > 0) {
         const size_t slots = (size_t) residentSlots(b->device)*4u*MSDF_SIMPLE_WAVES_PER_SIMD;
@@ -885,9 +912,9 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
         rc = planLds(b, SelTraits<SEL>::NCH, false, simple, 1, b->oneMaxE, shortLaunch ? 1 : (int) QUAD);
         if (rc == MSDFHIP_OK && shortLaunch) {
             simple.bytes = tileListBytes(b->oneMaxE, 1, true);
-            rc = launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, simple, sOne, b->dBucket, b->nOne);
+            rc = counted(launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, simple, sOne, b->dBucket, b->nOne), MSDFHIP_ROUTE_DIST_ONE_SINGLE);
         } else if (rc == MSDFHIP_OK)
-            rc = launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, simple, sOne, b->dBucket, b->nOne);
+            rc = counted(launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, simple, sOne, b->dBucket, b->nOne), MSDFHIP_ROUTE_DIST_ONE_QUAD);
     }
     hipError_t joinError = hipSuccess;
     if (sRest != stream) {
@@ -1011,13 +1038,14 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
     // 22 KB; measured: 2.67 -> 2.60 ms of correction on the distinct-glyph set)
     const int slotCapWanted = tuning().querySlotCap, lpcContoursWanted = tuning().queryLpcContours;   // 160, 24 (MSDFHIP_QUERY_LDS)
     int slotCap = b->maxEdges < slotCapWanted ? (b->maxEdges > 0 ? b->maxEdges : 1) : slotCapWanted;
+    bool wideSlots = false;
     // A launch of few glyphs is a latency chain of its largest one (the 926-edge logo: one distance check per wavefront, 40 contours walked one
     // after the other without the slots: correction 0.61 ms, with them 0.39): slots for up to 1024 edges there, LDS permitting.
     if (b->nGlyphs < 256 && !tuning().hasQueryLds) {
         const int wide = b->maxEdges < 1024 ? (b->maxEdges > 0 ? b->maxEdges : 1) : 1024;
         const int wideMerged = b->maxContours < wide ? (b->maxContours > 0 ? b->maxContours : 1) : wide;
         if ((size_t) b->maxContours*sizeof(double)+(size_t) (wide+wideMerged)*sizeof(PBSlot) <= (size_t) 64*1024 && wide > slotCap)
-            slotCap = wide;
+            slotCap = wide, wideSlots = true;
     }
     // LDS of a query wavefront: the lane-per-candidate scratch [maxContours][64], or (cooperative) [maxContours] + the slots -- one or the other
     EcQueryPolicy lpcMaxContours;
@@ -1049,6 +1077,7 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(slowGrid), dim3(WAVE), slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
                            (const EcCandidate *) NULL, 0u, 0, gres, gresStride);
         HIPCHK(hipGetLastError());
+        countRoute(MSDFHIP_ROUTE_EC_SLOW_ALL);
         return MSDFHIP_OK;
     }
     if (fastLds > (size_t) gLdsLimit.load() || queryLds > (size_t) gLdsLimit.load())
@@ -1098,6 +1127,9 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(slowGrid), dim3(WAVE), slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
                            (const EcCandidate *) deferred, seg, 1, gres, gresStride);
     HIPCHK(hipGetLastError());
+    countRoute(ecOrder ? MSDFHIP_ROUTE_EC_QUERY_HEAVIEST : MSDFHIP_ROUTE_EC_QUERY_BATCH);
+    if (wideSlots)
+        countRoute(MSDFHIP_ROUTE_EC_WIDE_SLOTS);
     return MSDFHIP_OK;
 }
 
@@ -1188,6 +1220,9 @@ int launchSign(const MsdfHipBatch *b, int w, int h, const MsdfHipGlyph *dGlyphs,
     hipLaunchKernelGGL((k_sign_correction<N>), dim3((unsigned) blocks), dim3(WAVE), lds, stream, viewOf(b), dGlyphs, w, h, spansX, span, spans, (int) cap,
                        src, out, dstPacked, zero, fillRule, rasterizeOnly);
     HIPCHK(hipGetLastError());
+    countRoute(span == tilesX ? MSDFHIP_ROUTE_SIGN_WHOLE_ROWS : MSDFHIP_ROUTE_SIGN_SPLIT);
+    if (cap < 3*(size_t) (b->maxEdges > 0 ? b->maxEdges : 1))
+        countRoute(MSDFHIP_ROUTE_SIGN_CHUNKED);
     return MSDFHIP_OK;
 }
 
@@ -4180,6 +4215,16 @@ int msdfhip_single_call_fallbacks(unsigned long long *barrier_timeouts, unsigned
     if (reset)
         gSingleTimeouts.store(0), gSingleLost.store(0), gSingleRefused.store(0);
     return MSDFHIP_OK;
+}
+
+int msdfhip_debug_route_counts(unsigned long long *out, int cap, int reset) {
+    int n = 0;
+    for (; out && n < cap && n < MSDFHIP_ROUTE_COUNT; ++n)
+        out[n] = gRouteCounts[n].load(std::memory_order_relaxed);
+    if (reset)
+        for (int k = 0; k < MSDFHIP_ROUTE_COUNT; ++k)
+            gRouteCounts[k].store(0, std::memory_order_relaxed);
+    return n;
 }
 
 int msdfhip_debug_single_call_phases(double *out8, int reset) {

@@ -126,9 +126,15 @@ _PROTOS = {
                                                                 C.POINTER(OrientConfig)]),
     "msdfhip_set_host_threads": (C.c_int, [C.c_int]),
     "msdfhip_single_call_fallbacks": (C.c_int, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_int]),
+    "msdfhip_debug_route_counts": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_PROTOS))
+
+# Launch routes of the batched passes, in the order of the MSDFHIP_ROUTE_* indices of msdfgen_hip.h (msdfhip_debug_route_counts).
+ROUTE_NAMES = ("dist_small_simple", "dist_small_overlap", "dist_one_quad", "dist_one_single", "dist_lds_quad", "dist_lds_single", "dist_global_direct",
+               "dist_global_persistent", "dist_full_simple", "dist_unculled", "ec_query_heaviest", "ec_query_batch", "ec_wide_slots", "ec_slow_all",
+               "sign_whole_rows", "sign_split", "sign_chunked")
 
 _lib = None
 _lock = threading.Lock()
@@ -209,3 +215,12 @@ def microbatch_stats(reset=False):
     check(load().msdfhip_microbatch_times(C.byref(x), C.byref(y), C.byref(z), int(reset)))
     check(load().msdfhip_microbatch_stats(C.byref(a), C.byref(b), C.byref(c), int(reset)))
     return {"calls": a.value, "batches": b.value, "largest": c.value, "stage_ms": round(x.value, 3), "device_ms": round(y.value, 3), "scatter_ms": round(z.value, 3)}
+
+
+def route_counts(reset=False):
+    """{route name: launches since the last reset} of the batched passes (msdfhip_debug_route_counts; names ROUTE_NAMES)."""
+    out = (C.c_ulonglong*len(ROUTE_NAMES))()
+    n = load().msdfhip_debug_route_counts(out, len(ROUTE_NAMES), int(reset))
+    if n != len(ROUTE_NAMES):
+        raise MsdfHipError(ERR_INVALID, "the library has %d route counters, the binding names %d" % (n, len(ROUTE_NAMES)))
+    return dict(zip(ROUTE_NAMES, (int(v) for v in out)))

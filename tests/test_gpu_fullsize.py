@@ -111,7 +111,7 @@ def test_config4_cjk_like_512_distinct_shapes_every_tile_both_mappings(oracle):
     48x48 -- the workload that takes the PERSISTENT global-scratch form of k_distance (per-XCD work queues, one workspace slice per
     resident wavefront). Each of the 8 192 tiles must hash to the compiled reference's tile of its shape, in the persistent and in the
     direct mapping. core/contour-combiners.cpp:77-134."""
-    import os
+    import fuzzlib
     from msdfgen_amd import synth
     from msdfgen_amd.shape import autoframe
     zc = load_npz("cjk512.npz")
@@ -122,17 +122,14 @@ def test_config4_cjk_like_512_distinct_shapes_every_tile_both_mappings(oracle):
     batch = ShapeBatch.from_shapes([base[i % 512] for i in range(8192)])
     xfs = xfs512[np.arange(8192) % 512]
     want = zc["sha48"]
-    for knob, what in ((None, "persistent"), ("0", "direct")):
-        if knob is not None:
-            os.environ["MSDFHIP_PERSISTENT_ROUNDS"] = knob
-            M.load().msdfhip_reload_tuning()
-        try:
+    for env, what in (({}, "persistent"), ({"MSDFHIP_PERSISTENT_ROUNDS": "0"}, "direct")):
+        with fuzzlib.tuned(env):
+            before = M.route_counts()
             gb = M.GlyphBatch(batch)
             tiles = gb.generate(M.MODE_MSDF, 48, 48, xfs).cpu().numpy()
             gb.close()
-        finally:
-            os.environ.pop("MSDFHIP_PERSISTENT_ROUNDS", None)
-            M.load().msdfhip_reload_tuning()
+            routes = M.route_counts()
+        assert routes["dist_global_%s" % what] > before["dist_global_%s" % what], (what, routes)
         bad = [g for g in range(8192) if not (sha(tiles[g]) == want[g % 512]).all()]
         for g in bad[:4]:
             ref = oracle.generate(base[g % 512], 3, 48, 48, xfs[g])

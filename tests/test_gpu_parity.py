@@ -314,14 +314,9 @@ def test_config4_full_size_atlas_8192_glyphs_48(oracle):
     assert (bits(np.concatenate(parts)) == bits(got)).all()
     # 295 k tiles of the global-scratch class = a PERSISTENT launch (work queue, one workspace slice per resident wavefront); the direct
     # mapping (one slice per tile, chunked launches) must give the same bytes
-    import os
-    os.environ["MSDFHIP_PERSISTENT_ROUNDS"] = "0"
-    M.load().msdfhip_reload_tuning()
-    try:
+    import fuzzlib
+    with fuzzlib.tuned({"MSDFHIP_PERSISTENT_ROUNDS": "0"}):
         direct = M.GlyphBatch(batch).generate(3, 48, 48, xfs).cpu().numpy()
-    finally:
-        del os.environ["MSDFHIP_PERSISTENT_ROUNDS"]
-        M.load().msdfhip_reload_tuning()
     assert (bits(direct) == bits(got)).all()
     print("config 4: 24 sampled tiles, %d texels differing bitwise" % worst)
 
@@ -332,7 +327,7 @@ def test_scheduling_knobs_do_not_change_a_byte():
     get LDS slots (MSDFHIP_QUERY_POLICY, MSDFHIP_QUERY_LDS -- i.e. k_ec_query's cooperative path with register records vs its chunk walk with
     batched scalar loads on the SAME candidates). 1 024 distinct DejaVu glyphs incl. the 543-edge symbol, msdf with the default correction and
     mtsdf with ALWAYS_CHECK."""
-    import os
+    import fuzzlib
     z = load_npz("dejavu8192.npz")
     full = ShapeBatch(z["glyph_contour_offsets"].astype(np.int32), z["contour_offsets"].astype(np.int32), z["points"], z["types"].astype(np.int32),
                       z["colors"].astype(np.int32), np.zeros(len(z["names"]), bool), [str(n) for n in z["names"]])
@@ -358,14 +353,8 @@ def test_scheduling_knobs_do_not_change_a_byte():
              {"MSDFHIP_QUERY_STATIC": "0"}, {"MSDFHIP_QUERY_STATIC": "1"}, {"MSDFHIP_QUERY_STATIC": "1", "MSDFHIP_QUERY_GRID": "0", "MSDFHIP_QUERY_BATCH": "3"},
              {"MSDFHIP_QUERY_STATIC": "2", "MSDFHIP_QUERY_BATCH": "4"}]
     for env in knobs:
-        os.environ.update(env)
-        M.load().msdfhip_reload_tuning()
-        try:
+        with fuzzlib.tuned(env):
             got = render()
-        finally:
-            for k in env:
-                del os.environ[k]
-            M.load().msdfhip_reload_tuning()
         assert (bits(got[0]) == bits(want[0])).all() and (bits(got[1]) == bits(want[1])).all(), env
 
 
@@ -1025,9 +1014,12 @@ def test_estimate_sdf_error_on_device(latin, oracle):
 
 
 def test_mixed_batch_is_bucketed_by_contour_count(latin, oracle):
-    """A batch of mostly few-contour glyphs plus some many-contour ones: the kernels split it (LDS scratch for the former, global
-    workspace for the latter); the result must not depend on that -- compared per glyph with the oracle, msdf and mtsdf, and through
-    the single-shape entry point (which owns and frees its workspaces per call)."""
+    """A batch of mostly few-contour glyphs plus some many-contour ones, compared per glyph with the oracle, msdf and mtsdf. At its size (736 tiles)
+    the batch takes the small route: one tile per wavefront, every multi-contour glyph with its combiner scratch in the global workspace. A second
+    pass with MSDFHIP_SMALL_LAUNCH_TILES=0 really splits it into the glyph classes -- one-contour glyphs, the LDS-scratch class for the few-contour
+    ones and the global-scratch class for the many-contour ones, on concurrent streams -- which the route counters must show; the result must not
+    depend on the split. Last, through the single-shape entry point (which owns and frees its workspaces per call)."""
+    import fuzzlib
     batch, xf64, bounds = latin
     many = [synth.cjk_like_shape(8600+i) for i in range(5)]+[synth.random_shape(8700, n_contours=30, edges_per_contour=(3, 5), kinds=(1, 2))]
     shapes = [batch.shape(g) for g in range(0, 40)]
@@ -1037,11 +1029,27 @@ def test_mixed_batch_is_bucketed_by_contour_count(latin, oracle):
     xfs = np.stack([autoframe(s.bounds(), w, h, 4) for s in shapes])
     gb = M.GlyphBatch(ShapeBatch.from_shapes(shapes))
     assert gb.max_contours >= 20
+    want = {mode: [oracle.generate(s, mode, w, h, xfs[g]) for g, s in enumerate(shapes)] for mode in (3, 4)}
     for mode in (3, 4):
+        before = M.route_counts()
         got = gb.generate(mode, w, h, xfs).cpu().numpy()
+        routes = M.route_counts()
+        assert routes["dist_small_overlap"] > before["dist_small_overlap"], routes
         for g, s in enumerate(shapes):
-            close(got[g], oracle.generate(s, mode, w, h, xfs[g]), "mixed batch glyph %d (%d contours) mode %d" % (g, s.n_contours, mode))
+            close(got[g], want[mode][g], "mixed batch glyph %d (%d contours) mode %d" % (g, s.n_contours, mode))
     gb.close()
+    with fuzzlib.tuned({"MSDFHIP_SMALL_LAUNCH_TILES": "0"}):
+        gb = M.GlyphBatch(ShapeBatch.from_shapes(shapes))
+        for mode in (3, 4):
+            before = M.route_counts()
+            got = gb.generate(mode, w, h, xfs).cpu().numpy()
+            d = {k: v-before[k] for k, v in M.route_counts().items()}
+            assert d["dist_small_simple"] == d["dist_small_overlap"] == 0, d
+            assert d["dist_one_quad"]+d["dist_one_single"] > 0 and d["dist_lds_quad"]+d["dist_lds_single"] > 0, d
+            assert d["dist_global_direct"]+d["dist_global_persistent"] > 0, d
+            for g, s in enumerate(shapes):
+                close(got[g], want[mode][g], "split mixed batch glyph %d (%d contours) mode %d" % (g, s.n_contours, mode))
+        gb.close()
     for s, xf in zip(many[:3], xfs[3::6]):
         for _ in range(3):
             close(gen(3, s, w, h, xf), oracle.generate(s, 3, w, h, xf), "single call, %d contours" % s.n_contours)
