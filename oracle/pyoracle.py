@@ -18,6 +18,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(HERE, "libmsdf_oracle.so")
 REF_SO = os.path.join(HERE, "_ref", "libmsdfgen_ref.so")
+REF_EXACT_SO = os.path.join(HERE, "_ref", "libmsdfgen_ref_exact.so")   # same sources, uncached distance queries (oracle/Makefile)
 REF_OMP_SO = os.path.join(HERE, "_ref", "libmsdfgen_ref_omp.so")   # same sources, MSDFGEN_USE_OPENMP (CPU baseline of one large bitmap)
 
 _dp = C.POINTER(C.c_double)
@@ -266,11 +267,12 @@ class Ref:
     kind = "reference"
 
     @staticmethod
-    def available():
-        return os.path.exists(REF_SO)
+    def available(exact=False):
+        return os.path.exists(REF_EXACT_SO if exact else REF_SO)
 
-    def __init__(self, openmp=False):
-        so = REF_OMP_SO if openmp else REF_SO
+    def __init__(self, openmp=False, exact=False):
+        """exact: the build whose generator and ShapeDistanceChecker query oneShotDistance instead of a caching finder (oracle/Makefile)."""
+        so = REF_OMP_SO if openmp else REF_EXACT_SO if exact else REF_SO
         if not os.path.exists(so):
             if os.path.isdir("/root/reference/core"):
                 build("ref")

@@ -77,14 +77,51 @@ MIXED_KIND = -1                                                       # a group 
 _MIX_FIRST = (5, 6, 2)                                                # a mixed group starts with one glyph of each distance class
 
 
-def plan(n_shapes, seed, framing=None, scale="small", scanline=False, modes=None):
+def _plan_geometry(n_shapes, seed, geometry, modes):
+    """plan(geometry=...): every group draws one outline family of tests/geomcases.py and one bitmap size (the cases' own sizes by their size, or one
+    of geomcases.BIG_SIZES for all), jitters every case by lattice-preserving moves (integer translations and dyadic scales undone by the transform,
+    contour order, colour channel permutations, reversed contours) and cycles through the error-correction pairs. A generator of its own: the
+    default sequence of draws is not touched."""
+    import geomcases
+    rng = np.random.default_rng([seed, 0x6e0])
+    pairs = [EC_PAIRS[k] for k in rng.permutation(len(EC_PAIRS))]
+    order = [list(geometry)[k] for k in rng.permutation(len(geometry))]       # the families in turn: a short sweep has them all
+    done = index = 0
+    while done < n_shapes:
+        family = str(order[index % len(order)])
+        size = int(rng.integers(0, 1+len(geomcases.BIG_SIZES)))
+        w, h = (None, None) if size == 0 else geomcases.BIG_SIZES[size-1]
+        cs = geomcases.bit_exact(geomcases.family_cases(family, 0, w, h))
+        if size == 0:                                                 # a batch has one bitmap size: the cases of one of the family's own sizes
+            sizes = sorted({(c.w, c.h) for c in cs})
+            w, h = sizes[int(rng.integers(0, len(sizes)))]
+            cs = [c for c in cs if (c.w, c.h) == (w, h)]
+        reps = int(rng.integers(1, 4))
+        cs = [c for c in cs for _ in range(reps)]
+        framed = [geomcases.jitter(c.shape, c.xf, rng) for c in cs]
+        ec_mode, ec_dist = pairs[index % len(pairs)]
+        yield {"index": index, "n": len(framed), "mode": int(rng.choice(modes or [1, 2, 3, 3, 4])), "w": w, "h": h, "overlap": index % 2 == 0,
+               "ec": (ec_mode, ec_dist), "kind": MIXED_KIND, "shapes": [f[0] for f in framed], "xfs": np.stack([f[1] for f in framed]),
+               "y_down": bool(rng.integers(0, 2)), "family": family, "min_dev": DEFAULT_RATIO, "min_imp": DEFAULT_RATIO, "scanline": None,
+               "names": [c.name for c in cs]}
+        done += len(framed)
+        index += 1
+
+
+def plan(n_shapes, seed, framing=None, scale="small", scanline=False, modes=None, geometry=None):
     """Yields the groups of a sweep as dicts (shapes, transforms and the config of one generate call), drawn from `seed` alone.
     scale="small" with the other arguments at their defaults is the sweep's original sequence of random draws: tests pin seeds to it.
     scale="mixed": groups of 40-80 glyphs whose shape kinds are mixed, so that one launch holds every distance class, and which cycle through
                    the 4 x 3 error-correction pairs, both combiners, Y-down bitmaps and non-default ratios.
     scale="full":  the same at throughput size: at least 256 glyphs and more than 8 192 tiles per group (the launches' large routes).
     scanline: every other group runs the -scanline flow (sign pass between distance and correction), the fill rules in turn.
-    modes: the field types to draw from (default sdf, psdf, msdf twice, mtsdf)."""
+    modes: the field types to draw from (default sdf, psdf, msdf twice, mtsdf).
+    geometry: family names of tests/geomcases.py; the groups then come from _plan_geometry() instead (alone: no framing, scale or scanline with it)."""
+    if geometry is not None:
+        if framing is not None or scale != "small" or scanline:
+            raise ValueError("geometry families go alone")
+        yield from _plan_geometry(n_shapes, seed, geometry, modes)
+        return
     import xformcases
     from msdfgen_amd.shape import autoframe
     if framing is not None and scale != "small":
@@ -155,12 +192,13 @@ def _delta(after, before):
 
 
 def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="small", scanline=False, tuning=None, modes=None, min_groups=0, stencil=False,
-        paths=False):
+        paths=False, geometry=None):
     """Returns a dict: shapes, groups, values_compared, values_differing_bitwise, max_abs_delta, worst_case, seed, routes (route-counter deltas of
     the whole run), group_routes (those of each group's batched call), ...
     single: every shape through its own generate*() call (the literal drop-in: one fused launch per call, msdf_single.hpp) instead of one batch per group.
     framing: family names of tests/xformcases.py; each group then takes one of them (its transforms, Y orientation, and for tiny_bitmaps its bitmap size)
     instead of autoframe. None keeps the autoframed sweep and its exact sequence of random draws.
+    geometry: family names of tests/geomcases.py instead (see plan()); NaN and infinity then count as equal only with the same bits.
     scale, scanline, modes: see plan(). tuning: MSDFHIP_* variables set for the run (tuned()).
     min_groups: groups run even past the deadline (a slow box trims a sweep, it does not empty it).
     stencil: the correction's stencil of every batched msdf / mtsdf group with error correction is compared with the oracle's too.
@@ -185,7 +223,7 @@ def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="smal
     min_glyphs, min_tiles = None, None
     with tuned(tuning or {}):
         routes0 = M.route_counts()
-        for grp in plan(n_shapes, seed, framing=framing, scale=scale, scanline=scanline, modes=modes):
+        for grp in plan(n_shapes, seed, framing=framing, scale=scale, scanline=scanline, modes=modes, geometry=geometry):
             if deadline_s is not None and time.time()-t0 >= deadline_s and groups >= min_groups:
                 break
             n, mode, w, h, overlap, kind = grp["n"], grp["mode"], grp["w"], grp["h"], grp["overlap"], grp["kind"]
@@ -244,7 +282,8 @@ def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="smal
             res = list(pool.map(want, range(n)))
             want_f = np.stack([r[0] for r in res])
             bad = got.view(np.uint32) != want_f.view(np.uint32)
-            bad &= ~(np.isnan(got) & np.isnan(want_f))
+            if geometry is None:
+                bad &= ~(np.isnan(got) & np.isnan(want_f))
             total += got.size
             differing += int(bad.sum())
             if want_st:
@@ -254,6 +293,8 @@ def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="smal
             if bad.any():
                 d = np.abs(got.astype(np.float64)-want_f.astype(np.float64))
                 d[~bad] = 0
+                if geometry is not None:
+                    d[np.isnan(d)] = np.inf                           # differing bits where a side is not finite: no smaller than any delta
                 m = float(np.nanmax(d))
                 if m > worst:
                     worst = m

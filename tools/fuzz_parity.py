@@ -4,6 +4,7 @@ values compared, the number differing bitwise and the worst |delta|; exit status
 
     python tools/fuzz_parity.py [--shapes 1500] [--seed 1] [--single] [--framing mirror_x,aniso,...|all]
                                 [--scale small|mixed|full] [--scanline] [--tuning NAME] [--stencil] [--paths]
+                                [--geometry lattice_ties,coincident,...|all]
 """
 import argparse
 import json
@@ -28,7 +29,15 @@ def main():
     ap.add_argument("--tuning", default=None, choices=sorted(fuzzlib.TUNINGS), help="a named MSDFHIP_* table of tests/fuzzlib.py (TUNINGS) for the run")
     ap.add_argument("--stencil", action="store_true", help="compare the error correction's stencils with the oracle's too")
     ap.add_argument("--paths", action="store_true", help="also run the groups through generate_stream and HostBatch.generate_host (bytes must match)")
+    ap.add_argument("--geometry", default=None, help="comma-separated outline families of tests/geomcases.py (or 'all'), jittered on their lattice")
     args = ap.parse_args()
+    geometry = None
+    if args.geometry:
+        import geomcases
+        geometry = list(geomcases.FAMILIES) if args.geometry == "all" else args.geometry.split(",")
+        bad = [f for f in geometry if f not in geomcases.FAMILIES]
+        if bad:
+            ap.error("unknown outline families %s; known: %s" % (bad, ", ".join(geomcases.FAMILIES)))
     framing = None
     if args.framing:
         import xformcases
@@ -37,10 +46,10 @@ def main():
         if bad:
             ap.error("unknown framing families %s; known: %s" % (bad, ", ".join(xformcases.FAMILIES)))
     r = fuzzlib.run(args.shapes, args.seed, single=args.single, framing=framing, scale=args.scale, scanline=args.scanline,
-                    tuning=fuzzlib.TUNINGS[args.tuning] if args.tuning else None, stencil=args.stencil, paths=args.paths)
+                    tuning=fuzzlib.TUNINGS[args.tuning] if args.tuning else None, stencil=args.stencil, paths=args.paths, geometry=geometry)
     r.pop("group_routes")
     print(json.dumps(r))
-    sys.exit(1 if r["max_abs_delta"] > 1e-5 or r["stencil_values_differing"] or r["path_values_differing"] else 0)
+    sys.exit(1 if r["max_abs_delta"] > 1e-5 or (geometry and r["values_differing_bitwise"]) or r["stencil_values_differing"] or r["path_values_differing"] else 0)
 
 
 if __name__ == "__main__":
