@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -23,6 +24,7 @@
 
 #include <sched.h>
 
+#include "msdf_classplan.hpp"
 #include "msdf_kernels.hpp"
 #include "msdf_single.hpp"
 
@@ -262,51 +264,120 @@ struct ScopedTimer {
     }
 };
 
+// A grow-on-demand allocation of a workspace: device memory, or (PINNED) host staging through pinnedAlloc / pinnedFree. It is OWNED -- freed when it has
+// to grow and when it goes -- or BORROWED from a caller's arena (the single-shape calls carve theirs), and then only dropped. Freed on the thread's
+// current device: the launches are bound to the batch's device, and a Workspace binds to its device before its buffers go.
+template <class T, bool PINNED = false>
+struct WorkBuffer {
+    T *ptr = NULL;
+    size_t cap = 0;                   // elements
+    bool owned = false;
+    WorkBuffer() { }
+    WorkBuffer(const WorkBuffer &) = delete;
+    WorkBuffer &operator=(const WorkBuffer &) = delete;
+    ~WorkBuffer() { release(); }
+    void release() {
+        if (owned && ptr)
+            (void) (PINNED ? pinnedFree(ptr) : hipFree(ptr));
+        ptr = NULL, cap = 0, owned = false;
+    }
+    void borrow(T *p, size_t n) { release(); ptr = p, cap = n; }
+    hipError_t ensure(size_t n) {
+        if (cap >= n)
+            return hipSuccess;
+        release();
+        const hipError_t e = PINNED ? pinnedAlloc((void **) &ptr, n*sizeof(T)) : hipMalloc((void **) &ptr, n*sizeof(T));
+        if (e != hipSuccess) {
+            ptr = NULL;
+            return e;
+        }
+        cap = n, owned = true;
+        return hipSuccess;
+    }
+};
+
+// What the launches on one batch (or on one glyph range after the other: pipeline slots, single-shape groups) work in. Launches on one batch are
+// ordered by the caller; the mutex guards the buffers against concurrent callers that only size them.
+struct Workspace {
+    int device = 0;
+    std::mutex mutex;
+    WorkBuffer<float> scratch;        // intermediate fields of a generate call whose caller brought no scratch
+    WorkBuffer<EcCandidate> deferred; // [0] = header (count), [1..] = distance checks deferred to k_ec_query, then its work list and k_ec_params' corner list
+    WorkBuffer<EcGlyphParams> ecParams;   // per glyph: constants of the error-correction pass
+    WorkBuffer<double> gres;          // global combiner scratch for glyphs whose contour count exceeds what LDS can hold
+    WorkBuffer<unsigned> workQueue;   // item counters of the persistent distance launch: TWO sets of 8 per-XCD counters, 64 bytes apart; zeroed once by the host, then each launch zeroes the set the NEXT one uses
+    unsigned queueParity = 0;         // which set the next persistent launch draws from
+    WorkBuffer<int> bucket;           // per glyph: the class list (msdf_classplan.hpp) of the batch's ClassPlan
+    WorkBuffer<int, true> hBucket;    // pinned host copy the list is uploaded from, ON THE LAUNCH STREAM (a synchronous copy of pageable memory may
+                                      // still be in flight on the null stream when a kernel of a non-blocking stream starts)
+    int bucketKey = -1;               // the contour limit and edge bound the list in `bucket` was built for (-1: none)
+    bool bucketUploaded = false;      // an upload from hBucket may still be in flight
+    WorkBuffer<int> ecOrder;          // glyph indices heaviest first (k_ec_scan / k_ec_query), built on first use; none: batch order
+    WorkBuffer<int, true> hEcOrder;   // (pinned host copy it is uploaded from)
+    hipEvent_t ecOrderReady = NULL;   // (recorded behind that upload)
+    bool ecOrderTried = false;
+    hipStream_t sideStream[2] = { NULL, NULL };   // the three glyph classes of the distance pass run concurrently: two of them on these (fork / join by events)
+    hipEvent_t forkEvent = NULL, joinEvent[2] = { NULL, NULL };
+
+    size_t reservedGlyphs = 0;        // the per-glyph buffers (bucket, hBucket, ecParams) are allocated for ranges of at least this many glyphs
+
+    // A new glyph range follows (a pipeline slot is pointed at its next chunk): the class list is not its list. The caller has seen the range before it
+    // finish -- the pipeline waits for the slot's `done` event, recorded behind everything of its previous chunk -- so no upload still reads hBucket.
+    void newGlyphRange() { bucketKey = -1, bucketUploaded = false; }
+    // Glyph ranges of up to n glyphs follow (a pipeline slot: a full chunk, whatever the length of its first one). Nothing of the workspace is in flight.
+    void reserveGlyphs(size_t n) {
+        bucket.release(), hBucket.release(), ecParams.release();   // (allocated again by the launches that need them)
+        reservedGlyphs = n;
+        newGlyphRange();
+    }
+    size_t glyphCapacity(int nGlyphs) const { return std::max(std::max((size_t) (nGlyphs > 0 ? nGlyphs : 0), reservedGlyphs), (size_t) 1); }
+    ~Workspace() {
+        if (!(scratch.owned || deferred.owned || ecParams.owned || gres.owned || workQueue.owned || bucket.owned || hBucket.owned || ecOrder.owned || hEcOrder.owned ||
+              ecOrderReady || forkEvent || sideStream[0] || sideStream[1]))
+            return;                                              // (a view over an arena that never had to grow: no device call)
+        (void) hipSetDevice(device);
+        for (int k = 0; k < 2; ++k) {
+            if (sideStream[k])
+                hipStreamDestroy(sideStream[k]);
+            if (joinEvent[k])
+                hipEventDestroy(joinEvent[k]);
+        }
+        if (forkEvent)
+            hipEventDestroy(forkEvent);
+        if (ecOrderReady)
+            hipEventDestroy(ecOrderReady);
+    }                                                            // (then the buffers, on that device)
+};
+
+// The shapes of a batch, fixed once it is digested: CSR arrays and edge records on the device, per-glyph counts on the host.
+struct ShapeData {
+    int nGlyphs = 0, nContours = 0, nEdges = 0, maxContours = 0, maxEdges = 0;
+    int32_t *dGlyphContourOffsets = NULL, *dContourOffsets = NULL;
+    double *dPoints = NULL;
+    uint8_t *dTypes = NULL, *dColors = NULL;
+    EdgeRec *dRecs = NULL;
+    int8_t *dWindings = NULL;
+    mutable std::vector<int> hContours, hEdges;   // contours / edges per glyph (batches of device arrays: fetched on first need, fetchGlyphCounts)
+    void countMaxima() {                          // maxContours / maxEdges of the per-glyph counts
+        maxContours = maxEdges = 0;
+        for (size_t g = 0; g < hContours.size(); ++g)
+            maxContours = std::max(maxContours, hContours[g]), maxEdges = std::max(maxEdges, hEdges[g]);
+    }
+    void setCounts(const int *contours, const int *edges, int n) {
+        hContours.assign(contours, contours+n), hEdges.assign(edges, edges+n);
+        countMaxima();
+    }
+};
+
 } // namespace
 
-struct MsdfHipBatch {
-    int device;                       // the HIP device the batch lives on; every call on the batch binds the calling thread to it
-    int nGlyphs, nContours, nEdges, maxContours, maxEdges;
-    bool ownsInputs;
-    int32_t *dGlyphContourOffsets, *dContourOffsets;
-    double *dPoints;
-    uint8_t *dTypes, *dColors;
-    EdgeRec *dRecs;
-    int8_t *dWindings;
-    mutable float *dScratch;
-    mutable size_t scratchFloats;
-    mutable EcCandidate *dDeferred;   // [0] = header (count), [1..cap] = distance checks deferred to k_ec_query
-    mutable EcGlyphParams *dEcParams; // per-glyph constants of the error-correction pass
-    mutable double *dGres;            // global combiner scratch for glyphs whose contour count exceeds what LDS can hold
-    mutable unsigned *dWorkQueue;     // item counters of the persistent distance launch: TWO sets of 8 per-XCD counters, 64 bytes apart; zeroed once by the host, then each launch zeroes the set the NEXT one uses
-    mutable unsigned queueParity;     // which set the next persistent launch draws from
-    mutable size_t gresBytes;
-    mutable bool gresExternal;        // dGres belongs to someone else (the single-shape calls carve it from their arena)
-    mutable size_t deferredCap;
-    mutable std::mutex scratchMutex;
-    mutable std::vector<int> hContours; // contours per glyph (host copy, fetched on first need)
-    mutable std::vector<int> hEdges;    // edges per glyph (host copy, fetched with hContours)
-    mutable int bucketLimit;          // the contour limit dBucket was built for (-1 = none)
-    mutable int *dBucket;             // glyph indices: [nOne with <= 1 contour][nSmall with 2..bucketLimit contours][the others]
-    mutable int *hBucket;             // pinned host copy the device list is uploaded from, ON THE LAUNCH STREAM (a synchronous copy of pageable
-                                      // memory may still be in flight on the null stream when a kernel of a non-blocking stream starts)
-    mutable bool bucketExternal;      // dBucket / hBucket belong to someone else (the single-shape calls carve them from their arena)
-    mutable bool bucketUploaded;
-    mutable int nOne, nSmall, smallMaxC, smallMaxE, oneMaxE;
-    mutable int nHuge, restMaxC, restMaxE;   // glyphs whose survivor lists exceed a CU's LDS (list-free kernel, last in dBucket); maxima of the class before them
-    mutable float restShare;          // the global-scratch class's share of the batch's modelled cost (glyphCost): sizes its persistent launch
-    bool serialClasses;               // launch the glyph classes one after the other on the caller's stream (host-output pipeline: its chunks overlap instead)
-    mutable int *hEcOrder;            // (pinned host copy the list below is uploaded from)
-    mutable hipEvent_t ecOrderReady;  // (recorded behind that upload)
-    mutable int *dEcOrder;            // glyph indices heaviest first (k_ec_scan / k_ec_query), built on first use; NULL: batch order
-    mutable bool ecOrderTried;
-    int glyphCap;                     // per-glyph work buffers are sized for max(nGlyphs, glyphCap) glyphs (views of the host-output pipeline)
-    mutable hipStream_t sideStream[2];   // the three glyph classes of the distance pass run concurrently: two of them on these (fork / join by events)
-    mutable hipEvent_t forkEvent, joinEvent[2];
-    MsdfHipBatch() : device(0), nGlyphs(0), nContours(0), nEdges(0), maxContours(0), maxEdges(0), ownsInputs(false), dGlyphContourOffsets(NULL),
-                     dContourOffsets(NULL), dPoints(NULL), dTypes(NULL), dColors(NULL), dRecs(NULL), dWindings(NULL), dScratch(NULL), scratchFloats(0),
-                     dDeferred(NULL), dEcParams(NULL), dGres(NULL), dWorkQueue(NULL), queueParity(0), gresBytes(0), gresExternal(false), deferredCap(0), bucketLimit(-1), dBucket(NULL), hBucket(NULL), bucketExternal(false), bucketUploaded(false), nOne(0), nSmall(0),
-                     smallMaxC(0), smallMaxE(0), oneMaxE(0), nHuge(0), restMaxC(0), restMaxE(0), restShare(1.f), serialClasses(false), hEcOrder(NULL), ecOrderReady(NULL), dEcOrder(NULL), ecOrderTried(false), glyphCap(0), forkEvent(NULL) { sideStream[0] = sideStream[1] = NULL, joinEvent[0] = joinEvent[1] = NULL; }
+struct MsdfHipBatch : ShapeData {
+    int device = 0;                   // the HIP device the batch lives on; every call on the batch binds the calling thread to it
+    bool ownsInputs = false;          // the five input arrays are the batch's (dRecs / dWindings: a batch made with `new` owns them, a view never does)
+    bool serialClasses = false;       // launch the glyph classes one after the other on the caller's stream (host-output pipeline: its chunks overlap instead)
+    mutable Workspace work;
+    mutable ClassPlan plan;           // the classes of work.bucket
+    void onDevice(int d) { device = work.device = d; }
 };
 
 namespace {
@@ -342,11 +413,24 @@ int digest(MsdfHipBatch *b, hipStream_t stream) {
     return MSDFHIP_OK;
 }
 
+int fetchGlyphCounts(const MsdfHipBatch *b) {             // device-array batches: the per-glyph counts are read back once
+    if (!b->hContours.empty() || b->nGlyphs == 0)
+        return MSDFHIP_OK;
+    std::vector<int32_t> gco((size_t) b->nGlyphs+1), co((size_t) b->nContours+1);
+    HIPCHK(hipMemcpy(gco.data(), b->dGlyphContourOffsets, sizeof(int32_t)*gco.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(co.data(), b->dContourOffsets, sizeof(int32_t)*co.size(), hipMemcpyDeviceToHost));
+    b->hContours.resize((size_t) b->nGlyphs);
+    b->hEdges.resize((size_t) b->nGlyphs);
+    for (int g = 0; g < b->nGlyphs; ++g) {
+        b->hContours[g] = gco[g+1]-gco[g];
+        b->hEdges[g] = co[gco[g+1]]-co[gco[g]];
+    }
+    return MSDFHIP_OK;
+}
+
 // LDS plan for a launch: bytes of dynamic LDS, the stride of the per-tile survivor lists, and where the combiner scratch lives.
 struct LdsPlan { size_t bytes; bool globalRes; size_t resBytes, ldsBudget, idxBytes; int listStride; };
 const size_t GRES_WORKSPACE_CAP = (size_t) 1<<30;   // bound of the global combiner scratch; larger launches are chunked
-const int SMALL_MAX_EDGES = 128;                    // cost model only: the edge bound of the LDS-scratch class (tuning().smallMaxEdges is what the launches use)
-const int COST_LDS_MAX_CONTOURS = 5;                // cost model only: the LDS class's contour bound at the default LDS budget, msdf (ensureBuckets derives the real one per launch)
 
 // SIMDs of a device (4 per compute unit): the number of wavefronts of a W-waves-per-SIMD kernel it holds at once is residentSlots()*W.
 int residentSlots(int device) {
@@ -361,10 +445,6 @@ int residentSlots(int device) {
     }
     return n;
 }
-
-// LDS of k_distance's phase 1 per tile: survivor list [maxEdges], list offsets per contour [C+1] (+1 spare) and, in the global-scratch
-// form, the per-contour channel bounds [C][3] (the LDS form keeps those in the combiner scratch's region)
-size_t tileListBytes(int maxEdges, int maxContours, bool withBounds) { return ((size_t) maxEdges+(withBounds ? 4 : 1)*(size_t) maxContours+2)*sizeof(int); }
 
 size_t ldsBudget() {
     // The combiner scratch lives in LDS only while 16 wavefronts (4 per SIMD, the register-limited occupancy: MSDF_DISTANCE_WAVES_PER_SIMD) fit a CU's
@@ -409,34 +489,28 @@ int setLds(K kernel, size_t bytes) {
 // and zeroes the other (distanceBody), so the host zeroes them once, when a batch (or pipeline view) first needs them. (Launches on one batch are ordered
 // on the caller's stream, as they always had to be: they share the batch's workspaces.) Their one-time zeroing goes onto the stream of the first launch.
 int ensureWorkQueue(const MsdfHipBatch *b, unsigned **out, hipStream_t stream) {
-    std::lock_guard<std::mutex> lock(b->scratchMutex);
-    if (!b->dWorkQueue) {
-        HIPCHK(hipMalloc((void **) &b->dWorkQueue, 256));
+    std::lock_guard<std::mutex> lock(b->work.mutex);
+    WorkBuffer<unsigned> &q = b->work.workQueue;
+    if (!q.ptr) {
+        HIPCHK(q.ensure(64));
         // Zeroed ON THE STREAM of the launch that needs it first, i.e. ordered in front of that launch. (hipMemset would run on the legacy default stream, which
         // a non-blocking stream does not wait for, and may return before it has run: the counters could be zeroed UNDER the first launch -- the race the
         // sanitizer run of round 4 found in the single-call arenas, DESIGN.md 3.9. Later launches on this batch are ordered behind the first by the caller, as
         // they always had to be: they share the batch's workspaces.)
-        const hipError_t e = hipMemsetAsync(b->dWorkQueue, 0, 256, stream);
+        const hipError_t e = hipMemsetAsync(q.ptr, 0, 256, stream);
         if (e != hipSuccess) {
-            hipFree(b->dWorkQueue);
-            b->dWorkQueue = NULL;
+            q.release();
             return fail(MSDFHIP_ERR_HIP, "work queue of the persistent launch: %s", hipGetErrorString(e));
         }
     }
-    *out = b->dWorkQueue;
+    *out = q.ptr;
     return MSDFHIP_OK;
 }
 
 int ensureGres(const MsdfHipBatch *b, size_t bytes, double **out) {
-    std::lock_guard<std::mutex> lock(b->scratchMutex);
-    if (b->gresBytes < bytes) {
-        if (b->dGres && !b->gresExternal)
-            hipFree(b->dGres);
-        b->dGres = NULL, b->gresBytes = 0, b->gresExternal = false;
-        HIPCHK(hipMalloc((void **) &b->dGres, bytes));
-        b->gresBytes = bytes;
-    }
-    *out = b->dGres;
+    std::lock_guard<std::mutex> lock(b->work.mutex);
+    HIPCHK(b->work.gres.ensure((bytes+sizeof(double)-1)/sizeof(double)));
+    *out = b->work.gres.ptr;
     return MSDFHIP_OK;
 }
 
@@ -497,12 +571,12 @@ int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
             // be issued has neither dirtied its own set nor zeroed the other, so the next launch must draw from the same (still zero) set again --
             // flipped up front, it would draw from the set the last successful launch left dirty and render no tile of the class.
             // Launches on one batch are ordered by the caller (they share the batch's workspaces).
-            std::lock_guard<std::mutex> lock(b->scratchMutex);
-            queue += b->queueParity ? 16 : 0;                    // (the kernel finds the other set at `queue ^ 64 bytes`)
+            std::lock_guard<std::mutex> lock(b->work.mutex);
+            queue += b->work.queueParity ? 16 : 0;                    // (the kernel finds the other set at `queue ^ 64 bytes`)
             args.gres = gres, args.gresStride = stride, args.workQueue = queue, args.workItems = (unsigned) blocks;
             launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) chunk, plan.bytes, stream, args);
             HIPCHK(hipGetLastError());
-            b->queueParity ^= 1u;
+            b->work.queueParity ^= 1u;
             if (persistent)
                 *persistent = true;
             return MSDFHIP_OK;
@@ -537,154 +611,83 @@ int uploadSmall(void *dst, const void *srcPinned, size_t bytes, hipStream_t stre
     return MSDFHIP_OK;
 }
 
-// Cost of one glyph in microseconds at 64x64 (only the ratios matter): a + b*E + c*C + d*E*C per kernel class, fitted to measured kernel
-// times (tools/fit_cost_model.py, profiles/r06_cost_model.json: refitted in round 6; the same table as msdfgen_amd/shard.py: COST_MODEL).
-static double glyphCost(int contours, int edges) {
-    static const double kOne[4] = { 0.25625, 0.01190, 0.00000, 0.00000 }, kLds[4] = { 0.38398, 0.00846, -0.02755, 0.003446 }, kGlobal[4] = { 1.11611, 0.015776, -0.05039, 0.000681 };
-    const double *k = contours <= 1 ? kOne : (contours <= COST_LDS_MAX_CONTOURS && edges <= SMALL_MAX_EDGES) ? kLds : kGlobal;
-    const double c = k[0]+k[1]*edges+k[2]*contours+k[3]*(double) edges*contours;
-    return c > k[0] ? c : k[0];                                  // never below the class's intercept (the fit's negative contour terms are local to the measured range)
-}
-
-// Glyph indices sorted into three classes of the overlapping combiner; cached per limit:
-//   one    <= 1 contour: the combiner reduces to the simple one (contour-combiners.cpp:104-133 with a single selector) -- these run the
-//          simple-combiner kernel, which needs 95 VGPRs instead of ~150 and therefore runs 5 instead of 3 wavefronts per SIMD;
-//   small  2..limit contours: per-contour distances in LDS;
-//   rest   more: per-contour distances in the global workspace.
+// The class list of the overlapping combiner (msdf_classplan.hpp) for this contour limit, cached with the batch: b->work.bucket + b->plan.
 int ensureBuckets(const MsdfHipBatch *b, int limit, hipStream_t stream) {
-    std::lock_guard<std::mutex> lock(b->scratchMutex);
+    Workspace &ws = b->work;
+    std::lock_guard<std::mutex> lock(ws.mutex);
     const int bucketKey = limit+(tuning().smallMaxEdges<<12);    // what the class lists depend on
-    if (b->bucketLimit == bucketKey && b->dBucket)
+    if (ws.bucketKey == bucketKey && ws.bucket.ptr)
         return MSDFHIP_OK;
-    if ((b->hContours.empty() || b->hEdges.empty()) && b->nGlyphs > 0) {   // batch created from device arrays: read the offsets back once
-        std::vector<int32_t> gco((size_t) b->nGlyphs+1), co((size_t) b->nContours+1);
-        HIPCHK(hipMemcpy(gco.data(), b->dGlyphContourOffsets, sizeof(int32_t)*gco.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(co.data(), b->dContourOffsets, sizeof(int32_t)*co.size(), hipMemcpyDeviceToHost));
-        b->hContours.resize((size_t) b->nGlyphs);
-        b->hEdges.resize((size_t) b->nGlyphs);
-        for (int g = 0; g < b->nGlyphs; ++g) {
-            b->hContours[g] = gco[g+1]-gco[g];
-            b->hEdges[g] = co[gco[g+1]]-co[gco[g]];
-        }
-    }
-    const size_t cap = (size_t) (b->nGlyphs > b->glyphCap ? b->nGlyphs : b->glyphCap > 0 ? b->glyphCap : 1);
-    if (!b->dBucket)
-        HIPCHK(hipMalloc((void **) &b->dBucket, sizeof(int)*cap));
-    if (!b->hBucket)
-        HIPCHK(pinnedAlloc((void **) &b->hBucket, sizeof(int)*cap));
-    if (b->bucketUploaded)                                       // an earlier upload from hBucket (same batch, other limit) must have left it
+    const int rcCounts = fetchGlyphCounts(b);
+    if (rcCounts != MSDFHIP_OK)
+        return rcCounts;
+    const size_t cap = ws.glyphCapacity(b->nGlyphs);
+    HIPCHK(ws.bucket.ensure(cap));
+    HIPCHK(ws.hBucket.ensure(cap));
+    if (ws.bucketUploaded)                                       // an earlier upload from hBucket (same batch, other limit) must have left it
         HIPCHK(hipStreamSynchronize(stream));
-    int *order = b->hBucket;
-    int at = 0, nOne = 0, nSmall = 0, smallMaxC = 0, smallMaxE = 0, oneMaxE = 0, restMaxC = 0, restMaxE = 0;
-    // A glyph whose survivor lists do not fit a CU's LDS (edges + 4 contours > ~40 000) takes the list-free kernel -- ALONE: round 3 sent the whole
-    // batch there with it. Such glyphs go last in the list, whatever their contour count; the three classes are formed of the others.
-    const size_t ldsLimit = (size_t) gLdsLimit.load();
-    const int smallMaxEdges = tuning().smallMaxEdges;
-    auto huge = [b, ldsLimit](int g) { return tileListBytes(b->hEdges[g], b->hContours[g], true) > ldsLimit; };
-    for (int g = 0; g < b->nGlyphs; ++g)
-        if (!huge(g) && b->hContours[g] <= 1) {
-            order[at++] = g;
-            oneMaxE = b->hEdges[g] > oneMaxE ? b->hEdges[g] : oneMaxE;
-        }
-    nOne = at;
-    for (int g = 0; g < b->nGlyphs; ++g)
-        if (!huge(g) && b->hContours[g] > 1 && b->hContours[g] <= limit && b->hEdges[g] <= smallMaxEdges) {
-            order[at++] = g;
-            smallMaxC = b->hContours[g] > smallMaxC ? b->hContours[g] : smallMaxC;
-            smallMaxE = b->hEdges[g] > smallMaxE ? b->hEdges[g] : smallMaxE;
-        }
-    nSmall = at-nOne;
-    for (int g = 0; g < b->nGlyphs; ++g)
-        if (!huge(g) && b->hContours[g] > 1 && !(b->hContours[g] <= limit && b->hEdges[g] <= smallMaxEdges)) {
-            order[at++] = g;
-            restMaxC = b->hContours[g] > restMaxC ? b->hContours[g] : restMaxC;
-            restMaxE = b->hEdges[g] > restMaxE ? b->hEdges[g] : restMaxE;
-        }
-    const int nCulled = at;
-    for (int g = 0; g < b->nGlyphs; ++g)
-        if (huge(g))
-            order[at++] = g;
-    // Heaviest glyphs first inside each class (longest-processing-time order: a launch is ~26 rounds of workgroups, its tail is the last round's
-    // heaviest glyph; the output does not depend on the order -- a glyph writes its own tiles).
-    {
-        const int *hE = b->hEdges.data(), *hC = b->hContours.data();
-        auto heavier = [hE, hC](int x, int y) { return (long long) hE[x]*(hC[x] > 1 ? hC[x] : 1) > (long long) hE[y]*(hC[y] > 1 ? hC[y] : 1); };
-        std::stable_sort(order, order+nOne, heavier);
-        std::stable_sort(order+nOne, order+nOne+nSmall, heavier);
-        std::stable_sort(order+nOne+nSmall, order+nCulled, heavier);
-    }
-    {
-        const int rcUp = uploadSmall(b->dBucket, b->hBucket, sizeof(int)*(size_t) b->nGlyphs, stream);   // (hBucket is pinned)
-        if (rcUp != MSDFHIP_OK)
-            return rcUp;
-    }
-    b->bucketUploaded = true;
-    {
-        double all = 0, rest = 0;
-        for (int g = 0; g < b->nGlyphs; ++g)
-            all += glyphCost(b->hContours[g], b->hEdges[g]);
-        for (int k = nOne+nSmall; k < nCulled; ++k)
-            rest += glyphCost(b->hContours[order[k]], b->hEdges[order[k]]);
-        b->restShare = all > 0 ? (float) (rest/all) : 1.f;
-    }
-    b->bucketLimit = bucketKey, b->nOne = nOne, b->nSmall = nSmall, b->smallMaxC = smallMaxC, b->smallMaxE = smallMaxE, b->oneMaxE = oneMaxE;
-    b->nHuge = at-nCulled, b->restMaxC = restMaxC, b->restMaxE = restMaxE;
+    const ClassPlan plan = planClasses(b->hContours.data(), b->hEdges.data(), b->nGlyphs, limit, tuning().smallMaxEdges, (size_t) gLdsLimit.load(), ws.hBucket.ptr);
+    const int rcUp = uploadSmall(ws.bucket.ptr, ws.hBucket.ptr, sizeof(int)*(size_t) b->nGlyphs, stream);   // (hBucket is pinned)
+    if (rcUp != MSDFHIP_OK)
+        return rcUp;
+    ws.bucketUploaded = true;
+    b->plan = plan, ws.bucketKey = bucketKey;
     return MSDFHIP_OK;
 }
 
 // The work list of the distance checks in heaviest-first order (edges x contours, like the glyph classes above): whole batches of at least
 // 256 glyphs whose per-glyph counts are on the host; views of the host-output pipeline and the single-shape groups keep batch order.
 int ensureEcOrder(const MsdfHipBatch *b, const int **order, hipStream_t stream) {
-    std::lock_guard<std::mutex> lock(b->scratchMutex);
-    *order = b->dEcOrder;
-    if (b->ecOrderTried) {
-        if (b->dEcOrder && b->ecOrderReady)                      // uploaded on the first caller's stream: any other stream waits for that (a no-op once it has landed)
-            HIPCHK(hipStreamWaitEvent(stream, b->ecOrderReady, 0));
+    Workspace &ws = b->work;
+    std::lock_guard<std::mutex> lock(ws.mutex);
+    *order = ws.ecOrder.ptr;
+    if (ws.ecOrderTried) {
+        if (ws.ecOrder.ptr && ws.ecOrderReady)                   // uploaded on the first caller's stream: any other stream waits for that (a no-op once it has landed)
+            HIPCHK(hipStreamWaitEvent(stream, ws.ecOrderReady, 0));
         return MSDFHIP_OK;
     }
-    b->ecOrderTried = true;
-    if (b->serialClasses || b->bucketExternal || b->nGlyphs < 256 || b->hEdges.size() != (size_t) b->nGlyphs ||
+    ws.ecOrderTried = true;
+    // (a borrowed class list marks the view of a single-shape group, which lives for one call: a list built for it would be an allocation per call)
+    if (b->serialClasses || (ws.bucket.ptr && !ws.bucket.owned) || b->nGlyphs < 256 || b->hEdges.size() != (size_t) b->nGlyphs ||
         b->hContours.size() != (size_t) b->nGlyphs)
         return MSDFHIP_OK;
     const size_t bytes = sizeof(int)*(size_t) b->nGlyphs;
     // The list is an optimisation: every failure below leaves *order = NULL (batch order) and the call succeeds.
-    if (pinnedAlloc((void **) &b->hEcOrder, bytes) != hipSuccess) {   // pinned and kept with the batch: the upload is ordered on the launch stream, nobody waits
+    if (ws.hEcOrder.ensure((size_t) b->nGlyphs) != hipSuccess) {  // pinned and kept with the batch: the upload is ordered on the launch stream, nobody waits
         (void) hipGetLastError();
-        b->hEcOrder = NULL;
         return MSDFHIP_OK;
     }
-    int *host = b->hEcOrder;
+    int *host = ws.hEcOrder.ptr;
     for (int g = 0; g < b->nGlyphs; ++g)
         host[g] = g;
     const int *hE = b->hEdges.data(), *hC = b->hContours.data();
     std::stable_sort(host, host+b->nGlyphs, [hE, hC](int x, int y) { return (long long) hE[x]*(hC[x] > 1 ? hC[x] : 1) > (long long) hE[y]*(hC[y] > 1 ? hC[y] : 1); });
-    int *dOrder = NULL;
-    if (hipMalloc((void **) &dOrder, bytes) != hipSuccess) {
+    if (ws.ecOrder.ensure((size_t) b->nGlyphs) != hipSuccess) {
         (void) hipGetLastError();
         return MSDFHIP_OK;
     }
-    if (uploadSmall(dOrder, host, bytes, stream) != MSDFHIP_OK) {
-        hipFree(dOrder);
+    if (uploadSmall(ws.ecOrder.ptr, host, bytes, stream) != MSDFHIP_OK) {
+        ws.ecOrder.release();
         return MSDFHIP_OK;
     }
-    if (hipEventCreateWithFlags(&b->ecOrderReady, hipEventDisableTiming) != hipSuccess || hipEventRecord(b->ecOrderReady, stream) != hipSuccess) {
+    if (hipEventCreateWithFlags(&ws.ecOrderReady, hipEventDisableTiming) != hipSuccess || hipEventRecord(ws.ecOrderReady, stream) != hipSuccess) {
         (void) hipGetLastError();
-        if (b->ecOrderReady)
-            hipEventDestroy(b->ecOrderReady);
-        b->ecOrderReady = NULL;
-        if (hipStreamSynchronize(stream) != hipSuccess) {        // no event for the other streams to wait on: the list must have landed before it is published
+        if (ws.ecOrderReady)
+            hipEventDestroy(ws.ecOrderReady);
+        ws.ecOrderReady = NULL;
+        if (hipStreamSynchronize(stream) != hipSuccess) {        // no event for the other streams to wait on: the list must have landed before it is used
             (void) hipGetLastError();
-            hipFree(dOrder);
+            ws.ecOrder.release();
             return MSDFHIP_OK;
         }
     }
-    b->dEcOrder = dOrder;                                        // published only once it is (or is ordered to be) complete
-    *order = b->dEcOrder;
+    *order = ws.ecOrder.ptr;                                     // handed out only once it is (or is ordered to be) complete
     return MSDFHIP_OK;
 }
 
 int ensureSideStreams(const MsdfHipBatch *b) {
-    if (b->forkEvent)
+    Workspace &ws = b->work;
+    if (ws.forkEvent)
         return MSDFHIP_OK;
     int least = 0, greatest = 0;
     (void) hipDeviceGetStreamPriorityRange(&least, &greatest);
@@ -692,26 +695,13 @@ int ensureSideStreams(const MsdfHipBatch *b) {
         // The two side classes run at LOW queue priority: the long LDS-class launch on the caller's stream gets the slots first and the side
         // classes fill what it leaves, its tail included (distance pass 3.93 -> 3.80-3.88 ms; high: 4.01).
         if (least != 0)
-            HIPCHK(hipStreamCreateWithPriority(&b->sideStream[k], hipStreamNonBlocking, least));
+            HIPCHK(hipStreamCreateWithPriority(&ws.sideStream[k], hipStreamNonBlocking, least));
         else
-            HIPCHK(hipStreamCreateWithFlags(&b->sideStream[k], hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&b->joinEvent[k], hipEventDisableTiming));
+            HIPCHK(hipStreamCreateWithFlags(&ws.sideStream[k], hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&ws.joinEvent[k], hipEventDisableTiming));
     }
-    HIPCHK(hipEventCreateWithFlags(&b->forkEvent, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ws.forkEvent, hipEventDisableTiming));
     return MSDFHIP_OK;
-}
-
-void destroySideStreams(const MsdfHipBatch *b) {
-    for (int k = 0; k < 2; ++k) {
-        if (b->sideStream[k])
-            hipStreamDestroy(b->sideStream[k]);
-        if (b->joinEvent[k])
-            hipEventDestroy(b->joinEvent[k]);
-        b->sideStream[k] = NULL, b->joinEvent[k] = NULL;
-    }
-    if (b->forkEvent)
-        hipEventDestroy(b->forkEvent);
-    b->forkEvent = NULL;
 }
 
 // The glyphs whose survivor lists exceed a CU's LDS take the list-free kernel (see k_distance_unculled): all of the batch, or those of dGlyphMap.
@@ -761,6 +751,18 @@ int overlapClassLimit(int nch) {
     return limitAll;
 }
 
+// How the distance pass of b at w x h takes its glyphs. hugeBatch: a glyph's survivor lists exceed a CU's LDS. smallLaunch: too few tiles to fill the
+// device -- one tile per wavefront, combiner scratch (overlap: nch channels per contour, bounded) in the global workspace.
+struct LaunchShape { bool hugeBatch, smallLaunch; };
+LaunchShape launchShape(const MsdfHipBatch *b, int w, int h, int nch, bool overlap) {
+    const size_t tilesAll = (size_t) b->nGlyphs*(size_t) (((w+TILE-1)/TILE)*((h+TILE-1)/TILE));
+    const size_t gresAll = tilesAll*(size_t) b->maxContours*nch*WAVE*sizeof(double);
+    LaunchShape l;
+    l.hugeBatch = tileListBytes(b->maxEdges, b->maxContours, true) > (size_t) gLdsLimit.load();
+    l.smallLaunch = !l.hugeBatch && tilesAll <= (size_t) tuning().smallLaunchTiles && (!overlap || gresAll <= ((size_t) 64<<20));
+    return l;
+}
+
 int runCorrection(const MsdfHipBatch *b, int channels, int w, int h, const MsdfHipGlyph *dGlyphs, const float *src, float *out, uint8_t *stencil,
                   const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call, bool paramsOnly = false);   // (below)
 // ecAhead: the config of the coming correction pass, whose k_ec_params may run next to the distance pass (NULL: not wanted); call.ecParamsQueued says whether it did.
@@ -770,7 +772,8 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
     // A glyph whose survivor lists exceed a CU's LDS takes the list-free kernel (the reference cannot fail on a large shape; neither may this) --
     // alone: in a batch, the OTHER glyphs keep the culled kernels (ensureBuckets puts the oversized ones last in the class list; maxE / maxC below
     // are the maxima of the rest). Round 3 sent the whole batch through the list-free kernel with it.
-    const bool hugeBatch = tileListBytes(b->maxEdges, b->maxContours, true) > (size_t) gLdsLimit.load();
+    const LaunchShape shape = launchShape(b, w, h, SelTraits<SEL>::NCH, overlap);
+    const bool hugeBatch = shape.hugeBatch, smallLaunch = shape.smallLaunch;
     if (hugeBatch && b->nGlyphs == 1) {
         ScopedTimer timer(stream, 0);
         return overlap && b->maxContours > 1 ? launchUnculled<SEL, true>(b, dGlyphs, w, h, dst, toScratch, stream)
@@ -783,9 +786,9 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
         rc = ensureBuckets(b, limitAll < 1 ? 1 : limitAll, stream);
         if (rc != MSDFHIP_OK)
             return rc;
-        nHuge = b->nHuge;
-        maxE = b->oneMaxE > b->smallMaxE ? b->oneMaxE : b->smallMaxE, maxE = b->restMaxE > maxE ? b->restMaxE : maxE;
-        maxC = b->smallMaxC > b->restMaxC ? b->smallMaxC : b->restMaxC, maxC = b->nOne > 0 && maxC < 1 ? 1 : maxC;
+        nHuge = b->plan.nHuge;
+        maxE = b->plan.oneMaxE > b->plan.smallMaxE ? b->plan.oneMaxE : b->plan.smallMaxE, maxE = b->plan.restMaxE > maxE ? b->plan.restMaxE : maxE;
+        maxC = b->plan.smallMaxC > b->plan.restMaxC ? b->plan.smallMaxC : b->plan.restMaxC, maxC = b->plan.nOne > 0 && maxC < 1 ? 1 : maxC;
         // (the lists are sized by the two maxima, which may come from different glyphs: if even those do not fit, or nothing is left, the whole batch goes list-free)
         if (nHuge == b->nGlyphs || tileListBytes(maxE, maxC, true) > (size_t) gLdsLimit.load()) {
             ScopedTimer timer(stream, 0);
@@ -803,8 +806,6 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
     // wavefront instead of four -- four times the wavefronts, a quarter of the serial work each -- with the combiner scratch in the
     // global workspace (single 64x64 glyph: 19 -> 8 us simple, ~100 -> ~30 us overlapping combiner).
     const int tilesAll = ((w+TILE-1)/TILE)*((h+TILE-1)/TILE);
-    const size_t gresAll = (size_t) b->nGlyphs*tilesAll*(size_t) maxC*SelTraits<SEL>::NCH*WAVE*sizeof(double);
-    const bool smallLaunch = !hugeBatch && (size_t) b->nGlyphs*tilesAll <= (size_t) tuning().smallLaunchTiles && (!overlap || gresAll <= ((size_t) 64<<20));
     LdsPlan single = plan;                                       // one tile per wavefront: one survivor list, scratch (if any) in global memory
     single.globalRes = true;
     single.bytes = tileListBytes(maxE, maxC, true);
@@ -819,11 +820,11 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
         }
         if (!hugeBatch)
             return counted(launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream), MSDFHIP_ROUTE_DIST_FULL_SIMPLE);
-        rc = nCulled > 0 ? counted(launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream, b->dBucket, nCulled), MSDFHIP_ROUTE_DIST_FULL_SIMPLE)
+        rc = nCulled > 0 ? counted(launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream, b->work.bucket.ptr, nCulled), MSDFHIP_ROUTE_DIST_FULL_SIMPLE)
                          : MSDFHIP_OK;
         if (rc == MSDFHIP_OK)                                    // (the oversized glyphs after the others on the same stream: they share the batch's workspace)
-            rc = overlap && b->maxContours > 1 ? launchUnculled<SEL, true>(b, dGlyphs, w, h, dst, toScratch, stream, b->dBucket+nCulled, nHuge)
-                                               : launchUnculled<SEL, false>(b, dGlyphs, w, h, dst, toScratch, stream, b->dBucket+nCulled, nHuge);
+            rc = overlap && b->maxContours > 1 ? launchUnculled<SEL, true>(b, dGlyphs, w, h, dst, toScratch, stream, b->work.bucket.ptr+nCulled, nHuge)
+                                               : launchUnculled<SEL, false>(b, dGlyphs, w, h, dst, toScratch, stream, b->work.bucket.ptr+nCulled, nHuge);
         return rc;
     }
     if (smallLaunch && b->nGlyphs == 1)
@@ -839,36 +840,36 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
     rc = ensureBuckets(b, limit < 1 ? 1 : limit, stream);
     if (rc != MSDFHIP_OK)
         return rc;
-    const int nRest = nCulled-b->nOne-b->nSmall;
+    const int nRest = nCulled-b->plan.nOne-b->plan.nSmall;
     if (smallLaunch) {
-        if (b->nOne > 0) {
-            rc = counted(launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, b->dBucket, b->nOne), MSDFHIP_ROUTE_DIST_SMALL_SIMPLE);
+        if (b->plan.nOne > 0) {
+            rc = counted(launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, b->work.bucket.ptr, b->plan.nOne), MSDFHIP_ROUTE_DIST_SMALL_SIMPLE);
             if (rc != MSDFHIP_OK)
                 return rc;
         }
-        if (b->nGlyphs > b->nOne)
-            return counted(launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, b->dBucket+b->nOne, b->nGlyphs-b->nOne),
+        if (b->nGlyphs > b->plan.nOne)
+            return counted(launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, b->work.bucket.ptr+b->plan.nOne, b->nGlyphs-b->plan.nOne),
                            MSDFHIP_ROUTE_DIST_SMALL_OVERLAP);
         return MSDFHIP_OK;
     }
     // The classes are disjoint sets of glyphs: their launches run CONCURRENTLY (the long LDS-class launch on the caller's stream, the other
     // two on the batch's side streams, forked and joined by events), so that the tail of one fills with the wavefronts of the others --
     // two processes sharing the GPU had measured 12 % more throughput than one.
-    const int classes = (b->nOne > 0)+(b->nSmall > 0)+(nRest > 0);
+    const int classes = (b->plan.nOne > 0)+(b->plan.nSmall > 0)+(nRest > 0);
     const bool concurrent = classes > 1 && !tuning().serialClasses && !b->serialClasses;
     hipStream_t sOne = stream, sRest = stream;
     if (concurrent) {
         rc = ensureSideStreams(b);
         if (rc != MSDFHIP_OK)
             return rc;
-        HIPCHK(hipEventRecord(b->forkEvent, stream));
-        if (nRest > 0 && b->nSmall > 0) {
-            sRest = b->sideStream[0];
-            HIPCHK(hipStreamWaitEvent(sRest, b->forkEvent, 0));
+        HIPCHK(hipEventRecord(b->work.forkEvent, stream));
+        if (nRest > 0 && b->plan.nSmall > 0) {
+            sRest = b->work.sideStream[0];
+            HIPCHK(hipStreamWaitEvent(sRest, b->work.forkEvent, 0));
         }
-        if (b->nOne > 0 && (b->nSmall > 0 || nRest > 0)) {
-            sOne = b->sideStream[1];
-            HIPCHK(hipStreamWaitEvent(sOne, b->forkEvent, 0));
+        if (b->plan.nOne > 0 && (b->plan.nSmall > 0 || nRest > 0)) {
+            sOne = b->work.sideStream[1];
+            HIPCHK(hipStreamWaitEvent(sOne, b->work.forkEvent, 0));
         }
     }
     // (an error between fork and join must not leave side-stream kernels unordered with the caller's stream: the launches only set rc,
@@ -886,47 +887,47 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
         size_t shareGrid = 0;
         if (tuning().shareGridFactor > 0 && concurrent) {
             const size_t slots = (size_t) residentSlots(b->device)*4u*MSDF_DISTANCE_WAVES_PER_SIMD;
-            shareGrid = (size_t) ((double) slots*b->restShare*tuning().shareGridFactor);
+            shareGrid = (size_t) ((double) slots*b->plan.restShare*tuning().shareGridFactor);
             shareGrid = shareGrid < 256 ? 256 : shareGrid;
         }
-        rc = launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, rest, sRest, b->dBucket+b->nOne+b->nSmall, nRest, shareGrid, &persistent);
+        rc = launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, rest, sRest, b->work.bucket.ptr+b->plan.nOne+b->plan.nSmall, nRest, shareGrid, &persistent);
         rc = counted(rc, persistent ? MSDFHIP_ROUTE_DIST_GLOBAL_PERSISTENT : MSDFHIP_ROUTE_DIST_GLOBAL_DIRECT);
     }
-    if (rc == MSDFHIP_OK && b->nSmall > 0) {
+    if (rc == MSDFHIP_OK && b->plan.nSmall > 0) {
         // A launch of few rounds of wavefronts (a shard of an atlas: BASELINE config 4 over 8 GPUs leaves 1 024 glyphs per device) ends when its
         // last wavefronts do, and a wavefront of four tiles is four times as long: below shortRounds rounds the class takes one tile per wavefront.
         const size_t slots = (size_t) residentSlots(b->device)*4u*MSDF_DISTANCE_WAVES_PER_SIMD;
-        const bool shortLaunch = classTpw == 1 || (size_t) b->nSmall*(size_t) ((tilesAll+QUAD-1)/QUAD) < (size_t) tuning().shortRounds*slots;
+        const bool shortLaunch = classTpw == 1 || (size_t) b->plan.nSmall*(size_t) ((tilesAll+QUAD-1)/QUAD) < (size_t) tuning().shortRounds*slots;
         LdsPlan small;
-        rc = planLds(b, SelTraits<SEL>::NCH, true, small, b->smallMaxC, b->smallMaxE, shortLaunch ? 1 : (int) QUAD);
+        rc = planLds(b, SelTraits<SEL>::NCH, true, small, b->plan.smallMaxC, b->plan.smallMaxE, shortLaunch ? 1 : (int) QUAD);
         if (rc == MSDFHIP_OK)
-            rc = shortLaunch ? counted(launchDistance<SEL, true, false, 1>(b, dGlyphs, w, h, dst, toScratch, small, stream, b->dBucket+b->nOne, b->nSmall),
+            rc = shortLaunch ? counted(launchDistance<SEL, true, false, 1>(b, dGlyphs, w, h, dst, toScratch, small, stream, b->work.bucket.ptr+b->plan.nOne, b->plan.nSmall),
                                        MSDFHIP_ROUTE_DIST_LDS_SINGLE)
-                             : counted(launchDistance<SEL, true, false>(b, dGlyphs, w, h, dst, toScratch, small, stream, b->dBucket+b->nOne, b->nSmall),
+                             : counted(launchDistance<SEL, true, false>(b, dGlyphs, w, h, dst, toScratch, small, stream, b->work.bucket.ptr+b->plan.nOne, b->plan.nSmall),
                                        MSDFHIP_ROUTE_DIST_LDS_QUAD);
     }
-    if (rc == MSDFHIP_OK && b->nOne > 0) {
+    if (rc == MSDFHIP_OK && b->plan.nOne > 0) {
         const size_t slots = (size_t) residentSlots(b->device)*4u*MSDF_SIMPLE_WAVES_PER_SIMD;
-        const bool shortLaunch = (size_t) b->nOne*(size_t) ((tilesAll+QUAD-1)/QUAD) < (size_t) tuning().shortRounds*slots;   // as for the LDS class above
+        const bool shortLaunch = (size_t) b->plan.nOne*(size_t) ((tilesAll+QUAD-1)/QUAD) < (size_t) tuning().shortRounds*slots;   // as for the LDS class above
         LdsPlan simple;
-        rc = planLds(b, SelTraits<SEL>::NCH, false, simple, 1, b->oneMaxE, shortLaunch ? 1 : (int) QUAD);
+        rc = planLds(b, SelTraits<SEL>::NCH, false, simple, 1, b->plan.oneMaxE, shortLaunch ? 1 : (int) QUAD);
         if (rc == MSDFHIP_OK && shortLaunch) {
-            simple.bytes = tileListBytes(b->oneMaxE, 1, true);
-            rc = counted(launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, simple, sOne, b->dBucket, b->nOne), MSDFHIP_ROUTE_DIST_ONE_SINGLE);
+            simple.bytes = tileListBytes(b->plan.oneMaxE, 1, true);
+            rc = counted(launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, simple, sOne, b->work.bucket.ptr, b->plan.nOne), MSDFHIP_ROUTE_DIST_ONE_SINGLE);
         } else if (rc == MSDFHIP_OK)
-            rc = counted(launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, simple, sOne, b->dBucket, b->nOne), MSDFHIP_ROUTE_DIST_ONE_QUAD);
+            rc = counted(launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, simple, sOne, b->work.bucket.ptr, b->plan.nOne), MSDFHIP_ROUTE_DIST_ONE_QUAD);
     }
     hipError_t joinError = hipSuccess;
     if (sRest != stream) {
-        hipError_t e = hipEventRecord(b->joinEvent[0], sRest);
+        hipError_t e = hipEventRecord(b->work.joinEvent[0], sRest);
         if (e == hipSuccess)
-            e = hipStreamWaitEvent(stream, b->joinEvent[0], 0);
+            e = hipStreamWaitEvent(stream, b->work.joinEvent[0], 0);
         joinError = e != hipSuccess ? e : joinError;
     }
     if (sOne != stream) {
-        hipError_t e = hipEventRecord(b->joinEvent[1], sOne);
+        hipError_t e = hipEventRecord(b->work.joinEvent[1], sOne);
         if (e == hipSuccess)
-            e = hipStreamWaitEvent(stream, b->joinEvent[1], 0);
+            e = hipStreamWaitEvent(stream, b->work.joinEvent[1], 0);
         joinError = e != hipSuccess ? e : joinError;
     }
     rc = aheadRc != MSDFHIP_OK ? aheadRc : rc;                   // (queued before the classes: its error is the call's first)
@@ -940,7 +941,7 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
             rc = fail(MSDFHIP_ERR_HIP, "joining the glyph-class streams failed: %s", hipGetErrorString(joinError));
     }
     if (rc == MSDFHIP_OK && nHuge > 0)                           // after the join: the list-free kernel shares the batch's workspace with the global-scratch class
-        rc = launchUnculled<SEL, true>(b, dGlyphs, w, h, dst, toScratch, stream, b->dBucket+nCulled, nHuge);
+        rc = launchUnculled<SEL, true>(b, dGlyphs, w, h, dst, toScratch, stream, b->work.bucket.ptr+nCulled, nHuge);
     return rc;
 }
 
@@ -954,18 +955,10 @@ size_t deferredRecords(int nGlyphs, size_t texelsPerGlyph, int nEdges) {
 }
 
 int ensureDeferred(const MsdfHipBatch *b, size_t cap, EcCandidate **out) {
-    std::lock_guard<std::mutex> lock(b->scratchMutex);
-    if (b->deferredCap < cap) {
-        if (b->dDeferred)
-            hipFree(b->dDeferred);
-        b->dDeferred = NULL;
-        b->deferredCap = 0;
-        HIPCHK(hipMalloc((void **) &b->dDeferred, cap*sizeof(EcCandidate)));
-        b->deferredCap = cap;
-    }
-    if (!b->dEcParams)
-        HIPCHK(hipMalloc((void **) &b->dEcParams, sizeof(EcGlyphParams)*(size_t) (b->nGlyphs > b->glyphCap ? b->nGlyphs : b->glyphCap > 0 ? b->glyphCap : 1)));
-    *out = b->dDeferred;
+    std::lock_guard<std::mutex> lock(b->work.mutex);
+    HIPCHK(b->work.deferred.ensure(cap));
+    HIPCHK(b->work.ecParams.ensure(b->work.glyphCapacity(b->nGlyphs)));
+    *out = b->work.deferred.ptr;
     return MSDFHIP_OK;
 }
 
@@ -1103,7 +1096,7 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
             queryBlocks = resident;
     }
     if (!call.ecParamsQueued)
-        hipLaunchKernelGGL(k_ec_params, dim3((unsigned) b->nGlyphs), dim3(WAVE), 0, stream, b->dEcParams, viewOf(b), dGlyphs, cfg,
+        hipLaunchKernelGGL(k_ec_params, dim3((unsigned) b->nGlyphs), dim3(WAVE), 0, stream, b->work.ecParams.ptr, viewOf(b), dGlyphs, cfg,
                            reinterpret_cast<unsigned *>(deferred), corners, offsets+ecSizesAt(b->nGlyphs));   // also zeroes the candidate header
     const int *ecOrder = NULL;                                   // glyphs heaviest first for the distance checks' work list (NULL: batch order)
     rc = ensureEcOrder(b, &ecOrder, stream);
@@ -1115,11 +1108,11 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         return MSDFHIP_OK;
     }
     hipLaunchKernelGGL((k_ec_fast<N>), dim3(blocks), dim3(WAVE), fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
-                       (const EcGlyphParams *) b->dEcParams, deferred, seg, b->maxEdges, (const int *) corners);
+                       (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
     hipLaunchKernelGGL(k_ec_scan, dim3(1), dim3(1024), 0, stream, b->nGlyphs, reinterpret_cast<const unsigned *>(deferred), seg, offsets, lpcMaxContours, ecOrder);
     hipLaunchKernelGGL((k_ec_query<N, OVERLAP>), dim3(queryBlocks), dim3(WAVE), queryLds, stream, b->nGlyphs, b->dGlyphContourOffsets, b->dContourOffsets,
                        (const EdgeRec *) viewOf(b).recs, viewOf(b).windings, dGlyphs, w, h, src, out, stencil, cfg,
-                       (const EcGlyphParams *) b->dEcParams, (const EcCandidate *) deferred, seg, (const int *) offsets, offsets+2*(size_t) b->nGlyphs+2, tuning().queryBatch, slotCap, slotOffset, lpcMaxContours,
+                       (const EcGlyphParams *) b->work.ecParams.ptr, (const EcCandidate *) deferred, seg, (const int *) offsets, offsets+2*(size_t) b->nGlyphs+2, tuning().queryBatch, slotCap, slotOffset, lpcMaxContours,
                        call.overflowOut, ecOrder, staticDeal ? (tuning().queryStatic == 2 ? 5 : 1) : 0);
     if (call.overflowOut)
         call.overflowMirrored = true;                            // the caller looks at the count after its copy back and reruns with the pass below if needed
@@ -1152,16 +1145,9 @@ int checkConfig(const MsdfHipConfig *cfg) {
 }
 
 int ensureScratch(const MsdfHipBatch *b, size_t floats, float **out) {
-    std::lock_guard<std::mutex> lock(b->scratchMutex);
-    if (b->scratchFloats < floats) {
-        if (b->dScratch)
-            hipFree(b->dScratch);
-        b->dScratch = NULL;
-        b->scratchFloats = 0;
-        HIPCHK(hipMalloc((void **) &b->dScratch, floats*sizeof(float)));
-        b->scratchFloats = floats;
-    }
-    *out = b->dScratch;
+    std::lock_guard<std::mutex> lock(b->work.mutex);
+    HIPCHK(b->work.scratch.ensure(floats));
+    *out = b->work.scratch.ptr;
     return MSDFHIP_OK;
 }
 
@@ -1179,11 +1165,10 @@ int runCorrection(const MsdfHipBatch *b, int channels, int w, int h, const MsdfH
 int prepareAhead(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGlyph *dGlyphs, const MsdfHipConfig *cfg, hipStream_t stream, GenerateCall &call) {
     if (b->nGlyphs == 0 || w == 0 || h == 0)
         return MSDFHIP_OK;
-    const int nch = channelsOf(mode), tilesAll = ((w+TILE-1)/TILE)*((h+TILE-1)/TILE);
-    const bool smallLaunch = (size_t) b->nGlyphs*tilesAll <= (size_t) tuning().smallLaunchTiles;
-    const bool hugeBatch = tileListBytes(b->maxEdges, b->maxContours, true) > (size_t) gLdsLimit.load();
+    const int nch = channelsOf(mode);
+    const LaunchShape shape = launchShape(b, w, h, nch, false);  // (without dispatchDistance's bound on the combiner scratch: a launch of few tiles beyond it builds its class lists there, as before)
     int rc = MSDFHIP_OK;
-    if (cfg->overlap_support && b->maxContours > 1 && b->nGlyphs > 1 && !hugeBatch && !smallLaunch) {
+    if (cfg->overlap_support && b->maxContours > 1 && b->nGlyphs > 1 && !shape.hugeBatch && !shape.smallLaunch) {
         const int limit = overlapClassLimit(nch);
         rc = ensureBuckets(b, limit < 1 ? 1 : limit, stream);
     }
@@ -1307,7 +1292,7 @@ int msdfhip_batch_create_device(MsdfHipBatch **batch, int n_glyphs, int n_contou
     if (rc != MSDFHIP_OK)
         return rc;
     MsdfHipBatch *b = new MsdfHipBatch();
-    b->device = currentDevice();                                 // ... not the process default
+    b->onDevice(currentDevice());                                // ... not the process default
     b->nGlyphs = n_glyphs, b->nContours = n_contours, b->nEdges = n_edges;
     b->maxContours = max_contours_per_glyph, b->maxEdges = max_edges_per_glyph;
     b->ownsInputs = false;
@@ -1379,7 +1364,7 @@ int msdfhip_batch_create_on(MsdfHipBatch **batch, int device, int n_glyphs, cons
         return rc;
     const int nC = gco[n_glyphs], nE = co[nC];
     MsdfHipBatch *b = new MsdfHipBatch();
-    b->device = currentDevice();
+    b->onDevice(currentDevice());
     b->nGlyphs = n_glyphs, b->nContours = nC, b->nEdges = nE, b->maxContours = maxC, b->maxEdges = maxE;
     b->ownsInputs = true;
     b->hContours.swap(hContours);
@@ -1649,7 +1634,7 @@ int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, c
         maxE = e > maxE ? e : maxE;
     }
     MsdfHipBatch *b = new MsdfHipBatch();
-    b->device = currentDevice();
+    b->onDevice(currentDevice());
     b->nGlyphs = n_glyphs, b->nContours = nC, b->nEdges = finalCo[nC], b->maxContours = maxC, b->maxEdges = maxE;
     b->ownsInputs = true;                                        // the batch takes over the final arrays
     b->dGlyphContourOffsets = dGco, b->dContourOffsets = dFinalCo, b->dPoints = fin.points, b->dTypes = fin.types, b->dColors = fin.colors;
@@ -1668,13 +1653,13 @@ int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, c
 int msdfhip_batch_candidate_counts(const MsdfHipBatch *b, uint32_t *counts) {
     if (!b || !counts)
         return fail(MSDFHIP_ERR_INVALID, "NULL argument");
-    if (!b->dDeferred)
+    if (!b->work.deferred.ptr)
         return fail(MSDFHIP_ERR_INVALID, "no error-correction pass has run on this batch");
     int rc = ensureDevice(b->device);
     if (rc != MSDFHIP_OK)
         return rc;
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(counts, b->dDeferred, sizeof(uint32_t)*(size_t) (b->nGlyphs+1), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(counts, b->work.deferred.ptr, sizeof(uint32_t)*(size_t) (b->nGlyphs+1), hipMemcpyDeviceToHost));
     return MSDFHIP_OK;
 }
 
@@ -1720,7 +1705,6 @@ void msdfhip_batch_destroy(MsdfHipBatch *b) {
     if (!b)
         return;
     (void) hipSetDevice(b->device);
-    destroySideStreams(b);
     if (b->ownsInputs) {
         hipFree(b->dGlyphContourOffsets);
         hipFree(b->dContourOffsets);
@@ -1730,22 +1714,7 @@ void msdfhip_batch_destroy(MsdfHipBatch *b) {
     }
     hipFree(b->dRecs);
     hipFree(b->dWindings);
-    hipFree(b->dScratch);
-    hipFree(b->dDeferred);
-    hipFree(b->dEcParams);
-    hipFree(b->dEcOrder);
-    if (b->hEcOrder)
-        pinnedFree(b->hEcOrder);
-    if (b->ecOrderReady)
-        hipEventDestroy(b->ecOrderReady);
-    hipFree(b->dGres);
-    hipFree(b->dWorkQueue);
-    if (!b->bucketExternal) {
-        hipFree(b->dBucket);
-        if (b->hBucket)
-            pinnedFree(b->hBucket);
-    }
-    delete b;
+    delete b;                                                    // (its workspace releases itself)
 }
 
 int msdfhip_batch_windings(const MsdfHipBatch *b, int32_t *windings) {
@@ -1959,8 +1928,7 @@ struct PipeSlot {
     char *pinnedTiles;                // pinned staging of the chunk's output when the caller's layout is not packed (scattered on the host)
     size_t pinnedTilesCap;
     int pendingFirst, pendingCount;   // the chunk waiting in pinnedTiles for its scatter
-    int viewCap;                      // glyphs the view's per-glyph work buffers (class lists, correction constants) were sized for
-    MsdfHipBatch view;                // glyph range of the parent batch + this slot's own work buffers
+    MsdfHipBatch view;                // glyph range of the parent batch + this slot's own workspace (its per-glyph buffers hold a full chunk)
     // streamed calls (msdfhip_generate_stream): the chunk's own inputs
     char *pinnedIn;                   // pinned staging the host threads flatten the chunk's shapes into: [gco | co | points | types | colors]
     size_t pinnedInCap;
@@ -2013,7 +1981,8 @@ struct PipeLease {
         fresh->device = device;
         for (int k = 0; k < PIPE_SLOTS; ++k) {
             PipeSlot &s = fresh->slot[k];
-            s.stream = NULL, s.done = NULL, s.kernelsDone = NULL, s.distanceDone = NULL, s.pinnedOverflow = NULL, s.busy = false, s.dev = NULL, s.devCap = 0, s.pinnedGlyphs = NULL, s.pinnedGlyphCap = 0, s.viewCap = 0;
+            s.view.onDevice(device);
+            s.stream = NULL, s.done = NULL, s.kernelsDone = NULL, s.distanceDone = NULL, s.pinnedOverflow = NULL, s.busy = false, s.dev = NULL, s.devCap = 0, s.pinnedGlyphs = NULL, s.pinnedGlyphCap = 0;
             s.pinnedTiles = NULL, s.pinnedTilesCap = 0, s.pendingFirst = 0, s.pendingCount = 0;
             s.pinnedIn = NULL, s.pinnedInCap = 0, s.devIn = NULL, s.devInCap = 0, s.inputsUploaded = NULL, s.inputsInFlight = false, s.prepCounted = NULL;
         }
@@ -2047,37 +2016,14 @@ struct PipeLease {
 
 // Points slot.view at glyphs [g0, g0+n) of b (shared, read-only inputs; the slot keeps its own work buffers across chunks and calls).
 static void sliceBatch(const MsdfHipBatch *b, MsdfHipBatch &v, int g0, int n) {
-    v.device = b->device;
+    v.onDevice(b->device);
     v.nGlyphs = n, v.nContours = b->nContours, v.nEdges = b->nEdges;
-    v.ownsInputs = false;
     v.dGlyphContourOffsets = b->dGlyphContourOffsets+g0;        // entries are absolute contour indices: valid from any starting glyph
     v.dContourOffsets = b->dContourOffsets, v.dPoints = b->dPoints, v.dTypes = b->dTypes, v.dColors = b->dColors;
     v.dRecs = b->dRecs, v.dWindings = b->dWindings;
-    v.hContours.assign(b->hContours.begin()+g0, b->hContours.begin()+g0+n);
-    v.hEdges.assign(b->hEdges.begin()+g0, b->hEdges.begin()+g0+n);
-    int maxC = 0, maxE = 0;
-    for (int g = 0; g < n; ++g) {
-        maxC = v.hContours[g] > maxC ? v.hContours[g] : maxC;
-        maxE = v.hEdges[g] > maxE ? v.hEdges[g] : maxE;
-    }
-    v.maxContours = maxC, v.maxEdges = maxE;
-    v.bucketLimit = -1;                                          // the class lists are per glyph range
+    v.setCounts(b->hContours.data()+g0, b->hEdges.data()+g0, n);
+    v.work.newGlyphRange();                                      // the class lists are per glyph range
     v.serialClasses = true;                                      // pipeline chunks overlap each other; side streams per chunk only alias the few hardware queues
-}
-
-static int fetchGlyphCounts(const MsdfHipBatch *b) {             // device-array batches: the per-glyph counts are read back once
-    if (!b->hContours.empty() || b->nGlyphs == 0)
-        return MSDFHIP_OK;
-    std::vector<int32_t> gco((size_t) b->nGlyphs+1), co((size_t) b->nContours+1);
-    HIPCHK(hipMemcpy(gco.data(), b->dGlyphContourOffsets, sizeof(int32_t)*gco.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(co.data(), b->dContourOffsets, sizeof(int32_t)*co.size(), hipMemcpyDeviceToHost));
-    b->hContours.resize((size_t) b->nGlyphs);
-    b->hEdges.resize((size_t) b->nGlyphs);
-    for (int g = 0; g < b->nGlyphs; ++g) {
-        b->hContours[g] = gco[g+1]-gco[g];
-        b->hEdges[g] = co[gco[g+1]]-co[gco[g]];
-    }
-    return MSDFHIP_OK;
 }
 
 static std::atomic<int> gPipeChunkGlyphs(0);                     // 0 = automatic (about 96 MB of float tiles per chunk)
@@ -2445,28 +2391,20 @@ struct StreamFeeder : ChunkFeeder {
         HIPCHK(hipEventRecord(p.inputsUploaded, stream));
         p.inputsInFlight = true;
         MsdfHipBatch &v = p.view;
-        v.device = currentDevice();
+        v.onDevice(currentDevice());
         v.nGlyphs = n, v.nContours = (int) nC, v.nEdges = (int) nE;
-        v.ownsInputs = false;
         v.dGlyphContourOffsets = reinterpret_cast<int32_t *>(p.devIn+l.gco), v.dContourOffsets = reinterpret_cast<int32_t *>(p.devIn+l.co);
         v.dPoints = reinterpret_cast<double *>(p.devIn+l.points), v.dTypes = reinterpret_cast<uint8_t *>(p.devIn+l.types), v.dColors = reinterpret_cast<uint8_t *>(p.devIn+l.colors);
         const size_t recOff = (l.bytes+255)/256*256;
         v.dRecs = reinterpret_cast<EdgeRec *>(p.devIn+recOff);
         v.dWindings = reinterpret_cast<int8_t *>(p.devIn+recOff+(sizeof(EdgeRec)*(nE ? nE : 1)+255)/256*256);
-        v.hContours.assign(hContours.begin()+g0, hContours.begin()+g0+n);
-        v.hEdges.assign(hEdges.begin()+g0, hEdges.begin()+g0+n);
+        v.setCounts(hContours.data()+g0, hEdges.data()+g0, n);
         if (prep) {
             const int rcPrep = prepareChunk(p, l, n, (int) nC, bound2, longest, stream);
             if (rcPrep != MSDFHIP_OK)
                 return rcPrep;
         }
-        int maxC = 0, maxE = 0;
-        for (int g = 0; g < n; ++g) {
-            maxC = v.hContours[(size_t) g] > maxC ? v.hContours[(size_t) g] : maxC;
-            maxE = v.hEdges[(size_t) g] > maxE ? v.hEdges[(size_t) g] : maxE;
-        }
-        v.maxContours = maxC, v.maxEdges = maxE;
-        v.bucketLimit = -1;
+        v.work.newGlyphRange();
         v.serialClasses = true;
         return digest(&v, stream);
     }
@@ -2479,9 +2417,7 @@ struct StreamFeeder : ChunkFeeder {
         const int32_t *hCo1 = reinterpret_cast<const int32_t *>(p.pinnedIn+l.co1), *hGco = reinterpret_cast<const int32_t *>(p.pinnedIn+l.gco);
         const int nE1 = hCo1[nC];
         const bool big = longest > PREP_WAVE_MAX_EDGES;
-        int maxRaw = 0;                                          // (p.view.hEdges: still the raw counts)
-        for (int g = 0; g < n; ++g)
-            maxRaw = p.view.hEdges[(size_t) g] > maxRaw ? p.view.hEdges[(size_t) g] : maxRaw;
+        const int maxRaw = p.view.maxEdges;                      // (still of the raw counts)
         const bool hitsBig = orient.orient_contours && orientHitsBig(maxRaw);
         const PrepLayout pl = prepLayout(l.bytes, (size_t) nC, (size_t) reinterpret_cast<const int32_t *>(p.pinnedIn+l.co)[nC], (size_t) nE1, bound2, big, hitsBig);
         EdgeArrays raw = { reinterpret_cast<double *>(d+l.points), reinterpret_cast<uint8_t *>(d+l.types), reinterpret_cast<uint8_t *>(d+l.colors) };
@@ -2526,6 +2462,7 @@ struct StreamFeeder : ChunkFeeder {
         v.dRecs = reinterpret_cast<EdgeRec *>(d+pl.recs), v.dWindings = reinterpret_cast<int8_t *>(d+pl.windings);
         for (int g = 0; g < n; ++g)
             v.hEdges[(size_t) g] = hFinal[hGco[g+1]]-hFinal[hGco[g]];
+        v.countMaxima();
         return MSDFHIP_OK;
     }
 
@@ -2620,7 +2557,6 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
     const size_t offBytes = offStencil+stencilBytes, devBytes = offBytes+(atlas ? (size_t) chunk*tile : 0)+256;
     for (int k = 0; k < PIPE_SLOTS; ++k) {
         PipeSlot &p = pipe[k];
-        p.view.bucketUploaded = false;                           // (the previous call drained every stream of this pipe before it returned it)
         if (p.devCap < devBytes) {
             HIPCHK(hipStreamSynchronize(p.stream));
             if (p.dev)
@@ -2636,15 +2572,10 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
             HIPCHK(pinnedAlloc((void **) &p.pinnedGlyphs, sizeof(MsdfHipGlyph)*2*(size_t) chunk));
             p.pinnedGlyphCap = (size_t) chunk;
         }
-        if (p.viewCap < chunk) {                                 // per-glyph work buffers of the view: reallocated on demand by the launches
+        if (p.view.work.reservedGlyphs < (size_t) chunk) {       // per-glyph work buffers of the view: reallocated on demand by the launches
             HIPCHK(hipStreamSynchronize(p.stream));
-            hipFree(p.view.dBucket), hipFree(p.view.dEcParams);
-            if (p.view.hBucket)
-                pinnedFree(p.view.hBucket);
-            p.view.dBucket = NULL, p.view.hBucket = NULL, p.view.dEcParams = NULL, p.view.bucketLimit = -1, p.view.bucketUploaded = false;
-            p.viewCap = chunk;
+            p.view.work.reserveGlyphs((size_t) chunk);
         }
-        p.view.glyphCap = p.viewCap;                             // sized for a full chunk whatever the length of the slot's first chunk
         p.pendingCount = 0;
     }
     // Chunk lengths: what the pipeline cannot hide is the kernels (streamed calls: also flatten + upload + digest) of the FIRST chunk and the kernels' tail +
@@ -2703,7 +2634,6 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
         if (p.busy) {                                            // the slot's previous copy must have left its buffers
             HIPCHK(hipEventSynchronize(p.done));
             p.busy = false;
-            p.view.bucketUploaded = false;
             if (mirrorOverflow && p.pinnedOverflow[0] != 0)
                 *overflowed = true;
             if (p.pendingCount)
@@ -3235,10 +3165,6 @@ static void destroyPipe(Pipe *p) {
         PipeSlot &s = p->slot[k];
         if (s.stream)
             (void) hipStreamSynchronize(s.stream);
-        destroySideStreams(&s.view);
-        hipFree(s.view.dScratch), hipFree(s.view.dDeferred), hipFree(s.view.dEcParams), hipFree(s.view.dGres), hipFree(s.view.dWorkQueue), hipFree(s.view.dBucket);
-        if (s.view.hBucket)
-            pinnedFree(s.view.hBucket);
         hipFree(s.dev);
         if (s.pinnedGlyphs)
             pinnedFree(s.pinnedGlyphs);
@@ -3262,8 +3188,8 @@ static void destroyPipe(Pipe *p) {
         if (s.stream)
             hipStreamDestroy(s.stream);
     }
+    delete p;                                                    // (the views' workspaces release themselves)
     (void) hipGetLastError();
-    delete p;
 }
 
 enum SingleOp { OP_GENERATE = 0, OP_ERROR_CORRECTION = 1, OP_SIGN_CORRECTION = 2, OP_RASTERIZE = 3 };   // what the single-shape call does to `pixels`
@@ -3555,10 +3481,9 @@ static int runGroup(ShapeCall *const *calls, int n) {
     } else
         HIPCHK(hipMemcpyAsync(a.dev, a.pinned, inputBytes, hipMemcpyHostToDevice, a.stream));
 
-    MsdfHipBatch b;                                              // non-owning view into the arena
-    b.device = a.device;
-    b.nGlyphs = n, b.nContours = (int) sumC, b.nEdges = (int) sumE, b.maxContours = maxC, b.maxEdges = maxE;
-    b.ownsInputs = false;
+    MsdfHipBatch b;                                              // a view into the arena: its workspace borrows the arena's regions and owns only what has to grow beyond them
+    b.onDevice(a.device);
+    b.nGlyphs = n, b.nContours = (int) sumC, b.nEdges = (int) sumE;
     b.dGlyphContourOffsets = reinterpret_cast<int32_t *>(a.dev+hGco);
     b.dContourOffsets = reinterpret_cast<int32_t *>(a.dev+hCo);
     b.dPoints = reinterpret_cast<double *>(a.dev+hPts);
@@ -3566,22 +3491,19 @@ static int runGroup(ShapeCall *const *calls, int n) {
     b.dColors = reinterpret_cast<uint8_t *>(a.dev+hColors);
     b.dRecs = reinterpret_cast<EdgeRec *>(a.dev+dRecs);
     b.dWindings = reinterpret_cast<int8_t *>(a.dev+dWind);
-    b.dDeferred = correct ? reinterpret_cast<EcCandidate *>(a.dev+dCands) : NULL;
-    b.deferredCap = correct ? candCap : 0;
-    b.dEcParams = reinterpret_cast<EcGlyphParams *>(a.dev+dParams);
-    b.dBucket = reinterpret_cast<int *>(a.dev+hBucketOff), b.hBucket = reinterpret_cast<int *>(a.pinned+hBucketOff), b.bucketExternal = true;
+    if (correct)
+        b.work.deferred.borrow(reinterpret_cast<EcCandidate *>(a.dev+dCands), candCap);
+    b.work.ecParams.borrow(reinterpret_cast<EcGlyphParams *>(a.dev+dParams), (size_t) n);
+    b.work.bucket.borrow(reinterpret_cast<int *>(a.dev+hBucketOff), (size_t) n), b.work.hBucket.borrow(reinterpret_cast<int *>(a.pinned+hBucketOff), (size_t) n);
     if (gresNeed)
-        b.dGres = reinterpret_cast<double *>(a.dev+dGresOff), b.gresBytes = gresNeed, b.gresExternal = true;
+        b.work.gres.borrow(reinterpret_cast<double *>(a.dev+dGresOff), gresNeed/sizeof(double));
     b.hContours.resize((size_t) n);
     b.hEdges.resize((size_t) n);
     for (int g = 0; g < n; ++g) {
         b.hContours[g] = calls[g]->nC;
         b.hEdges[g] = calls[g]->co[calls[g]->nC];
     }
-    struct Owned {                                               // workspaces the launches may have allocated for this view (many-contour shapes)
-        MsdfHipBatch &b;
-        ~Owned() { if (!b.gresExternal) hipFree(b.dGres); hipFree(b.dWorkQueue); destroySideStreams(&b); }
-    } owned = { b };
+    b.countMaxima();
     const MsdfHipGlyph *dGlyph = reinterpret_cast<const MsdfHipGlyph *>(a.dev+hGlyph);
     float *dOut = reinterpret_cast<float *>(a.dev+hOut);
     uint8_t *dStencil = anyStencil ? reinterpret_cast<uint8_t *>(a.dev+hStencil) : NULL;
@@ -3623,8 +3545,8 @@ static int runGroup(ShapeCall *const *calls, int n) {
             sa.out = zeroCopy ? reinterpret_cast<float *>(a.pinnedDev+hOut) : dOut, sa.stencil = dStencil;
             sa.gres = overlapEff && !resInLds ? reinterpret_cast<double *>(a.dev+dGresOff) : NULL, sa.gresStride = resBytes/sizeof(double);
             // candidates: a counter and a segment of SINGLE_TILE_SEGMENT records per TILE (the tile's workgroup judges them itself), then the corner list
-            sa.cfg = *cfg, sa.correct = correct ? 1 : 0, sa.ecParams = b.dEcParams, sa.cands = b.dDeferred, sa.seg = SINGLE_TILE_SEGMENT;
-            sa.corners = correct ? reinterpret_cast<int *>(b.dDeferred+ecHeaderRecords((int) tilesAll)+tilesAll*SINGLE_TILE_SEGMENT) : NULL;
+            sa.cfg = *cfg, sa.correct = correct ? 1 : 0, sa.ecParams = b.work.ecParams.ptr, sa.cands = b.work.deferred.ptr, sa.seg = SINGLE_TILE_SEGMENT;
+            sa.corners = correct ? reinterpret_cast<int *>(b.work.deferred.ptr+ecHeaderRecords((int) tilesAll)+tilesAll*SINGLE_TILE_SEGMENT) : NULL;
             sa.sizes = NULL;
             sa.slotCap = slotCap, sa.slotOffset = slotOffset;
             sa.teamXchgOffset = (unsigned) teamXchgOffset;

@@ -17,6 +17,7 @@
 #include "../../msdfgen_amd/csrc/msdf_cull.hpp"
 #include "../../msdfgen_amd/csrc/msdf_scanline.hpp"
 #include "../../msdfgen_amd/csrc/msdf_shapeprep.hpp"
+#include "../../msdfgen_amd/csrc/msdf_classplan.hpp"
 
 using namespace msdfhip;
 
@@ -878,4 +879,12 @@ extern "C" void emu_lane_relevance_stats(int w, int h, int nC, const int32_t *co
                 }
             }
         }
+}
+
+// planClasses (msdf_classplan.hpp: the class list msdf_capi.hip's ensureBuckets uploads). counts: nOne, nSmall, nHuge, oneMaxE, smallMaxC, smallMaxE, restMaxC, restMaxE.
+extern "C" void emu_class_plan(const int *contours, const int *edges, int n, int limit, int smallMaxEdges, long ldsLimit, int *order, int *counts, float *restShare) {
+    const ClassPlan p = planClasses(contours, edges, n, limit, smallMaxEdges, (size_t) ldsLimit, order);
+    const int c[8] = { p.nOne, p.nSmall, p.nHuge, p.oneMaxE, p.smallMaxC, p.smallMaxE, p.restMaxC, p.restMaxE };
+    memcpy(counts, c, sizeof(c));
+    *restShare = p.restShare;
 }

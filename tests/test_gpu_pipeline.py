@@ -245,6 +245,60 @@ def test_device_memory_stays_flat_over_many_calls(glyphs):
     assert free0-free1 < 24 << 20, "device memory grew by %.1f MB over 25 rounds of fresh threads" % ((free0-free1)/2**20)
 
 
+def test_resident_batch_reused_across_growing_requests_matches_fresh_batches(glyphs):
+    """One resident batch serves requests that make each of its workspaces grow and its class plan be rebuilt: 16x16 first (small candidate buffer and
+    combiner scratch), then 48x48 (nine times the candidate records and work items), MTSDF (four channels: another contour limit, so other class
+    lists, and more scratch per contour), SDF without overlap support (no classes at all), MSDF twice in a row (the class plan of the MTSDF call
+    must not serve it; if the global-scratch class runs persistent, the second call draws from the other set of work-queue counters) and 16x16
+    again (every buffer now larger than it needs).  Each result must equal, bit for bit, what a fresh batch computes for the same request.
+    The 1 500 glyphs fork the distance pass into its classes (asserted: LDS class and global-scratch class both launched).  Route counters: at
+    48x48 the global-scratch class (77 glyphs at the msdf contour limit of 5: 2 772 work items against a share grid of 763 workgroups) fires
+    dist_global_persistent, so the two consecutive MSDF calls alternate the work-queue sets (asserted: that counter rises by 2 over the pair);
+    at 16x16 its 308 items stay below the share grid and fire dist_global_direct."""
+    sub, xfs, want = glyphs
+    small = np.array(xfs, np.float64, copy=True)
+    small[:, :2] /= 3                                                         # the 48x48 frames at a third of the scale: 16x16
+    no_overlap = M.GeneratorConfig(overlap_support=False)
+    requests = [(M.MODE_MSDF, 16, small, None), (M.MODE_MSDF, 48, xfs, None), (M.MODE_MTSDF, 48, xfs, None), (M.MODE_SDF, 48, xfs, no_overlap),
+                (M.MODE_MSDF, 48, xfs, None), (M.MODE_MSDF, 48, xfs, None), (M.MODE_MSDF, 16, small, None)]
+    fresh = {}
+    for mode, size, frames, config in requests:
+        if (mode, size) not in fresh:
+            fresh[mode, size] = M.GlyphBatch(sub).generate(mode, size, size, frames, config=config).cpu().numpy()
+    assert (bits(fresh[M.MODE_MSDF, 48]) == bits(want)).all()
+    gb = M.GlyphBatch(sub)
+    M.route_counts(reset=True)
+    for k, (mode, size, frames, config) in enumerate(requests):
+        if k == 4:
+            before_pair = M.route_counts()["dist_global_persistent"]
+        got = gb.generate(mode, size, size, frames, config=config).cpu().numpy()
+        assert (bits(got) == bits(fresh[mode, size])).all(), "request %d (mode %d, %dx%d)" % (k, mode, size, size)
+        if k == 1:                                                            # the first 48x48 call forked its classes: this is not the small-launch path
+            routes = M.route_counts()
+            print("routes after the first 48x48 call:", {name: n for name, n in routes.items() if n})
+            assert routes["dist_lds_quad"]+routes["dist_lds_single"] > 0 and routes["dist_global_direct"]+routes["dist_global_persistent"] > 0, routes
+        if k == 5:                                                            # the two consecutive MSDF calls each drew from a set of work-queue counters
+            assert M.route_counts()["dist_global_persistent"]-before_pair >= 2, M.route_counts()
+    routes = M.route_counts()
+    print("routes of the sequence:", {name: n for name, n in routes.items() if n})
+    assert routes["dist_lds_quad"]+routes["dist_lds_single"] >= 4 and routes["dist_global_direct"]+routes["dist_global_persistent"] >= 4, routes
+
+
+def test_single_shape_calls_of_many_and_one_contour_share_an_arena(glyphs):
+    """A single-shape call on the glyph with the most contours, at once followed by a one-contour glyph on the same thread: the second call takes
+    the arena the first one returned, and both build their view over it with borrowed work buffers -- whatever the first call's view had to
+    allocate of its own has gone with that view."""
+    sub, xfs, want = glyphs
+    n_c = np.diff(sub.glyph_contour_offsets)
+    many, one = int(np.argmax(n_c)), int(np.flatnonzero(n_c == 1)[0])
+    assert n_c[many] >= 10
+    for _ in range(2):
+        for g in (many, one):
+            out = np.zeros((48, 48, 3), np.float32)
+            M.generate_msdf(out, sub.shape(g), M.SDFTransformation.from_xf(xfs[g]))
+            assert (bits(out) == bits(want[g])).all(), "glyph %d (%d contours)" % (g, n_c[g])
+
+
 def test_sharded_into_one_interleaved_atlas(glyphs):
     """Two "devices" writing rectangles of ONE float atlas whose memory ranges interleave (column-major placement): a device only ever
     writes its own glyphs' rows, whatever the split."""
