@@ -254,10 +254,18 @@ void renderSDF(const BitmapSection<float, 1> &output, const BitmapConstSection<f
 void renderSDF(const BitmapSection<float, 3> &output, const BitmapConstSection<float, 3> &sdf, Range sdfPxRange, float sdThreshold) { render<3, 3>(output, sdf, sdfPxRange, sdThreshold); }
 void renderSDF(const BitmapSection<float, 1> &output, const BitmapConstSection<float, 4> &sdf, Range sdfPxRange, float sdThreshold) { render<1, 4>(output, sdf, sdfPxRange, sdThreshold); }
 void renderSDF(const BitmapSection<float, 4> &output, const BitmapConstSection<float, 4> &sdf, Range sdfPxRange, float sdThreshold) { render<4, 4>(output, sdf, sdfPxRange, sdThreshold); }
-// (the reference walks N*width*height contiguous floats and ignores rowStride, core/render-sdf.cpp:172-188; rows are honoured here)
-void simulate8bit(const BitmapSection<float, 1> &bitmap) { check(msdfhip_simulate_8bit_host(bitmap.pixels, bitmap.width, bitmap.height, bitmap.rowStride, 1), "simulate8bit"); }
-void simulate8bit(const BitmapSection<float, 3> &bitmap) { check(msdfhip_simulate_8bit_host(bitmap.pixels, bitmap.width, bitmap.height, bitmap.rowStride, 3), "simulate8bit"); }
-void simulate8bit(const BitmapSection<float, 4> &bitmap) { check(msdfhip_simulate_8bit_host(bitmap.pixels, bitmap.width, bitmap.height, bitmap.rowStride, 4), "simulate8bit"); }
+// The reference walks N*width*height contiguous floats on from the section's first row and ignores rowStride (core/render-sdf.cpp:176-192): on a
+// padded, bottom-up or atlas-interior section that is not the section's texels. A drop-in converts the floats the reference converts.
+namespace {
+template <int N>
+void simulate(const BitmapSection<float, N> &bitmap) {
+    const int texels = bitmap.width*bitmap.height;
+    check(msdfhip_simulate_8bit_host(bitmap.pixels, texels, 1, N*texels, N), "simulate8bit");
+}
+}
+void simulate8bit(const BitmapSection<float, 1> &bitmap) { simulate<1>(bitmap); }
+void simulate8bit(const BitmapSection<float, 3> &bitmap) { simulate<3>(bitmap); }
+void simulate8bit(const BitmapSection<float, 4> &bitmap) { simulate<4>(bitmap); }
 
 // ---- core/rasterization.h:13-27: together these replace the whole of core/rasterization.cpp
 void rasterize(BitmapSection<float, 1> output, const Shape &shape, const Projection &projection, FillRule fillRule) {

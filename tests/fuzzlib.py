@@ -192,7 +192,7 @@ def _delta(after, before):
 
 
 def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="small", scanline=False, tuning=None, modes=None, min_groups=0, stencil=False,
-        paths=False, geometry=None):
+        paths=False, geometry=None, zero_values=(.5,)):
     """Returns a dict: shapes, groups, values_compared, values_differing_bitwise, max_abs_delta, worst_case, seed, routes (route-counter deltas of
     the whole run), group_routes (those of each group's batched call), ...
     single: every shape through its own generate*() call (the literal drop-in: one fused launch per call, msdf_single.hpp) instead of one batch per group.
@@ -202,7 +202,9 @@ def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="smal
     scale, scanline, modes: see plan(). tuning: MSDFHIP_* variables set for the run (tuned()).
     min_groups: groups run even past the deadline (a slow box trims a sweep, it does not empty it).
     stencil: the correction's stencil of every batched msdf / mtsdf group with error correction is compared with the oracle's too.
-    paths: the same groups also through generate_stream and HostBatch.generate_host (with a stencil): their bytes must equal the batch's."""
+    paths: the same groups also through generate_stream and HostBatch.generate_host (with a stencil): their bytes must equal the batch's.
+    zero_values: the sdfZeroValue levels of the sign pass. With more than one, the scanline groups take them in turn: the group's distance mapping is
+    moved (same range width) so that distance 0 maps to that level, and the level goes to the product's sign pass and to the oracle's."""
     import time
     import msdfgen_amd as M
     from msdfgen_amd.shape import ShapeBatch
@@ -220,6 +222,8 @@ def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="smal
     t0 = time.time()
     seen = set()
     fill_rules = set()
+    zeros_used = set()
+    scan_groups = 0
     min_glyphs, min_tiles = None, None
     with tuned(tuning or {}):
         routes0 = M.route_counts()
@@ -229,6 +233,14 @@ def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="smal
             n, mode, w, h, overlap, kind = grp["n"], grp["mode"], grp["w"], grp["h"], grp["overlap"], grp["kind"]
             (ec_mode, ec_dist), shapes, xfs, y_down, family, rule = grp["ec"], grp["shapes"], grp["xfs"], grp["y_down"], grp["family"], grp["scanline"]
             min_dev, min_imp = grp["min_dev"], grp["min_imp"]
+            zero = float(zero_values[0])
+            if rule is not None and len(zero_values) > 1:
+                zero = float(zero_values[scan_groups % len(zero_values)])
+                scan_groups += 1
+                xfs = np.array(xfs, np.float64)
+                width = xfs[:, 5]-xfs[:, 4]                               # DistanceMapping: (d-lower)/(upper-lower); 0 -> zero with lower = -zero*width
+                xfs[:, 4] = -zero*width
+                xfs[:, 5] = xfs[:, 4]+width
             batch = ShapeBatch.from_shapes(shapes)
             cfg = M.MSDFGeneratorConfig(overlap, M.ErrorCorrectionConfig(ec_mode, ec_dist, min_dev, min_imp)) if mode >= 3 else M.GeneratorConfig(overlap)
             y = M.Y_DOWNWARD if y_down else M.Y_UPWARD
@@ -243,7 +255,7 @@ def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="smal
                 dst = torch.full((n, h, w), 77, dtype=torch.uint8, device="cuda") if want_st else None
                 before = M.route_counts()
                 out = gb.generate(mode, w, h, xfs, config=cfg, y_orientation=y, stencil=dst, scanline_pass=rule is not None,
-                                  fill_rule=rule if rule is not None else 0)
+                                  fill_rule=rule if rule is not None else 0, sdf_zero_value=zero)
                 group_routes.append(_delta(M.route_counts(), before))
                 got = out.cpu().numpy()
                 st = dst.cpu().numpy() if want_st else None
@@ -274,7 +286,7 @@ def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="smal
                                      stencil=sb)
                 else:
                     f = orc.generate(s, mode, w, h, xfs[g], overlap=overlap, ec_mode=0, y_down=y_down)
-                    f = orc.sign_correction(s, f, xfs[g], .5, rule, y_down=y_down)
+                    f = orc.sign_correction(s, f, xfs[g], zero, rule, y_down=y_down)
                     if mode >= 3 and ec_mode != 0:
                         f = orc.error_correction(s, f, xfs[g], overlap=overlap, ec_mode=ec_mode, ec_dist=ec_dist, min_dev=min_dev, min_imp=min_imp, y_down=y_down,
                                                  stencil=sb)
@@ -306,6 +318,7 @@ def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="smal
                         worst_case.update(glyphs=n, glyph=g, y_down=y_down, ratios=[min_dev, min_imp], scanline=rule, tuning=tuning)
             if rule is not None:
                 fill_rules.add(rule)
+                zeros_used.add(zero)
             seen.add((mode, overlap, ec_mode if mode >= 3 else -1, ec_dist if mode >= 3 else -1, kind, family))
             done += n
             groups += 1
@@ -315,5 +328,5 @@ def run(n_shapes, seed, deadline_s=None, single=False, framing=None, scale="smal
             "worst_case": worst_case, "seed": seed, "single_calls": bool(single), "distinct_mode_combiner_ec_kind": len(seen), "seconds": round(time.time()-t0, 1),
             "framings": sorted({k[-1] for k in seen if k[-1] is not None}), "scale": scale, "tuning": tuning or {}, "routes": routes,
             "group_routes": group_routes, "stencil_values_compared": st_total, "stencil_values_differing": st_differing,
-            "path_values_compared": path_total, "path_values_differing": path_differing, "fill_rules": sorted(fill_rules),
+            "path_values_compared": path_total, "path_values_differing": path_differing, "fill_rules": sorted(fill_rules), "zero_values": sorted(zeros_used),
             "min_glyphs_per_group": min_glyphs, "min_tiles_per_group": min_tiles}

@@ -673,6 +673,101 @@ def test_distance_sign_correction_standalone_vs_oracle(oracle, seed):
         assert (bits(got) == bits(want)).all()
 
 
+# sdfZeroValue levels off .5 (an asymmetric Range puts the field's zero there): off the middle, on the edge of and outside the [0, 1] of a byte pipeline,
+# and 1/3 as a float, where zero+zero and (zero+zero)-v round
+ZERO_VALUES = (.25, .75, 0., float(np.float32(1/3)), 1.5)
+
+
+@pytest.mark.parametrize("zero", ZERO_VALUES)
+def test_distance_sign_correction_zero_levels_vs_oracle(oracle, zero):
+    """msdfhip_distance_sign_correction about a zero level other than .5, bit for bit against the oracle: fields of `zero` plus signed noise on 1, 3 and 4
+    channels, signs flipped at random texels, medians exactly == zero at random texels and at the four corners (the neighbour vote compares with `zero`,
+    the mirror is (zero+zero)-v), all fill rules, Y-down bitmaps and inverse-Y shapes. A pass that kept .5 anywhere differs at every mirrored texel."""
+    z = np.float32(zero)
+    for seed in range(4):
+        rng = np.random.default_rng([1400+seed, ZERO_VALUES.index(zero)])
+        s = synth.random_shape(7150+seed, n_contours=1+seed % 4, kinds=(1, 2, 3), holes=bool(seed & 1))
+        s.inverse_y = bool(seed & 1)
+        yd = bool(seed & 2)
+        w, h = int(rng.integers(9, 41)), int(rng.integers(9, 41))
+        xf = autoframe(s.bounds(), w, h, 3)
+        width = xf[5]-xf[4]
+        xf[4], xf[5] = -zero*width, (1-zero)*width                              # distance 0 maps to `zero`
+        for mode in (1, 3, 4):
+            n = M.CHANNELS[mode]
+            field = oracle.generate(s, mode, w, h, xf, ec_mode=0, y_down=yd)
+            field = (field+rng.normal(0, .05, field.shape)).astype(np.float32)   # zero plus signed noise near the outline
+            flips = rng.random((h, w)) < .2
+            field[flips] = (z+z)-field[flips]
+            ys, xs = rng.integers(0, h, 10), rng.integers(0, w, 10)
+            for y, x in list(zip(ys, xs))+[(0, 0), (0, w-1), (h-1, 0), (h-1, w-1)]:
+                field[y, x, :min(n, 3)] = z                                      # median exactly == zero
+                if n >= 3:
+                    field[y, x, int(rng.integers(0, 3))] += np.float32(rng.normal(0, .1))   # two of three channels at zero: still the median
+            assert n == 1 or (np.median(field[..., :3], axis=2) == z).sum() >= 4
+            for rule in range(4):
+                want = oracle.sign_correction(s, field, xf, zero, rule, y_down=yd)
+                got = M.distance_sign_correction(field.copy(), s, M.SDFTransformation.from_xf(xf), zero, rule, M.Y_DOWNWARD if yd else M.Y_UPWARD)
+                assert (bits(got) == bits(want)).all(), "zero %r seed %d mode %d rule %d: %d texels differ" % (
+                    zero, seed, mode, rule, int((bits(got) != bits(want)).sum()))
+                assert (bits(want) != bits(field)).any()
+
+
+@pytest.mark.parametrize("entry,zero", [("single", .25), ("host", .75), ("stream", float(np.float32(1/3)))])
+def test_scanline_flow_zero_level_through_every_entry(latin, oracle, entry, zero):
+    """generate -> sign correction about a zero level off .5 -> error correction as ONE call of the single-shape entry (msdfhip_generate with the sign pass
+    in its config), of the host pipeline (msdfhip_batch_generate_host) and of the streamed entry (msdfhip_generate_stream_csr): the resident batch's
+    bytes, and the oracle's chain generate(ec off) -> sign_correction(zero) -> error_correction."""
+    import torch
+    from msdfgen_amd import api, lib as L
+    batch, xf64, _ = latin
+    pick = list(range(3, 94, 9))
+    sub = batch.select(pick)
+    sub.inverse_y = (np.arange(sub.n_glyphs) % 3 == 1).astype(np.uint8)
+    w, h, mode, rule = 40, 32, 4, M.FILL_ODD
+    xfs = np.stack([autoframe(sub.shape(g).bounds(), w, h, 4) for g in range(sub.n_glyphs)])
+    width = xfs[:, 5]-xfs[:, 4]
+    xfs[:, 4], xfs[:, 5] = -zero*width, (1-zero)*width
+    c = cfg(overlap=False, ec_mode=M.EC_EDGE_PRIORITY, ec_dist=M.DO_NOT_CHECK_DISTANCE)
+    G = sub.n_glyphs
+    gb = M.GlyphBatch(sub)
+    st = torch.full((G, h, w), 77, dtype=torch.uint8, device="cuda")
+    resident = gb.generate(mode, w, h, xfs, config=c, stencil=st, scanline_pass=True, fill_rule=rule, sdf_zero_value=zero).cpu().numpy()
+    resident_st = st.cpu().numpy()
+    gb.close()
+    want, want_st = np.zeros_like(resident), np.zeros((G, h, w), np.uint8)
+    for g in range(G):
+        s = sub.shape(g)
+        f = oracle.generate(s, mode, w, h, xfs[g], overlap=False, ec_mode=0)
+        f = oracle.sign_correction(s, f, xfs[g], zero, rule)
+        assert (bits(f) != bits(oracle.sign_correction(s, f, xfs[g], .5, rule))).any()        # the level matters on this field
+        want[g] = oracle.error_correction(s, f, xfs[g], overlap=False, ec_mode=2, ec_dist=0, stencil=want_st[g])
+    assert (bits(resident) == bits(want)).all() and (resident_st == want_st).all()
+    cc = api._with_scanline_pass(api._c_config(c, M.Y_UPWARD), True, rule, zero)
+    got, got_st = np.full_like(resident, -7), np.full((G, h, w), 77, np.uint8)
+    if entry == "single":
+        for g in range(G):
+            s = sub.shape(g)
+            keep, sargs = api._shape_args(s)
+            xf = M.SDFTransformation.from_xf(xfs[g]).xf6()
+            L.check(L.load().msdfhip_generate(mode, L.ptr(got[g], L._fp), w, h, w*4, int(bool(s.inverse_y)), *sargs, L.ptr(xf, L._dp), C.byref(cc),
+                                              L.ptr(got_st[g], L._bp)))
+    else:
+        d = api._descriptors_host(sub, xfs, np.arange(G, dtype=np.int64)*w*h*4, w*4, M.Y_UPWARD)
+        if entry == "host":
+            hb = M.HostBatch(sub)
+            L.check(L.load().msdfhip_batch_generate_host(hb._handle, mode, w, h, d.ctypes.data, got.ctypes.data, got.size, got_st.ctypes.data, C.byref(cc)))
+            hb.close()
+        else:
+            gco, co = np.ascontiguousarray(sub.glyph_contour_offsets, np.int32), np.ascontiguousarray(sub.contour_offsets, np.int32)
+            pts = np.ascontiguousarray(sub.points, np.float64).reshape(-1, 8)
+            types, colors = np.ascontiguousarray(sub.types, np.uint8), np.ascontiguousarray(sub.colors, np.uint8)
+            L.check(L.load().msdfhip_generate_stream_csr(-1, mode, w, h, G, L.ptr(gco, L._ip), L.ptr(co, L._ip), L.ptr(pts, L._dp), L.ptr(types, L._bp),
+                                                         L.ptr(colors, L._bp), d.ctypes.data, got.ctypes.data, got.size, None, 0, got_st.ctypes.data, C.byref(cc)))
+    assert (bits(got) == bits(resident)).all(), "%s: %d values differ from the resident batch" % (entry, int((bits(got) != bits(resident)).sum()))
+    assert (got_st == resident_st).all()
+
+
 def test_distance_sign_correction_many_edges_chunked_lists(oracle):
     """Shapes with more than 128 edges exceed the per-row list capacity kept in LDS: the kernel then walks the edges in chunks
     (k_sign_correction). CJK-like glyphs (~100 edges, unchunked), 150-300 edge blobs, the 926-edge cubic logo on a wide bitmap."""

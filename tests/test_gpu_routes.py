@@ -6,6 +6,7 @@ wavefront or one; the global class direct or persistent), heaviest-first correct
 nGlyphs x tilesY >= 4 096. The other sweeps are too small to leave the small route, so here (a) small groups run under MSDFHIP_* tables that force each
 large route, and (b) throughput-sized groups run with no knobs at all. Every value is compared with the oracle, the route counters
 (msdfhip_debug_route_counts) prove that the route under test ran."""
+import numpy as np
 import pytest
 
 import msdfgen_amd as M
@@ -83,3 +84,34 @@ def test_throughput_sized_groups_vs_oracle():
              g["dist_global_direct"]+g["dist_global_persistent"] > 0]
     assert three, r["group_routes"]
     assert r["path_values_compared"] > 0 and r["stencil_values_compared"] > 0, r
+
+
+# sdfZeroValue levels of the sign pass: off the middle, on the edge of and outside [0, 1], and one (1/3 as a float) whose doubling and mirroring round
+ZERO_VALUES = (.25, .75, 0., float(np.float32(1/3)), 1.5)
+
+
+def check_zero_levels(r):
+    check_parity(r)
+    assert r["zero_values"] == sorted(ZERO_VALUES), r["zero_values"]
+    assert r["fill_rules"] == [0, 1, 2, 3], r["fill_rules"]
+    assert r["stencil_values_compared"] > 0, r
+
+
+def test_sign_pass_zero_levels_chunked_and_split_vs_oracle():
+    """The -scanline flow with the field's zero level moved off .5 (an asymmetric Range) and that level handed to the sign pass, under MSDFHIP_SIGN_CAP=3:
+    the row lists walked in chunks, the tile rows split into spans. k_sign_correction mirrors about zero+zero and votes against zero; a kernel or a
+    dispatch path that kept .5 differs from the oracle at every flipped texel."""
+    r = fuzzlib.run(1200, 520, min_groups=10, deadline_s=1, scale="mixed", scanline=True, stencil=True, modes=(1, 3, 4), tuning=fuzzlib.TUNINGS["sign_chunked"],
+                    zero_values=ZERO_VALUES)
+    check_zero_levels(r)
+    assert r["routes"]["sign_chunked"] > 0 and r["routes"]["sign_split"] > 0, r["routes"]
+
+
+def test_sign_pass_zero_levels_whole_rows_vs_oracle():
+    """The same with no knobs at the size from which the sign pass keeps whole tile rows per wavefront (nGlyphs x tilesY >= 4 096): the scanline groups
+    of the throughput-sized plan, 456-520 glyphs of nine tile rows, the smallest that plan has."""
+    r = fuzzlib.run(6000, 602, min_groups=10, deadline_s=1, scale="full", scanline=True, stencil=True, modes=(1, 3, 4), zero_values=ZERO_VALUES)
+    check_zero_levels(r)
+    assert r["routes"]["sign_whole_rows"] > 0, r["routes"]
+    scan = [g for g in r["group_routes"] if g["sign_whole_rows"]+g["sign_split"] > 0]
+    assert len(scan) >= len(ZERO_VALUES) and all(g["sign_whole_rows"] > 0 and g["sign_split"] == 0 for g in scan), scan

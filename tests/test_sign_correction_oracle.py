@@ -9,6 +9,10 @@ from msdfgen_amd import synth
 from msdfgen_amd.shape import autoframe
 
 
+# sdfZeroValue levels other than .5: off the middle, on the edge of and outside [0, 1], and 1/3 as a float (zero+zero and its mirror round)
+ZERO_VALUES = (.25, .75, 0., float(np.float32(1/3)), 1.5)
+
+
 @pytest.fixture(scope="module")
 def emu():
     return Emu()
@@ -46,6 +50,15 @@ def test_sign_correction_vs_reference(oracle, ref, seed):
             assert_bit_equal(b, a, "seed %d mode %d rule %d" % (seed, mode, rule))
         a = ref.sign_correction(s, field, xf, .25, 0)
         assert_bit_equal(oracle.sign_correction(s, field, xf, .25, 0), a, "zero value .25")
+        for zero in ZERO_VALUES:                                            # the field moved to that level, exact == zero medians included
+            z = np.float32(zero)
+            moved = ((field-np.float32(.5))+z).astype(np.float32)
+            if n >= 3:
+                moved[rng.integers(0, h, 6), rng.integers(0, w, 6)] = z
+                moved[0, 0] = moved[h-1, w-1] = moved[0, w-1] = moved[h-1, 0] = z
+            rule = int(rng.integers(0, 4))
+            a = ref.sign_correction(s, moved, xf, zero, rule, y_down=bool(seed & 4))
+            assert_bit_equal(oracle.sign_correction(s, moved, xf, zero, rule, y_down=bool(seed & 4)), a, "seed %d mode %d zero %r" % (seed, mode, zero))
 
 
 # ---- the product's device code (msdf_scanline.hpp + the k_sign_correction walk) compiled for the host, against the oracle
@@ -82,6 +95,14 @@ def test_device_sign_correction_host(oracle, emu, seed):
             a = oracle.sign_correction(s, field, xf, .5, rule, y_down=bool(seed & 4))
             b = emu.sign_correction(s, field, xf, .5, rule, y_down=bool(seed & 4))
             assert_bit_equal(b, a, "seed %d mode %d rule %d" % (seed, mode, rule))
+        for zero in ZERO_VALUES:
+            z = np.float32(zero)
+            moved = ((field-np.float32(.5))+z).astype(np.float32)
+            if mode >= 3:
+                moved[field == .5] = z
+            rule = int(rng.integers(0, 4))
+            a = oracle.sign_correction(s, moved, xf, zero, rule, y_down=bool(seed & 4))
+            assert_bit_equal(emu.sign_correction(s, moved, xf, zero, rule, y_down=bool(seed & 4)), a, "seed %d mode %d zero %r" % (seed, mode, zero))
 
 
 @pytest.mark.parametrize("seed", range(8))
