@@ -25,6 +25,7 @@
 #include <sched.h>
 
 #include "msdf_classplan.hpp"
+#include "msdf_hostplan.hpp"
 #include "msdf_kernels.hpp"
 #include "msdf_single.hpp"
 
@@ -1921,19 +1922,14 @@ struct PipeSlot {
     hipEvent_t distanceDone;          // the distance pass of the slot's last chunk has finished (its correction pass may still run)
     unsigned *pinnedOverflow;         // pinned, device-visible word: k_ec_query mirrors the chunk's candidate-overflow count here (no k_ec_slow launch per chunk)
     bool busy;
-    char *dev;                        // [descriptors | float tiles | stencil | byte tiles]
-    size_t devCap;
-    MsdfHipGlyph *pinnedGlyphs;       // pinned staging of the chunk's descriptors
-    size_t pinnedGlyphCap;
-    char *pinnedTiles;                // pinned staging of the chunk's output when the caller's layout is not packed (scattered on the host)
-    size_t pinnedTilesCap;
+    WorkBuffer<char> dev;             // [descriptors | float tiles | stencil | byte tiles] (slotLayout)
+    WorkBuffer<MsdfHipGlyph, true> pinnedGlyphs;   // pinned staging of the chunk's descriptors: the generators' in the first half, the byte conversion's in the second
+    WorkBuffer<char, true> pinnedTiles;   // pinned staging of the chunk's output when the caller's layout is not packed (scattered on the host)
     int pendingFirst, pendingCount;   // the chunk waiting in pinnedTiles for its scatter
     MsdfHipBatch view;                // glyph range of the parent batch + this slot's own workspace (its per-glyph buffers hold a full chunk)
     // streamed calls (msdfhip_generate_stream): the chunk's own inputs
-    char *pinnedIn;                   // pinned staging the host threads flatten the chunk's shapes into: [gco | co | points | types | colors]
-    size_t pinnedInCap;
-    char *devIn;                      // the same on the device, followed by the chunk's records and windings
-    size_t devInCap;
+    WorkBuffer<char, true> pinnedIn;  // pinned staging the host threads flatten the chunk's shapes into: [gco | co | points | types | colors]
+    WorkBuffer<char> devIn;           // the same on the device, followed by the chunk's records and windings
     hipEvent_t inputsUploaded;        // the chunk's upload has left pinnedIn
     bool inputsInFlight;
     hipEvent_t prepCounted;           // streamed calls of raw outlines: the chunk's coloured contour offsets have reached pinnedIn (StreamFeeder::prepare)
@@ -1982,9 +1978,9 @@ struct PipeLease {
         for (int k = 0; k < PIPE_SLOTS; ++k) {
             PipeSlot &s = fresh->slot[k];
             s.view.onDevice(device);
-            s.stream = NULL, s.done = NULL, s.kernelsDone = NULL, s.distanceDone = NULL, s.pinnedOverflow = NULL, s.busy = false, s.dev = NULL, s.devCap = 0, s.pinnedGlyphs = NULL, s.pinnedGlyphCap = 0;
-            s.pinnedTiles = NULL, s.pinnedTilesCap = 0, s.pendingFirst = 0, s.pendingCount = 0;
-            s.pinnedIn = NULL, s.pinnedInCap = 0, s.devIn = NULL, s.devInCap = 0, s.inputsUploaded = NULL, s.inputsInFlight = false, s.prepCounted = NULL;
+            s.stream = NULL, s.done = NULL, s.kernelsDone = NULL, s.distanceDone = NULL, s.pinnedOverflow = NULL, s.busy = false;
+            s.pendingFirst = 0, s.pendingCount = 0;
+            s.inputsUploaded = NULL, s.inputsInFlight = false, s.prepCounted = NULL;
         }
         for (int k = 0; k < PIPE_SLOTS; ++k) {                   // a half-built pipe never reaches the pool
             hipError_t e = hipStreamCreateWithFlags(&fresh->slot[k].stream, hipStreamNonBlocking);
@@ -2027,12 +2023,6 @@ static void sliceBatch(const MsdfHipBatch *b, MsdfHipBatch &v, int g0, int n) {
 }
 
 static std::atomic<int> gPipeChunkGlyphs(0);                     // 0 = automatic (about 96 MB of float tiles per chunk)
-
-struct Carver {                                                  // 256-byte aligned sub-allocation inside an arena
-    size_t off;
-    Carver() : off(0) { }
-    size_t take(size_t bytes) { const size_t at = off; off += (bytes+255)/256*256; return at; }
-};
 
 // ---- host threads of the streamed generator (msdfhip_generate_stream): a small persistent pool that flattens the NEXT chunk's shapes into pinned staging
 // while the device works on the chunks before it. Jobs are index ranges; whoever waits for a job helps to finish it. Created on first use, lives as long
@@ -2271,9 +2261,9 @@ struct StreamFeeder : ChunkFeeder {
         PipeSlot &p = slots[ci%PIPE_SLOTS];
         const long long c0 = contourBase[(size_t) g0], e0 = edgeBase[(size_t) g0];
         const Layout l = layout((size_t) n, (size_t) (contourBase[(size_t) g0+n]-c0), (size_t) (edgeBase[(size_t) g0+n]-e0));
-        int32_t *gco = reinterpret_cast<int32_t *>(p.pinnedIn+l.gco), *co = reinterpret_cast<int32_t *>(p.pinnedIn+l.co);
-        double *points = reinterpret_cast<double *>(p.pinnedIn+l.points);
-        uint8_t *types = reinterpret_cast<uint8_t *>(p.pinnedIn+l.types), *colors = reinterpret_cast<uint8_t *>(p.pinnedIn+l.colors);
+        int32_t *gco = reinterpret_cast<int32_t *>(p.pinnedIn.ptr+l.gco), *co = reinterpret_cast<int32_t *>(p.pinnedIn.ptr+l.co);
+        double *points = reinterpret_cast<double *>(p.pinnedIn.ptr+l.points);
+        uint8_t *types = reinterpret_cast<uint8_t *>(p.pinnedIn.ptr+l.types), *colors = reinterpret_cast<uint8_t *>(p.pinnedIn.ptr+l.colors);
         const int first = item*GRAIN, last = first+GRAIN < n ? first+GRAIN : n;
         if (item == 0)
             gco[0] = 0, co[0] = 0;
@@ -2335,22 +2325,11 @@ struct StreamFeeder : ChunkFeeder {
         const size_t recBytes = (sizeof(EdgeRec)*(needE ? needE : 1)+255)/256*256, devNeed = prep ? prepDev+256 : needIn+recBytes+(needC ? needC : 1)+256;
         for (int k = 0; k < PIPE_SLOTS; ++k) {                   // every slot can take the largest chunk (grown once, kept with the pooled pipe)
             PipeSlot &p = slots[k];
-            if (p.pinnedInCap < needIn) {
-                if (p.pinnedIn)
-                    HIPCHK(pinnedFree(p.pinnedIn));
-                p.pinnedIn = NULL, p.pinnedInCap = 0;
-                const size_t cap = needIn+needIn/4+4096;
-                HIPCHK(pinnedAlloc((void **) &p.pinnedIn, cap));
-                p.pinnedInCap = cap;
-            }
-            if (p.devInCap < devNeed) {
+            if (p.pinnedIn.cap < needIn)
+                HIPCHK(p.pinnedIn.ensure(needIn+needIn/4+4096));
+            if (p.devIn.cap < devNeed) {
                 HIPCHK(hipStreamSynchronize(p.stream));
-                if (p.devIn)
-                    HIPCHK(hipFree(p.devIn));
-                p.devIn = NULL, p.devInCap = 0;
-                const size_t cap = devNeed+devNeed/4+4096;
-                HIPCHK(hipMalloc((void **) &p.devIn, cap));
-                p.devInCap = cap;
+                HIPCHK(p.devIn.ensure(devNeed+devNeed/4+4096));
             }
             p.inputsInFlight = false;
         }
@@ -2380,12 +2359,12 @@ struct StreamFeeder : ChunkFeeder {
         size_t bound2 = 0;
         int longest = 0;
         if (prep) {                                              // the normalized offsets and the seeds travel with the chunk's upload
-            prepOffsets(reinterpret_cast<const int32_t *>(p.pinnedIn+l.co), (int) nC, prep->normalize != 0, reinterpret_cast<int32_t *>(p.pinnedIn+l.co1), &bound2, &longest);
+            prepOffsets(reinterpret_cast<const int32_t *>(p.pinnedIn.ptr+l.co), (int) nC, prep->normalize != 0, reinterpret_cast<int32_t *>(p.pinnedIn.ptr+l.co1), &bound2, &longest);
             if (seeds)
-                memcpy(p.pinnedIn+l.seeds, seeds+g0, sizeof(uint64_t)*(size_t) n);
+                memcpy(p.pinnedIn.ptr+l.seeds, seeds+g0, sizeof(uint64_t)*(size_t) n);
         }
         // (a kernel reading the pinned staging: never queues behind another chunk's copy back)
-        const int rcUp = uploadSmall(p.devIn, p.pinnedIn, (l.bytes+15)/16*16, stream);
+        const int rcUp = uploadSmall(p.devIn.ptr, p.pinnedIn.ptr, (l.bytes+15)/16*16, stream);
         if (rcUp != MSDFHIP_OK)
             return rcUp;
         HIPCHK(hipEventRecord(p.inputsUploaded, stream));
@@ -2393,11 +2372,11 @@ struct StreamFeeder : ChunkFeeder {
         MsdfHipBatch &v = p.view;
         v.onDevice(currentDevice());
         v.nGlyphs = n, v.nContours = (int) nC, v.nEdges = (int) nE;
-        v.dGlyphContourOffsets = reinterpret_cast<int32_t *>(p.devIn+l.gco), v.dContourOffsets = reinterpret_cast<int32_t *>(p.devIn+l.co);
-        v.dPoints = reinterpret_cast<double *>(p.devIn+l.points), v.dTypes = reinterpret_cast<uint8_t *>(p.devIn+l.types), v.dColors = reinterpret_cast<uint8_t *>(p.devIn+l.colors);
+        v.dGlyphContourOffsets = reinterpret_cast<int32_t *>(p.devIn.ptr+l.gco), v.dContourOffsets = reinterpret_cast<int32_t *>(p.devIn.ptr+l.co);
+        v.dPoints = reinterpret_cast<double *>(p.devIn.ptr+l.points), v.dTypes = reinterpret_cast<uint8_t *>(p.devIn.ptr+l.types), v.dColors = reinterpret_cast<uint8_t *>(p.devIn.ptr+l.colors);
         const size_t recOff = (l.bytes+255)/256*256;
-        v.dRecs = reinterpret_cast<EdgeRec *>(p.devIn+recOff);
-        v.dWindings = reinterpret_cast<int8_t *>(p.devIn+recOff+(sizeof(EdgeRec)*(nE ? nE : 1)+255)/256*256);
+        v.dRecs = reinterpret_cast<EdgeRec *>(p.devIn.ptr+recOff);
+        v.dWindings = reinterpret_cast<int8_t *>(p.devIn.ptr+recOff+(sizeof(EdgeRec)*(nE ? nE : 1)+255)/256*256);
         v.setCounts(hContours.data()+g0, hEdges.data()+g0, n);
         if (prep) {
             const int rcPrep = prepareChunk(p, l, n, (int) nC, bound2, longest, stream);
@@ -2413,13 +2392,13 @@ struct StreamFeeder : ChunkFeeder {
     // launches are planned from are the PREPARED ones, and the colouring may split a contour in a way only the device knows: its contour offsets come back
     // (one small copy + an event). runPipelineOnce calls this after the previous chunk's kernels are queued, so the device has work while the host waits.
     int prepareChunk(PipeSlot &p, const Layout &l, int n, int nC, size_t bound2, int longest, hipStream_t stream) {
-        char *d = p.devIn;
-        const int32_t *hCo1 = reinterpret_cast<const int32_t *>(p.pinnedIn+l.co1), *hGco = reinterpret_cast<const int32_t *>(p.pinnedIn+l.gco);
+        char *d = p.devIn.ptr;
+        const int32_t *hCo1 = reinterpret_cast<const int32_t *>(p.pinnedIn.ptr+l.co1), *hGco = reinterpret_cast<const int32_t *>(p.pinnedIn.ptr+l.gco);
         const int nE1 = hCo1[nC];
         const bool big = longest > PREP_WAVE_MAX_EDGES;
         const int maxRaw = p.view.maxEdges;                      // (still of the raw counts)
         const bool hitsBig = orient.orient_contours && orientHitsBig(maxRaw);
-        const PrepLayout pl = prepLayout(l.bytes, (size_t) nC, (size_t) reinterpret_cast<const int32_t *>(p.pinnedIn+l.co)[nC], (size_t) nE1, bound2, big, hitsBig);
+        const PrepLayout pl = prepLayout(l.bytes, (size_t) nC, (size_t) reinterpret_cast<const int32_t *>(p.pinnedIn.ptr+l.co)[nC], (size_t) nE1, bound2, big, hitsBig);
         EdgeArrays raw = { reinterpret_cast<double *>(d+l.points), reinterpret_cast<uint8_t *>(d+l.types), reinterpret_cast<uint8_t *>(d+l.colors) };
         EdgeArrays norm = { reinterpret_cast<double *>(d+pl.norm[0]), reinterpret_cast<uint8_t *>(d+pl.norm[1]), reinterpret_cast<uint8_t *>(d+pl.norm[2]) };
         EdgeArrays fin = norm;
@@ -2447,7 +2426,7 @@ struct StreamFeeder : ChunkFeeder {
         if (prep->coloring) {
             // the offsets come back by the word-copy kernel writing into the pinned staging rather than by a copy, which would share the copy engine with
             // the earlier chunks' tiles (measured the same either way on 8 192 glyphs, tools/stream_raw_bench.py: the wait is the preparation itself)
-            int32_t *hCo2 = reinterpret_cast<int32_t *>(p.pinnedIn+(l.bytes+255)/256*256);
+            int32_t *hCo2 = reinterpret_cast<int32_t *>(p.pinnedIn.ptr+(l.bytes+255)/256*256);
             rc = uploadSmall(hCo2, dCo2, sizeof(int32_t)*(size_t) (nC+1), stream);
             if (rc != MSDFHIP_OK)
                 return rc;
@@ -2474,7 +2453,7 @@ static void scatterPending(PipeSlot &p, const MsdfHipGlyph *glyphs, char *dst, s
     const size_t rowBytes = (size_t) w*N*elem, tileBytes = rowBytes*h;
     for (int g = 0; g < p.pendingCount; ++g) {
         const MsdfHipGlyph &gd = glyphs[p.pendingFirst+g];
-        const char *src = p.pinnedTiles+(size_t) g*tileBytes;
+        const char *src = p.pinnedTiles.ptr+(size_t) g*tileBytes;
         for (int y = 0; y < h; ++y)
             memcpy(dst+((long long) gd.out_offset+(long long) gd.row_stride*y)*(long long) elem, src+(size_t) y*rowBytes, rowBytes);
     }
@@ -2497,6 +2476,144 @@ static void hintHwQueuesOnce() {
     if ((q == 0 || q < 8) && getenv("MSDFHIP_VERBOSE") && !said.exchange(true))    // opt-in: a drop-in library does not write to its host's stderr; msdfhip_hw_queues_env() reports the same
         fprintf(stderr, "msdfgen_hip: note: GPU_MAX_HW_QUEUES is %s; the host-output pipeline overlaps its chunks on distinct hardware queues -- export "
                         "GPU_MAX_HW_QUEUES=8 before the process starts (INTEGRATION.md, \"environment\")\n", q ? "below 8" : "not set (HIP uses 4)");
+}
+
+// MSDFHIP_PIPELINE_TRACE: timed events per chunk (kernels enqueued / finished, copy finished) relative to the first enqueue; tools/pipeline_timeline.py reads the line
+struct PipeTrace {
+    struct Events { hipEvent_t start, kernels, copied; long long hostEnqueued; };
+    std::vector<Events> chunks;
+    const bool on;
+    const long long t0;
+    PipeTrace() : on(tuning().pipelineTrace), t0(nowNsEarly()) { }
+    void chunkStarts(hipStream_t stream) {
+        if (!on)
+            return;
+        Events te;
+        hipEventCreate(&te.start), hipEventCreate(&te.kernels), hipEventCreate(&te.copied);
+        te.hostEnqueued = nowNsEarly()-t0;
+        hipEventRecord(te.start, stream);
+        chunks.push_back(te);
+    }
+    void kernelsQueued(hipStream_t stream) {
+        if (on)
+            hipEventRecord(chunks.back().kernels, stream);
+    }
+    void copyQueued(hipStream_t stream) {
+        if (on)
+            hipEventRecord(chunks.back().copied, stream);
+    }
+    void print(bool floatOutput, int nG, const std::vector<int> &lengths) {   // (every stream of the pipe has been synchronised)
+        if (!on || chunks.empty())
+            return;
+        fprintf(stderr, "{\"pipeline_trace\": \"%s\", \"glyphs\": %d, \"host_total_ms\": %.3f, \"chunks\": [", floatOutput ? "float" : "uint8", nG, (nowNsEarly()-t0)/1e6);
+        for (size_t i = 0; i < chunks.size(); ++i) {
+            float a = 0, k = 0, c = 0;
+            hipEventElapsedTime(&a, chunks[0].start, chunks[i].start);
+            hipEventElapsedTime(&k, chunks[0].start, chunks[i].kernels);
+            hipEventElapsedTime(&c, chunks[0].start, chunks[i].copied);
+            fprintf(stderr, "%s{\"glyphs\": %d, \"host_enqueue_ms\": %.3f, \"stream_start_ms\": %.3f, \"kernels_done_ms\": %.3f, \"copy_done_ms\": %.3f}", i ? ", " : "",
+                    lengths[i], chunks[i].hostEnqueued/1e6, a, k, c);
+        }
+        fprintf(stderr, "]}\n");
+        for (size_t i = 0; i < chunks.size(); ++i)
+            hipEventDestroy(chunks[i].start), hipEventDestroy(chunks[i].kernels), hipEventDestroy(chunks[i].copied);
+    }
+};
+
+// What the chunks of one host-output call share.
+struct PipeCall {
+    int mode, w, h, N;
+    const MsdfHipGlyph *glyphs;
+    const MsdfHipConfig *cfg;
+    float *out;                       // float tiles into the caller's bitmaps, or
+    uint8_t *atlas;                   // bytes into the caller's atlas
+    uint8_t *stencil;                 // NULL: not wanted (or no correction pass runs)
+    char *dstBytes;                   // `out` or `atlas`
+    size_t texels, tile, elem;        // texels / values per tile (also bytes per 8-bit tile); bytes per value of the caller's buffer
+    int chunk, depth;                 // glyphs a slot holds; chunks whose kernels may run at a time
+    SlotLayout at;                    // of every slot's device buffer
+    bool mirrorOverflow;
+};
+
+// A chunk's inputs: everything here -- the chunk's shapes (streamed calls: upload + digest), its descriptors and the two preparations of prepareAhead --
+// does not depend on the chunks before it: it is queued AHEAD of the chunk's turn on the device and runs under the earlier chunks' kernels.
+static int queueChunkInputs(const PipeCall &pc, ChunkFeeder *feeder, PipeSlot &p, int slot, size_t ci, int g0, int n, ChunkSpan &span, GenerateCall &call) {
+    const int w = pc.w, h = pc.h, N = pc.N;
+    hipStream_t compute = p.stream;
+    int rc = feeder->prepare(p, slot, ci, g0, n, compute);       // a view of the resident batch, or: flattened shapes -> upload -> digest on the chunk's stream
+    if (rc != MSDFHIP_OK)
+        return rc;
+    MsdfHipGlyph *dGlyphs = reinterpret_cast<MsdfHipGlyph *>(p.dev.ptr+pc.at.offGlyphs);
+    // dense (chunkSpan): the chunk goes back as ONE copy. Otherwise the chunk is rendered as packed tiles, copied into pinned staging and scattered
+    // row by row on the host (pendingCount).
+    span = chunkSpan(pc.glyphs+g0, n, w, h, N);
+    const bool floatsInCallerLayout = pc.out != NULL && span.dense;
+    for (int g = 0; g < n; ++g) {                                // descriptors of the generators: the caller's layout (relative to the range) or packed tiles
+        p.pinnedGlyphs.ptr[g] = pc.glyphs[g0+g];
+        if (floatsInCallerLayout)
+            p.pinnedGlyphs.ptr[g].out_offset -= span.spanLo;
+        else
+            p.pinnedGlyphs.ptr[g].out_offset = (int64_t) ((size_t) g*pc.tile), p.pinnedGlyphs.ptr[g].row_stride = w*N;
+    }
+    rc = uploadSmall(dGlyphs, p.pinnedGlyphs.ptr, sizeof(MsdfHipGlyph)*(size_t) n, compute);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    if (pc.atlas) {                                              // descriptors of the conversion: it reads the packed float tiles and blits into the byte layout
+        MsdfHipGlyph *hBlit = p.pinnedGlyphs.ptr+p.pinnedGlyphs.cap/2;
+        for (int g = 0; g < n; ++g) {
+            hBlit[g] = pc.glyphs[g0+g];
+            if (span.dense)
+                hBlit[g].out_offset -= span.spanLo;
+            else
+                hBlit[g].out_offset = (int64_t) ((size_t) g*pc.tile), hBlit[g].row_stride = w*N;
+        }
+        rc = uploadSmall(dGlyphs+pc.chunk, hBlit, sizeof(MsdfHipGlyph)*(size_t) n, compute);
+        if (rc != MSDFHIP_OK)
+            return rc;
+    }
+    call.afterDistance = p.distanceDone;
+    call.overflowOut = pc.mirrorOverflow ? p.pinnedOverflow : NULL;
+    return prepareAhead(&p.view, pc.mode, w, h, dGlyphs, pc.cfg, compute, call);
+}
+
+// The chunk's turn: its kernels once the chunk `depth` back has finished its own, then its way back to the caller -- one copy where its rectangles
+// tile a range of the caller's buffer, else pinned staging (scattered when the slot is taken next) -- on the slot's stream.
+static int queueChunkWork(const PipeCall &pc, PipeSlot *pipe, int slot, size_t ci, int g0, int n, const ChunkSpan &span, GenerateCall &call, PipeTrace &trace) {
+    const int w = pc.w, h = pc.h, N = pc.N;
+    PipeSlot &p = pipe[slot];
+    hipStream_t compute = p.stream;
+    MsdfHipGlyph *dGlyphs = reinterpret_cast<MsdfHipGlyph *>(p.dev.ptr+pc.at.offGlyphs);
+    float *dTiles = reinterpret_cast<float *>(p.dev.ptr+pc.at.offTiles);
+    uint8_t *dStencil = pc.stencil ? reinterpret_cast<uint8_t *>(p.dev.ptr+pc.at.offStencil) : NULL;
+    uint8_t *dBytes = reinterpret_cast<uint8_t *>(p.dev.ptr+pc.at.offBytes);
+    if (ci >= (size_t) pc.depth)                                 // at most `depth` (two) chunks' kernels at a time, in order: chunk k starts when chunk k-depth's KERNELS are done
+        HIPCHK(hipStreamWaitEvent(compute, pipe[(slot+PIPE_SLOTS-pc.depth)%PIPE_SLOTS].kernelsDone, 0));
+    p.pinnedOverflow[0] = 0;                                     // (the slot's previous chunk is done: nothing on the device writes it any more)
+    int rc = runGenerate(&p.view, pc.mode, w, h, dGlyphs, dTiles, dStencil, NULL, pc.cfg, compute, call);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    const char *dResult = reinterpret_cast<const char *>(dTiles);
+    if (pc.atlas) {
+        rc = msdfhip_tiles_to_bytes(dTiles, n, w, h, N, dGlyphs+pc.chunk, dBytes, compute);
+        if (rc != MSDFHIP_OK)
+            return rc;
+        dResult = reinterpret_cast<const char *>(dBytes);
+    }
+    trace.kernelsQueued(compute);
+    HIPCHK(hipEventRecord(p.kernelsDone, compute));
+    if (span.dense)
+        HIPCHK(hipMemcpyAsync(pc.dstBytes+(size_t) span.spanLo*pc.elem, dResult, (size_t) n*pc.tile*pc.elem, hipMemcpyDeviceToHost, p.stream));
+    else {
+        HIPCHK(p.pinnedTiles.ensure((size_t) pc.chunk*pc.tile*pc.elem));
+        HIPCHK(hipMemcpyAsync(p.pinnedTiles.ptr, dResult, (size_t) n*pc.tile*pc.elem, hipMemcpyDeviceToHost, p.stream));
+        p.pendingFirst = g0, p.pendingCount = n;
+    }
+    if (pc.stencil)
+        HIPCHK(hipMemcpyAsync(pc.stencil+(size_t) g0*pc.texels, dStencil, (size_t) n*pc.texels, hipMemcpyDeviceToHost, p.stream));
+    HIPCHK(hipEventRecord(p.done, p.stream));
+    trace.copyQueued(p.stream);
+    p.busy = true;
+    return MSDFHIP_OK;
 }
 
 // mirrorOverflow: the chunks' correction passes do not launch the per-texel overflow pass (k_ec_slow: a launch at the END of every chunk's chain that almost
@@ -2531,233 +2648,67 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
         ~FeederDrain() { f->drain(); }
     } drainGuard = { feeder };
     PipeSlot *pipe = lease.p->slot;
-    const size_t texels = (size_t) w*h, tile = texels*N;         // floats per tile; also bytes per 8-bit tile
-    const size_t total = out ? outFloats : atlasBytes, elem = out ? sizeof(float) : 1;
-    // every rectangle must lie inside the caller's buffer (how a chunk travels back is decided per chunk below: one contiguous copy when
+    PipeCall pc;
+    pc.mode = mode, pc.w = w, pc.h = h, pc.N = N, pc.glyphs = glyphs, pc.cfg = cfg, pc.out = out, pc.atlas = atlas, pc.mirrorOverflow = mirrorOverflow;
+    pc.texels = (size_t) w*h, pc.tile = pc.texels*N, pc.elem = out ? sizeof(float) : 1;
+    pc.dstBytes = out ? reinterpret_cast<char *>(out) : reinterpret_cast<char *>(atlas);
+    // every rectangle must lie inside the caller's buffer (how a chunk travels back is decided per chunk, chunkSpan: one contiguous copy when
     // its rectangles exactly tile a contiguous range, else pinned staging + a row scatter on the host; either way texels outside the
     // rectangles are never touched, and devices sharing one atlas cannot disturb each other)
+    const size_t total = out ? outFloats : atlasBytes;
     for (int g = 0; g < nG; ++g) {
-        const long long o = glyphs[g].out_offset, rs = glyphs[g].row_stride;
-        const long long lo = rs >= 0 ? o : o+rs*(h-1), hi = (rs >= 0 ? o+rs*(h-1) : o)+(long long) w*N;
-        if (lo < 0 || (unsigned long long) hi > total)
-            return fail(MSDFHIP_ERR_INVALID, "glyph %d's rectangle [%lld, %lld) lies outside the output buffer of %zu elements", g, lo, hi, total);
+        const RectSpan r = rectSpan(glyphs[g], w, h, N);
+        if (r.lo < 0 || (unsigned long long) r.hi > total)
+            return fail(MSDFHIP_ERR_INVALID, "glyph %d's rectangle [%lld, %lld) lies outside the output buffer of %zu elements", g, r.lo, r.hi, total);
     }
-    int chunk = gPipeChunkGlyphs.load();
-    if (chunk <= 0) {
-        chunk = (int) ((96u<<20)/(tile*sizeof(float) ? tile*sizeof(float) : 1));   // measured on 8192 64x64 glyphs: 512 / 1024 / 2048 / 4096 glyphs per chunk -> 18.6 / 14.6 / 12.7 / 14.7 ms
-        chunk = chunk < 64 ? 64 : chunk/64*64;
-    }
-    if (chunk > nG)
-        chunk = nG;
+    const int set = gPipeChunkGlyphs.load(), wanted = set > 0 ? set : defaultChunk(pc.tile);
+    const int chunk = pc.chunk = wanted > nG ? nG : wanted;
     const bool correct = mode >= 3 && cfg->ec_mode != MSDFHIP_EC_DISABLED;
-    const bool wantStencil = stencil != NULL && correct;         // the reference leaves the caller's buffer alone when no correction runs
-    char *dstBytes = out ? reinterpret_cast<char *>(out) : reinterpret_cast<char *>(atlas);
-    const size_t offGlyphs = 0, offTiles = (2*(size_t) chunk*sizeof(MsdfHipGlyph)+255)/256*256, tilesBytes = ((size_t) chunk*tile*sizeof(float)+255)/256*256;
-    const size_t offStencil = offTiles+tilesBytes, stencilBytes = wantStencil ? ((size_t) chunk*texels+255)/256*256 : 0;
-    const size_t offBytes = offStencil+stencilBytes, devBytes = offBytes+(atlas ? (size_t) chunk*tile : 0)+256;
-    for (int k = 0; k < PIPE_SLOTS; ++k) {
+    pc.stencil = correct ? stencil : NULL;                       // the reference leaves the caller's buffer alone when no correction runs
+    pc.at = slotLayout(chunk, pc.tile, pc.texels, pc.stencil != NULL, atlas != NULL);
+    for (int k = 0; k < PIPE_SLOTS; ++k) {                       // every slot holds a full chunk (grown once, kept with the pooled pipe)
         PipeSlot &p = pipe[k];
-        if (p.devCap < devBytes) {
+        if (p.dev.cap < pc.at.devBytes) {
             HIPCHK(hipStreamSynchronize(p.stream));
-            if (p.dev)
-                HIPCHK(hipFree(p.dev));
-            p.dev = NULL, p.devCap = 0;
-            HIPCHK(hipMalloc((void **) &p.dev, devBytes));
-            p.devCap = devBytes;
+            HIPCHK(p.dev.ensure(pc.at.devBytes));
         }
-        if (p.pinnedGlyphCap < (size_t) chunk) {
-            if (p.pinnedGlyphs)
-                HIPCHK(pinnedFree(p.pinnedGlyphs));
-            p.pinnedGlyphs = NULL, p.pinnedGlyphCap = 0;
-            HIPCHK(pinnedAlloc((void **) &p.pinnedGlyphs, sizeof(MsdfHipGlyph)*2*(size_t) chunk));
-            p.pinnedGlyphCap = (size_t) chunk;
-        }
+        HIPCHK(p.pinnedGlyphs.ensure(2*(size_t) chunk));
         if (p.view.work.reservedGlyphs < (size_t) chunk) {       // per-glyph work buffers of the view: reallocated on demand by the launches
             HIPCHK(hipStreamSynchronize(p.stream));
             p.view.work.reserveGlyphs((size_t) chunk);
         }
         p.pendingCount = 0;
     }
-    // Chunk lengths: what the pipeline cannot hide is the kernels (streamed calls: also flatten + upload + digest) of the FIRST chunk and the kernels' tail +
-    // copy of the LAST ones. Round 5 swept the schedule on the streamed end-to-end path (profiles/r05_ab_notes.md, tools/r05_call3.sh; 8 192 glyphs at 64x64):
-    //   float tiles (copy bound: 403 MB at the link's 57 GB/s are 7.4 ms, the kernels 5.7): HALF chunks with a quarter chunk in front -- the copy engine starts
-    //     after 512 glyphs' kernels and never waits again: 512, 1 024 x 7, 512 -> 9.29 ms against 10.0-10.2 for 1 024, 2 048 x 3, 1 024;
-    //   8-bit atlas (kernel bound, a quarter of the bytes): full chunks keep the device fuller; 3/8 of a chunk in front, the remainder in two falling pieces
-    //     (768, 2 048 x 3, 768, 512 -> 7.25-7.30 ms against 7.34-7.38).
-    std::vector<int> lengths;
-    {
-        int rem = nG;
-        const int unit = out ? (chunk/2 >= 64 ? chunk/2/64*64 : chunk) : chunk;     // the schedule's full chunk (the slots are sized for `chunk` either way)
-        const int first = out ? (unit/2 >= 64 ? unit/2/64*64 : unit) : (unit*3/8 >= 64 ? unit*3/8/64*64 : unit);
-        if (nG >= 2*chunk && first < unit) {
-            lengths.push_back(first);
-            for (rem -= first; rem > unit+unit/2; rem -= unit)
-                lengths.push_back(unit);
-            if (!out && rem > unit/2) {                          // (8-bit) the tail in two falling pieces
-                const int a = (rem*3/5+63)/64*64 < rem ? (rem*3/5+63)/64*64 : rem;
-                lengths.push_back(a), rem -= a;
-            } else if (out && rem > unit)
-                lengths.push_back(unit), rem -= unit;
-        } else
-            for (; rem > chunk; rem -= chunk)
-                lengths.push_back(chunk);
-        if (rem > 0)
-            lengths.push_back(rem);
-        // Every slot (device tiles, descriptors, pinned staging) holds `chunk` glyphs. The schedule's rounded pieces can exceed that when `chunk` is not a
-        // multiple of 64 (msdfhip_set_pipeline_chunk(171), 450 glyphs: 64, 171, 192, 23 -- ADVICE r5): an oversized piece is cut, the cut-off part follows it.
-        for (size_t i = 0; i < lengths.size(); ++i)
-            if (lengths[i] > chunk) {
-                lengths.insert(lengths.begin()+(ptrdiff_t) i+1, lengths[i]-chunk);
-                lengths[i] = chunk;
-            }
-    }
+    const std::vector<int> lengths = chunkSchedule(nG, chunk, out != NULL);
     if (lengths.size() > 1)
         hintHwQueuesOnce();
-    // MSDFHIP_PIPELINE_TRACE: timed events per chunk (kernels enqueued / finished, copy finished) relative to the first enqueue
-    struct TraceEvents { hipEvent_t start, kernels, copied; long long hostEnqueued; };
-    std::vector<TraceEvents> trace;
-    const bool tracing = tuning().pipelineTrace;
-    const long long traceT0 = nowNsEarly();
+    PipeTrace trace;
     // Schedule: chunk k runs -- kernels, then its copy back -- on the stream of slot k % PIPE_SLOTS, so the copy of one chunk overlaps the
     // kernels of the next ones, and the kernels of two consecutive chunks overlap each other (a 2 048-glyph step alone leaves the device
     // half empty in its tails: serialising the chunks' kernels on one stream was measured, 17 instead of 12 ms). THREE slots: with two, the
     // device idled 0.8 ms per chunk while a copy held the slot the next chunk needed (MSDFHIP_PIPELINE_TRACE, profiles/r03_ab_notes.md).
-    const int depth = tuning().pipelineDepth;
+    pc.depth = tuning().pipelineDepth;
     rc = feeder->begin(pipe, lengths);
     if (rc != MSDFHIP_OK)
         return rc;
     int slot = 0, g0 = 0;
     for (size_t ci = 0; ci < lengths.size() && rc == MSDFHIP_OK; g0 += lengths[ci], ++ci, slot = (slot+1)%PIPE_SLOTS) {
-        const int n = lengths[ci];
         PipeSlot &p = pipe[slot];
-        hipStream_t compute = p.stream;
         if (p.busy) {                                            // the slot's previous copy must have left its buffers
             HIPCHK(hipEventSynchronize(p.done));
             p.busy = false;
             if (mirrorOverflow && p.pinnedOverflow[0] != 0)
                 *overflowed = true;
             if (p.pendingCount)
-                scatterPending(p, glyphs, dstBytes, elem, w, h, N);
+                scatterPending(p, glyphs, pc.dstBytes, pc.elem, w, h, N);
             p.pendingCount = 0;
         }
-        if (tracing) {
-            TraceEvents te;
-            hipEventCreate(&te.start), hipEventCreate(&te.kernels), hipEventCreate(&te.copied);
-            te.hostEnqueued = nowNsEarly()-traceT0;
-            hipEventRecord(te.start, compute);
-            trace.push_back(te);
-        }
-        rc = feeder->prepare(p, slot, ci, g0, n, compute);       // a view of the resident batch, or: flattened shapes -> upload -> digest on the chunk's stream
-        if (rc != MSDFHIP_OK)
-            break;
-        MsdfHipGlyph *dGlyphs = reinterpret_cast<MsdfHipGlyph *>(p.dev+offGlyphs);
-        float *dTiles = reinterpret_cast<float *>(p.dev+offTiles);
-        uint8_t *dStencil = wantStencil ? reinterpret_cast<uint8_t *>(p.dev+offStencil) : NULL;
-        uint8_t *dBytes = reinterpret_cast<uint8_t *>(p.dev+offBytes);
-        // dense: the chunk's rectangles exactly tile one contiguous range of the caller's buffer (tiles packed in glyph order; whole
-        // row bands of an atlas) -> the device writes that range in the caller's layout and it goes back as ONE copy. Otherwise the
-        // chunk is rendered as packed tiles, copied into pinned staging and scattered row by row on the host (pendingCount).
-        long long spanLo = glyphs[g0].out_offset, spanHi = spanLo;
-        bool dense = true;
-        for (int g = 0; g < n; ++g) {
-            const long long o = glyphs[g0+g].out_offset, rs = glyphs[g0+g].row_stride;
-            dense = dense && rs >= (long long) w*N;
-            const long long lo = rs >= 0 ? o : o+rs*(h-1), hi = (rs >= 0 ? o+rs*(h-1) : o)+(long long) w*N;
-            spanLo = lo < spanLo ? lo : spanLo, spanHi = hi > spanHi ? hi : spanHi;
-        }
-        dense = dense && (unsigned long long) (spanHi-spanLo) == (unsigned long long) n*tile;
-        // Equal area is an exact tiling only if the rectangles are DISJOINT (two glyphs on one cell + a free cell elsewhere have the same
-        // area: the free cell would come back as whatever the device buffer held). Accept the two layouts that make it so by construction:
-        // packed tiles in glyph order, or the cells of a grid whose pitch is the common row stride, each used once.
-        if (dense) {
-            bool packed = true;
-            for (int g = 0; g < n && packed; ++g)
-                packed = glyphs[g0+g].row_stride == (int64_t) w*N && glyphs[g0+g].out_offset == spanLo+(long long) g*(long long) tile;
-            if (!packed) {
-                const long long pitch = glyphs[g0].row_stride, cellW = (long long) w*N;
-                bool grid = pitch > 0 && pitch%cellW == 0 && (long long) n%(pitch/cellW) == 0;
-                std::vector<bool> used(grid ? (size_t) n : 0, false);
-                for (int g = 0; g < n && grid; ++g) {
-                    const long long rel = glyphs[g0+g].out_offset-spanLo;
-                    const long long row = rel/pitch, col = rel%pitch;
-                    grid = glyphs[g0+g].row_stride == pitch && row%h == 0 && col%cellW == 0;
-                    if (grid) {
-                        const size_t cell = (size_t) ((row/h)*(pitch/cellW)+col/cellW);
-                        grid = cell < used.size() && !used[cell];
-                        if (grid)
-                            used[cell] = true;
-                    }
-                }
-                dense = grid;
-            }
-        }
-        const bool floatsInCallerLayout = out != NULL && dense;
-        for (int g = 0; g < n; ++g) {                            // descriptors of the generators: the caller's layout (relative to the range) or packed tiles
-            p.pinnedGlyphs[g] = glyphs[g0+g];
-            if (floatsInCallerLayout)
-                p.pinnedGlyphs[g].out_offset -= spanLo;
-            else
-                p.pinnedGlyphs[g].out_offset = (int64_t) ((size_t) g*tile), p.pinnedGlyphs[g].row_stride = w*N;
-        }
-        rc = uploadSmall(dGlyphs, p.pinnedGlyphs, sizeof(MsdfHipGlyph)*(size_t) n, compute);
-        if (rc != MSDFHIP_OK)
-            break;
-        MsdfHipGlyph *hBlit = p.pinnedGlyphs+p.pinnedGlyphCap, *dBlit = dGlyphs+chunk;
-        if (atlas) {                                             // descriptors of the conversion: it reads the packed float tiles and blits into the byte layout
-            for (int g = 0; g < n; ++g) {
-                hBlit[g] = glyphs[g0+g];
-                if (dense)
-                    hBlit[g].out_offset -= spanLo;
-                else
-                    hBlit[g].out_offset = (int64_t) ((size_t) g*tile), hBlit[g].row_stride = w*N;
-            }
-            rc = uploadSmall(dBlit, hBlit, sizeof(MsdfHipGlyph)*(size_t) n, compute);
-            if (rc != MSDFHIP_OK)
-                break;
-        }
-        // Everything up to here -- the chunk's inputs (streamed calls: upload + digest), its descriptors -- and the two preparations below do not depend on
-        // the chunks before it: they are queued AHEAD of the chunk's turn on the device and run under the earlier chunks' kernels.
+        trace.chunkStarts(p.stream);
+        ChunkSpan span;
         GenerateCall call;
-        call.afterDistance = p.distanceDone;
-        call.overflowOut = mirrorOverflow ? p.pinnedOverflow : NULL;
-        rc = prepareAhead(&p.view, mode, w, h, dGlyphs, cfg, compute, call);
-        if (rc != MSDFHIP_OK)
-            break;
-        if (ci >= (size_t) depth)                                // at most `depth` (two) chunks' kernels at a time, in order: chunk k starts when chunk k-depth's KERNELS are done
-            HIPCHK(hipStreamWaitEvent(compute, pipe[(slot+PIPE_SLOTS-depth)%PIPE_SLOTS].kernelsDone, 0));
-        p.pinnedOverflow[0] = 0;                                 // (the slot's previous chunk is done: nothing on the device writes it any more)
-        rc = runGenerate(&p.view, mode, w, h, dGlyphs, dTiles, dStencil, NULL, cfg, compute, call);
-        if (rc != MSDFHIP_OK)
-            break;
-        const char *dResult = reinterpret_cast<const char *>(dTiles);
-        if (atlas) {
-            rc = msdfhip_tiles_to_bytes(dTiles, n, w, h, N, dBlit, dBytes, compute);
-            if (rc != MSDFHIP_OK)
-                break;
-            dResult = reinterpret_cast<const char *>(dBytes);
-        }
-        if (tracing)
-            hipEventRecord(trace.back().kernels, compute);
-        HIPCHK(hipEventRecord(p.kernelsDone, compute));
-        if (dense)
-            HIPCHK(hipMemcpyAsync(dstBytes+(size_t) spanLo*elem, dResult, (size_t) n*tile*elem, hipMemcpyDeviceToHost, p.stream));
-        else {
-            if (p.pinnedTilesCap < (size_t) chunk*tile*elem) {
-                if (p.pinnedTiles)
-                    HIPCHK(pinnedFree(p.pinnedTiles));
-                p.pinnedTiles = NULL, p.pinnedTilesCap = 0;
-                HIPCHK(pinnedAlloc((void **) &p.pinnedTiles, (size_t) chunk*tile*elem));
-                p.pinnedTilesCap = (size_t) chunk*tile*elem;
-            }
-            HIPCHK(hipMemcpyAsync(p.pinnedTiles, dResult, (size_t) n*tile*elem, hipMemcpyDeviceToHost, p.stream));
-            p.pendingFirst = g0, p.pendingCount = n;
-        }
-        if (wantStencil)
-            HIPCHK(hipMemcpyAsync(stencil+(size_t) g0*texels, dStencil, (size_t) n*texels, hipMemcpyDeviceToHost, p.stream));
-        HIPCHK(hipEventRecord(p.done, p.stream));
-        if (tracing)
-            hipEventRecord(trace.back().copied, p.stream);
-        p.busy = true;
+        rc = queueChunkInputs(pc, feeder, p, slot, ci, g0, lengths[ci], span, call);
+        if (rc == MSDFHIP_OK)
+            rc = queueChunkWork(pc, pipe, slot, ci, g0, lengths[ci], span, call, trace);
     }
     for (int k = 0; k < PIPE_SLOTS; ++k) {
         PipeSlot &p = pipe[k];
@@ -2768,23 +2719,10 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
         if (mirrorOverflow && e == hipSuccess && p.pinnedOverflow[0] != 0)
             *overflowed = true;
         if (rc == MSDFHIP_OK && p.pendingCount)
-            scatterPending(p, glyphs, dstBytes, elem, w, h, N);
+            scatterPending(p, glyphs, pc.dstBytes, pc.elem, w, h, N);
         p.pendingCount = 0;
     }
-    if (tracing && !trace.empty()) {
-        fprintf(stderr, "{\"pipeline_trace\": \"%s\", \"glyphs\": %d, \"host_total_ms\": %.3f, \"chunks\": [", out ? "float" : "uint8", nG, (nowNsEarly()-traceT0)/1e6);
-        for (size_t i = 0; i < trace.size(); ++i) {
-            float a = 0, k = 0, c = 0;
-            hipEventElapsedTime(&a, trace[0].start, trace[i].start);
-            hipEventElapsedTime(&k, trace[0].start, trace[i].kernels);
-            hipEventElapsedTime(&c, trace[0].start, trace[i].copied);
-            fprintf(stderr, "%s{\"glyphs\": %d, \"host_enqueue_ms\": %.3f, \"stream_start_ms\": %.3f, \"kernels_done_ms\": %.3f, \"copy_done_ms\": %.3f}", i ? ", " : "",
-                    lengths[i], trace[i].hostEnqueued/1e6, a, k, c);
-        }
-        fprintf(stderr, "]}\n");
-        for (size_t i = 0; i < trace.size(); ++i)
-            hipEventDestroy(trace[i].start), hipEventDestroy(trace[i].kernels), hipEventDestroy(trace[i].copied);
-    }
+    trace.print(out != NULL, nG, lengths);
     return rc;
 }
 
@@ -2989,24 +2927,9 @@ int msdfhip_host_free(void *p) {
 
 // ------------------------------------------------------------------------------------------- glyph-sharded, multi-device
 //
-// glyphs are independent, so a glyph list is cut into contiguous ranges of equal modelled cost (glyphCost), one range per device, one
-// host thread + its own streams per device, no exchange between devices; every device copies its tiles straight into the caller's
+// glyphs are independent, so a glyph list is cut into contiguous ranges of equal modelled cost (shardRanges, msdf_hostplan.hpp), one range
+// per device, one host thread + its own streams per device, no exchange between devices; every device copies its tiles straight into the caller's
 // buffer. The bytes do not depend on the split.
-
-static void shardRanges(const int32_t *gco, const int32_t *co, int nGlyphs, int parts, std::vector<int> &bounds) {
-    bounds.assign((size_t) parts+1, nGlyphs);
-    bounds[0] = 0;
-    double total = 0;
-    for (int g = 0; g < nGlyphs; ++g)
-        total += glyphCost(gco[g+1]-gco[g], co[gco[g+1]]-co[gco[g]]);
-    double acc = 0;
-    int part = 1;
-    for (int g = 0; g < nGlyphs && part < parts; ++g) {
-        acc += glyphCost(gco[g+1]-gco[g], co[gco[g+1]]-co[gco[g]]);
-        while (part < parts && acc >= total*part/parts)
-            bounds[part++] = g+1;
-    }
-}
 
 int msdfhip_generate_sharded(const int *devices, int n_devices, int mode, int w, int h, int n_glyphs, const int32_t *gco, const int32_t *co,
                              const double *points, const uint8_t *types, const uint8_t *colors, const MsdfHipGlyph *glyphs,
@@ -3165,14 +3088,6 @@ static void destroyPipe(Pipe *p) {
         PipeSlot &s = p->slot[k];
         if (s.stream)
             (void) hipStreamSynchronize(s.stream);
-        hipFree(s.dev);
-        if (s.pinnedGlyphs)
-            pinnedFree(s.pinnedGlyphs);
-        if (s.pinnedTiles)
-            pinnedFree(s.pinnedTiles);
-        if (s.pinnedIn)
-            pinnedFree(s.pinnedIn);
-        hipFree(s.devIn);
         if (s.inputsUploaded)
             hipEventDestroy(s.inputsUploaded);
         if (s.prepCounted)
@@ -3188,7 +3103,7 @@ static void destroyPipe(Pipe *p) {
         if (s.stream)
             hipStreamDestroy(s.stream);
     }
-    delete p;                                                    // (the views' workspaces release themselves)
+    delete p;                                                    // (the slots' buffers and the views' workspaces release themselves)
     (void) hipGetLastError();
 }
 
@@ -3286,17 +3201,6 @@ static int frontDoorDevice() {
 // (hipOccupancyMaxActiveBlocksPerMultiprocessor x compute units) -- a call that would not fit takes the batched sequence; (2) what this process cannot
 // count (persistent k_distance launches of other threads, other processes) is covered by the bounded spin + rerun (msdf_single.hpp: gridBarrier).
 static std::atomic<int> gFusedInFlight[64];                     // workgroups of fused launches in flight, per device
-extern "C++" {
-template <int SEL, bool OVERLAP>
-static int fusedBlocksPerCu(size_t lds) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void *>(k_single_call<SEL, OVERLAP>), WAVE*SINGLE_TEAM, lds) != hipSuccess) {
-        (void) hipGetLastError();
-        return 0;
-    }
-    return n;
-}
-}
 static int fusedCapacity(int device, int variant, size_t lds) {  // variant = mode*2 + overlap (2..9)
     enum { LDS_STEP = 4096, LDS_STEPS = 17 };
     static std::atomic<int> cache[10][LDS_STEPS];                // (one gfx950 is like another: not keyed by device)
@@ -3307,16 +3211,13 @@ static int fusedCapacity(int device, int variant, size_t lds) {  // variant = mo
     if (!v) {
         const size_t rounded = step*LDS_STEP;
         int perCu = 0;
-        switch (variant) {
-            case 2: perCu = fusedBlocksPerCu<1, false>(rounded); break;
-            case 3: perCu = fusedBlocksPerCu<1, true>(rounded); break;
-            case 4: perCu = fusedBlocksPerCu<2, false>(rounded); break;
-            case 5: perCu = fusedBlocksPerCu<2, true>(rounded); break;
-            case 6: perCu = fusedBlocksPerCu<3, false>(rounded); break;
-            case 7: perCu = fusedBlocksPerCu<3, true>(rounded); break;
-            case 8: perCu = fusedBlocksPerCu<4, false>(rounded); break;
-            default: perCu = fusedBlocksPerCu<4, true>(rounded); break;
-        }
+        forSingleCallVariant(variant, [&](auto sel, auto overlap) {
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void *>(k_single_call<decltype(sel)::value, decltype(overlap)::value>),
+                                                             WAVE*SINGLE_TEAM, rounded) != hipSuccess) {
+                (void) hipGetLastError();
+                perCu = 0;
+            }
+        });
         v = perCu > 0 ? perCu*residentSlots(device) : -1;
         cache[variant][step].store(v);
     }
@@ -3346,70 +3247,79 @@ struct FusedReservation {                                        // the workgrou
     }
 };
 
-static int runGroup(ShapeCall *const *calls, int n) {
+// Everything about a group of n compatible calls that is known before its arena is leased and never changes afterwards.
+struct GroupPlan {
+    int n, maxC, maxE, stages;        // calls; the largest contour / edge count of one; intermediate fields of a generate call (correction, sign correction)
+    bool bitmapIsInput, correct, anyStencil;
+    bool fusedShape;                  // ONE generate*() call on a bitmap of at most 256 tiles: k_single_call's private areas are reserved
+    size_t sumC, sumE, eAlloc, cAlloc, texels, tileBytes, tilesAll, candCap;
+    // pinned staging, mirrored at the start of the device arena. Inputs first: one H2D copy of inputBytes; hStatus onwards: one D2H copy (copyBackAndWait)
+    size_t hGco, hCo, hPts, hTypes, hColors, hGlyph, hSrc, inputBytes, hBucket, hStatus, hOut, hStencil, resultBytes, pinnedBytes;
+    // device-only work buffers behind the mirror
+    size_t dRecs, dWind, dScratch, dCands, dParams, gresNeed, dGres, dPriv, devBytes;
+    size_t pvWind, pvOff, pvGco, pvGlyph, pvStride;   // k_single_call: offsets inside one workgroup's private digest area, and the areas' stride (msdf_single.hpp)
+};
+
+static GroupPlan planGroup(ShapeCall *const *calls, int n) {
     const ShapeCall &c0 = *calls[0];
-    const int mode = c0.mode, channels = c0.channels, op = c0.op, w = c0.w, h = c0.h;
+    const int channels = c0.channels, op = c0.op, w = c0.w, h = c0.h;
     const MsdfHipConfig *cfg = &c0.cfg;
-    int rc = ensureDevice(frontDoorDevice());
-    if (rc != MSDFHIP_OK)
-        return rc;
-    const bool bitmapIsInput = op == OP_ERROR_CORRECTION || op == OP_SIGN_CORRECTION;
-    const bool correct = op <= OP_ERROR_CORRECTION && channels >= 3 && cfg->ec_mode != MSDFHIP_EC_DISABLED;
-    const int stages = op == OP_GENERATE ? (correct ? 1 : 0)+(cfg->sign_correction ? 1 : 0) : 0;
-    bool anyStencil = false;
-    size_t sumC = 0, sumE = 0;
-    int maxC = 0, maxE = 0;
+    GroupPlan p;
+    p.n = n;
+    p.bitmapIsInput = op == OP_ERROR_CORRECTION || op == OP_SIGN_CORRECTION;
+    p.correct = op <= OP_ERROR_CORRECTION && channels >= 3 && cfg->ec_mode != MSDFHIP_EC_DISABLED;
+    p.stages = op == OP_GENERATE ? (p.correct ? 1 : 0)+(cfg->sign_correction ? 1 : 0) : 0;
+    p.anyStencil = false;
+    p.sumC = p.sumE = 0, p.maxC = p.maxE = 0;
     for (int g = 0; g < n; ++g) {
         const ShapeCall &c = *calls[g];
         const int nE = c.co[c.nC];
-        sumC += c.nC, sumE += nE;
-        maxC = c.nC > maxC ? c.nC : maxC, maxE = nE > maxE ? nE : maxE;
-        anyStencil = anyStencil || (c.stencil != NULL && correct);   // no correction pass: the reference leaves the caller's buffer untouched
+        p.sumC += c.nC, p.sumE += nE;
+        p.maxC = c.nC > p.maxC ? c.nC : p.maxC, p.maxE = nE > p.maxE ? nE : p.maxE;
+        p.anyStencil = p.anyStencil || (c.stencil != NULL && p.correct);   // no correction pass: the reference leaves the caller's buffer untouched
     }
-    const size_t texels = (size_t) w*h, tileBytes = texels*channels*sizeof(float);
-    const size_t eAlloc = sumE > 0 ? sumE : 1, cAlloc = sumC > 0 ? sumC : 1;
-    const size_t tilesAllEarly = (size_t) ((w+TILE-1)/TILE)*((h+TILE-1)/TILE);
-    const size_t singleCand = n == 1 && tilesAllEarly <= 256 ? ecHeaderRecords((int) tilesAllEarly)+tilesAllEarly*SINGLE_TILE_SEGMENT+(eAlloc*2*sizeof(int)+sizeof(EcCandidate)-1)/sizeof(EcCandidate) : 0;
-    const size_t candCap = deferredRecords(n, texels, (int) sumE) > singleCand ? deferredRecords(n, texels, (int) sumE) : singleCand;   // (k_single_call lays the buffer out per tile)
+    const size_t texels = p.texels = (size_t) w*h, tileBytes = p.tileBytes = texels*channels*sizeof(float);
+    const size_t eAlloc = p.eAlloc = p.sumE > 0 ? p.sumE : 1, cAlloc = p.cAlloc = p.sumC > 0 ? p.sumC : 1;
+    const size_t tilesAll = p.tilesAll = (size_t) ((w+TILE-1)/TILE)*((h+TILE-1)/TILE);
+    const size_t singleCand = n == 1 && tilesAll <= 256 ? ecHeaderRecords((int) tilesAll)+tilesAll*SINGLE_TILE_SEGMENT+(eAlloc*2*sizeof(int)+sizeof(EcCandidate)-1)/sizeof(EcCandidate) : 0;
+    p.candCap = deferredRecords(n, texels, (int) p.sumE) > singleCand ? deferredRecords(n, texels, (int) p.sumE) : singleCand;   // (k_single_call lays the buffer out per tile)
 
     // host staging layout (inputs first: one H2D copy; then the results: one D2H copy)
     Carver hc;
-    const size_t hGco = hc.take((n+1)*sizeof(int32_t)), hCo = hc.take((sumC+1)*sizeof(int32_t)), hPts = hc.take(eAlloc*8*sizeof(double));
-    const size_t hTypes = hc.take(eAlloc), hColors = hc.take(eAlloc), hGlyph = hc.take(n*sizeof(MsdfHipGlyph));
-    const size_t hSrc = bitmapIsInput ? hc.take(n*tileBytes) : hc.off;
-    const size_t inputBytes = hc.off;
-    const size_t hBucketOff = hc.take(n*sizeof(int));           // class lists of the overlapping combiner (uploaded on the stream by the launch code)
-    const size_t hStatus = hc.take(256);                         // [0]: candidate-overflow count of the correction pass, copied back with the results
-    const size_t hOut = hc.take(n*tileBytes), hStencil = hc.take(n*texels);
-    const size_t resultBytes = hc.off-hOut;
+    p.hGco = hc.take((n+1)*sizeof(int32_t)), p.hCo = hc.take((p.sumC+1)*sizeof(int32_t)), p.hPts = hc.take(eAlloc*8*sizeof(double));
+    p.hTypes = hc.take(eAlloc), p.hColors = hc.take(eAlloc), p.hGlyph = hc.take(n*sizeof(MsdfHipGlyph));
+    p.hSrc = p.bitmapIsInput ? hc.take(n*tileBytes) : hc.off;
+    p.inputBytes = hc.off;
+    p.hBucket = hc.take(n*sizeof(int));                          // class lists of the overlapping combiner (uploaded on the stream by the launch code)
+    p.hStatus = hc.take(256);                                    // [0]: candidate-overflow count of the correction pass, copied back with the results
+    p.hOut = hc.take(n*tileBytes), p.hStencil = hc.take(n*texels);
+    p.resultBytes = hc.off-p.hOut;
+    p.pinnedBytes = hc.off;
     // device layout: mirror of the staging area, then device-only work buffers
     Carver dc;
     dc.off = hc.off;
-    const size_t dRecs = dc.take(eAlloc*sizeof(EdgeRec)), dWind = dc.take(cAlloc), dScratch = dc.take(n*tileBytes*stages);
-    const size_t dCands = dc.take(correct ? candCap*sizeof(EcCandidate) : 0), dParams = dc.take(n*sizeof(EcGlyphParams));
+    p.dRecs = dc.take(eAlloc*sizeof(EdgeRec)), p.dWind = dc.take(cAlloc), p.dScratch = dc.take(n*tileBytes*p.stages);
+    p.dCands = dc.take(p.correct ? p.candCap*sizeof(EcCandidate) : 0), p.dParams = dc.take(n*sizeof(EcGlyphParams));
     // combiner scratch of the small-launch distance kernels (one tile per wavefront), see dispatchDistance
-    const size_t tilesAll = (size_t) ((w+TILE-1)/TILE)*((h+TILE-1)/TILE);
-    size_t gresNeed = op == OP_GENERATE && cfg->overlap_support && maxC > 1 && (size_t) n*tilesAll <= 8192 ? (size_t) n*tilesAll*maxC*channels*WAVE*sizeof(double) : 0;
-    if (gresNeed > ((size_t) 64<<20))
-        gresNeed = 0;
-    const size_t dGresOff = dc.take(gresNeed);
+    p.gresNeed = op == OP_GENERATE && cfg->overlap_support && p.maxC > 1 && (size_t) n*tilesAll <= 8192 ? (size_t) n*tilesAll*p.maxC*channels*WAVE*sizeof(double) : 0;
+    if (p.gresNeed > ((size_t) 64<<20))
+        p.gresNeed = 0;
+    p.dGres = dc.take(p.gresNeed);
     // k_single_call: one private digest area per workgroup (msdf_single.hpp) -- only reserved for calls that can take that path
-    const size_t pvWind = (eAlloc*sizeof(EdgeRec)+63)/64*64, pvOff = (pvWind+cAlloc+63)/64*64, pvGco = (pvOff+(cAlloc+1)*sizeof(int32_t)+63)/64*64;
-    const size_t pvGlyph = pvGco+64, pvStride = (pvGlyph+sizeof(MsdfHipGlyph)+255)/256*256;
-    const bool fusedShape = n == 1 && op == OP_GENERATE && tilesAll <= 256 && (tilesAll+1)*pvStride <= ((size_t) 32<<20);
-    const size_t dPriv = dc.take(fusedShape ? (tilesAll+1)*pvStride : 0);
-    ArenaLease lease;
-    rc = lease.take(currentDevice());
-    if (rc != MSDFHIP_OK)
-        return rc;
-    ThreadArena &a = *lease.a;
-    rc = arenaReserve(a, dc.off, hc.off);
-    if (rc != MSDFHIP_OK)
-        return rc;
+    p.pvWind = (eAlloc*sizeof(EdgeRec)+63)/64*64, p.pvOff = (p.pvWind+cAlloc+63)/64*64, p.pvGco = (p.pvOff+(cAlloc+1)*sizeof(int32_t)+63)/64*64;
+    p.pvGlyph = p.pvGco+64, p.pvStride = (p.pvGlyph+sizeof(MsdfHipGlyph)+255)/256*256;
+    p.fusedShape = n == 1 && op == OP_GENERATE && tilesAll <= 256 && (tilesAll+1)*p.pvStride <= ((size_t) 32<<20);
+    p.dPriv = dc.take(p.fusedShape ? (tilesAll+1)*p.pvStride : 0);
+    p.devBytes = dc.off;
+    return p;
+}
 
-    const long long t0 = nowNs();
-    int32_t *gco = reinterpret_cast<int32_t *>(a.pinned+hGco), *co = reinterpret_cast<int32_t *>(a.pinned+hCo);
-    MsdfHipGlyph *gd = reinterpret_cast<MsdfHipGlyph *>(a.pinned+hGlyph);
+// Flattens the calls' shapes (and, for the in-place operations, their bitmaps) into the arena's pinned staging as one CSR batch.
+static void stageGroup(const GroupPlan &p, ThreadArena &a, ShapeCall *const *calls, int n) {
+    const ShapeCall &c0 = *calls[0];
+    const int channels = c0.channels, w = c0.w, h = c0.h;
+    int32_t *gco = reinterpret_cast<int32_t *>(a.pinned+p.hGco), *co = reinterpret_cast<int32_t *>(a.pinned+p.hCo);
+    MsdfHipGlyph *gd = reinterpret_cast<MsdfHipGlyph *>(a.pinned+p.hGlyph);
     size_t cAt = 0, eAt = 0;
     co[0] = 0;
     for (int g = 0; g < n; ++g) {
@@ -3419,84 +3329,39 @@ static int runGroup(ShapeCall *const *calls, int n) {
         for (int k = 1; k <= c.nC; ++k)
             co[cAt+k] = (int32_t) (eAt+c.co[k]);
         if (nE) {
-            memcpy(a.pinned+hPts+eAt*8*sizeof(double), c.points, (size_t) nE*8*sizeof(double));
-            memcpy(a.pinned+hTypes+eAt, c.types, nE);
-            memcpy(a.pinned+hColors+eAt, c.colors, nE);
+            memcpy(a.pinned+p.hPts+eAt*8*sizeof(double), c.points, (size_t) nE*8*sizeof(double));
+            memcpy(a.pinned+p.hTypes+eAt, c.types, nE);
+            memcpy(a.pinned+p.hColors+eAt, c.colors, nE);
         }
         cAt += c.nC, eAt += nE;
         memcpy(gd[g].xf, c.xf, sizeof(gd[g].xf));
-        gd[g].out_offset = (int64_t) ((size_t) g*texels*channels);   // the device tiles are tightly packed in memory-row order
+        gd[g].out_offset = (int64_t) ((size_t) g*p.texels*channels);   // the device tiles are tightly packed in memory-row order
         gd[g].row_stride = w*channels;
         gd[g].flip = c.flip ? 1 : 0;
-        if (bitmapIsInput)
+        if (p.bitmapIsInput)
             for (int y = 0; y < h; ++y)
-                memcpy(a.pinned+hSrc+((size_t) g*texels+(size_t) y*w)*channels*sizeof(float), c.pixels+(ptrdiff_t) c.rowStride*y, sizeof(float)*(size_t) w*channels);
+                memcpy(a.pinned+p.hSrc+((size_t) g*p.texels+(size_t) y*w)*channels*sizeof(float), c.pixels+(ptrdiff_t) c.rowStride*y, sizeof(float)*(size_t) w*channels);
     }
     gco[n] = (int32_t) cAt;
-    const long long t1 = nowNs();
-    // Does the call take ONE launch (k_single_call, msdf_single.hpp)? ONE shape, a generate*() call without the scanline pass, a bitmap of at most
-    // 256 tiles, lists / correction scratch within 64 KB of LDS. Decided before the upload: with the staging area mapped into the device the
-    // kernel reads its inputs from there and nothing is uploaded at all.
-    const bool overlapEff = cfg->overlap_support && maxC > 1;
-    const int slotCapWanted = maxE > 0 ? (maxE < 1024 ? maxE : 1024) : 1;
-    const int slotOffset = overlapEff ? (maxC > 0 ? maxC : 1) : 0;
-    int slotCap = slotCapWanted;
-    size_t queryLds = (size_t) slotOffset*sizeof(double)+((size_t) slotCap+(size_t) (maxC < slotCap ? (maxC > 0 ? maxC : 1) : slotCap))*sizeof(PBSlot);
-    if (queryLds > (size_t) 48*1024) {                       // too many edges for the slots: per-contour lane merges instead (EdgesCooperative)
-        slotCap = 1;
-        queryLds = (size_t) slotOffset*sizeof(double)+2*sizeof(PBSlot);
-    }
-    const size_t resBytes = overlapEff ? (size_t) maxC*channels*WAVE*sizeof(double) : 0;
-    const size_t resLdsForm = resBytes+tileListBytes(maxE, maxC, false);      // combiner scratch in LDS (k_distance's LDS form with one tile per wavefront)
-    const bool resInLds = overlapEff && resLdsForm <= (size_t) 60*1024;
-    const size_t listLds = resInLds ? resLdsForm : tileListBytes(maxE, maxC, true);
-    size_t lds = listLds;
-    {
-        const size_t digestLds = (((size_t) maxC+3)/2+WAVE)*sizeof(double);   // the digest phase: contour offsets + the 64 shoelace terms of the windings
-        lds = lds > digestLds ? lds : digestLds;
-    }
-    if (correct) {
-        lds = lds > ecFastLdsBytes(maxE, channels) ? lds : ecFastLdsBytes(maxE, channels);
-        lds = lds > queryLds ? lds : queryLds;
-    }
-    // the exchange areas of a tile's team of wavefronts (msdf_kernels.hpp: TeamExchange) behind everything the phases use
-    const size_t teamXchgOffset = (lds+15)/16*16;
-    if (SINGLE_TEAM > 1)
-        lds = teamXchgOffset+(size_t) (SINGLE_TEAM-1)*TEAM_XCHG_DOUBLES*WAVE*sizeof(double);
-    bool fusedOK = fusedShape && !tuning().noFusedSingle && !cfg->sign_correction && cfg->ec_stage_limit == 0 &&
-                   lds <= (size_t) 64*1024 && (!overlapEff || resInLds || gresNeed >= tilesAll*resBytes);
-    FusedReservation fusedSlots;                                 // (see fusedCapacity: all workgroups of the launch must be resident together)
-    if (fusedOK) {
-        fusedOK = fusedSlots.take(a.device, mode*2+(overlapEff ? 1 : 0), lds, (int) tilesAll+(correct ? 1 : 0));
-        if (!fusedOK)
-            gSingleRefused += 1;
-    }
-    const bool zeroCopy = fusedOK && a.pinnedDev != NULL && !anyStencil && !tuning().noZeroCopySingle;
-    if (zeroCopy) {
-        // (nothing to upload)
-    } else if (inputBytes <= ((size_t) 1<<20)) {                 // a few KB: read from the pinned staging by a kernel -- no SDMA submission on the latency path
-        rc = uploadSmall(a.dev, a.pinned, inputBytes, a.stream);
-        if (rc != MSDFHIP_OK)
-            return rc;
-    } else
-        HIPCHK(hipMemcpyAsync(a.dev, a.pinned, inputBytes, hipMemcpyHostToDevice, a.stream));
+}
 
-    MsdfHipBatch b;                                              // a view into the arena: its workspace borrows the arena's regions and owns only what has to grow beyond them
+// b becomes a view into the arena: its workspace borrows the arena's regions and owns only what has to grow beyond them.
+static void buildView(const GroupPlan &p, ThreadArena &a, ShapeCall *const *calls, int n, MsdfHipBatch &b) {
     b.onDevice(a.device);
-    b.nGlyphs = n, b.nContours = (int) sumC, b.nEdges = (int) sumE;
-    b.dGlyphContourOffsets = reinterpret_cast<int32_t *>(a.dev+hGco);
-    b.dContourOffsets = reinterpret_cast<int32_t *>(a.dev+hCo);
-    b.dPoints = reinterpret_cast<double *>(a.dev+hPts);
-    b.dTypes = reinterpret_cast<uint8_t *>(a.dev+hTypes);
-    b.dColors = reinterpret_cast<uint8_t *>(a.dev+hColors);
-    b.dRecs = reinterpret_cast<EdgeRec *>(a.dev+dRecs);
-    b.dWindings = reinterpret_cast<int8_t *>(a.dev+dWind);
-    if (correct)
-        b.work.deferred.borrow(reinterpret_cast<EcCandidate *>(a.dev+dCands), candCap);
-    b.work.ecParams.borrow(reinterpret_cast<EcGlyphParams *>(a.dev+dParams), (size_t) n);
-    b.work.bucket.borrow(reinterpret_cast<int *>(a.dev+hBucketOff), (size_t) n), b.work.hBucket.borrow(reinterpret_cast<int *>(a.pinned+hBucketOff), (size_t) n);
-    if (gresNeed)
-        b.work.gres.borrow(reinterpret_cast<double *>(a.dev+dGresOff), gresNeed/sizeof(double));
+    b.nGlyphs = n, b.nContours = (int) p.sumC, b.nEdges = (int) p.sumE;
+    b.dGlyphContourOffsets = reinterpret_cast<int32_t *>(a.dev+p.hGco);
+    b.dContourOffsets = reinterpret_cast<int32_t *>(a.dev+p.hCo);
+    b.dPoints = reinterpret_cast<double *>(a.dev+p.hPts);
+    b.dTypes = reinterpret_cast<uint8_t *>(a.dev+p.hTypes);
+    b.dColors = reinterpret_cast<uint8_t *>(a.dev+p.hColors);
+    b.dRecs = reinterpret_cast<EdgeRec *>(a.dev+p.dRecs);
+    b.dWindings = reinterpret_cast<int8_t *>(a.dev+p.dWind);
+    if (p.correct)
+        b.work.deferred.borrow(reinterpret_cast<EcCandidate *>(a.dev+p.dCands), p.candCap);
+    b.work.ecParams.borrow(reinterpret_cast<EcGlyphParams *>(a.dev+p.dParams), (size_t) n);
+    b.work.bucket.borrow(reinterpret_cast<int *>(a.dev+p.hBucket), (size_t) n), b.work.hBucket.borrow(reinterpret_cast<int *>(a.pinned+p.hBucket), (size_t) n);
+    if (p.gresNeed)
+        b.work.gres.borrow(reinterpret_cast<double *>(a.dev+p.dGres), p.gresNeed/sizeof(double));
     b.hContours.resize((size_t) n);
     b.hEdges.resize((size_t) n);
     for (int g = 0; g < n; ++g) {
@@ -3504,187 +3369,242 @@ static int runGroup(ShapeCall *const *calls, int n) {
         b.hEdges[g] = calls[g]->co[calls[g]->nC];
     }
     b.countMaxima();
-    const MsdfHipGlyph *dGlyph = reinterpret_cast<const MsdfHipGlyph *>(a.dev+hGlyph);
-    float *dOut = reinterpret_cast<float *>(a.dev+hOut);
-    uint8_t *dStencil = anyStencil ? reinterpret_cast<uint8_t *>(a.dev+hStencil) : NULL;
-    unsigned *overflowOut = reinterpret_cast<unsigned *>(a.dev+hStatus);   // where k_ec_query mirrors the candidate-overflow count (NULL: rerun with the overflow pass)
+}
 
-    // ---- one launch for the whole call (msdf_single.hpp) where it applies: ONE shape, a generate*() call without the scanline pass, a bitmap of
-    // at most 256 tiles, lists / correction scratch within 64 KB of LDS. A candidate overflow (pathological inputs) reruns the batched sequence below.
-    bool fusedDone = false;
-    if (fusedOK) {
-        {
-            // Zero copy where the staging area is mapped into the device: the kernel reads the staged CSR arrays straight from pinned host memory
-            // (phase 0) and writes the result tile and its status words there -- no upload launch in front, no copy behind, and the host learns of
-            // the end by polling a word the last workgroup writes instead of a stream synchronisation. With a stencil (rare) the results take
-            // the device buffers and one copy, as the batched path does.
-            char *in = zeroCopy ? a.pinnedDev : a.dev;           // (a.dev already holds the inputs: uploaded above)
-            SingleArgs sa;
-            sa.srcContourOffsets = reinterpret_cast<const int32_t *>(in+hCo), sa.points = reinterpret_cast<const double *>(in+hPts);
-            sa.types = reinterpret_cast<const uint8_t *>(in+hTypes), sa.colors = reinterpret_cast<const uint8_t *>(in+hColors);
-            sa.srcGlyph = reinterpret_cast<const MsdfHipGlyph *>(in+hGlyph);
-            sa.priv = a.dev+dPriv, sa.privStride = pvStride, sa.privWindings = pvWind, sa.privOffsets = pvOff, sa.privGlyphOffsets = pvGco, sa.privGlyph = pvGlyph;
-            sa.nContours = (int) sumC, sa.nEdges = (int) sumE;
-            {   // small shapes inside the kernel arguments (msdf_single.hpp)
-                Carver pc;
-                const size_t pCo = pc.take((sumC+1)*sizeof(int32_t)), pPts = pc.take(sumE*8*sizeof(double)), pTypes = pc.take(sumE), pColors = pc.take(sumE);
-                const size_t pGlyph = pc.take(sizeof(MsdfHipGlyph));
-                sa.payloadBytes = 0;
-                if (pc.off <= sizeof(sa.payload) && !tuning().noArgPayloadSingle) {
-                    sa.payloadBytes = (unsigned) pc.off, sa.payOffsets = (unsigned) pCo, sa.payPoints = (unsigned) pPts, sa.payTypes = (unsigned) pTypes;
-                    sa.payColors = (unsigned) pColors, sa.payGlyph = (unsigned) pGlyph;
-                    memcpy(sa.payload+pCo, a.pinned+hCo, (sumC+1)*sizeof(int32_t));
-                    memcpy(sa.payload+pPts, a.pinned+hPts, sumE*8*sizeof(double));
-                    memcpy(sa.payload+pTypes, a.pinned+hTypes, sumE);
-                    memcpy(sa.payload+pColors, a.pinned+hColors, sumE);
-                    memcpy(sa.payload+pGlyph, a.pinned+hGlyph, sizeof(MsdfHipGlyph));
-                }
-            }
-            sa.width = w, sa.height = h, sa.tilesX = (w+TILE-1)/TILE, sa.tiles = (int) tilesAll, sa.listStride = maxE;
-            sa.scratch = correct ? reinterpret_cast<float *>(a.dev+dScratch) : NULL;
-            sa.out = zeroCopy ? reinterpret_cast<float *>(a.pinnedDev+hOut) : dOut, sa.stencil = dStencil;
-            sa.gres = overlapEff && !resInLds ? reinterpret_cast<double *>(a.dev+dGresOff) : NULL, sa.gresStride = resBytes/sizeof(double);
-            // candidates: a counter and a segment of SINGLE_TILE_SEGMENT records per TILE (the tile's workgroup judges them itself), then the corner list
-            sa.cfg = *cfg, sa.correct = correct ? 1 : 0, sa.ecParams = b.work.ecParams.ptr, sa.cands = b.work.deferred.ptr, sa.seg = SINGLE_TILE_SEGMENT;
-            sa.corners = correct ? reinterpret_cast<int *>(b.work.deferred.ptr+ecHeaderRecords((int) tilesAll)+tilesAll*SINGLE_TILE_SEGMENT) : NULL;
-            sa.sizes = NULL;
-            sa.slotCap = slotCap, sa.slotOffset = slotOffset;
-            sa.teamXchgOffset = (unsigned) teamXchgOffset;
-            const unsigned groups = (unsigned) tilesAll+(correct ? 1u : 0u);
-            sa.barrier = a.barrier, sa.barrierBase = a.barrierEpoch, sa.doneBase = a.doneCount;
-            sa.doneValue = a.doneEpoch+1u ? a.doneEpoch+1u : 1u;
-            {   // ~70 ns per iteration: 2-3 ms for a font glyph, growing with the edges a tile may have to walk, at most the old 0.3 s
-                const unsigned long long limit = (1ull<<15)+((unsigned long long) sumE<<8);
-                sa.spinLimit = tuning().singleSpinLimit ? (unsigned) tuning().singleSpinLimit : (unsigned) (limit < (1ull<<22) ? limit : (1ull<<22));
-            }
-            // Leaves the counters as a fresh arena has them (after a failed or abandoned launch the values on the device no longer match the epochs kept here).
-            auto resetCounters = [&a, &lease]() -> int {
-                lease.quiescent = false;
-                HIPCHK(hipStreamSynchronize(a.stream));
-                HIPCHK(hipMemsetAsync(a.barrier, 0, 256, a.stream));
-                a.barrierEpoch = a.doneCount = 0;
-                return MSDFHIP_OK;
-            };
-            volatile unsigned *hostStatus = reinterpret_cast<volatile unsigned *>(a.pinned+hStatus);
-            sa.status = reinterpret_cast<unsigned *>(zeroCopy ? a.pinnedDev+hStatus : a.dev+hStatus);
-            if (zeroCopy)
-                hostStatus[0] = hostStatus[1] = hostStatus[2] = 0;   // overflow / barrier flags are only ever RAISED by the kernel; [2]: the staging area is recycled, whatever sits there is not this call's flag
+// The status words and the results (with the stencils only where one is wanted) -> pinned staging, and the end of everything queued on the arena's stream.
+static int copyBackAndWait(const GroupPlan &p, ThreadArena &a) {
+    HIPCHK(hipMemcpyAsync(a.pinned+p.hStatus, a.dev+p.hStatus, 256+(p.anyStencil ? p.resultBytes : p.n*p.tileBytes), hipMemcpyDeviceToHost, a.stream));
+    HIPCHK(waitStream(a.stream));
+    return MSDFHIP_OK;
+}
+
+// k_single_call's arguments. Zero copy: the kernel reads the staged CSR arrays straight from pinned host memory (phase 0) and writes the result tile and
+// its status words there; else a.dev holds the inputs already.
+static void fillSingleArgs(SingleArgs &sa, const GroupPlan &p, const SinglePlan &single, ThreadArena &a, const MsdfHipBatch &b, const ShapeCall &c, bool overlapEff, bool zeroCopy) {
+    const size_t sumC = p.sumC, sumE = p.sumE;
+    char *in = zeroCopy ? a.pinnedDev : a.dev;
+    sa.srcContourOffsets = reinterpret_cast<const int32_t *>(in+p.hCo), sa.points = reinterpret_cast<const double *>(in+p.hPts);
+    sa.types = reinterpret_cast<const uint8_t *>(in+p.hTypes), sa.colors = reinterpret_cast<const uint8_t *>(in+p.hColors);
+    sa.srcGlyph = reinterpret_cast<const MsdfHipGlyph *>(in+p.hGlyph);
+    sa.priv = a.dev+p.dPriv, sa.privStride = p.pvStride, sa.privWindings = p.pvWind, sa.privOffsets = p.pvOff, sa.privGlyphOffsets = p.pvGco, sa.privGlyph = p.pvGlyph;
+    sa.nContours = (int) sumC, sa.nEdges = (int) sumE;
+    {   // small shapes inside the kernel arguments (msdf_single.hpp)
+        Carver pc;
+        const size_t pCo = pc.take((sumC+1)*sizeof(int32_t)), pPts = pc.take(sumE*8*sizeof(double)), pTypes = pc.take(sumE), pColors = pc.take(sumE);
+        const size_t pGlyph = pc.take(sizeof(MsdfHipGlyph));
+        sa.payloadBytes = 0;
+        if (pc.off <= sizeof(sa.payload) && !tuning().noArgPayloadSingle) {
+            sa.payloadBytes = (unsigned) pc.off, sa.payOffsets = (unsigned) pCo, sa.payPoints = (unsigned) pPts, sa.payTypes = (unsigned) pTypes;
+            sa.payColors = (unsigned) pColors, sa.payGlyph = (unsigned) pGlyph;
+            memcpy(sa.payload+pCo, a.pinned+p.hCo, (sumC+1)*sizeof(int32_t));
+            memcpy(sa.payload+pPts, a.pinned+p.hPts, sumE*8*sizeof(double));
+            memcpy(sa.payload+pTypes, a.pinned+p.hTypes, sumE);
+            memcpy(sa.payload+pColors, a.pinned+p.hColors, sumE);
+            memcpy(sa.payload+pGlyph, a.pinned+p.hGlyph, sizeof(MsdfHipGlyph));
+        }
+    }
+    sa.width = c.w, sa.height = c.h, sa.tilesX = (c.w+TILE-1)/TILE, sa.tiles = (int) p.tilesAll, sa.listStride = p.maxE;
+    sa.scratch = p.correct ? reinterpret_cast<float *>(a.dev+p.dScratch) : NULL;
+    sa.out = reinterpret_cast<float *>((zeroCopy ? a.pinnedDev : a.dev)+p.hOut);
+    sa.stencil = p.anyStencil ? reinterpret_cast<uint8_t *>(a.dev+p.hStencil) : NULL;
+    sa.gres = overlapEff && !single.resInLds ? reinterpret_cast<double *>(a.dev+p.dGres) : NULL, sa.gresStride = single.resBytes/sizeof(double);
+    // candidates: a counter and a segment of SINGLE_TILE_SEGMENT records per TILE (the tile's workgroup judges them itself), then the corner list
+    sa.cfg = c.cfg, sa.correct = p.correct ? 1 : 0, sa.ecParams = b.work.ecParams.ptr, sa.cands = b.work.deferred.ptr, sa.seg = SINGLE_TILE_SEGMENT;
+    sa.corners = p.correct ? reinterpret_cast<int *>(b.work.deferred.ptr+ecHeaderRecords((int) p.tilesAll)+p.tilesAll*SINGLE_TILE_SEGMENT) : NULL;
+    sa.sizes = NULL;
+    sa.slotCap = single.slotCap, sa.slotOffset = single.slotOffset;
+    sa.teamXchgOffset = (unsigned) single.teamXchgOffset;
+    sa.barrier = a.barrier, sa.barrierBase = a.barrierEpoch, sa.doneBase = a.doneCount;
+    sa.doneValue = a.doneEpoch+1u ? a.doneEpoch+1u : 1u;
+    {   // ~70 ns per iteration: 2-3 ms for a font glyph, growing with the edges a tile may have to walk, at most the old 0.3 s
+        const unsigned long long limit = (1ull<<15)+((unsigned long long) sumE<<8);
+        sa.spinLimit = tuning().singleSpinLimit ? (unsigned) tuning().singleSpinLimit : (unsigned) (limit < (1ull<<22) ? limit : (1ull<<22));
+    }
+    sa.status = reinterpret_cast<unsigned *>((zeroCopy ? a.pinnedDev : a.dev)+p.hStatus);
+}
+
+// ---- one launch for the whole call (msdf_single.hpp) where it applies: ONE shape, a generate*() call without the scanline pass, a bitmap of
+// at most 256 tiles, lists / correction scratch within 64 KB of LDS. FUSED_RERUN: the launch did not do its job -- it gave up at its grid barrier, ended
+// without its flag, or a tile's candidates overflowed their segment (pathological inputs) -- and the caller runs the batched sequence; the inputs are on
+// the device for it, and the arena's counters are as a fresh arena has them.
+// Zero copy where the staging area is mapped into the device: no upload launch in front, no copy behind, and the host learns of the end by polling a
+// word the last workgroup writes instead of a stream synchronisation. With a stencil (rare) the results take the device buffers and one copy, as the
+// batched path does.
+enum FusedOutcome { FUSED_DONE, FUSED_RERUN };
+static int runFused(const GroupPlan &p, const SinglePlan &single, ThreadArena &a, ArenaLease &lease, const MsdfHipBatch &b, FusedReservation &fusedSlots, const ShapeCall &c,
+                    bool overlapEff, bool zeroCopy, FusedOutcome &outcome) {
+    outcome = FUSED_RERUN;
+    SingleArgs sa;
+    fillSingleArgs(sa, p, single, a, b, c, overlapEff, zeroCopy);
+    const unsigned groups = (unsigned) p.tilesAll+(p.correct ? 1u : 0u);
+    volatile unsigned *hostStatus = reinterpret_cast<volatile unsigned *>(a.pinned+p.hStatus);
+    if (zeroCopy)
+        hostStatus[0] = hostStatus[1] = hostStatus[2] = 0;       // overflow / barrier flags are only ever RAISED by the kernel; [2]: the staging area is recycled, whatever sits there is not this call's flag
+    else
+        HIPCHK(hipMemsetAsync(a.dev+p.hStatus, 0, 64, a.stream));
+    forSingleCallVariant(c.mode*2+(overlapEff ? 1 : 0), [&](auto sel, auto overlap) {
+        hipLaunchKernelGGL((k_single_call<decltype(sel)::value, decltype(overlap)::value>), dim3(groups), dim3(WAVE*SINGLE_TEAM), single.lds, a.stream, sa);
+    });
+    {
+        const hipError_t launched = hipGetLastError();
+        if (launched != hipSuccess)                              // nothing ran: the counters and the epochs kept here still agree
+            return fail(MSDFHIP_ERR_HIP, "k_single_call launch failed: %s", hipGetErrorString(launched));
+    }
+    a.barrierEpoch += (p.correct ? 1u : 0u)*groups, a.doneCount += groups;   // what this launch adds to the two counters
+    a.doneEpoch = sa.doneValue;
+    bool abandoned = false;                                      // the launch did not do its job: rerun through the batched sequence, from fresh counters
+    if (zeroCopy) {
+        // Polls the completion word: pause between looks (the sibling hyperthread keeps its core), and once a call has outlasted the common
+        // case give the core away between looks -- 64 waiting leaders must not starve the threads that stage the next calls.
+        const long long deadline = nowNs()+2000000;              // 2 ms of polling, then the runtime's own wait (a failed launch never raises the flag)
+        for (unsigned looks = 0; hostStatus[2] != sa.doneValue && nowNs() < deadline; ++looks) {
+            if (looks < 4096)
+                __builtin_ia32_pause();
             else
-                HIPCHK(hipMemsetAsync(a.dev+hStatus, 0, 64, a.stream));
-            switch (mode*2+(overlapEff ? 1 : 0)) {
-                case 2: hipLaunchKernelGGL((k_single_call<1, false>), dim3(groups), dim3(WAVE*SINGLE_TEAM), lds, a.stream, sa); break;
-                case 3: hipLaunchKernelGGL((k_single_call<1, true>), dim3(groups), dim3(WAVE*SINGLE_TEAM), lds, a.stream, sa); break;
-                case 4: hipLaunchKernelGGL((k_single_call<2, false>), dim3(groups), dim3(WAVE*SINGLE_TEAM), lds, a.stream, sa); break;
-                case 5: hipLaunchKernelGGL((k_single_call<2, true>), dim3(groups), dim3(WAVE*SINGLE_TEAM), lds, a.stream, sa); break;
-                case 6: hipLaunchKernelGGL((k_single_call<3, false>), dim3(groups), dim3(WAVE*SINGLE_TEAM), lds, a.stream, sa); break;
-                case 7: hipLaunchKernelGGL((k_single_call<3, true>), dim3(groups), dim3(WAVE*SINGLE_TEAM), lds, a.stream, sa); break;
-                case 8: hipLaunchKernelGGL((k_single_call<4, false>), dim3(groups), dim3(WAVE*SINGLE_TEAM), lds, a.stream, sa); break;
-                default: hipLaunchKernelGGL((k_single_call<4, true>), dim3(groups), dim3(WAVE*SINGLE_TEAM), lds, a.stream, sa); break;
-            }
-            {
-                const hipError_t launched = hipGetLastError();
-                if (launched != hipSuccess)                      // nothing ran: the counters and the epochs kept here still agree
-                    return fail(MSDFHIP_ERR_HIP, "k_single_call launch failed: %s", hipGetErrorString(launched));
-            }
-            a.barrierEpoch += (correct ? 1u : 0u)*groups, a.doneCount += groups;   // what this launch adds to the two counters
-            a.doneEpoch = sa.doneValue;
-            bool abandoned = false;                              // the launch did not do its job: rerun through the batched sequence, from fresh counters
-            if (zeroCopy) {
-                // Polls the completion word: pause between looks (the sibling hyperthread keeps its core), and once a call has outlasted the common
-                // case give the core away between looks -- 64 waiting leaders must not starve the threads that stage the next calls.
-                const long long deadline = nowNs()+2000000;      // 2 ms of polling, then the runtime's own wait (a failed launch never raises the flag)
-                for (unsigned looks = 0; hostStatus[2] != sa.doneValue && nowNs() < deadline; ++looks) {
-                    if (looks < 4096)
-                        __builtin_ia32_pause();
-                    else
-                        sched_yield();
-                }
-                if (hostStatus[2] != sa.doneValue) {
-                    HIPCHK(hipStreamSynchronize(a.stream));
-                    if (hostStatus[2] != sa.doneValue) {
-                        unsigned counters[32] = { 0 };
-                        (void) hipMemcpy(counters, a.barrier, sizeof(counters), hipMemcpyDeviceToHost);
-                        gSingleLost += 1;
-                        if (tuning().singleVerbose)
-                            fprintf(stderr, "msdfgen_hip: k_single_call ended without raising its completion flag (flag %u, expected %u; status %u %u; finished-workgroup "
-                                    "counter %u, expected %u + %u; barrier counter %u, base %u): rerunning the call through the batched sequence\n", (unsigned) hostStatus[2],
-                                    sa.doneValue, (unsigned) hostStatus[0], (unsigned) hostStatus[1], counters[16], sa.doneBase, groups, counters[0], sa.barrierBase);
-                        abandoned = true;
-                    }
-                }
-                std::atomic_thread_fence(std::memory_order_acquire);
-                lease.quiescent = !abandoned;
-            } else {
-                HIPCHK(hipMemcpyAsync(a.pinned+hStatus, a.dev+hStatus, 256+(anyStencil ? resultBytes : n*tileBytes), hipMemcpyDeviceToHost, a.stream));
-                HIPCHK(waitStream(a.stream));
-            }
-            if (hostStatus[1] != 0) {                            // workgroups gave up at the grid barrier (the launch was not resident as a whole)
-                gSingleTimeouts += 1;
+                sched_yield();
+        }
+        if (hostStatus[2] != sa.doneValue) {
+            HIPCHK(hipStreamSynchronize(a.stream));
+            if (hostStatus[2] != sa.doneValue) {
+                unsigned counters[32] = { 0 };
+                (void) hipMemcpy(counters, a.barrier, sizeof(counters), hipMemcpyDeviceToHost);
+                gSingleLost += 1;
+                if (tuning().singleVerbose)
+                    fprintf(stderr, "msdfgen_hip: k_single_call ended without raising its completion flag (flag %u, expected %u; status %u %u; finished-workgroup "
+                            "counter %u, expected %u + %u; barrier counter %u, base %u): rerunning the call through the batched sequence\n", (unsigned) hostStatus[2],
+                            sa.doneValue, (unsigned) hostStatus[0], (unsigned) hostStatus[1], counters[16], sa.doneBase, groups, counters[0], sa.barrierBase);
                 abandoned = true;
             }
-            fusedSlots.release();
-            if (abandoned) {
-                rc = resetCounters();
-                if (rc != MSDFHIP_OK)
-                    return rc;
-            }
-            fusedDone = !abandoned && hostStatus[0] == 0;
-            if (fusedDone && correct && zeroCopy) {              // (all phases ran and the stamps are at hand: the diagnostics count these calls)
-                for (int k = 0; k < 7; ++k)
-                    gSinglePhase[k] += (unsigned long long) hostStatus[8+k];
-                gSinglePhase[7] += (unsigned long long) hostStatus[7];
-                gSingleCycles += (unsigned long long) hostStatus[15];
-                ++gSingleCalls;
-            }
-            if (!fusedDone && zeroCopy)                          // rerun through the batched sequence: it expects the inputs on the device
-                HIPCHK(hipMemcpyAsync(a.dev, a.pinned, inputBytes, hipMemcpyHostToDevice, a.stream));
         }
-    }
-    rc = fusedDone ? MSDFHIP_OK : digest(&b, a.stream);
-    for (int attempt = 0; !fusedDone && rc == MSDFHIP_OK && attempt < 2; ++attempt) {
-        GenerateCall call;
-        call.overflowOut = overflowOut;
-        if (op == OP_ERROR_CORRECTION)
-            rc = runCorrection(&b, channels, w, h, dGlyph, reinterpret_cast<const float *>(a.dev+hSrc), dOut, dStencil, *cfg, a.stream, call);
-        else if (op == OP_SIGN_CORRECTION)
-            rc = runSignCorrection(&b, channels, w, h, dGlyph, reinterpret_cast<const float *>(a.dev+hSrc), dOut, 0, cfg->sdf_zero_value, cfg->fill_rule, a.stream);
-        else if (op == OP_RASTERIZE)
-            rc = runSignCorrection(&b, 1, w, h, dGlyph, NULL, dOut, 0, 0.f, cfg->fill_rule, a.stream);
-        else
-            rc = runGenerate(&b, mode, w, h, dGlyph, dOut, dStencil, stages ? reinterpret_cast<float *>(a.dev+dScratch) : NULL, cfg, a.stream, call);
+        std::atomic_thread_fence(std::memory_order_acquire);
+        lease.quiescent = !abandoned;
+    } else {
+        const int rc = copyBackAndWait(p, a);
         if (rc != MSDFHIP_OK)
-            break;
-        HIPCHK(hipMemcpyAsync(a.pinned+hStatus, a.dev+hStatus, 256+(anyStencil ? resultBytes : n*tileBytes), hipMemcpyDeviceToHost, a.stream));
-        HIPCHK(waitStream(a.stream));
-        if (!(call.overflowMirrored && *reinterpret_cast<const unsigned *>(a.pinned+hStatus) != 0))
-            break;
-        // a glyph's candidate segment overflowed (more than 1/16 of its texels needed a distance check): once more, with the per-texel
-        // overflow pass in the launch sequence. Pathological inputs only.
-        overflowOut = NULL;
-        if (bitmapIsInput)
-            break;                                               // (in-place correction of a caller bitmap: the input copy on the device is intact, rerun below)
+            return rc;
     }
-    if (rc == MSDFHIP_OK && overflowOut == NULL && bitmapIsInput) {
+    if (hostStatus[1] != 0) {                                    // workgroups gave up at the grid barrier (the launch was not resident as a whole)
+        gSingleTimeouts += 1;
+        abandoned = true;
+    }
+    fusedSlots.release();
+    if (abandoned) {                                             // the values on the device no longer match the epochs kept here: leave the counters as a fresh arena has them
+        lease.quiescent = false;
+        HIPCHK(hipStreamSynchronize(a.stream));
+        HIPCHK(hipMemsetAsync(a.barrier, 0, 256, a.stream));
+        a.barrierEpoch = a.doneCount = 0;
+    }
+    if (!abandoned && hostStatus[0] == 0)
+        outcome = FUSED_DONE;
+    if (outcome == FUSED_DONE && p.correct && zeroCopy) {        // (all phases ran and the stamps are at hand: the diagnostics count these calls)
+        for (int k = 0; k < 7; ++k)
+            gSinglePhase[k] += (unsigned long long) hostStatus[8+k];
+        gSinglePhase[7] += (unsigned long long) hostStatus[7];
+        gSingleCycles += (unsigned long long) hostStatus[15];
+        ++gSingleCalls;
+    }
+    if (outcome == FUSED_RERUN && zeroCopy)                      // rerun through the batched sequence: it expects the inputs on the device
+        HIPCHK(hipMemcpyAsync(a.dev, a.pinned, p.inputBytes, hipMemcpyHostToDevice, a.stream));
+    return MSDFHIP_OK;
+}
+
+// The batched launch sequence of the group's operation, results and status words back in the pinned staging. k_ec_query mirrors the candidate-overflow count
+// next to the results instead of a launch of the overflow pass per call; where a glyph's candidate segment did overflow (more than 1/16 of its texels needed
+// a distance check: pathological inputs only) the operation runs once more, with the per-texel overflow pass in its launch sequence -- an in-place correction
+// too: the input copy on the device is intact.
+static int runBatched(const GroupPlan &p, ThreadArena &a, MsdfHipBatch &b, const ShapeCall &c) {
+    const MsdfHipGlyph *dGlyph = reinterpret_cast<const MsdfHipGlyph *>(a.dev+p.hGlyph);
+    const float *dSrc = reinterpret_cast<const float *>(a.dev+p.hSrc);
+    float *dOut = reinterpret_cast<float *>(a.dev+p.hOut);
+    uint8_t *dStencil = p.anyStencil ? reinterpret_cast<uint8_t *>(a.dev+p.hStencil) : NULL;
+    int rc = digest(&b, a.stream);
+    for (int attempt = 0; rc == MSDFHIP_OK && attempt < 2; ++attempt) {   // mirrored, then with the overflow pass
         GenerateCall call;
-        rc = runCorrection(&b, channels, w, h, dGlyph, reinterpret_cast<const float *>(a.dev+hSrc), dOut, dStencil, *cfg, a.stream, call);
-        if (rc == MSDFHIP_OK) {
-            HIPCHK(hipMemcpyAsync(a.pinned+hStatus, a.dev+hStatus, 256+(anyStencil ? resultBytes : n*tileBytes), hipMemcpyDeviceToHost, a.stream));
-            HIPCHK(waitStream(a.stream));
-        }
+        call.overflowOut = attempt == 0 ? reinterpret_cast<unsigned *>(a.dev+p.hStatus) : NULL;
+        if (c.op == OP_ERROR_CORRECTION)
+            rc = runCorrection(&b, c.channels, c.w, c.h, dGlyph, dSrc, dOut, dStencil, c.cfg, a.stream, call);
+        else if (c.op == OP_SIGN_CORRECTION)
+            rc = runSignCorrection(&b, c.channels, c.w, c.h, dGlyph, dSrc, dOut, 0, c.cfg.sdf_zero_value, c.cfg.fill_rule, a.stream);
+        else if (c.op == OP_RASTERIZE)
+            rc = runSignCorrection(&b, 1, c.w, c.h, dGlyph, NULL, dOut, 0, 0.f, c.cfg.fill_rule, a.stream);
+        else
+            rc = runGenerate(&b, c.mode, c.w, c.h, dGlyph, dOut, dStencil, p.stages ? reinterpret_cast<float *>(a.dev+p.dScratch) : NULL, &c.cfg, a.stream, call);
+        if (rc == MSDFHIP_OK)
+            rc = copyBackAndWait(p, a);
+        if (!(call.overflowMirrored && *reinterpret_cast<const unsigned *>(a.pinned+p.hStatus) != 0))
+            break;
     }
+    return rc;
+}
+
+// The tiles in the pinned staging -> the callers' bitmaps (any row stride) and stencils.
+static void scatterGroup(const GroupPlan &p, ThreadArena &a, ShapeCall *const *calls, int n) {
+    const int channels = calls[0]->channels, w = calls[0]->w, h = calls[0]->h;
+    for (int g = 0; g < n; ++g) {
+        const ShapeCall &c = *calls[g];
+        const float *tile = reinterpret_cast<const float *>(a.pinned+p.hOut)+(size_t) g*p.texels*channels;
+        for (int y = 0; y < h; ++y)
+            memcpy(c.pixels+(ptrdiff_t) c.rowStride*y, tile+(size_t) y*w*channels, sizeof(float)*(size_t) w*channels);
+        if (c.stencil && p.anyStencil)
+            memcpy(c.stencil, a.pinned+p.hStencil+(size_t) g*p.texels, p.texels);
+    }
+}
+
+static int runGroup(ShapeCall *const *calls, int n) {
+    const ShapeCall &c0 = *calls[0];
+    const MsdfHipConfig *cfg = &c0.cfg;
+    int rc = ensureDevice(frontDoorDevice());
+    if (rc != MSDFHIP_OK)
+        return rc;
+    const GroupPlan plan = planGroup(calls, n);
+    ArenaLease lease;
+    rc = lease.take(currentDevice());
+    if (rc != MSDFHIP_OK)
+        return rc;
+    ThreadArena &a = *lease.a;
+    rc = arenaReserve(a, plan.devBytes, plan.pinnedBytes);
+    if (rc != MSDFHIP_OK)
+        return rc;
+
+    const long long t0 = nowNs();
+    stageGroup(plan, a, calls, n);
+    const long long t1 = nowNs();
+    // Does the call take ONE launch (k_single_call, msdf_single.hpp)? ONE shape, a generate*() call without the scanline pass, a bitmap of at most
+    // 256 tiles, lists / correction scratch within 64 KB of LDS. Decided before the upload: with the staging area mapped into the device the
+    // kernel reads its inputs from there and nothing is uploaded at all.
+    const bool overlapEff = cfg->overlap_support && plan.maxC > 1;
+    const SinglePlan single = planSingleLaunch(plan.maxC, plan.maxE, c0.channels, overlapEff, plan.correct);
+    bool fused = plan.fusedShape && !tuning().noFusedSingle && !cfg->sign_correction && cfg->ec_stage_limit == 0 &&
+                 single.lds <= (size_t) 64*1024 && (!overlapEff || single.resInLds || plan.gresNeed >= plan.tilesAll*single.resBytes);
+    FusedReservation fusedSlots;                                 // (see fusedCapacity: all workgroups of the launch must be resident together)
+    if (fused) {
+        fused = fusedSlots.take(a.device, c0.mode*2+(overlapEff ? 1 : 0), single.lds, (int) plan.tilesAll+(plan.correct ? 1 : 0));
+        if (!fused)
+            gSingleRefused += 1;
+    }
+    const bool zeroCopy = fused && a.pinnedDev != NULL && !plan.anyStencil && !tuning().noZeroCopySingle;
+    if (zeroCopy) {
+        // (nothing to upload)
+    } else if (plan.inputBytes <= ((size_t) 1<<20)) {            // a few KB: read from the pinned staging by a kernel -- no SDMA submission on the latency path
+        rc = uploadSmall(a.dev, a.pinned, plan.inputBytes, a.stream);
+        if (rc != MSDFHIP_OK)
+            return rc;
+    } else
+        HIPCHK(hipMemcpyAsync(a.dev, a.pinned, plan.inputBytes, hipMemcpyHostToDevice, a.stream));
+
+    MsdfHipBatch b;
+    buildView(plan, a, calls, n, b);
+    FusedOutcome outcome = FUSED_RERUN;
+    if (fused)
+        rc = runFused(plan, single, a, lease, b, fusedSlots, c0, overlapEff, zeroCopy, outcome);
+    if (rc == MSDFHIP_OK && outcome == FUSED_RERUN)
+        rc = runBatched(plan, a, b, c0);
     if (rc != MSDFHIP_OK) {
         hipStreamSynchronize(a.stream);
         return rc;
     }
     const long long t2 = nowNs();
-    for (int g = 0; g < n; ++g) {
-        const ShapeCall &c = *calls[g];
-        const float *tile = reinterpret_cast<const float *>(a.pinned+hOut)+(size_t) g*texels*channels;
-        for (int y = 0; y < h; ++y)
-            memcpy(c.pixels+(ptrdiff_t) c.rowStride*y, tile+(size_t) y*w*channels, sizeof(float)*(size_t) w*channels);
-        if (c.stencil && anyStencil)
-            memcpy(c.stencil, a.pinned+hStencil+(size_t) g*texels, texels);
-    }
+    scatterGroup(plan, a, calls, n);
     gNsStage += t1-t0, gNsDevice += t2-t1, gNsScatter += nowNs()-t2;
     return MSDFHIP_OK;
 }

@@ -28,6 +28,9 @@
 // (digest 8, slowest tile's distance field 33, barrier + slowest sweep 25).
 #pragma once
 
+#include <type_traits>
+
+#include "msdf_classplan.hpp"
 #include "msdf_kernels.hpp"
 
 namespace msdfhip {
@@ -83,7 +86,7 @@ struct SingleArgs {
 static_assert(sizeof(SingleArgs) <= 4096, "kernel arguments are limited to 4 KB");
 
 // The launch is not cooperative: nothing GUARANTEES that its tiles+1 workgroups are resident together. The host only takes this path while the
-// fused launches in flight fit the device (runGroup: fusedCapacity), but a persistent k_distance launch of another thread or process may still hold
+// fused launches in flight fit the device (msdf_capi.hip: fusedCapacity), but a persistent k_distance launch of another thread or process may still hold
 // the slots. The spin is therefore bounded (spinLimit, scaled by the host with the shape's size: ~2 ms for a font glyph, at most ~0.3 s): a workgroup that
 // gives up raises status[1], the rest of the launch drains, and the host reruns the call through the batched sequence -- generate*() never fails for it.
 // Returns false (wave-uniform) when this workgroup gave up: what lies behind the barrier is then NOT complete -- the caller must skip its next phase (the
@@ -302,6 +305,65 @@ k_single_call(SingleArgs a) {
             __hip_atomic_store(a.status+2, a.doneValue, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
+}
+
+// ---- host side: the launch's dynamic LDS, as the phases above use it (all regions start at smemSingle; the phases follow each other, so the need is their
+// maximum), and the kernel's eight instantiations.
+//   digest    contour offsets [C+1] as int32 + the 64 shoelace terms of the windings
+//   distance  k_distance's one-tile-per-wavefront map: the survivor lists (tileListBytes), behind the combiner scratch where that fits (resInLds; else a.gres)
+//   sweep     k_ec_fast's map (ecFastLdsBytes), then the cooperative distance checks: per-contour results [slotOffset doubles], slots [slotCap], merged slots
+//   team      the exchange areas of a tile's helpers (TeamExchange) behind all of it, at teamXchgOffset
+struct SinglePlan {
+    int slotCap, slotOffset;          // SingleArgs::slotCap / slotOffset
+    size_t resBytes;                  // the overlapping combiner's scratch per tile
+    bool resInLds;                    // ... lives in LDS (else in the global workspace, SingleArgs::gres)
+    size_t lds, teamXchgOffset;       // dynamic LDS of the launch (at most 64 KB where the launch is possible); SingleArgs::teamXchgOffset
+};
+inline SinglePlan planSingleLaunch(int maxC, int maxE, int channels, bool overlapEff, bool correct) {
+    SinglePlan s;
+    const int slotCapWanted = maxE > 0 ? (maxE < 1024 ? maxE : 1024) : 1;
+    s.slotOffset = overlapEff ? (maxC > 0 ? maxC : 1) : 0;
+    s.slotCap = slotCapWanted;
+    size_t queryLds = (size_t) s.slotOffset*sizeof(double)+((size_t) s.slotCap+(size_t) (maxC < s.slotCap ? (maxC > 0 ? maxC : 1) : s.slotCap))*sizeof(PBSlot);
+    if (queryLds > (size_t) 48*1024) {                           // too many edges for the slots: per-contour lane merges instead (EdgesCooperative)
+        s.slotCap = 1;
+        queryLds = (size_t) s.slotOffset*sizeof(double)+2*sizeof(PBSlot);
+    }
+    s.resBytes = overlapEff ? (size_t) maxC*channels*WAVE*sizeof(double) : 0;
+    const size_t resLdsForm = s.resBytes+tileListBytes(maxE, maxC, false);    // combiner scratch in LDS (k_distance's LDS form with one tile per wavefront)
+    s.resInLds = overlapEff && resLdsForm <= (size_t) 60*1024;
+    const size_t listLds = s.resInLds ? resLdsForm : tileListBytes(maxE, maxC, true);
+    size_t lds = listLds;
+    {
+        const size_t digestLds = (((size_t) maxC+3)/2+WAVE)*sizeof(double);   // the digest phase: contour offsets + the 64 shoelace terms of the windings
+        lds = lds > digestLds ? lds : digestLds;
+    }
+    if (correct) {
+        lds = lds > ecFastLdsBytes(maxE, channels) ? lds : ecFastLdsBytes(maxE, channels);
+        lds = lds > queryLds ? lds : queryLds;
+    }
+    // the exchange areas of a tile's team of wavefronts (msdf_kernels.hpp: TeamExchange) behind everything the phases use
+    s.teamXchgOffset = (lds+15)/16*16;
+    if (SINGLE_TEAM > 1)
+        lds = s.teamXchgOffset+(size_t) (SINGLE_TEAM-1)*TEAM_XCHG_DOUBLES*WAVE*sizeof(double);
+    s.lds = lds;
+    return s;
+}
+
+// variant = mode*2 + overlap (2..9): calls fn(integral_constant<int, SEL>, bool_constant<OVERLAP>) for k_single_call<SEL, OVERLAP>; false: no such variant.
+template <class F>
+inline bool forSingleCallVariant(int variant, F &&fn) {
+    switch (variant) {
+        case 2: fn(std::integral_constant<int, 1>(), std::false_type()); return true;
+        case 3: fn(std::integral_constant<int, 1>(), std::true_type()); return true;
+        case 4: fn(std::integral_constant<int, 2>(), std::false_type()); return true;
+        case 5: fn(std::integral_constant<int, 2>(), std::true_type()); return true;
+        case 6: fn(std::integral_constant<int, 3>(), std::false_type()); return true;
+        case 7: fn(std::integral_constant<int, 3>(), std::true_type()); return true;
+        case 8: fn(std::integral_constant<int, 4>(), std::false_type()); return true;
+        case 9: fn(std::integral_constant<int, 4>(), std::true_type()); return true;
+    }
+    return false;
 }
 
 } // namespace msdfhip

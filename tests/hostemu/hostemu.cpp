@@ -18,6 +18,7 @@
 #include "../../msdfgen_amd/csrc/msdf_scanline.hpp"
 #include "../../msdfgen_amd/csrc/msdf_shapeprep.hpp"
 #include "../../msdfgen_amd/csrc/msdf_classplan.hpp"
+#include "../../msdfgen_amd/csrc/msdf_hostplan.hpp"
 
 using namespace msdfhip;
 
@@ -888,3 +889,31 @@ extern "C" void emu_class_plan(const int *contours, const int *edges, int n, int
     memcpy(counts, c, sizeof(c));
     *restShare = p.restShare;
 }
+
+// msdf_hostplan.hpp: the planning of the host-output pipeline (msdf_capi.hip: runPipelineOnce) and of msdfhip_generate_sharded.
+extern "C" int emu_default_chunk(long tileFloats) { return defaultChunk((size_t) tileFloats); }
+extern "C" int emu_chunk_schedule(int nGlyphs, int chunk, int floatOutput, int *lengths, int cap) {   // returns the number of pieces (the first `cap` are written)
+    const std::vector<int> l = chunkSchedule(nGlyphs, chunk, floatOutput != 0);
+    for (size_t i = 0; i < l.size() && i < (size_t) cap; ++i)
+        lengths[i] = l[i];
+    return (int) l.size();
+}
+extern "C" void emu_rect_span(const MsdfHipGlyph *glyph, int w, int h, int N, long long *lohi) {
+    const RectSpan r = rectSpan(*glyph, w, h, N);
+    lohi[0] = r.lo, lohi[1] = r.hi;
+}
+extern "C" int emu_chunk_span(const MsdfHipGlyph *glyphs, int n, int w, int h, int N, long long *spanLo) {   // returns dense
+    const ChunkSpan s = chunkSpan(glyphs, n, w, h, N);
+    *spanLo = s.spanLo;
+    return s.dense ? 1 : 0;
+}
+extern "C" void emu_slot_layout(int chunk, long tileFloats, long texels, int wantStencil, int bytesOutput, long long *out5) {
+    const SlotLayout l = slotLayout(chunk, (size_t) tileFloats, (size_t) texels, wantStencil != 0, bytesOutput != 0);
+    out5[0] = (long long) l.offGlyphs, out5[1] = (long long) l.offTiles, out5[2] = (long long) l.offStencil, out5[3] = (long long) l.offBytes, out5[4] = (long long) l.devBytes;
+}
+extern "C" void emu_shard_ranges(const int32_t *gco, const int32_t *co, int nGlyphs, int parts, int *bounds) {   // bounds[parts+1]
+    std::vector<int> b;
+    shardRanges(gco, co, nGlyphs, parts, b);
+    memcpy(bounds, b.data(), sizeof(int)*b.size());
+}
+extern "C" double emu_glyph_cost(int contours, int edges) { return glyphCost(contours, edges); }

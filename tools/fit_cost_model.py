@@ -1,4 +1,4 @@
-"""Fits the per-glyph cost model the sharding uses (msdfgen_amd.shard.glyph_costs, msdf_capi.hip: shardRanges) to MEASURED kernel times
+"""Fits the per-glyph cost model the sharding uses (msdfgen_amd.shard.glyph_costs, msdf_hostplan.hpp: shardRanges) to MEASURED kernel times
 on one MI355X (VERDICT r2 next #5b), and checks the split it produces.
 
 The 8 192 distinct DejaVu glyphs are binned by (contours, edges); every bin is rendered on its own (msdf 64x64, library-default config =

@@ -1,4 +1,4 @@
-"""The chunk schedules of the host-output pipeline at list lengths and tile sizes other than the bench's (msdf_capi.hip: runPipelineOnce, `lengths`): the streamed
+"""The chunk schedules of the host-output pipeline at list lengths and tile sizes other than the bench's (msdf_hostplan.hpp: chunkSchedule): the streamed
 generator (float tiles and the 8-bit atlas) against the device batch, for 3 000 / 5 000 / 9 000 / 20 000 glyphs at 32x32 and 64x64 -- bytes must be identical."""
 import os
 import sys
