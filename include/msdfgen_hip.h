@@ -330,6 +330,38 @@ int msdfhip_generate_stream_csr_prepared_oriented(int device, int mode, int widt
                                                   const MsdfHipGlyph *glyphs, float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes,
                                                   uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep, const uint64_t *seeds,
                                                   const MsdfHipOrientConfig *orient);
+/* Framing on the device: Shape::getBounds (core/Shape.cpp:104-115, without border / miters) and what the reference CLI's -autoframe makes of it
+ * (main.cpp:1153-1183), per glyph, so that a caller hands over outlines and ONE tile size instead of a transformation per glyph.
+ *   range_mode / range_lower / range_upper   the CLI's -range / -arange (0: in shape units) or -pxrange / -apxrange (1: in pixels of the tile)
+ *   scale_specified                          0: the glyph is fitted into width x height (less the pixel range); 1: centred at scale_x / scale_y (-scale)
+ * A glyph whose bounds are empty (l >= r or b >= t: no edges, a single vertical or horizontal line) is framed as the unit box, like the CLI.
+ * The bounds are those of the NORMALIZED shape, before any colouring (main.cpp:1125-1132): batches made by msdfhip_batch_create_prepared[_oriented] took
+ * them at that point; batches made from arrays that are prepared already take them from those arrays.
+ * A frame that cannot fit ("Cannot fit the specified pixel range", main.cpp:1164: width or height + 2*range_lower <= 0 for a pixel range without a given
+ * scale), a range_mode outside 0..1, range_lower == range_upper and scale_specified with a zero scale fail with MSDFHIP_ERR_INVALID before anything is read
+ * or the device is touched. */
+typedef struct MsdfHipFrameConfig {
+    int32_t range_mode;        /* 0 unit range (-range / -arange), 1 pixel range (-pxrange / -apxrange) */
+    int32_t scale_specified;   /* 0: fit the glyph (autoframe picks scale); 1: centre it at scale_x / scale_y */
+    double range_lower, range_upper;
+    double scale_x, scale_y;
+} MsdfHipFrameConfig;
+/* Shape::getBounds of every glyph of the batch: host double[n_glyphs*4] = l, b, r, t (an empty glyph: 1e240, 1e240, -1e240, -1e240). Synchronous. */
+int msdfhip_batch_bounds(const MsdfHipBatch *batch, double *bounds);
+/* Writes xf[0..5] of d_glyphs[g] (device, MsdfHipGlyph[n_glyphs]) for a width x height tile; out_offset, row_stride and flip stay as the caller set them.
+ * Asynchronous on `stream`; msdfhip_batch_generate with the same d_glyphs on that stream follows without a host round trip. */
+int msdfhip_batch_frame(const MsdfHipBatch *batch, const MsdfHipFrameConfig *frame, int width, int height, MsdfHipGlyph *d_glyphs, void *stream);
+/* The streamed generators over raw outlines with framing: with `frame` the xf of the host glyphs[] are ignored and every chunk is framed on its own stream
+ * between its preparation and its digest; frame == NULL is the twin above. Same bytes as the twin given the xf that msdfhip_batch_frame writes. */
+int msdfhip_generate_stream_prepared_oriented_framed(int device, int mode, int width, int height, int n_glyphs, const MsdfHipShapeSource *source,
+                                                     const MsdfHipGlyph *glyphs, float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes,
+                                                     uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep, const uint64_t *seeds,
+                                                     const MsdfHipOrientConfig *orient, const MsdfHipFrameConfig *frame);
+int msdfhip_generate_stream_csr_prepared_oriented_framed(int device, int mode, int width, int height, int n_glyphs, const int32_t *glyph_contour_offsets,
+                                                         const int32_t *contour_offsets, const double *points, const uint8_t *types, const uint8_t *colors,
+                                                         const MsdfHipGlyph *glyphs, float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes,
+                                                         uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep, const uint64_t *seeds,
+                                                         const MsdfHipOrientConfig *orient, const MsdfHipFrameConfig *frame);
 /* Diagnostics: after an error-correction pass, counts[0] = 1 if some glyph's candidate segment overflowed (those glyphs were redone by
  * the full per-texel pipeline), counts[1+g] = deferred distance checks pushed for glyph g. counts holds n_glyphs+1 entries. */
 int msdfhip_batch_candidate_counts(const MsdfHipBatch *batch, uint32_t *counts);

@@ -19,6 +19,17 @@
 
 namespace msdfgen_hip {
 
+/// Framing on the device, per glyph, as the reference CLI's -autoframe does it (main.cpp:1153-1183) from Shape::getBounds of the shape as it is handed over
+/// (normalized by the caller, like every shape the generators take): every section of width x height gets the transformation the CLI would have computed.
+struct FrameConfig {
+    enum RangeMode { RANGE_UNIT, RANGE_PX } rangeMode;   ///< -range / -arange (shape units) or -pxrange / -apxrange (pixels of the section)
+    msdfgen::Range range;
+    bool scaleSpecified;                                 ///< false: fit every glyph into its section; true: centre it at `scale` (-scale)
+    msdfgen::Vector2 scale;
+    explicit FrameConfig(msdfgen::Range pxRange = msdfgen::Range(2), RangeMode mode = RANGE_PX) : rangeMode(mode), range(pxRange), scaleSpecified(false), scale(1) { }
+    FrameConfig(msdfgen::Range r, RangeMode mode, msdfgen::Vector2 givenScale) : rangeMode(mode), range(r), scaleSpecified(true), scale(givenScale) { }
+};
+
 /// outputs[i] <- generateSDF(shapes[i], transformations[i]); sections of equal size are rendered together, any placement / row stride / orientation per section
 void generateSDFBatch(const msdfgen::BitmapSection<float, 1> *outputs, const msdfgen::Shape *const *shapes, const msdfgen::SDFTransformation *transformations, int count,
                       const msdfgen::GeneratorConfig &config = msdfgen::GeneratorConfig());
@@ -39,6 +50,25 @@ void generatePSDFBatch(const msdfgen::BitmapSection<msdfgen::byte, 1> *outputs, 
 void generateMSDFBatch(const msdfgen::BitmapSection<msdfgen::byte, 3> *outputs, const msdfgen::Shape *const *shapes, const msdfgen::SDFTransformation *transformations, int count,
                        const msdfgen::MSDFGeneratorConfig &config = msdfgen::MSDFGeneratorConfig());
 void generateMTSDFBatch(const msdfgen::BitmapSection<msdfgen::byte, 4> *outputs, const msdfgen::Shape *const *shapes, const msdfgen::SDFTransformation *transformations, int count,
+                        const msdfgen::MSDFGeneratorConfig &config = msdfgen::MSDFGeneratorConfig());
+
+/// The same eight with ONE FrameConfig in place of the transformations: outputs[i] <- generate*(shapes[i], the CLI's -autoframe transformation of shapes[i] for
+/// a section of outputs[i]'s size). An unusable frame ("Cannot fit the specified pixel range", equal range ends, a zero scale) fails like any bad argument.
+void generateSDFBatch(const msdfgen::BitmapSection<float, 1> *outputs, const msdfgen::Shape *const *shapes, const FrameConfig &frame, int count,
+                      const msdfgen::GeneratorConfig &config = msdfgen::GeneratorConfig());
+void generatePSDFBatch(const msdfgen::BitmapSection<float, 1> *outputs, const msdfgen::Shape *const *shapes, const FrameConfig &frame, int count,
+                       const msdfgen::GeneratorConfig &config = msdfgen::GeneratorConfig());
+void generateMSDFBatch(const msdfgen::BitmapSection<float, 3> *outputs, const msdfgen::Shape *const *shapes, const FrameConfig &frame, int count,
+                       const msdfgen::MSDFGeneratorConfig &config = msdfgen::MSDFGeneratorConfig());
+void generateMTSDFBatch(const msdfgen::BitmapSection<float, 4> *outputs, const msdfgen::Shape *const *shapes, const FrameConfig &frame, int count,
+                        const msdfgen::MSDFGeneratorConfig &config = msdfgen::MSDFGeneratorConfig());
+void generateSDFBatch(const msdfgen::BitmapSection<msdfgen::byte, 1> *outputs, const msdfgen::Shape *const *shapes, const FrameConfig &frame, int count,
+                      const msdfgen::GeneratorConfig &config = msdfgen::GeneratorConfig());
+void generatePSDFBatch(const msdfgen::BitmapSection<msdfgen::byte, 1> *outputs, const msdfgen::Shape *const *shapes, const FrameConfig &frame, int count,
+                       const msdfgen::GeneratorConfig &config = msdfgen::GeneratorConfig());
+void generateMSDFBatch(const msdfgen::BitmapSection<msdfgen::byte, 3> *outputs, const msdfgen::Shape *const *shapes, const FrameConfig &frame, int count,
+                       const msdfgen::MSDFGeneratorConfig &config = msdfgen::MSDFGeneratorConfig());
+void generateMTSDFBatch(const msdfgen::BitmapSection<msdfgen::byte, 4> *outputs, const msdfgen::Shape *const *shapes, const FrameConfig &frame, int count,
                         const msdfgen::MSDFGeneratorConfig &config = msdfgen::MSDFGeneratorConfig());
 
 }

@@ -123,6 +123,25 @@ class PrepareConfig:
         return _lib.OrientConfig(int(bool(self.orient_contours)), int(self.winding))
 
 
+class FrameConfig:
+    """Framing on the device (msdfgen_hip.h, MsdfHipFrameConfig): what the reference CLI's -autoframe does per glyph (main.cpp:1153-1183), from
+    Shape::getBounds of the normalized shape. Exactly one of px_range (-pxrange w / -apxrange lower upper) and unit_range (-range / -arange): a width
+    (symmetrical, Range(w) = (-w/2, w/2)) or a (lower, upper) pair. scale: None fits every glyph into the tile; a number or an (x, y) pair centres it at
+    that scale (-scale)."""
+
+    def __init__(self, px_range=None, unit_range=None, scale=None):
+        if (px_range is None) == (unit_range is None):
+            raise ValueError("FrameConfig takes exactly one of px_range and unit_range")
+        r = px_range if px_range is not None else unit_range
+        self.range_mode = 1 if px_range is not None else 0
+        self.range = (-.5*float(r), .5*float(r)) if np.isscalar(r) else (float(r[0]), float(r[1]))     # Range.hpp:14
+        self.scale = None if scale is None else (float(scale), float(scale)) if np.isscalar(scale) else (float(scale[0]), float(scale[1]))
+
+    def c_struct(self) -> _lib.FrameConfig:
+        sx, sy = self.scale if self.scale is not None else (1., 1.)
+        return _lib.FrameConfig(self.range_mode, int(self.scale is not None), self.range[0], self.range[1], sx, sy)
+
+
 def _c_config(config, y_orientation=None) -> _lib.Config:
     """y_orientation: the OUTPUT bitmap's orientation; the reference keeps the stencil's rows upward whatever it is
     (core/MSDFErrorCorrection.cpp:122,192,415), which is what MsdfHipConfig.stencil_y_down tells the device -- set on every path that
@@ -427,14 +446,35 @@ class GlyphBatch:
         _lib.check(_lib.load().msdfhip_batch_windings(self._handle, _lib.ptr(out, _lib._ip)))
         return out[:self.shapes.n_contours]
 
+    def bounds(self):
+        """Shape::getBounds (core/Shape.cpp:104-115) of every glyph as the device computes it: (G, 4) float64 rows l, b, r, t; an empty glyph keeps
+        the reference's (1e240, 1e240, -1e240, -1e240). For from_raw batches: of the normalized shape, before the colouring (main.cpp:1125-1132)."""
+        out = np.zeros((max(self.n_glyphs, 1), 4), np.float64)
+        _lib.check(_lib.load().msdfhip_batch_bounds(self._handle, _lib.ptr(out, _lib._dp)))
+        return out[:self.n_glyphs]
+
+    def frame(self, width, height, frame: "FrameConfig", descriptors=None, stream=None):
+        """The reference CLI's -autoframe per glyph on the device (msdfhip_batch_frame): writes xf of `descriptors` (default: fresh ones for packed
+        tiles) and returns the (G, 6) rows sx, sy, tx, ty, mapScale, mapTranslate it wrote (read back: this synchronizes)."""
+        if descriptors is None:
+            descriptors = self.descriptors(None, width, height, 1)
+        fc = frame.c_struct()
+        s = (stream or self.torch.cuda.current_stream(self.device)).cuda_stream
+        _lib.check(_lib.load().msdfhip_batch_frame(self._handle, C.byref(fc), int(width), int(height), descriptors.data_ptr(), s))
+        if stream is not None:
+            stream.synchronize()
+        d = descriptors.cpu().numpy().reshape(-1).view(_lib.GLYPH_DTYPE)
+        return d["xf"].copy()
+
     def descriptors(self, xfs, width, height, channels, y_orientation=Y_UPWARD, out_offsets=None, row_stride=None):
         """Device array of MsdfHipGlyph for contiguous tiles [g][h][w][N] (or custom atlas placement via out_offsets/row_stride).
-        xfs: (G, 6) rows (sx, sy, tx, ty, range_lower, range_upper)."""
-        xfs = np.ascontiguousarray(xfs, np.float64).reshape(self.n_glyphs, 6)
+        xfs: (G, 6) rows (sx, sy, tx, ty, range_lower, range_upper); None leaves xf zero (for frame() / generate(frame=...) to fill)."""
         d = np.zeros(self.n_glyphs, _lib.GLYPH_DTYPE)
-        d["xf"][:, :4] = xfs[:, :4]
-        d["xf"][:, 4] = np.float64(1)/(xfs[:, 5]-xfs[:, 4])  # DistanceMapping.cpp:13
-        d["xf"][:, 5] = -xfs[:, 4]
+        if xfs is not None:
+            xfs = np.ascontiguousarray(xfs, np.float64).reshape(self.n_glyphs, 6)
+            d["xf"][:, :4] = xfs[:, :4]
+            d["xf"][:, 4] = np.float64(1)/(xfs[:, 5]-xfs[:, 4])  # DistanceMapping.cpp:13
+            d["xf"][:, 5] = -xfs[:, 4]
         tile = width*height*channels
         d["out_offset"] = np.arange(self.n_glyphs, dtype=np.int64)*tile if out_offsets is None else np.asarray(out_offsets, np.int64)
         d["row_stride"] = width*channels if row_stride is None else row_stride
@@ -481,9 +521,11 @@ class GlyphBatch:
         return atlas
 
     def generate(self, mode, width, height, xfs=None, config=None, out=None, stencil=None, descriptors=None, stream=None, y_orientation=Y_UPWARD,
-                 scanline_pass=False, fill_rule=FILL_NONZERO, sdf_zero_value=.5):
+                 scanline_pass=False, fill_rule=FILL_NONZERO, sdf_zero_value=.5, frame: Optional["FrameConfig"] = None):
         """Renders every glyph of the batch into its tile; returns the float32 device tensor (G, height, width, N).
         Asynchronous on `stream` (torch.cuda.Stream) or torch's current stream.
+        frame: the glyphs are framed on the device first (msdfhip_batch_frame on the same stream; xfs is then not needed and the xf of `descriptors` are
+        overwritten).
         scanline_pass: run distanceSignCorrection(field, shape, projection, sdf_zero_value, fill_rule) between distance generation
         and error correction, the order of the reference's -scanline flow (main.cpp:1281-1298) -- the field stays on the device.
         The caller picks the configs that flow uses (overlap_support False, distance_check_mode DO_NOT_CHECK_DISTANCE)."""
@@ -503,6 +545,9 @@ class GlyphBatch:
                 self._scratch = torch.empty(need, dtype=torch.float32, device=self.device)
             scratch_ptr = self._scratch.data_ptr()
         s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        if frame is not None:
+            fc = frame.c_struct()
+            _lib.check(_lib.load().msdfhip_batch_frame(self._handle, C.byref(fc), int(width), int(height), descriptors.data_ptr(), s))
         _lib.check(_lib.load().msdfhip_batch_generate(self._handle, mode, width, height, descriptors.data_ptr(), out.data_ptr(),
                                                       stencil.data_ptr() if stencil is not None else None, scratch_ptr, C.byref(cfg), s))
         return out
@@ -533,11 +578,12 @@ def host_free(a):
 
 
 def _descriptors_host(shapes: ShapeBatch, xfs, out_offsets, row_stride, y_orientation=Y_UPWARD):
-    xfs = np.ascontiguousarray(xfs, np.float64).reshape(shapes.n_glyphs, 6)
     d = np.zeros(shapes.n_glyphs, _lib.GLYPH_DTYPE)
-    d["xf"][:, :4] = xfs[:, :4]
-    d["xf"][:, 4] = np.float64(1)/(xfs[:, 5]-xfs[:, 4])  # DistanceMapping.cpp:13
-    d["xf"][:, 5] = -xfs[:, 4]
+    if xfs is not None:                                      # (None: a framed call, the device writes xf)
+        xfs = np.ascontiguousarray(xfs, np.float64).reshape(shapes.n_glyphs, 6)
+        d["xf"][:, :4] = xfs[:, :4]
+        d["xf"][:, 4] = np.float64(1)/(xfs[:, 5]-xfs[:, 4])  # DistanceMapping.cpp:13
+        d["xf"][:, 5] = -xfs[:, 4]
     d["out_offset"] = np.asarray(out_offsets, np.int64)
     d["row_stride"] = row_stride
     d["flip"] = (np.asarray(shapes.inverse_y).astype(bool) != (y_orientation == Y_DOWNWARD)).astype(np.int32)
@@ -628,14 +674,19 @@ def generate_sharded(devices, shapes: ShapeBatch, mode, width, height, xfs, out=
     return out if out is not None else atlas
 
 
-def generate_stream(shapes: ShapeBatch, mode, width, height, xfs, out=None, atlas=None, out_offsets=None, row_stride=None, config=None, stencil=None,
-                    y_orientation=Y_UPWARD, device=-1, prepare: Optional[PrepareConfig] = None, seeds=None):
+def generate_stream(shapes: ShapeBatch, mode, width, height, xfs=None, out=None, atlas=None, out_offsets=None, row_stride=None, config=None, stencil=None,
+                    y_orientation=Y_UPWARD, device=-1, prepare: Optional[PrepareConfig] = None, seeds=None, frame: Optional[FrameConfig] = None):
     """msdfhip_generate_stream_csr: host CSR arrays in, host tiles (float32 `out`) or an 8-bit `atlas` out, as ONE pipelined call -- the glyph list is cut
     into chunks and chunk k+1's staging + upload + digest run under chunk k's kernels and chunk k-1's copy back (SURVEY.md 8d's end-to-end metric;
     msdfgen_hip::generate*Batch() of the C++ shim is the same pipeline fed from msdfgen::Shape objects).
     prepare: `shapes` are RAW outlines, prepared on the device chunk by chunk inside the pipeline (msdfhip_generate_stream_csr_prepared) -- the same
     bytes as GlyphBatch.from_raw(shapes, normalize, coloring, angle_threshold, seeds=seeds, seed=seed, orient_contours=orient_contours, winding=winding)
-    followed by generate(); `seeds`: one per glyph."""
+    followed by generate(); `seeds`: one per glyph.
+    frame: every chunk is framed on the device (msdfhip_generate_stream_csr_prepared_oriented_framed) from Shape::getBounds of its normalized glyphs, as the
+    reference CLI's -autoframe would; xfs may then be None (it is ignored). Without `prepare` the shapes are taken as prepared already (nothing is
+    normalized or coloured, the bounds are those of the arrays given)."""
+    if xfs is None and frame is None:
+        raise ValueError("generate_stream needs xfs or frame")
     n = CHANNELS[mode]
     tile = width*height*n
     if out is None and atlas is None:
@@ -650,15 +701,19 @@ def generate_stream(shapes: ShapeBatch, mode, width, height, xfs, out=None, atla
     colors = np.ascontiguousarray(shapes.colors, np.uint8)
     if stencil is not None:
         assert stencil.dtype == np.uint8 and stencil.flags.c_contiguous and stencil.size >= shapes.n_glyphs*width*height
-    if prepare is not None:
+    if prepare is not None or frame is not None:
+        if prepare is None:                                  # prepared shapes, framed: the raw-outline pipeline with a preparation that changes nothing
+            prepare = PrepareConfig(normalize=False, coloring=0)
         pc, po = prepare.c_struct(), prepare.c_orient()
+        fc = frame.c_struct() if frame is not None else None
         sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint64)
         assert sd is None or sd.size == shapes.n_glyphs
-        _lib.check(_lib.load().msdfhip_generate_stream_csr_prepared_oriented(
+        _lib.check(_lib.load().msdfhip_generate_stream_csr_prepared_oriented_framed(
             int(device), mode, width, height, shapes.n_glyphs, _lib.ptr(gco, _lib._ip), _lib.ptr(co, _lib._ip), _lib.ptr(pts, _lib._dp), _lib.ptr(types, _lib._bp),
             _lib.ptr(colors, _lib._bp), d.ctypes.data, out.ctypes.data if out is not None else None, out.size if out is not None else 0,
             atlas.ctypes.data if atlas is not None else None, atlas.size if atlas is not None else 0, stencil.ctypes.data if stencil is not None else None,
-            C.byref(cfg), C.byref(pc), sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None, C.byref(po)))
+            C.byref(cfg), C.byref(pc), sd.ctypes.data_as(C.POINTER(C.c_uint64)) if sd is not None else None, C.byref(po),
+            C.byref(fc) if fc is not None else None))
         return out if out is not None else atlas
     _lib.check(_lib.load().msdfhip_generate_stream_csr(int(device), mode, width, height, shapes.n_glyphs, _lib.ptr(gco, _lib._ip), _lib.ptr(co, _lib._ip),
                                                        _lib.ptr(pts, _lib._dp), _lib.ptr(types, _lib._bp), _lib.ptr(colors, _lib._bp), d.ctypes.data,

@@ -376,6 +376,8 @@ struct MsdfHipBatch : ShapeData {
     int device = 0;                   // the HIP device the batch lives on; every call on the batch binds the calling thread to it
     bool ownsInputs = false;          // the five input arrays are the batch's (dRecs / dWindings: a batch made with `new` owns them, a view never does)
     bool serialClasses = false;       // launch the glyph classes one after the other on the caller's stream (host-output pipeline: its chunks overlap instead)
+    mutable double *dBounds = NULL;   // [nGlyphs][4] l, b, r, t of Shape::getBounds (msdfhip_batch_bounds / _frame; allocated on first need, the batch's own)
+    bool boundsFixed = false;         // dBounds were taken at creation from the normalized edges (batches prepared from raw outlines: the arrays they keep are the coloured ones)
     mutable Workspace work;
     mutable ClassPlan plan;           // the classes of work.bucket
     void onDevice(int d) { device = work.device = d; }
@@ -1508,6 +1510,45 @@ int checkOrientConfig(const MsdfHipOrientConfig *orient, const char *who, MsdfHi
     return MSDFHIP_OK;
 }
 
+// NULL frame: no framing (*out untouched, *framed = false). What the CLI answers with "Cannot fit the specified pixel range." (main.cpp:1164-1165) depends on
+// the call's size and range alone, so it is refused here, like every other bad field, before anything is read or the device is touched.
+int checkFrameConfig(const MsdfHipFrameConfig *frame, int w, int h, const char *who, FrameParams *out, bool *framed) {
+    *framed = false;
+    if (!frame)
+        return MSDFHIP_OK;
+    if (frame->range_mode < 0 || frame->range_mode > 1)
+        return fail(MSDFHIP_ERR_INVALID, "%s: range_mode %d (0 unit range, 1 pixel range)", who, frame->range_mode);
+    if (!(frame->range_lower != frame->range_upper))
+        return fail(MSDFHIP_ERR_INVALID, "%s: range_lower == range_upper (%g): the distance mapping divides by their difference", who, frame->range_lower);
+    if (frame->scale_specified < 0 || frame->scale_specified > 1)
+        return fail(MSDFHIP_ERR_INVALID, "%s: scale_specified %d (0 or 1)", who, frame->scale_specified);
+    if (frame->scale_specified && !(frame->scale_x != 0 && frame->scale_y != 0))
+        return fail(MSDFHIP_ERR_INVALID, "%s: scale_specified with scale (%g, %g)", who, frame->scale_x, frame->scale_y);
+    if (w < 0 || h < 0)
+        return fail(MSDFHIP_ERR_INVALID, "%s: a %d x %d frame", who, w, h);
+    FrameParams f;
+    f.rangeMode = frame->range_mode, f.scaleSpecified = frame->scale_specified;
+    f.lower = frame->range_lower, f.upper = frame->range_upper;
+    f.sx = frame->scale_specified ? frame->scale_x : 1., f.sy = frame->scale_specified ? frame->scale_y : 1.;
+    const V2 extent = frameExtent(f, w, h);
+    if ((w > 0 && h > 0) && (extent.x <= 0 || extent.y <= 0))
+        return fail(MSDFHIP_ERR_INVALID, "%s: cannot fit the specified pixel range (%g to %g) into %d x %d", who, frame->range_lower, frame->range_upper, w, h);
+    *out = f, *framed = true;
+    return MSDFHIP_OK;
+}
+
+// k_frame on `stream`: bounds[g][4] of the glyphs of (gco, co) over the NORMALIZED edges (haveBounds: they are there already), and with dGlyphs their xf.
+int queueFrame(const EdgeArrays &norm, const int32_t *gco, const int32_t *co, int nGlyphs, double *dBounds, bool haveBounds, const FrameParams *frame, int w, int h,
+               MsdfHipGlyph *dGlyphs, hipStream_t stream) {
+    if (!nGlyphs)
+        return MSDFHIP_OK;
+    const FrameParams none = { 0, 0, 0., 1., 1., 1. };
+    hipLaunchKernelGGL(k_frame, dim3((unsigned) nGlyphs), dim3(WAVE), 0, stream, norm, gco, co, nGlyphs, dBounds, haveBounds ? 1 : 0, frame ? *frame : none, w, h,
+                       frame ? dGlyphs : (MsdfHipGlyph *) NULL);
+    HIPCHK(hipGetLastError());
+    return MSDFHIP_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1617,6 +1658,12 @@ int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, c
     rc = queuePreparation(cfg, orient, n_glyphs, nC, nE1, longest, crossThreshold, pb, 0);
     if (rc != MSDFHIP_OK)
         return rc;
+    // Shape::getBounds where the CLI takes it (main.cpp:1125-1132): of the normalized edges, which do not outlive this call when a colouring follows
+    double *dBounds = NULL;
+    PREP_CHK(dev.alloc((void **) &dBounds, sizeof(double)*4*(size_t) (n_glyphs > 0 ? n_glyphs : 1)));
+    rc = queueFrame(norm, dGco, dCo1, n_glyphs, dBounds, false, NULL, 0, 0, NULL, 0);
+    if (rc != MSDFHIP_OK)
+        return rc;
     const int32_t *finalCo = co1.data();
     int32_t *dFinalCo = dCo1;
     if (cfg->coloring) {
@@ -1639,7 +1686,8 @@ int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, c
     b->nGlyphs = n_glyphs, b->nContours = nC, b->nEdges = finalCo[nC], b->maxContours = maxC, b->maxEdges = maxE;
     b->ownsInputs = true;                                        // the batch takes over the final arrays
     b->dGlyphContourOffsets = dGco, b->dContourOffsets = dFinalCo, b->dPoints = fin.points, b->dTypes = fin.types, b->dColors = fin.colors;
-    dev.release(dGco), dev.release(dFinalCo), dev.release(fin.points), dev.release(fin.types), dev.release(fin.colors);
+    b->dBounds = dBounds, b->boundsFixed = true;
+    dev.release(dGco), dev.release(dFinalCo), dev.release(fin.points), dev.release(fin.types), dev.release(fin.colors), dev.release(dBounds);
     rc = digest(b, NULL);
     if (rc == MSDFHIP_OK && hipStreamSynchronize(NULL) != hipSuccess)
         rc = fail(MSDFHIP_ERR_HIP, "edge digestion failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1715,6 +1763,7 @@ void msdfhip_batch_destroy(MsdfHipBatch *b) {
     }
     hipFree(b->dRecs);
     hipFree(b->dWindings);
+    hipFree(b->dBounds);
     delete b;                                                    // (its workspace releases itself)
 }
 
@@ -1731,6 +1780,46 @@ int msdfhip_batch_windings(const MsdfHipBatch *b, int32_t *windings) {
     for (int c = 0; c < b->nContours; ++c)
         windings[c] = tmp[c];
     return MSDFHIP_OK;
+}
+
+// Shape::getBounds of the batch's glyphs into b->dBounds on `stream` (and, with `frame`, the framed xf into dGlyphs): one k_frame launch.
+static int frameBatch(const MsdfHipBatch *b, const FrameParams *frame, int w, int h, MsdfHipGlyph *dGlyphs, hipStream_t stream) {
+    if (!b->dBounds)
+        HIPCHK(hipMalloc((void **) &b->dBounds, sizeof(double)*4*(size_t) (b->nGlyphs > 0 ? b->nGlyphs : 1)));
+    const EdgeArrays edges = { b->dPoints, b->dTypes, b->dColors };
+    return queueFrame(edges, b->dGlyphContourOffsets, b->dContourOffsets, b->nGlyphs, b->dBounds, b->boundsFixed, frame, w, h, dGlyphs, stream);
+}
+
+int msdfhip_batch_bounds(const MsdfHipBatch *b, double *bounds) {
+    if (!b || !bounds)
+        return fail(MSDFHIP_ERR_INVALID, "NULL argument");
+    int rc = ensureDevice(b->device);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    HIPCHK(hipDeviceSynchronize());                              // (the edge arrays may still be written by work the caller queued)
+    if (!b->boundsFixed) {
+        rc = frameBatch(b, NULL, 0, 0, NULL, NULL);
+        if (rc != MSDFHIP_OK)
+            return rc;
+    }
+    HIPCHK(hipStreamSynchronize(NULL));
+    if (b->nGlyphs)
+        HIPCHK(hipMemcpy(bounds, b->dBounds, sizeof(double)*4*(size_t) b->nGlyphs, hipMemcpyDeviceToHost));
+    return MSDFHIP_OK;
+}
+
+int msdfhip_batch_frame(const MsdfHipBatch *b, const MsdfHipFrameConfig *frame, int w, int h, MsdfHipGlyph *dGlyphs, void *stream) {
+    FrameParams f;
+    bool framed = false;
+    int rc = checkFrameConfig(frame, w, h, "msdfhip_batch_frame", &f, &framed);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    if (!b || !framed || !dGlyphs)
+        return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_frame: NULL argument");
+    rc = ensureDevice(b->device);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    return frameBatch(b, &f, w, h, dGlyphs, (hipStream_t) stream);
 }
 
 // One generate call on b (arguments checked, device bound): distance pass -> sign correction -> error correction.
@@ -1933,6 +2022,7 @@ struct PipeSlot {
     hipEvent_t inputsUploaded;        // the chunk's upload has left pinnedIn
     bool inputsInFlight;
     hipEvent_t prepCounted;           // streamed calls of raw outlines: the chunk's coloured contour offsets have reached pinnedIn (StreamFeeder::prepare)
+    MsdfHipGlyph *frameGlyphs;        // framed streamed calls: the chunk's descriptors on the device, uploaded BEFORE its shapes so that k_frame can write their xf
 };
 
 // The slots of a pipeline in flight. Pipelines live in a process-wide pool per device (like the arenas of the single-shape calls):
@@ -1980,7 +2070,7 @@ struct PipeLease {
             s.view.onDevice(device);
             s.stream = NULL, s.done = NULL, s.kernelsDone = NULL, s.distanceDone = NULL, s.pinnedOverflow = NULL, s.busy = false;
             s.pendingFirst = 0, s.pendingCount = 0;
-            s.inputsUploaded = NULL, s.inputsInFlight = false, s.prepCounted = NULL;
+            s.inputsUploaded = NULL, s.inputsInFlight = false, s.prepCounted = NULL, s.frameGlyphs = NULL;
         }
         for (int k = 0; k < PIPE_SLOTS; ++k) {                   // a half-built pipe never reaches the pool
             hipError_t e = hipStreamCreateWithFlags(&fresh->slot[k].stream, hipStreamNonBlocking);
@@ -2139,6 +2229,7 @@ static HostPool &hostPool() {
 struct ChunkFeeder {
     virtual ~ChunkFeeder() { }
     virtual void drain() { }                                     // no host work of the feeder is running or will start after this (every exit of runPipelineOnce)
+    virtual bool frames() const { return false; }                // prepare() writes the xf of the chunk's descriptors (PipeSlot::frameGlyphs) on the device
     virtual int begin(PipeSlot *slots, const std::vector<int> &lengths) = 0;
     virtual int prepare(PipeSlot &p, int slot, size_t chunkIndex, int g0, int n, hipStream_t stream) = 0;
 };
@@ -2170,14 +2261,18 @@ struct StreamFeeder : ChunkFeeder {
     MsdfHipOrientConfig orient;                                  // orientation around the preparation (checked; all 0: keep)
     double crossThreshold;                                       // sin(angle_threshold), by the host's libm (edge-coloring.cpp:69)
     std::vector<char> mayHaveLong;                               // per chunk: a glyph whose normalized contours could exceed PREP_WAVE_MAX_EDGES (the `big` tables)
+    const FrameParams *frame;                                    // raw outlines only: every chunk is framed between its preparation and its digest (k_frame); NULL: the caller's xf
+    int frameW, frameH;
     enum { GRAIN = 32 };                                         // glyphs per flatten item
 
     StreamFeeder(const MsdfHipShapeSource *source, int n, const MsdfHipPrepConfig *prepCfg = NULL, const uint64_t *glyphSeeds = NULL,
-                 const MsdfHipOrientConfig *orientCfg = NULL)
-        : src(source), nG(n), slots(NULL), prep(prepCfg), seeds(glyphSeeds), crossThreshold(prepCfg && prepCfg->coloring ? sin(prepCfg->angle_threshold) : 0.) {
+                 const MsdfHipOrientConfig *orientCfg = NULL, const FrameParams *frameCfg = NULL, int w = 0, int h = 0)
+        : src(source), nG(n), slots(NULL), prep(prepCfg), seeds(glyphSeeds), crossThreshold(prepCfg && prepCfg->coloring ? sin(prepCfg->angle_threshold) : 0.),
+          frame(prepCfg ? frameCfg : NULL), frameW(w), frameH(h) {
         orient.orient_contours = orientCfg ? orientCfg->orient_contours : 0, orient.winding = orientCfg ? orientCfg->winding : 0;
     }
     ~StreamFeeder() { drain(); }
+    bool frames() const { return frame != NULL; }
 
     // The flatten jobs run on the detached pool threads, capture `this`, call the caller's fill callbacks and write into the leased pipe's pinned staging:
     // when the pipeline leaves early (a bad glyph, a HIP error inside the chunk loop) the jobs of the chunks ahead must not outlive the call.
@@ -2231,8 +2326,8 @@ struct StreamFeeder : ChunkFeeder {
     // one edge becomes three, one of two edges at most six), a chunk carves its exact counts -- the same pieces in the same order, so never beyond.
     // With orient_contours: the votes (nC) and, when a glyph of the chunk can overflow k_prep_orient's LDS (hitsBig), 3 hits per raw edge (nE).
     struct PrepLayout { size_t cusp, count, co2, norm[3], fin[3], bigMask, bigSpline, bigEdgeLength, bigCornerLength, bigCornerIndex, bigMinor, votes, hitX, hitTag,
-                        recs, windings, bytes; };
-    PrepLayout prepLayout(size_t at, size_t nC, size_t nE, size_t nE1, size_t nE2, bool big, bool hitsBig) const {
+                        bounds, recs, windings, bytes; };
+    PrepLayout prepLayout(size_t at, size_t n, size_t nC, size_t nE, size_t nE1, size_t nE2, bool big, bool hitsBig) const {
         Carver c;
         c.off = (at+255)/256*256;
         PrepLayout l = PrepLayout();
@@ -2252,6 +2347,8 @@ struct StreamFeeder : ChunkFeeder {
             if (hitsBig)
                 l.hitX = c.take(3*(nE ? nE : 1)*sizeof(double)), l.hitTag = c.take(3*(nE ? nE : 1)*sizeof(int32_t));
         }
+        if (frame)                                               // Shape::getBounds per glyph (k_frame)
+            l.bounds = c.take(4*(n ? n : 1)*sizeof(double));
         l.recs = c.take(sizeof(EdgeRec)*(prep->coloring ? e2 : e1)), l.windings = c.take(nC ? nC : 1), l.bytes = c.off;
         return l;
     }
@@ -2312,7 +2409,7 @@ struct StreamFeeder : ChunkFeeder {
                     maxRaw = hEdges[(size_t) k] > maxRaw ? hEdges[(size_t) k] : maxRaw;
                 }
                 const size_t pin = (l.bytes+255)/256*256+(nC+1)*sizeof(int32_t);
-                const size_t dev = prepLayout(l.bytes, nC, nE, nE+2*nC, nE+4*nC, mayHaveLong[ci] != 0, orientHitsBig(maxRaw)).bytes;
+                const size_t dev = prepLayout(l.bytes, (size_t) lengths[ci], nC, nE, nE+2*nC, nE+4*nC, mayHaveLong[ci] != 0, orientHitsBig(maxRaw)).bytes;
                 prepPinned = pin > prepPinned ? pin : prepPinned, prepDev = dev > prepDev ? dev : prepDev;
             }
         }
@@ -2398,7 +2495,7 @@ struct StreamFeeder : ChunkFeeder {
         const bool big = longest > PREP_WAVE_MAX_EDGES;
         const int maxRaw = p.view.maxEdges;                      // (still of the raw counts)
         const bool hitsBig = orient.orient_contours && orientHitsBig(maxRaw);
-        const PrepLayout pl = prepLayout(l.bytes, (size_t) nC, (size_t) reinterpret_cast<const int32_t *>(p.pinnedIn.ptr+l.co)[nC], (size_t) nE1, bound2, big, hitsBig);
+        const PrepLayout pl = prepLayout(l.bytes, (size_t) n, (size_t) nC, (size_t) reinterpret_cast<const int32_t *>(p.pinnedIn.ptr+l.co)[nC], (size_t) nE1, bound2, big, hitsBig);
         EdgeArrays raw = { reinterpret_cast<double *>(d+l.points), reinterpret_cast<uint8_t *>(d+l.types), reinterpret_cast<uint8_t *>(d+l.colors) };
         EdgeArrays norm = { reinterpret_cast<double *>(d+pl.norm[0]), reinterpret_cast<uint8_t *>(d+pl.norm[1]), reinterpret_cast<uint8_t *>(d+pl.norm[2]) };
         EdgeArrays fin = norm;
@@ -2422,6 +2519,11 @@ struct StreamFeeder : ChunkFeeder {
         int rc = queuePreparation(prep, orient, n, nC, nE1, longest, crossThreshold, pb, stream);
         if (rc != MSDFHIP_OK)
             return rc;
+        if (frame) {                                             // bounds of the normalized edges -> xf of the chunk's descriptors, which are on the device already
+            rc = queueFrame(norm, pb.gco, dCo1, n, reinterpret_cast<double *>(d+pl.bounds), false, frame, frameW, frameH, p.frameGlyphs, stream);
+            if (rc != MSDFHIP_OK)
+                return rc;
+        }
         const int32_t *hFinal = hCo1;                            // without colouring the host knows the final offsets already
         if (prep->coloring) {
             // the offsets come back by the word-copy kernel writing into the pinned staging rather than by a copy, which would share the copy engine with
@@ -2535,15 +2637,12 @@ struct PipeCall {
     bool mirrorOverflow;
 };
 
-// A chunk's inputs: everything here -- the chunk's shapes (streamed calls: upload + digest), its descriptors and the two preparations of prepareAhead --
-// does not depend on the chunks before it: it is queued AHEAD of the chunk's turn on the device and runs under the earlier chunks' kernels.
-static int queueChunkInputs(const PipeCall &pc, ChunkFeeder *feeder, PipeSlot &p, int slot, size_t ci, int g0, int n, ChunkSpan &span, GenerateCall &call) {
+// The chunk's descriptors on the slot's stream: the generators' (the caller's layout relative to the chunk's range, or packed tiles) and, for 8-bit output,
+// the conversion's behind them.
+static int queueChunkDescriptors(const PipeCall &pc, PipeSlot &p, int g0, int n, MsdfHipGlyph *dGlyphs, ChunkSpan &span) {
     const int w = pc.w, h = pc.h, N = pc.N;
     hipStream_t compute = p.stream;
-    int rc = feeder->prepare(p, slot, ci, g0, n, compute);       // a view of the resident batch, or: flattened shapes -> upload -> digest on the chunk's stream
-    if (rc != MSDFHIP_OK)
-        return rc;
-    MsdfHipGlyph *dGlyphs = reinterpret_cast<MsdfHipGlyph *>(p.dev.ptr+pc.at.offGlyphs);
+    int rc;
     // dense (chunkSpan): the chunk goes back as ONE copy. Otherwise the chunk is rendered as packed tiles, copied into pinned staging and scattered
     // row by row on the host (pendingCount).
     span = chunkSpan(pc.glyphs+g0, n, w, h, N);
@@ -2568,6 +2667,31 @@ static int queueChunkInputs(const PipeCall &pc, ChunkFeeder *feeder, PipeSlot &p
                 hBlit[g].out_offset = (int64_t) ((size_t) g*pc.tile), hBlit[g].row_stride = w*N;
         }
         rc = uploadSmall(dGlyphs+pc.chunk, hBlit, sizeof(MsdfHipGlyph)*(size_t) n, compute);
+        if (rc != MSDFHIP_OK)
+            return rc;
+    }
+    return MSDFHIP_OK;
+}
+
+// A chunk's inputs: everything here -- the chunk's shapes (streamed calls: upload + digest), its descriptors and the two preparations of prepareAhead --
+// does not depend on the chunks before it: it is queued AHEAD of the chunk's turn on the device and runs under the earlier chunks' kernels.
+static int queueChunkInputs(const PipeCall &pc, ChunkFeeder *feeder, PipeSlot &p, int slot, size_t ci, int g0, int n, ChunkSpan &span, GenerateCall &call) {
+    const int w = pc.w, h = pc.h;
+    hipStream_t compute = p.stream;
+    MsdfHipGlyph *dGlyphs = reinterpret_cast<MsdfHipGlyph *>(p.dev.ptr+pc.at.offGlyphs);
+    int rc;
+    const bool framed = feeder->frames();                        // the feeder's k_frame writes xf into the descriptors: they go up first (same stream: in order)
+    p.frameGlyphs = framed ? dGlyphs : NULL;
+    if (framed) {
+        rc = queueChunkDescriptors(pc, p, g0, n, dGlyphs, span);
+        if (rc != MSDFHIP_OK)
+            return rc;
+    }
+    rc = feeder->prepare(p, slot, ci, g0, n, compute);           // a view of the resident batch, or: flattened shapes -> upload -> digest on the chunk's stream
+    if (rc != MSDFHIP_OK)
+        return rc;
+    if (!framed) {
+        rc = queueChunkDescriptors(pc, p, g0, n, dGlyphs, span);
         if (rc != MSDFHIP_OK)
             return rc;
     }
@@ -2769,7 +2893,7 @@ int msdfhip_batch_generate_bytes_host(const MsdfHipBatch *b, int mode, int w, in
 // prep != NULL (msdfhip_generate_stream_prepared): the source delivers RAW outlines, each chunk is prepared on the device on its own stream.
 static int generateStream(const char *who, int device, int mode, int w, int h, int n_glyphs, const MsdfHipShapeSource *source, const MsdfHipGlyph *glyphs,
                           float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg,
-                          const MsdfHipPrepConfig *prep, const uint64_t *seeds, const MsdfHipOrientConfig *orient = NULL) {
+                          const MsdfHipPrepConfig *prep, const uint64_t *seeds, const MsdfHipOrientConfig *orient = NULL, const FrameParams *frame = NULL) {
     if (!source || !source->count || !source->fill || n_glyphs < 0 || (!out) == (!atlas) || (n_glyphs > 0 && !glyphs))
         return fail(MSDFHIP_ERR_INVALID, "bad arguments to %s (a shape source with count and fill, exactly one of out / atlas)", who);
     if (atlas && stencil)
@@ -2787,7 +2911,7 @@ static int generateStream(const char *who, int device, int mode, int w, int h, i
     int rc = ensureDevice(device);
     if (rc != MSDFHIP_OK)
         return rc;
-    StreamFeeder feeder(source, n_glyphs, prep, seeds, orient);
+    StreamFeeder feeder(source, n_glyphs, prep, seeds, orient, frame, w, h);
     rc = feeder.count();
     if (rc != MSDFHIP_OK)
         return rc;
@@ -2811,6 +2935,15 @@ int msdfhip_generate_stream_prepared(int device, int mode, int w, int h, int n_g
 int msdfhip_generate_stream_prepared_oriented(int device, int mode, int w, int h, int n_glyphs, const MsdfHipShapeSource *source, const MsdfHipGlyph *glyphs,
                                               float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg,
                                               const MsdfHipPrepConfig *prep, const uint64_t *seeds, const MsdfHipOrientConfig *orient) {
+    return msdfhip_generate_stream_prepared_oriented_framed(device, mode, w, h, n_glyphs, source, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg, prep, seeds,
+                                                            orient, NULL);
+}
+
+// + framing on the device (frame NULL: the caller's xf); every config is checked before the source is read.
+int msdfhip_generate_stream_prepared_oriented_framed(int device, int mode, int w, int h, int n_glyphs, const MsdfHipShapeSource *source, const MsdfHipGlyph *glyphs,
+                                                     float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg,
+                                                     const MsdfHipPrepConfig *prep, const uint64_t *seeds, const MsdfHipOrientConfig *orient,
+                                                     const MsdfHipFrameConfig *frame) {
     int rc = checkPrepConfig(prep, "msdfhip_generate_stream_prepared");
     if (rc != MSDFHIP_OK)
         return rc;
@@ -2818,8 +2951,13 @@ int msdfhip_generate_stream_prepared_oriented(int device, int mode, int w, int h
     rc = checkOrientConfig(orient, "msdfhip_generate_stream_prepared_oriented", &o);
     if (rc != MSDFHIP_OK)
         return rc;
+    FrameParams f;
+    bool framed = false;
+    rc = checkFrameConfig(frame, w, h, "msdfhip_generate_stream_prepared_oriented_framed", &f, &framed);
+    if (rc != MSDFHIP_OK)
+        return rc;
     return generateStream("msdfhip_generate_stream_prepared", device, mode, w, h, n_glyphs, source, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg, prep, seeds,
-                          &o);
+                          &o, framed ? &f : NULL);
 }
 
 namespace {
@@ -2870,11 +3008,25 @@ int msdfhip_generate_stream_csr_prepared_oriented(int device, int mode, int w, i
                                                   const uint8_t *types, const uint8_t *colors, const MsdfHipGlyph *glyphs, float *out, size_t out_floats,
                                                   uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep,
                                                   const uint64_t *seeds, const MsdfHipOrientConfig *orient) {
+    return msdfhip_generate_stream_csr_prepared_oriented_framed(device, mode, w, h, n_glyphs, gco, co, points, types, colors, glyphs, out, out_floats, atlas,
+                                                                atlas_bytes, stencil, cfg, prep, seeds, orient, NULL);
+}
+
+int msdfhip_generate_stream_csr_prepared_oriented_framed(int device, int mode, int w, int h, int n_glyphs, const int32_t *gco, const int32_t *co,
+                                                         const double *points, const uint8_t *types, const uint8_t *colors, const MsdfHipGlyph *glyphs, float *out,
+                                                         size_t out_floats, uint8_t *atlas, size_t atlas_bytes, uint8_t *stencil, const MsdfHipConfig *cfg,
+                                                         const MsdfHipPrepConfig *prep, const uint64_t *seeds, const MsdfHipOrientConfig *orient,
+                                                         const MsdfHipFrameConfig *frame) {
     int rc = checkPrepConfig(prep, "msdfhip_generate_stream_csr_prepared");
     if (rc != MSDFHIP_OK)
         return rc;
     MsdfHipOrientConfig o;
     rc = checkOrientConfig(orient, "msdfhip_generate_stream_csr_prepared_oriented", &o);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    FrameParams f;
+    bool framed = false;
+    rc = checkFrameConfig(frame, w, h, "msdfhip_generate_stream_csr_prepared_oriented_framed", &f, &framed);
     if (rc != MSDFHIP_OK)
         return rc;
     std::vector<int> hc, he;
@@ -2885,7 +3037,7 @@ int msdfhip_generate_stream_csr_prepared_oriented(int device, int mode, int w, i
     CsrSource csr = { gco, co, points, types, colors };
     MsdfHipShapeSource source = { &csr, CsrSource::count, CsrSource::fill };
     return generateStream("msdfhip_generate_stream_csr_prepared", device, mode, w, h, n_glyphs, &source, glyphs, out, out_floats, atlas, atlas_bytes, stencil, cfg,
-                          prep, seeds, &o);
+                          prep, seeds, &o, framed ? &f : NULL);
 }
 
 int msdfhip_set_host_threads(int threads) {

@@ -23,6 +23,7 @@
 #include "msdf_cull.hpp"
 #include "msdf_scanline.hpp"
 #include "msdf_shapeprep.hpp"
+#include "msdf_frame.hpp"
 #include "../../include/msdfgen_hip.h"
 
 namespace msdfhip {
@@ -2177,6 +2178,37 @@ __global__ void __launch_bounds__(WAVE) k_prep_winding(EdgeArrays norm, const in
     ctx.lane = threadIdx.x;
     const WindingScratch s = { lo, hi, d, dot, idx };
     windingGlyphWave(ctx, norm, co1, gco[g], gco[g+1], mode, s);
+}
+
+// Shape::getBounds of every glyph and the CLI's -autoframe from it (msdf_frame.hpp), one wavefront per glyph, lanes = edges, on the NORMALIZED edges.
+// bounds[g][4] = l, b, r, t is written, or with haveBounds only read (a batch prepared from raw outlines took them before its colouring);
+// with glyphs != NULL lane 0 then writes xf[0..5] of glyphs[g] (frameGlyph) and leaves out_offset / row_stride / flip as they are.
+__global__ void __launch_bounds__(WAVE) k_frame(EdgeArrays norm, const int32_t *gco, const int32_t *co, int nGlyphs, double *bounds, int haveBounds,
+                                                FrameParams frame, int width, int height, MsdfHipGlyph *glyphs) {
+    __shared__ double part[4*WAVE], run[4];
+    const int g = blockIdx.x;
+    if (g >= nGlyphs)
+        return;
+    WaveCtx ctx;
+    ctx.lane = threadIdx.x;
+    if (!haveBounds) {
+        const BoundsScratch s = { part, run };
+        boundsGlyphWave(ctx, norm, co, gco[g], gco[g+1], s);
+    }
+    if (threadIdx.x == 0) {
+        double b[4];
+        for (int k = 0; k < 4; ++k)
+            b[k] = haveBounds ? bounds[4*(size_t) g+k] : run[k];
+        if (!haveBounds)
+            for (int k = 0; k < 4; ++k)
+                bounds[4*(size_t) g+k] = b[k];
+        if (glyphs) {
+            double xf[6];
+            frameGlyph(frame, width, height, b, xf);
+            for (int k = 0; k < 6; ++k)
+                glyphs[g].xf[k] = xf[k];
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------- 8-bit atlas output (row f2)

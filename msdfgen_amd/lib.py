@@ -45,6 +45,12 @@ class OrientConfig(C.Structure):
     _fields_ = [("orient_contours", C.c_int32), ("winding", C.c_int32)]
 
 
+class FrameConfig(C.Structure):
+    """MsdfHipFrameConfig."""
+    _fields_ = [("range_mode", C.c_int32), ("scale_specified", C.c_int32), ("range_lower", C.c_double), ("range_upper", C.c_double),
+                ("scale_x", C.c_double), ("scale_y", C.c_double)]
+
+
 class Glyph(C.Structure):
     """MsdfHipGlyph."""
     _fields_ = [("xf", C.c_double*6), ("out_offset", C.c_int64), ("row_stride", C.c_int32), ("flip", C.c_int32)]
@@ -124,6 +130,14 @@ _PROTOS = {
     "msdfhip_generate_stream_csr_prepared_oriented": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _bp, _bp, _vp, _vp, C.c_size_t, _vp,
                                                                 C.c_size_t, _vp, C.POINTER(Config), C.POINTER(PrepConfig), C.POINTER(C.c_uint64),
                                                                 C.POINTER(OrientConfig)]),
+    "msdfhip_batch_bounds": (C.c_int, [_vp, _dp]),
+    "msdfhip_batch_frame": (C.c_int, [_vp, C.POINTER(FrameConfig), C.c_int, C.c_int, _vp, _vp]),
+    "msdfhip_generate_stream_prepared_oriented_framed": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp,
+                                                                   C.POINTER(Config), C.POINTER(PrepConfig), C.POINTER(C.c_uint64), C.POINTER(OrientConfig),
+                                                                   C.POINTER(FrameConfig)]),
+    "msdfhip_generate_stream_csr_prepared_oriented_framed": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _ip, _dp, _bp, _bp, _vp, _vp, C.c_size_t,
+                                                                       _vp, C.c_size_t, _vp, C.POINTER(Config), C.POINTER(PrepConfig), C.POINTER(C.c_uint64),
+                                                                       C.POINTER(OrientConfig), C.POINTER(FrameConfig)]),
     "msdfhip_set_host_threads": (C.c_int, [C.c_int]),
     "msdfhip_single_call_fallbacks": (C.c_int, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_int]),
     "msdfhip_debug_route_counts": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int, C.c_int]),

@@ -351,10 +351,10 @@ struct ShapeList {
 
 template <typename T, int N>
 void generateBatch(int mode, const BitmapSection<T, N> *outputs, const Shape *const *shapes, const SDFTransformation *transformations, int count, bool overlapSupport,
-                   const ErrorCorrectionConfig *ec) {
+                   const ErrorCorrectionConfig *ec, const FrameConfig *frame = NULL) {
     if (count <= 0)
         return;
-    if (!outputs || !shapes || !transformations) {
+    if (!outputs || !shapes || (!transformations && !frame)) {
         msdfgen::check(MSDFHIP_ERR_INVALID, "generateBatch (NULL argument)");
         return;
     }
@@ -384,7 +384,10 @@ void generateBatch(int mode, const BitmapSection<T, N> *outputs, const Shape *co
             glyphs.resize((size_t) n);
             for (int g = 0; g < n; ++g) {
                 const int i = order[first+(size_t) g];
-                msdfgen::transformationToXf(transformations[i], glyphs[(size_t) g].xf);
+                if (frame)                                                 // (the device frames the glyph: k_frame writes xf)
+                    std::fill(glyphs[(size_t) g].xf, glyphs[(size_t) g].xf+6, 0.);
+                else
+                    msdfgen::transformationToXf(transformations[i], glyphs[(size_t) g].xf);
                 glyphs[(size_t) g].out_offset = (int64_t) (outputs[i].pixels-base);
                 glyphs[(size_t) g].row_stride = outputs[i].rowStride;
                 glyphs[(size_t) g].flip = shapes[i]->getYAxisOrientation() != outputs[i].yOrientation;   // output.reorient(shape.getYAxisOrientation()), core/msdfgen.cpp:55
@@ -392,8 +395,17 @@ void generateBatch(int mode, const BitmapSection<T, N> *outputs, const Shape *co
             MsdfHipConfig cfg = msdfgen::makeConfig(overlapSupport, ec);
             ShapeList list = { shapes, order.data()+first };
             MsdfHipShapeSource source = { &list, ShapeList::count, ShapeList::fill };
-            const int rc = msdfhip_generate_stream(-1, mode, w, h, n, &source, glyphs.data(), bytes ? NULL : (float *) base, bytes ? 0 : (size_t) (end-base),
-                                                   bytes ? (uint8_t *) base : NULL, bytes ? (size_t) (end-base) : 0, NULL, &cfg);
+            int rc;
+            if (frame) {                                                   // the shapes are prepared already (the caller's normalize + colouring): keep them as they are
+                const MsdfHipPrepConfig keep = { 0, 0, 3., 0 };
+                const MsdfHipFrameConfig fc = { frame->rangeMode == FrameConfig::RANGE_PX ? 1 : 0, frame->scaleSpecified ? 1 : 0, frame->range.lower, frame->range.upper,
+                                                frame->scale.x, frame->scale.y };
+                rc = msdfhip_generate_stream_prepared_oriented_framed(-1, mode, w, h, n, &source, glyphs.data(), bytes ? NULL : (float *) base,
+                                                                      bytes ? 0 : (size_t) (end-base), bytes ? (uint8_t *) base : NULL, bytes ? (size_t) (end-base) : 0,
+                                                                      NULL, &cfg, &keep, NULL, NULL, &fc);
+            } else
+                rc = msdfhip_generate_stream(-1, mode, w, h, n, &source, glyphs.data(), bytes ? NULL : (float *) base, bytes ? 0 : (size_t) (end-base),
+                                             bytes ? (uint8_t *) base : NULL, bytes ? (size_t) (end-base) : 0, NULL, &cfg);
             msdfgen::check(rc, "generateBatch");
             if (rc != MSDFHIP_OK)
                 return;
@@ -427,6 +439,32 @@ void generateMSDFBatch(const BitmapSection<byte, 3> *outputs, const Shape *const
 }
 void generateMTSDFBatch(const BitmapSection<byte, 4> *outputs, const Shape *const *shapes, const SDFTransformation *transformations, int count, const MSDFGeneratorConfig &config) {
     generateBatch<byte, 4>(MSDFHIP_MODE_MTSDF, outputs, shapes, transformations, count, config.overlapSupport, &config.errorCorrection);
+}
+
+// framed on the device: a FrameConfig for the list instead of a transformation per shape
+void generateSDFBatch(const BitmapSection<float, 1> *outputs, const Shape *const *shapes, const FrameConfig &frame, int count, const GeneratorConfig &config) {
+    generateBatch<float, 1>(MSDFHIP_MODE_SDF, outputs, shapes, NULL, count, config.overlapSupport, NULL, &frame);
+}
+void generatePSDFBatch(const BitmapSection<float, 1> *outputs, const Shape *const *shapes, const FrameConfig &frame, int count, const GeneratorConfig &config) {
+    generateBatch<float, 1>(MSDFHIP_MODE_PSDF, outputs, shapes, NULL, count, config.overlapSupport, NULL, &frame);
+}
+void generateMSDFBatch(const BitmapSection<float, 3> *outputs, const Shape *const *shapes, const FrameConfig &frame, int count, const MSDFGeneratorConfig &config) {
+    generateBatch<float, 3>(MSDFHIP_MODE_MSDF, outputs, shapes, NULL, count, config.overlapSupport, &config.errorCorrection, &frame);
+}
+void generateMTSDFBatch(const BitmapSection<float, 4> *outputs, const Shape *const *shapes, const FrameConfig &frame, int count, const MSDFGeneratorConfig &config) {
+    generateBatch<float, 4>(MSDFHIP_MODE_MTSDF, outputs, shapes, NULL, count, config.overlapSupport, &config.errorCorrection, &frame);
+}
+void generateSDFBatch(const BitmapSection<byte, 1> *outputs, const Shape *const *shapes, const FrameConfig &frame, int count, const GeneratorConfig &config) {
+    generateBatch<byte, 1>(MSDFHIP_MODE_SDF, outputs, shapes, NULL, count, config.overlapSupport, NULL, &frame);
+}
+void generatePSDFBatch(const BitmapSection<byte, 1> *outputs, const Shape *const *shapes, const FrameConfig &frame, int count, const GeneratorConfig &config) {
+    generateBatch<byte, 1>(MSDFHIP_MODE_PSDF, outputs, shapes, NULL, count, config.overlapSupport, NULL, &frame);
+}
+void generateMSDFBatch(const BitmapSection<byte, 3> *outputs, const Shape *const *shapes, const FrameConfig &frame, int count, const MSDFGeneratorConfig &config) {
+    generateBatch<byte, 3>(MSDFHIP_MODE_MSDF, outputs, shapes, NULL, count, config.overlapSupport, &config.errorCorrection, &frame);
+}
+void generateMTSDFBatch(const BitmapSection<byte, 4> *outputs, const Shape *const *shapes, const FrameConfig &frame, int count, const MSDFGeneratorConfig &config) {
+    generateBatch<byte, 4>(MSDFHIP_MODE_MTSDF, outputs, shapes, NULL, count, config.overlapSupport, &config.errorCorrection, &frame);
 }
 
 }
