@@ -1082,7 +1082,9 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
     rc = setLds(k_ec_query<N, OVERLAP>, queryLds);
     if (rc != MSDFHIP_OK)
         return rc;
-    rc = setLds(k_ec_fast<N>, fastLds);
+    // the sweep's order (msdf_ec_fast.hpp: ecLazyProtect) is fixed per launch: an instantiation each
+    const bool lazyProtect = cfg.ec_mode == EC_MODE_EDGE_PRIORITY && cfg.ec_distance_check == EC_CHECK_AT_EDGE;
+    rc = lazyProtect ? setLds(k_ec_fast<N, true>, fastLds) : setLds(k_ec_fast<N, false>, fastLds);
     if (rc != MSDFHIP_OK)
         return rc;
     int *offsets = reinterpret_cast<int *>(deferred+candidateRecords(b->nGlyphs, (size_t) w*h));
@@ -1110,8 +1112,12 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         call.ecParamsQueued = true;
         return MSDFHIP_OK;
     }
-    hipLaunchKernelGGL((k_ec_fast<N>), dim3(blocks), dim3(WAVE), fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
-                       (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
+    if (lazyProtect)
+        hipLaunchKernelGGL((k_ec_fast<N, true>), dim3(blocks), dim3(WAVE), fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
+                           (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
+    else
+        hipLaunchKernelGGL((k_ec_fast<N, false>), dim3(blocks), dim3(WAVE), fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
+                           (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
     hipLaunchKernelGGL(k_ec_scan, dim3(1), dim3(1024), 0, stream, b->nGlyphs, reinterpret_cast<const unsigned *>(deferred), seg, offsets, lpcMaxContours, ecOrder);
     hipLaunchKernelGGL((k_ec_query<N, OVERLAP>), dim3(queryBlocks), dim3(WAVE), queryLds, stream, b->nGlyphs, b->dGlyphContourOffsets, b->dContourOffsets,
                        (const EdgeRec *) viewOf(b).recs, viewOf(b).windings, dGlyphs, w, h, src, out, stencil, cfg,

@@ -15,6 +15,14 @@
 //  * Diagonal pairs: solveQuadratic (sqrt + 2 divisions) is skipped when the quadratic provably has no real root in
 //    [0.005, 0.995] (the reference keeps only roots in (0.01, 0.99); the computed roots are within ~1e-4 of the real ones because
 //    |b| <= 1e12*|a| in that branch).  The extremum parameters tEx (3 divisions) are computed only when a root survives.
+//  * Lazy protection (EDGE_PRIORITY with CHECK_DISTANCE_AT_EDGE, the library default): protectAll() precedes the shape pass, so the
+//    stencil byte carries PROTECTED whatever protectCorners / protectEdges found, and the shape classifier never reads their bit.
+//    The base classifier reads it only for a candidate that is no inversion, lies outside the range of its end points and fails the
+//    span test: a CONDITIONAL artifact, an ERROR iff the texel is unprotected.  The sweep therefore runs as if every texel were
+//    protected, reports such candidates in a third verdict bit, and only a texel that has one and no unconditional ERROR takes the
+//    corner test and the protectEdges pairs afterwards.  Where a diagonal pair would hand a distance-check candidate to the sink at or
+//    after a conditional artifact of the same pair (unprotected, the eager order has left the pair by then), the candidate is held
+//    back (fourth bit) and handed over in a second visit of that pair once the texel is known to be protected: same candidate set.
 #pragma once
 
 #include "msdf_ec.hpp"
@@ -23,38 +31,54 @@ namespace msdfhip {
 
 enum { EC_DEFER = 0x80 };   // internal: texel must be re-evaluated by the full pipeline (needs a shape-distance query)
 
+// Verdict bits of judge() / evaluatePair() / texelFindFast(). The last two only arise in the lazy order.
+enum { EC_V_ERROR = 1,      // ERROR decided
+       EC_V_CHECK = 2,      // some candidate needs the distance check
+       EC_V_COND = 4,       // conditional artifact: ERROR iff the texel turns out unprotected
+       EC_V_HELD = 8 };     // a distance-check candidate was held back behind a conditional artifact of its pair
+// Order of a sweep: eager (protection known, `p1`), the lazy first visit (protection assumed), the lazy second visit of a pair of a
+// texel now known to be protected (hands over the held-back candidates, nothing else).
+enum { EC_ORDER_EAGER = 0, EC_ORDER_LAZY = 1, EC_ORDER_LAZY_HELD = 2 };
+
 // Which of the reference's two findErrors passes apply (core/msdf-error-correction.cpp:36-46).
 MSDF_HD bool ecHasBasePass(const EcParams &p) { return p.distanceCheck == EC_DO_NOT_CHECK || (p.distanceCheck == EC_CHECK_AT_EDGE && p.mode != EC_MODE_EDGE_ONLY); }
 MSDF_HD bool ecHasShapePass(const EcParams &p) { return p.distanceCheck == EC_ALWAYS_CHECK || p.distanceCheck == EC_CHECK_AT_EDGE; }
+// The one configuration in which a texel's protection can be resolved after the sweep (header comment): elsewhere the shape pass
+// reads the bit (ALWAYS_CHECK), the stencil shows it (DO_NOT_CHECK) or there is nothing to resolve (EDGE_ONLY, INDISCRIMINATE).
+MSDF_HD bool ecLazyProtect(const EcParams &p) { return p.mode == EC_MODE_EDGE_PRIORITY && p.distanceCheck == EC_CHECK_AT_EDGE; }
 
 struct FastCtx {
     double span;
     bool p1;          // protectedFlag of the base pass (and of the shape pass under ALWAYS_CHECK)
     bool pShape;      // protectedFlag of the shape pass
     bool basePass, shapePass;
+    int order;        // EC_ORDER_*; the lazy orders run with p1 = pShape = true
 };
 
-// rangeTest (:30-40) for both classifiers at once. Returns flags of the base pass in bits 0-1 and of the shape pass in bits 2-3.
+// rangeTest (:30-40) for both classifiers at once. Returns flags of the base pass in bits 0-1 and of the shape pass in bits 2-3; in the
+// lazy order bit 4: the base pass has an artifact here iff its protectedFlag is false (it exists only through `!p1 && outside`).
 MSDF_HD int rangeTest2(const FastCtx &c, double at, double bt, double xt, float am, float bm, float xm) {
     const bool inversion = (am > .5f && bm > .5f && xm <= .5f) || (am < .5f && bm < .5f && xm >= .5f);
     const bool outside = medianf(am, bm, xm) != xm;
     const bool candBase = c.basePass && (inversion || (!c.p1 && outside));
     const bool candShape = c.shapePass && (inversion || (!c.pShape && outside));
-    if (!(candBase || candShape))
+    const bool candCond = c.order != EC_ORDER_EAGER && !inversion && outside;
+    if (!(candBase || candShape || candCond))
         return 0;
     const double axSpan = (xt-at)*c.span, bxSpan = (bt-xt)*c.span;
     const int f = (xm >= am-axSpan && xm <= am+axSpan && xm >= bm-bxSpan && xm <= bm+bxSpan) ? 1 : 3;
-    return (candBase ? f : 0)|(candShape ? f<<2 : 0);
+    return (candBase ? f : 0)|(candShape ? f<<2 : 0)|(candCond && f == 3 ? 16 : 0);
 }
 
-// 1: ERROR decided; 2: needs the distance check; 0: nothing.
+// EC_V_ERROR: ERROR decided; EC_V_CHECK: needs the distance check; 0: nothing. EC_V_COND rides along from bit 4 of rangeTest2.
 MSDF_HD int judge(int flags) {
+    const int cond = (flags&16) ? EC_V_COND : 0;
     if (flags&2)
-        return 1;                     // base classifier: evaluate() == (flags&ARTIFACT) (:42-44)
-    const int fs = flags>>2;
+        return EC_V_ERROR|cond;       // base classifier: evaluate() == (flags&ARTIFACT) (:42-44)
+    const int fs = (flags>>2)&3;
     if (fs&1)
-        return (fs&2) ? 1 : 2;        // shape classifier: artifact already, or candidate -> distance check (:60-64)
-    return 0;
+        return ((fs&2) ? EC_V_ERROR : EC_V_CHECK)|cond;   // shape classifier: artifact already, or candidate -> distance check (:60-64)
+    return cond;
 }
 
 // Conservative: false only if a*t^2+b*t+c has no real root in [0.005, 0.995] (see header comment). a, b, c as passed to solveQuadratic.
@@ -109,7 +133,9 @@ MSDF_HD int edgeBetweenTexelsFast(const float *a, const float *b) {
 }
 
 // One diagonal channel pair (:291-327) with lazy extremum parameters. Returns judge() of the accumulated flags, OR-ed over roots;
-// candidates that need the distance check are handed to `sink(t)`.
+// candidates that need the distance check are handed to `sink(t)`. Lazy order: a candidate at or after a conditional artifact of this
+// pair is held back (EC_V_HELD) -- were the texel unprotected, the eager order would have returned ERROR at that artifact -- and
+// handed over by the EC_ORDER_LAZY_HELD visit, which hands over nothing else.
 template <class Sink>
 MSDF_HD int diagonalPairFast(const FastCtx &cx, float am, float dm, const float *a, const float *l, const float *q,
                              float dA, float dBC, float dD, float l0, float q0, float l1, float q1, Sink &sink) {
@@ -145,10 +171,15 @@ MSDF_HD int diagonalPairFast(const FastCtx &cx, float am, float dm, const float 
                 rangeFlags |= rangeTest2(cx, tEnd0, tEnd1, t[i], em0, em1, xm);
             }
             const int v = judge(rangeFlags);
-            if (v&2)
-                sink(t[i]);
             verdict |= v;
-            if (verdict&1)
+            if (v&EC_V_CHECK) {
+                const bool held = (verdict&EC_V_COND) != 0;
+                if (held)
+                    verdict |= EC_V_HELD;
+                if (held == (cx.order == EC_ORDER_LAZY_HELD))
+                    sink(t[i]);
+            }
+            if (verdict&EC_V_ERROR)
                 return verdict;
         }
     }
@@ -291,26 +322,31 @@ MSDF_HD void texelCandidatePairs(const Neighbourhood &nb, Emit &emit) {
 MSDF_HD float pick3(const float *v, int i) { return i == 0 ? v[0] : i == 1 ? v[1] : v[2]; }
 
 // Stage 2: one surviving test. c: centre texel, n: the neighbour k, hb / vc: the horizontal / vertical neighbours on the way to a
-// diagonal one (unused for k < 4); any memory (registers, LDS). Returns judge() bits (1: ERROR decided, 2: needs the distance check, then
-// also reported as sink(t, dx, dyShape)). Same operands and operations as hasLinearArtifact / hasDiagonalArtifact (:330-381).
+// diagonal one (unused for k < 4); any memory (registers, LDS). Returns EC_V_* bits (a candidate that needs the distance check is also
+// reported as sink(t, dx, dyShape)). Same operands and operations as hasLinearArtifact / hasDiagonalArtifact (:330-381).
+// order: EC_ORDER_EAGER with the texel's protection in p1, or one of the lazy orders (only where ecLazyProtect(p); p1 is ignored).
 template <class Sink>
-MSDF_HD int evaluatePair(const float *c, const float *n, const float *hb, const float *vc, const EcParams &p, bool p1, int flip, int k, int j, Sink &sink) {
+MSDF_HD int evaluatePair(const float *c, const float *n, const float *hb, const float *vc, const EcParams &p, bool p1, int flip, int k, int j, Sink &sink,
+                         int order = EC_ORDER_EAGER) {
     FastCtx cx;
     cx.basePass = ecHasBasePass(p);
     cx.shapePass = ecHasShapePass(p);
-    cx.p1 = p1;
-    cx.pShape = (p.distanceCheck == EC_CHECK_AT_EDGE) ? true : p1;   // protectAll() precedes the shape pass only in that mode (:38-39, :33)
+    cx.order = order;
+    cx.p1 = order != EC_ORDER_EAGER || p1;
+    cx.pShape = (p.distanceCheck == EC_CHECK_AT_EDGE) ? true : cx.p1;   // protectAll() precedes the shape pass only in that mode (:38-39, :33)
     const int dx = ecNeighbourDx(k), dy = ecNeighbourDy(k);
     const int i0 = j, i1 = j == 2 ? 0 : j+1;
     const float cm = medianf(c[0], c[1], c[2]), nm = medianf(n[0], n[1], n[2]);
     if (k < 4) {
+        if (order == EC_ORDER_LAZY_HELD)
+            return 0;                                    // one range test per pair: a candidate (inversion) is never conditional as well
         cx.span = dy == 0 ? p.hSpan : p.vSpan;
         const float dA = pick3(c, i1)-pick3(c, i0), dB = pick3(n, i1)-pick3(n, i0);
         const double t = (double) dA/(dA-dB);            // :281
         if (t > MSDF_ARTIFACT_T_EPSILON && t < 1-MSDF_ARTIFACT_T_EPSILON) {
             const float xm = interpolatedMedianLin(c, n, t);
             const int v = judge(rangeTest2(cx, 0, 1, t, cm, nm, xm));
-            if (v&2)
+            if (v&EC_V_CHECK)
                 sink(t, dx, flip ? -dy : dy);
             return v;
         }
@@ -331,10 +367,10 @@ MSDF_HD int evaluatePair(const float *c, const float *n, const float *hb, const 
     return diagonalPairFast(cx, cm, nm, a3, l, q, dA, dBC, dD, pick3(l, i0), pick3(q, i0), pick3(l, i1), pick3(q, i1), dirSink);
 }
 
-// Both stages for one texel, test after test (host walk; the kernel queues the items instead). Returns bit0: ERROR decided, bit1: some
-// candidate needs the distance check; every such candidate is reported as sink(t, dx, dyShape) (MSDFErrorCorrection.cpp:446-453).
+// Both stages for one texel, test after test (host walk; the kernel queues the items instead). Returns EC_V_* bits OR-ed over the tests;
+// every candidate that needs the distance check is reported as sink(t, dx, dyShape) (MSDFErrorCorrection.cpp:446-453).
 template <class Sink>
-MSDF_HD int texelFindFast(const Neighbourhood &nb, const EcParams &p, bool p1, int flip, Sink &sink) {
+MSDF_HD int texelFindFast(const Neighbourhood &nb, const EcParams &p, bool p1, int flip, Sink &sink, int order = EC_ORDER_EAGER) {
     struct Items {
         unsigned char k[24], j[24];
         int n;
@@ -345,38 +381,56 @@ MSDF_HD int texelFindFast(const Neighbourhood &nb, const EcParams &p, bool p1, i
     int verdict = 0;
     for (int i = 0; i < items.n; ++i) {
         const int k = items.k[i], dx = ecNeighbourDx(k), dy = ecNeighbourDy(k);
-        verdict |= evaluatePair(nb.v[1][1], nb.v[dy+1][dx+1], nb.v[1][dx+1], nb.v[dy+1][1], p, p1, flip, k, items.j[i], sink);
+        verdict |= evaluatePair(nb.v[1][1], nb.v[dy+1][dx+1], nb.v[1][dx+1], nb.v[dy+1][1], p, p1, flip, k, items.j[i], sink, order);
     }
     return verdict;
 }
 
+// Does texel (x, ys) [shape orientation] belong to one of the corner pairs? corners: (l, b) of protectCorners (:131-134).
+MSDF_HD bool protectedByCornerList(const int *corners, int nCorners, int x, int ys) {
+    for (int i = 0; i < nCorners; ++i) {
+        const int l = corners[2*i], b = corners[2*i+1];
+        if ((x == l || x == l+1) && (ys == b || ys == b+1))
+            return true;
+    }
+    return false;
+}
+
+// Does the lazy first visit leave the texel's protection to be resolved? A conditional artifact decides the texel unless an
+// unconditional ERROR already has; a held-back candidate is handed over iff the texel is protected, whatever its verdict.
+MSDF_HD bool ecNeedsProtection(int verdict) { return ((verdict&EC_V_COND) && !(verdict&EC_V_ERROR)) || (verdict&EC_V_HELD); }
+
 // Stencil byte of texel (x, yn) [native order] by the fast path: PROTECTED/ERROR as in ecTexelStencil, plus EC_DEFER if the verdict
 // hinges on shape-distance checks (each reported through `sink`). corners: (l, b) pairs of protectCorners (:131-134) in shape
-// orientation, precomputed per tile.
+// orientation, precomputed per tile. Takes the lazy order where the mode allows it, as the kernel does (allowLazy = false: the eager
+// order everywhere; the two are compared by tests/test_ec_lazy_host.py).
 template <class Sink>
-MSDF_HD int ecTexelFast(const SdfView &sdf, const EcParams &p, const int *corners, int nCorners, int x, int yn, Sink &sink) {
+MSDF_HD int ecTexelFast(const SdfView &sdf, const EcParams &p, const int *corners, int nCorners, int x, int yn, Sink &sink, bool allowLazy = true) {
     const int ys = sdf.flip ? sdf.h-1-yn : yn;
     Neighbourhood nb;
     loadNeighbourhood(nb, sdf, x, yn);
-    int st = 0;
-    if (p.mode == EC_MODE_EDGE_PRIORITY) {
-        for (int i = 0; i < nCorners; ++i) {
-            const int l = corners[2*i], b = corners[2*i+1];
-            if ((x == l || x == l+1) && (ys == b || ys == b+1)) {
-                st |= EC_PROTECTED;
-                break;
-            }
+    int st = 0, verdict;
+    if (allowLazy && ecLazyProtect(p)) {
+        verdict = texelFindFast(nb, p, true, sdf.flip, sink, EC_ORDER_LAZY);
+        if (ecNeedsProtection(verdict)) {
+            if (!(protectedByCornerList(corners, nCorners, x, ys) || protectedByEdgesNb(nb, p)))
+                verdict |= EC_V_ERROR;                       // (a held-back candidate implies a conditional artifact)
+            else if (verdict&EC_V_HELD)
+                texelFindFast(nb, p, true, sdf.flip, sink, EC_ORDER_LAZY_HELD);
         }
-        if (!(st&EC_PROTECTED) && protectedByEdgesNb(nb, p))
+    } else {
+        if (p.mode == EC_MODE_EDGE_PRIORITY) {
+            if (protectedByCornerList(corners, nCorners, x, ys) || protectedByEdgesNb(nb, p))
+                st |= EC_PROTECTED;
+        } else if (p.mode == EC_MODE_EDGE_ONLY)
             st |= EC_PROTECTED;
-    } else if (p.mode == EC_MODE_EDGE_ONLY)
-        st |= EC_PROTECTED;
-    const int verdict = texelFindFast(nb, p, (st&EC_PROTECTED) != 0, sdf.flip, sink);
+        verdict = texelFindFast(nb, p, (st&EC_PROTECTED) != 0, sdf.flip, sink);
+    }
     if (ecHasBasePass(p) && p.distanceCheck == EC_CHECK_AT_EDGE)
         st |= EC_PROTECTED;                              // protectAll (:38-39)
-    if (verdict&1)
+    if (verdict&EC_V_ERROR)
         st |= EC_ERROR;
-    else if (verdict&2)
+    else if (verdict&EC_V_CHECK)
         st |= EC_DEFER;
     return st;
 }

@@ -6,7 +6,8 @@
 //                                 selection tile after tile (lanes = texels) in fp64 registers; the surviving edge records are read
 //                                 with wave-uniform scalar loads. The overlapping contour combiner keeps its per-contour distances in
 //                                 LDS, laid out [contour][channel][lane] (lane-consecutive 8-byte accesses: bank-conflict free).
-//   k_ec_fast<N>                  error correction, lean single sweep over all texels (gather form, no atomics on the stencil);
+//   k_ec_fast<N, LAZY>            error correction, lean single sweep over all texels (gather form, no atomics on the stencil); LAZY: protection resolved
+//                                 after the sweep, only for the texels whose verdict hinges on it (the library-default configuration);
 //                                 texels whose verdict needs an exact shape-distance query (~0.1 %) are appended to a list
 //   k_ec_slow<N,OVERLAP>          full per-texel pipeline incl. the PSDF distance query for the listed texels
 //   k_shape_distance<SEL,OVERLAP> distance queries at arbitrary points (known-answer tests)
@@ -1207,7 +1208,7 @@ k_ec_params(EcGlyphParams *out, BatchView batch, const MsdfHipGlyph *glyphs, Msd
 // the stencil byte [g][h][w] (native rows). Candidates whose verdict needs an exact shape-distance query are appended to `cands`
 // and judged by k_ec_query; a texel with a cheaply decided ERROR never needs them (the flag is an OR).
 #ifndef MSDF_EC_FAST_WAVES_PER_SIMD
-#define MSDF_EC_FAST_WAVES_PER_SIMD 7   // 72 VGPRs, no spills; the kernel's 5.6 KB of LDS allow 7 wavefronts per SIMD anyway. Correction pass on the distinct-glyph set: 8 -> 1.94 ms, 7 -> 1.90, 6 -> 1.90
+#define MSDF_EC_FAST_WAVES_PER_SIMD 7   // lazy instantiation 63 VGPRs / 17 scalar registers parked in vector lanes, eager 65 / 2; no vector spills, no scratch (tests/test_ec_fast_isa_budget.py); the kernel's 5.6 KB of LDS allow 7 wavefronts per SIMD anyway. Correction pass on the distinct-glyph set: 8 -> 1.94 ms, 7 -> 1.90, 6 -> 1.90
 #endif
 // LDS of k_ec_fast per wavefront: 10x10 halo tile of the field | per-texel verdict words | item count | item queue (5.6 KB for msdf).
 enum { EC_HALO = TILE+2, EC_QUEUE_CAP = WAVE*24, EC_PROTECT_QUEUE_CAP = WAVE*8 };
@@ -1216,7 +1217,58 @@ __host__ __device__ inline size_t ecFastLdsBytes(int maxEdges, int n) {
            +(EC_QUEUE_CAP+EC_PROTECT_QUEUE_CAP)*sizeof(unsigned short);
 }
 
+// protectCorners (MSDFErrorCorrection.cpp:121-151) for the texels of one tile: lanes = the glyph's corner texel pairs (k_ec_params); the few that touch the
+// tile are broadcast one by one and every texel lane tests itself -- no list in LDS (it had been sized by the batch's largest glyph and capped the kernel at
+// 4 wavefronts per SIMD on a batch with one 543-edge symbol). All lanes of the wavefront call it together.
+__device__ __forceinline__ bool ecTileCornerTexel(const int *list, int nCorners, int tx, int ty, int height, int flip, int lane) {
+    const int lxT = lane&(TILE-1), lyT = lane>>3;
+    const int xT = tx*TILE+lxT, ysT = flip ? height-1-(ty*TILE+lyT) : ty*TILE+lyT;
+    const int x0 = tx*TILE, x1 = tx*TILE+TILE-1;
+    const int ya = flip ? height-1-(ty*TILE+TILE-1) : ty*TILE, yb = flip ? height-1-ty*TILE : ty*TILE+TILE-1;   // shape-space rows of the tile
+    bool cornerTexel = false;
+    for (int base = 0; base < nCorners; base += WAVE) {
+        const int k = base+lane;
+        int l = 0, b = 0;
+        bool near = false;
+        if (k < nCorners) {
+            l = list[2*k], b = list[2*k+1];
+            near = l+1 >= x0 && l <= x1 && b+1 >= ya && b <= yb;
+        }
+        for (unsigned long long mask = __ballot(near); mask; mask &= mask-1) {
+            const int src = __ffsll((long long) mask)-1;
+            const int cl = __builtin_amdgcn_readlane(l, src), cb = __builtin_amdgcn_readlane(b, src);
+            cornerTexel = cornerTexel || ((xT == cl || xT == cl+1) && (ysT == cb || ysT == cb+1));
+        }
+    }
+    return cornerTexel;
+}
+
+// protectEdges' edgeBetweenTexels tests of the queued pairs (lane | m<<6), densely: lane = pair; a hit protects the owning texel (bit 8 of its word).
 template <int N>
+__device__ __forceinline__ void ecRunProtectQueue(const float *halo, const unsigned short *protectQueue, int nProtect, int *verdictLds, int lane) {
+    for (int base = 0; base < nProtect; base += WAVE) {
+        const int it = base+lane;
+        if (it >= nProtect)
+            continue;
+        const unsigned item = protectQueue[it];
+        const int s = item&63, m = item>>6;
+        const int sx = s&(TILE-1), sy = s>>3;
+        const float *self = halo+((sy+1)*EC_HALO+sx+1)*N, *other = halo+((sy+m/3)*EC_HALO+sx+m%3)*N;
+        if (evaluateProtectPair(self, other, m))
+            atomicOr(&verdictLds[s], 0x100);
+    }
+}
+
+struct EcPushProtect {
+    unsigned short *queue;
+    int *count;
+    int lane;
+    __device__ void operator()(int m) { queue[atomicAdd(count, 1)] = (unsigned short) (lane|m<<6); }
+};
+
+// ORDER: 1 the lazy order, 0 the eager one -- k_ec_fast has an instantiation of each and the host picks by the configuration (63 / 65 VGPRs, 17 / 2 scalar
+// registers parked in vector lanes, all outside the queue loops; both orders in one body: 28) -- or -1: decided here, one body for k_single_call.
+template <int N, int ORDER = -1>
 __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHipGlyph *glyphs, int width, int height, int tilesX, int tilesPerGlyph,
           const float *src, float *out, uint8_t *stencilOut, const MsdfHipConfig &cfg, const EcGlyphParams *glyphParams, EcCandidate *cands, unsigned seg,
           int maxEdges, const int *corners, const unsigned blockId, int *smemFast, const int sinkSlots = 0, const int sinkSlot = 0) {
@@ -1226,7 +1278,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     if (!wk.valid)
         return;
     float *halo = reinterpret_cast<float *>(smemFast);                                      // [EC_HALO*EC_HALO][N]
-    int *verdictLds = reinterpret_cast<int *>(halo+EC_HALO*EC_HALO*N);                      // [WAVE]: bits 0-1 judge(), bit 8 protected
+    int *verdictLds = reinterpret_cast<int *>(halo+EC_HALO*EC_HALO*N);                      // [WAVE]: bits 0-3 EC_V_*, bit 8 protected
     int *itemCount = verdictLds+WAVE;
     unsigned short *queue = reinterpret_cast<unsigned short *>(itemCount+4);               // [EC_QUEUE_CAP]: lane | k<<6 | j<<9
     unsigned short *protectQueue = queue+EC_QUEUE_CAP;                                      // [EC_PROTECT_QUEUE_CAP]: lane | m<<6
@@ -1247,31 +1299,12 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     p.radiusH = gp.radiusH, p.radiusV = gp.radiusV, p.radiusD = gp.radiusD;
     const int tx = wk.tile%tilesX, ty = wk.tile/tilesX;
 
-    // protectCorners (MSDFErrorCorrection.cpp:121-151): lanes = the glyph's corner texel pairs (k_ec_params); the few that touch this
-    // tile are broadcast one by one and every texel lane tests itself -- no list in LDS (it had been sized by the batch's largest glyph
-    // and capped the kernel at 4 wavefronts per SIMD on a batch with one 543-edge symbol)
-    const int lxT = lane&(TILE-1), lyT = lane>>3;
-    const int xT = tx*TILE+lxT, ysT = gd.flip ? height-1-(ty*TILE+lyT) : ty*TILE+lyT;
+    // The lazy order (msdf_ec_fast.hpp: ecLazyProtect -- wave-uniform, the library default): protection is resolved after the sweep, for the few texels whose
+    // verdict hinges on it; every other configuration resolves it first, for all texels.
+    const bool lazy = ORDER < 0 ? ecLazyProtect(p) : ORDER != 0;
     bool cornerTexel = false;
-    if (p.mode == EC_MODE_EDGE_PRIORITY) {
-        const int x0 = tx*TILE, x1 = tx*TILE+TILE-1;
-        const int ya = gd.flip ? height-1-(ty*TILE+TILE-1) : ty*TILE, yb = gd.flip ? height-1-ty*TILE : ty*TILE+TILE-1;   // shape-space rows of the tile
-        const int *list = corners+2*(size_t) gp.cornerBegin;
-        for (int base = 0; base < gp.nCorners; base += WAVE) {
-            const int k = base+lane;
-            int l = 0, b = 0;
-            bool near = false;
-            if (k < gp.nCorners) {
-                l = list[2*k], b = list[2*k+1];
-                near = l+1 >= x0 && l <= x1 && b+1 >= ya && b <= yb;
-            }
-            for (unsigned long long mask = __ballot(near); mask; mask &= mask-1) {
-                const int src = __ffsll((long long) mask)-1;
-                const int cl = __builtin_amdgcn_readlane(l, src), cb = __builtin_amdgcn_readlane(b, src);
-                cornerTexel = cornerTexel || ((xT == cl || xT == cl+1) && (ysT == cb || ysT == cb+1));
-            }
-        }
-    }
+    if (p.mode == EC_MODE_EDGE_PRIORITY && !lazy)
+        cornerTexel = ecTileCornerTexel(corners+2*(size_t) gp.cornerBegin, gp.nCorners, tx, ty, height, gd.flip, lane);
 
     // ---- the tile and its one-texel halo go to LDS once (native rows); texels outside the bitmap are never read back
     const float *field = src+(size_t) wk.g*height*width*N;
@@ -1314,16 +1347,11 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     }
     waveSync();                                                         // devLds is dead from here on: the queue may grow into it
     if (classify) {
-        if (p.mode == EC_MODE_EDGE_PRIORITY) {
+        if (p.mode == EC_MODE_EDGE_PRIORITY && !lazy) {
             if (cornerTexel)
                 st |= EC_PROTECTED;
             if (!(st&EC_PROTECTED)) {
-                struct PushProtect {
-                    unsigned short *queue;
-                    int *count;
-                    int lane;
-                    __device__ void operator()(int m) { queue[atomicAdd(count, 1)] = (unsigned short) (lane|m<<6); }
-                } pushProtect = { protectQueue, itemCount+1, lane };
+                EcPushProtect pushProtect = { protectQueue, itemCount+1, lane };
                 texelProtectPairs(nb, p, pushProtect);
             }
         } else if (p.mode == EC_MODE_EDGE_ONLY)
@@ -1339,50 +1367,98 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     verdictLds[lane] = (st&EC_PROTECTED) ? 0x100 : 0;
     waveSync();
 
-    // ---- phase B (lane = queued pair): protectEdges' edgeBetweenTexels tests, densely; a hit protects the owning texel
-    const int nProtect = itemCount[1];
-    for (int base = 0; base < nProtect; base += WAVE) {
-        const int it = base+lane;
-        if (it >= nProtect)
-            continue;
-        const unsigned item = protectQueue[it];
-        const int s = item&63, m = item>>6;
-        const int sx = s&(TILE-1), sy = s>>3;
-        const float *self = halo+((sy+1)*EC_HALO+sx+1)*N, *other = halo+((sy+m/3)*EC_HALO+sx+m%3)*N;
-        if (evaluateProtectPair(self, other, m))
-            atomicOr(&verdictLds[s], 0x100);
+    // ---- phase B (lane = queued pair): protectEdges' edgeBetweenTexels tests, densely; a hit protects the owning texel (eager order; the lazy one has queued none)
+    if (!lazy) {
+        ecRunProtectQueue<N>(halo, protectQueue, itemCount[1], verdictLds, lane);
+        waveSync();
     }
+
+    // ---- phase C (lane = queued test): stage 2, densely; verdicts are OR-ed into the owning texel's word. The lazy order comes back once more
+    // (EC_ORDER_LAZY_HELD) for the pairs of texels that held a distance-check candidate back and turned out protected.
+    const int nItems = itemCount[0];
+    const auto runItems = [&](const int order) {
+        for (int base = 0; base < nItems; base += WAVE) {
+            const int it = base+lane;
+            if (it >= nItems)
+                continue;
+            const unsigned item = queue[it];
+            const int s = item&63, k = (item>>6)&7, jp = item>>9;
+            const int word = verdictLds[s];
+            if (order == EC_ORDER_LAZY_HELD && (word&(0x100|EC_V_HELD)) != (0x100|EC_V_HELD))
+                continue;
+            const int sx = s&(TILE-1), sy = s>>3;
+            const int dx = ecNeighbourDx(k), dy = ecNeighbourDy(k);
+            const float *c = halo+((sy+1)*EC_HALO+sx+1)*N, *n = halo+((sy+1+dy)*EC_HALO+sx+1+dx)*N;
+            const float *hb = halo+((sy+1)*EC_HALO+sx+1+dx)*N, *vc = halo+((sy+1+dy)*EC_HALO+sx+1)*N;
+            CandidateSink sink;
+            sink.header = reinterpret_cast<unsigned *>(cands);
+            sink.segment = sinkSlots > 0 ? cands+ecHeaderRecords(sinkSlots)+(size_t) sinkSlot*seg : cands+ecHeaderRecords(batch.nGlyphs)+(size_t) wk.g*seg;
+            sink.seg = seg, sink.g = sinkSlots > 0 ? sinkSlot : wk.g;
+            sink.texel = (unsigned) (((size_t) wk.g*height+ty*TILE+sy)*width+tx*TILE+sx);
+            const int v = evaluatePair(c, n, hb, vc, p, (word&0x100) != 0, gd.flip, k, jp, sink, order);
+            if (v && order != EC_ORDER_LAZY_HELD)
+                atomicOr(&verdictLds[s], v);
+        }
+    };
+    runItems(lazy ? EC_ORDER_LAZY : EC_ORDER_EAGER);
     waveSync();
 
-    // ---- phase C (lane = queued test): stage 2, densely; verdicts are OR-ed into the owning texel's word
-    const int nItems = itemCount[0];
-    for (int base = 0; base < nItems; base += WAVE) {
-        const int it = base+lane;
-        if (it >= nItems)
-            continue;
-        const unsigned item = queue[it];
-        const int s = item&63, k = (item>>6)&7, jp = item>>9;
-        const int sx = s&(TILE-1), sy = s>>3;
-        const int dx = ecNeighbourDx(k), dy = ecNeighbourDy(k);
-        const float *c = halo+((sy+1)*EC_HALO+sx+1)*N, *n = halo+((sy+1+dy)*EC_HALO+sx+1+dx)*N;
-        const float *hb = halo+((sy+1)*EC_HALO+sx+1+dx)*N, *vc = halo+((sy+1+dy)*EC_HALO+sx+1)*N;
-        CandidateSink sink;
-        sink.header = reinterpret_cast<unsigned *>(cands);
-        sink.segment = sinkSlots > 0 ? cands+ecHeaderRecords(sinkSlots)+(size_t) sinkSlot*seg : cands+ecHeaderRecords(batch.nGlyphs)+(size_t) wk.g*seg;
-        sink.seg = seg, sink.g = sinkSlots > 0 ? sinkSlot : wk.g;
-        sink.texel = (unsigned) (((size_t) wk.g*height+ty*TILE+sy)*width+tx*TILE+sx);
-        const int v = evaluatePair(c, n, hb, vc, p, (verdictLds[s]&0x100) != 0, gd.flip, k, jp, sink);
-        if (v)
-            atomicOr(&verdictLds[s], v);
+    // ---- lazy protection (lane = texel): only texels whose verdict hinges on it, and only in wavefronts that have one
+    const bool need = lazy && inside && ecNeedsProtection(verdictLds[lane]);
+    if (__ballot(need)) {
+        // (the glyph's radii and corner list are read AGAIN: held in scalar registers across phase C they spilled, and this round is rare)
+        // This is register allocation by hand for one compiler: after a compiler update re-check the kernel's resource lines (VGPRs <= 72 = 7 wavefronts
+        // per SIMD, no vector spills, no scratch: tests/test_ec_fast_isa_budget.py) and that the v_writelane / v_readlane pairs of the parked scalars still
+        // sit outside the queue loops (tools/isa_bbcount.py); if they do without the barrier and the second read, drop both.
+        __asm__ volatile("" ::: "memory");
+        const EcGlyphParams gl = glyphParams[wk.g];
+        EcParams pr = p;
+        pr.radiusH = gl.radiusH, pr.radiusV = gl.radiusV, pr.radiusD = gl.radiusD;
+        cornerTexel = ecTileCornerTexel(corners+2*(size_t) gl.cornerBegin, gl.nCorners, tx, ty, height, gd.flip, lane);
+        if (need) {
+            if (cornerTexel)
+                verdictLds[lane] |= 0x100;
+            else {
+                // |median - .5| of the 3x3 texels again, from the halo: the table of the staging loop lies under the item queue
+                Neighbourhood nd;
+                nd.valid = 0;
+                MSDF_UNROLL
+                for (int dy = -1; dy <= 1; ++dy) {
+                    MSDF_UNROLL
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const int nx = x+dx, ny = yn+dy;
+                        const bool in = nx >= 0 && ny >= 0 && nx < width && ny < height;
+                        nd.dev[dy+1][dx+1] = ecTexelDeviation(halo+((ly+1+(in ? dy : 0))*EC_HALO+lx+1+(in ? dx : 0))*N);
+                        if (in)
+                            nd.valid |= 1u<<((dy+1)*3+(dx+1));
+                    }
+                }
+                EcPushProtect pushProtect = { protectQueue, itemCount+1, lane };
+                texelProtectPairs(nd, pr, pushProtect);
+            }
+        }
+        waveSync();
+        ecRunProtectQueue<N>(halo, protectQueue, itemCount[1], verdictLds, lane);
+        waveSync();
+        bool revisit = false;
+        if (need) {
+            const int word = verdictLds[lane];
+            if (!(word&0x100))
+                verdictLds[lane] = word|EC_V_ERROR;                 // an unprotected conditional artifact is an ERROR (a held-back candidate implies one)
+            revisit = (word&0x100) && (word&EC_V_HELD);
+        }
+        if (__ballot(revisit)) {                                    // hand over what the protected texels held back
+            waveSync();
+            runItems(EC_ORDER_LAZY_HELD);
+        }
     }
-    waveSync();
 
     if (!inside)
         return;
     const int verdict = verdictLds[lane];
     if ((verdict&0x100) || (ecHasBasePass(p) && p.distanceCheck == EC_CHECK_AT_EDGE))
         st |= EC_PROTECTED;                                         // protectEdges hit (phase B) / protectAll (:38-39)
-    if (verdict&1)
+    if (verdict&EC_V_ERROR)
         st |= EC_ERROR;
     const size_t texel = ((size_t) wk.g*height+yn)*width+x;
     const float *in = halo+((ly+1)*EC_HALO+lx+1)*N;
@@ -1399,13 +1475,13 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     if (stencilOut)
         stencilOut[stencilIndex(texel, yn, width, height, cfg.stencil_y_down)] = (uint8_t) st;
 }
-template <int N>
+template <int N, bool LAZY>
 __global__ void __launch_bounds__(WAVE, MSDF_EC_FAST_WAVES_PER_SIMD)
 k_ec_fast(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, int tilesX, int tilesPerGlyph,
           const float *src, float *out, uint8_t *stencilOut, MsdfHipConfig cfg, const EcGlyphParams *glyphParams, EcCandidate *cands, unsigned seg,
           int maxEdges, const int *corners) {
     extern __shared__ int smemFast[];
-    ecFastBody<N>(batch, glyphs, width, height, tilesX, tilesPerGlyph, src, out, stencilOut, cfg, glyphParams, cands, seg, maxEdges, corners, blockIdx.x, smemFast);
+    ecFastBody<N, LAZY ? 1 : 0>(batch, glyphs, width, height, tilesX, tilesPerGlyph, src, out, stencilOut, cfg, glyphParams, cands, seg, maxEdges, corners, blockIdx.x, smemFast);
 }
 
 // Two ways to spend a wavefront on deferred distance checks of a glyph with nE edges:
