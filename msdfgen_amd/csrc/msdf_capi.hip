@@ -27,6 +27,7 @@
 #include "msdf_classplan.hpp"
 #include "msdf_hostplan.hpp"
 #include "msdf_kernels.hpp"
+#include "msdf_launchplan.hpp"
 #include "msdf_single.hpp"
 
 using namespace msdfhip;
@@ -60,30 +61,13 @@ static long long nowNsEarly() { return std::chrono::duration_cast<std::chrono::n
 // Measurement / experiment knobs from the environment, read ONCE (first use, or msdfhip_reload_tuning() -- tests and A/B scripts flip them
 // between calls); the launch paths never touch getenv.
 struct Tuning {
-    size_t resLdsBudget;             // MSDFHIP_RES_LDS_BUDGET      bytes of LDS per wavefront up to which the combiner scratch stays in LDS
-    long persistentRounds;           // MSDFHIP_PERSISTENT_ROUNDS   global-scratch launches of at least this many rounds run persistent; 0 = never
-    bool serialClasses;              // MSDFHIP_SERIAL_CLASSES      glyph classes one after the other instead of on side streams
-    int querySlotCap, queryLpcContours;   // MSDFHIP_QUERY_LDS      "slotCap,lpcMaxContours"
-    bool hasQueryLds;
-    bool hasQueryPolicy;             // MSDFHIP_QUERY_POLICY        "edgeCost,maxEdges,minCount,wideMaxEdges,wideLoad[,wideMeanCount]"
-    int qpEdgeCost, qpMaxEdges, qpMinCount, qpWideMaxEdges;
-    float qpWideLoad, qpWideMeanCount;
-    size_t signCap;                  // MSDFHIP_SIGN_CAP            row-list capacity of the sign pass
+    PlanTuning plan;                 // what the launch plans read (msdf_launchplan.hpp)
     bool pipelineTrace;              // MSDFHIP_PIPELINE_TRACE      host-output pipeline prints per chunk when its kernels / its copy back finished (stderr)
     int microbatch;                  // MSDFHIP_MICROBATCH          0 / 1 disables the grouping of concurrent single-shape calls; N caps the group
-    int queryStatic;                 // MSDFHIP_QUERY_STATIC        2: first ticket dealt, the others from eight counters; 0: k_ec_query draws its tickets from an atomic counter (rounds 2-5) instead of the static serpentine deal
-    int queryGridSteps;              // MSDFHIP_QUERY_GRID          grid form of the distance checks: edges a lane may walk per item (0 = off: the two older forms only)
-    int queryBatch;                  // MSDFHIP_QUERY_BATCH         cooperative distance checks a wavefront of k_ec_query takes per ticket (default 1: more only lengthens the tail)
     bool noArgPayloadSingle;         // MSDFHIP_NO_ARG_PAYLOAD_SINGLE k_single_call reads small shapes from the staging area instead of its kernel arguments (A/B)
     bool noZeroCopySingle;           // MSDFHIP_NO_ZERO_COPY_SINGLE k_single_call on uploaded inputs / device outputs + one copy back (A/B)
     bool noFusedSingle;              // MSDFHIP_NO_FUSED_SINGLE     single-shape calls through the batched launch sequence instead of k_single_call (A/B)
-    double shareGridFactor;          // MSDFHIP_SHARE_GRID          the global-scratch class's persistent grid = its share of the batch's cost x this factor of the slots (0: off)
-    long persistentGrid;             // MSDFHIP_PERSISTENT_GRID     workgroups of a persistent global-scratch launch (0: one per resident wavefront slot)
-    long shortRounds;                // MSDFHIP_SHORT_ROUNDS        LDS-class launches of fewer rounds of four-tile wavefronts take one tile per wavefront
-    long smallLaunchTiles;           // MSDFHIP_SMALL_LAUNCH_TILES  launches of at most this many tiles take one tile per wavefront (latency-shaped form)
     char devices[256];               // MSDFHIP_DEVICES             "all" | "0,1,..." devices the single-shape front door spreads over
-    int smallMaxEdges;               // MSDFHIP_SMALL_MAX_EDGES     glyphs of the LDS-scratch class have at most this many edges (128)
-    int ldsClassTpw;                 // MSDFHIP_LDS_CLASS_TPW       tiles per wavefront of the LDS-scratch class: 4 (default; 1 in short launches) or always 1
     int pipelineDepth;               // MSDFHIP_PIPELINE_DEPTH      chunks of the host-output pipeline whose kernels may run at the same time (2; at most PIPE_SLOTS-1)
     bool prepLargeTier;              // MSDFHIP_PREP_LARGE_TIER     tests: the colouring kernel always with its 2 048-edge LDS tables (default: 256-edge tier when no contour is longer)
     int hostThreads;                 // MSDFHIP_HOST_THREADS        host threads of the streamed generator's flatten pool (0 = the usable cores, at most 32); read when the pool is created
@@ -99,42 +83,39 @@ std::vector<Tuning *> gTuningTables;                             // every table 
 
 void readTuning() {
     Tuning &t = *new Tuning;
+    PlanTuning &p = t.plan;                                      // (at its defaults)
     const char *env;
-    t.resLdsBudget = (env = getenv("MSDFHIP_RES_LDS_BUDGET")) ? (size_t) atol(env) : (size_t) 10*1024;
-    t.persistentRounds = (env = getenv("MSDFHIP_PERSISTENT_ROUNDS")) ? atol(env) : 8;
-    t.serialClasses = getenv("MSDFHIP_SERIAL_CLASSES") != NULL;
-    t.querySlotCap = 160, t.queryLpcContours = 24;
-    t.hasQueryLds = (env = getenv("MSDFHIP_QUERY_LDS")) != NULL;
+    p.resLdsBudget = (env = getenv("MSDFHIP_RES_LDS_BUDGET")) ? (size_t) atol(env) : p.resLdsBudget;
+    p.persistentRounds = (env = getenv("MSDFHIP_PERSISTENT_ROUNDS")) ? atol(env) : p.persistentRounds;
+    p.serialClasses = getenv("MSDFHIP_SERIAL_CLASSES") != NULL;
+    p.hasQueryLds = (env = getenv("MSDFHIP_QUERY_LDS")) != NULL;
     if (env)
-        sscanf(env, "%d,%d", &t.querySlotCap, &t.queryLpcContours);
-    t.qpEdgeCost = 150, t.qpMaxEdges = 48, t.qpMinCount = 0x7fffffff, t.qpWideMaxEdges = 128, t.qpWideLoad = 4e8f, t.qpWideMeanCount = 24.f;
-    t.hasQueryPolicy = (env = getenv("MSDFHIP_QUERY_POLICY")) != NULL;
+        sscanf(env, "%d,%d", &p.querySlotCap, &p.queryLpcContours);
+    p.hasQueryPolicy = (env = getenv("MSDFHIP_QUERY_POLICY")) != NULL;
     if (env)
-        sscanf(env, "%d,%d,%d,%d,%f,%f", &t.qpEdgeCost, &t.qpMaxEdges, &t.qpMinCount, &t.qpWideMaxEdges, &t.qpWideLoad, &t.qpWideMeanCount);
-    t.signCap = (env = getenv("MSDFHIP_SIGN_CAP")) ? (size_t) atol(env) : (size_t) 192;
-    if (t.signCap < 3)                                           // one edge's intersections per row: below, the sign pass's chunks would hold no edge
-        t.signCap = 3;
+        sscanf(env, "%d,%d,%d,%d,%f,%f", &p.qpEdgeCost, &p.qpMaxEdges, &p.qpMinCount, &p.qpWideMaxEdges, &p.qpWideLoad, &p.qpWideMeanCount);
+    p.signCap = (env = getenv("MSDFHIP_SIGN_CAP")) ? (size_t) atol(env) : p.signCap;
+    if (p.signCap < 3)                                           // one edge's intersections per row: below, the sign pass's chunks would hold no edge
+        p.signCap = 3;
     t.pipelineTrace = getenv("MSDFHIP_PIPELINE_TRACE") != NULL;
     t.microbatch = (env = getenv("MSDFHIP_MICROBATCH")) ? atoi(env) : 256;
     if (t.microbatch < 1)
         t.microbatch = 1;
     t.devices[0] = 0;
-    t.queryStatic = (env = getenv("MSDFHIP_QUERY_STATIC")) ? atoi(env) : 2;
-    t.queryGridSteps = (env = getenv("MSDFHIP_QUERY_GRID")) ? atoi(env) : 16;
-    t.queryBatch = (env = getenv("MSDFHIP_QUERY_BATCH")) && atoi(env) > 0 ? atoi(env) : 1;
+    p.queryStatic = (env = getenv("MSDFHIP_QUERY_STATIC")) ? atoi(env) : p.queryStatic;
+    p.queryGridSteps = (env = getenv("MSDFHIP_QUERY_GRID")) ? atoi(env) : p.queryGridSteps;
+    p.queryBatch = (env = getenv("MSDFHIP_QUERY_BATCH")) && atoi(env) > 0 ? atoi(env) : p.queryBatch;
     t.noFusedSingle = getenv("MSDFHIP_NO_FUSED_SINGLE") != NULL;
     t.noZeroCopySingle = getenv("MSDFHIP_NO_ZERO_COPY_SINGLE") != NULL;
     t.noArgPayloadSingle = getenv("MSDFHIP_NO_ARG_PAYLOAD_SINGLE") != NULL;
-    t.shortRounds = (env = getenv("MSDFHIP_SHORT_ROUNDS")) ? atol(env) : 4;
-    t.persistentGrid = (env = getenv("MSDFHIP_PERSISTENT_GRID")) ? atol(env) : 0;
-    // (1.33 since the round-6 refit of glyphCost: the new table prices the global-workspace class at 0.146 of the bench workload where round 3's said 0.195, and
-    // the grid that finishes inside the pass is the one the old share gave -- x1.0 / 1.33 / 1.6 / 2.0: 5.22 / 5.00 / 5.04 / 5.03 ms per step, profiles/r06_ab_notes.md)
-    t.shareGridFactor = (env = getenv("MSDFHIP_SHARE_GRID")) ? atof(env) : 1.33;
-    t.smallLaunchTiles = (env = getenv("MSDFHIP_SMALL_LAUNCH_TILES")) ? atol(env) : 8192;
+    p.shortRounds = (env = getenv("MSDFHIP_SHORT_ROUNDS")) ? atol(env) : p.shortRounds;
+    p.persistentGrid = (env = getenv("MSDFHIP_PERSISTENT_GRID")) ? atol(env) : p.persistentGrid;
+    p.shareGridFactor = (env = getenv("MSDFHIP_SHARE_GRID")) ? atof(env) : p.shareGridFactor;
+    p.smallLaunchTiles = (env = getenv("MSDFHIP_SMALL_LAUNCH_TILES")) ? atol(env) : p.smallLaunchTiles;
     if ((env = getenv("MSDFHIP_DEVICES")))
         snprintf(t.devices, sizeof(t.devices), "%s", env);
-    t.smallMaxEdges = (env = getenv("MSDFHIP_SMALL_MAX_EDGES")) && atoi(env) > 0 ? atoi(env) : 128;
-    t.ldsClassTpw = (env = getenv("MSDFHIP_LDS_CLASS_TPW")) && atoi(env) == 1 ? 1 : 4;
+    p.smallMaxEdges = (env = getenv("MSDFHIP_SMALL_MAX_EDGES")) && atoi(env) > 0 ? atoi(env) : p.smallMaxEdges;
+    p.ldsClassTpw = (env = getenv("MSDFHIP_LDS_CLASS_TPW")) && atoi(env) == 1 ? 1 : 4;
     t.pipelineDepth = (env = getenv("MSDFHIP_PIPELINE_DEPTH")) && atoi(env) >= 1 && atoi(env) <= 3 ? atoi(env) : 2;
     t.prepLargeTier = getenv("MSDFHIP_PREP_LARGE_TIER") != NULL;
     t.hostThreads = (env = getenv("MSDFHIP_HOST_THREADS")) && atoi(env) > 0 ? atoi(env) : 0;
@@ -431,11 +412,11 @@ int fetchGlyphCounts(const MsdfHipBatch *b) {             // device-array batche
     return MSDFHIP_OK;
 }
 
-// LDS plan for a launch: bytes of dynamic LDS, the stride of the per-tile survivor lists, and where the combiner scratch lives.
-struct LdsPlan { size_t bytes; bool globalRes; size_t resBytes, ldsBudget, idxBytes; int listStride; };
-const size_t GRES_WORKSPACE_CAP = (size_t) 1<<30;   // bound of the global combiner scratch; larger launches are chunked
+static_assert(PLAN_TILE == TILE && PLAN_WAVE == WAVE && PLAN_QUAD == QUAD && PLAN_DISTANCE_WAVES_PER_SIMD == MSDF_DISTANCE_WAVES_PER_SIMD &&
+              PLAN_SIMPLE_WAVES_PER_SIMD == MSDF_SIMPLE_WAVES_PER_SIMD && PLAN_SIGN_ROWS == SIGN_ROWS && PLAN_PB_SLOT_BYTES == sizeof(PBSlot),
+              "msdf_launchplan.hpp plans for other kernels than those of msdf_kernels.hpp");
 
-// SIMDs of a device (4 per compute unit): the number of wavefronts of a W-waves-per-SIMD kernel it holds at once is residentSlots()*W.
+// Compute units of a device (4 SIMDs each): the number of wavefronts of a W-waves-per-SIMD kernel it holds at once is residentSlots()*4*W.
 int residentSlots(int device) {
     static std::atomic<int> cus[64];
     if (device < 0 || device >= 64)
@@ -449,34 +430,34 @@ int residentSlots(int device) {
     return n;
 }
 
-size_t ldsBudget() {
-    // The combiner scratch lives in LDS only while 16 wavefronts (4 per SIMD, the register-limited occupancy: MSDF_DISTANCE_WAVES_PER_SIMD) fit a CU's
-    // 160 KB: beyond 10 KB per wavefront LDS would cap the occupancy (a 20-contour glyph set ran at 1.25 wavefronts/SIMD), so it moves to a
-    // global workspace instead -- written and read once per contour with lane-consecutive addresses. (13 KB = 12 wavefronts until round 5.)
-    return tuning().resLdsBudget;                                // 10 KB unless MSDFHIP_RES_LDS_BUDGET says otherwise
+// Workgroups of `kernel` (blockThreads threads, lds bytes of dynamic LDS) the device holds at once: occupancy per compute unit x compute units, looked
+// up once per `slot` of the caller's cache (one gfx950 is like another: not keyed by device). 0: unknown.
+int residentBlocks(std::atomic<int> &slot, int device, const void *kernel, int blockThreads, size_t lds) {
+    int v = slot.load();
+    if (!v) {
+        int perCu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, kernel, blockThreads, lds) != hipSuccess) {
+            (void) hipGetLastError();
+            perCu = 0;
+        }
+        v = perCu > 0 ? perCu*residentSlots(device) : -1;
+        slot.store(v);
+    }
+    return v > 0 ? v : 0;
 }
 
-// maxContours / maxEdges: of the glyphs this launch covers (default: of the whole batch).
-int planLds(const MsdfHipBatch *b, int nch, bool overlap, LdsPlan &plan, int maxContours = -1, int maxEdges = -1, int tilesPerWave = QUAD) {
-    if (maxContours < 0)
-        maxContours = b->maxContours;
-    if (maxEdges < 0)
-        maxEdges = b->maxEdges;
-    const size_t resBytes = overlap ? (size_t) maxContours*nch*WAVE*sizeof(double) : 0;
-    const size_t idxOne = tileListBytes(maxEdges, maxContours, false);   // survivor list + per-contour offsets of one tile
-    const size_t idxBytes = (size_t) tilesPerWave*idxOne;        // the LDS-scratch variant culls a quad of tiles per wavefront (one in short launches)
-    plan.ldsBudget = ldsBudget();
-    const size_t limit = (size_t) gLdsLimit.load();
-    plan.resBytes = resBytes;
-    plan.globalRes = overlap && resBytes+idxBytes > plan.ldsBudget;
-    plan.idxBytes = idxBytes;
-    plan.listStride = maxEdges;
-    plan.bytes = plan.globalRes ? tileListBytes(maxEdges, maxContours, true) : resBytes+idxBytes;     // the global-scratch variant takes one tile per wavefront
-    if (plan.bytes > limit)
-        return fail(MSDFHIP_ERR_TOO_COMPLEX, "a glyph has %d contours / %d edges: the survivor lists need %zu B of LDS per wavefront, device limit is %zu B",
-                    maxContours, maxEdges, plan.bytes, limit);
-    // (Staging the surviving records in LDS instead of reading them with scalar loads was measured slower and is gone.)
-    return MSDFHIP_OK;
+// What the launch plans (msdf_launchplan.hpp) read: built per call, on its stack.
+PlanEnv planEnv(int device) {
+    const PlanEnv env = { tuning().plan, (size_t) gLdsLimit.load(), residentSlots(device) };
+    return env;
+}
+GlyphCounts countsOf(const MsdfHipBatch *b) {
+    const GlyphCounts c = { b->nGlyphs, b->maxContours, b->maxEdges };
+    return c;
+}
+int failTooComplex(const LdsPlan &plan, const PlanEnv &env) {
+    return fail(MSDFHIP_ERR_TOO_COMPLEX, "a glyph has %d contours / %d edges: the survivor lists need %zu B of LDS per wavefront, device limit is %zu B",
+                plan.maxContours, plan.listStride, plan.bytes, env.ldsLimit);
 }
 
 template <class K>
@@ -524,82 +505,66 @@ void launchDistanceKernel(unsigned grid, size_t lds, hipStream_t stream, const D
                        a.gresStride, a.glyphMap, a.nMapped, a.workQueue, a.workItems);
 }
 
-template <int SEL, bool OVERLAP, bool GRES, int TPW_ = (GRES ? 1 : (int) QUAD)>
-int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, float *dst, int toScratch, const LdsPlan &plan, hipStream_t stream,
-                   const int *dGlyphMap = NULL, int nMapped = 0, size_t shareGrid = 0, bool *persistent = NULL) {
-    const int tilesX = (w+TILE-1)/TILE, tilesY = (h+TILE-1)/TILE, tiles = tilesX*tilesY;
-    if (persistent)
-        *persistent = false;
-    const int nG = dGlyphMap ? nMapped : b->nGlyphs;
-    if (nG == 0)
+// One planned launch of the distance pass (msdf_launchplan.hpp: planDistance); counts its route once it is issued.
+template <int SEL, bool OVERLAP, bool GRES, int TPW_>
+int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, float *dst, int toScratch, const DistanceLaunch &l, const PlanEnv &env,
+                   hipStream_t stream) {
+    const size_t blocks = distanceBlocks(l.count, w, h, TPW_);
+    if (blocks == 0)
         return MSDFHIP_OK;
-    const int tpw = TPW_;                                        // tiles per wavefront (msdf_kernels.hpp)
-    const size_t blocks = (size_t) nG*(size_t) ((tiles+tpw-1)/tpw);               // decodeBlock (msdf_kernels.hpp)
     if (blocks > 0x7fffffffull)
         return fail(MSDFHIP_ERR_INVALID, "launch of %zu tile quads exceeds the grid limit; split the batch", blocks);
-    int rc = setLds(k_distance<SEL, OVERLAP, GRES, TPW_>, plan.bytes);
+    int rc = setLds(k_distance<SEL, OVERLAP, GRES, TPW_>, l.lds.bytes);
     if (rc != MSDFHIP_OK)
         return rc;
-    double *gres = NULL;
-    size_t chunk = blocks, stride = 0;
-    unsigned *queue = NULL;
+    const GridPlan grid = gridOf(l, w, h, env);
     DistanceArgs args;
-    args.batch = viewOf(b), args.glyphs = dGlyphs, args.width = w, args.height = h, args.tilesX = tilesX, args.tilesPerGlyph = tiles, args.maxEdges = plan.listStride;
-    args.dst = dst, args.toScratch = toScratch, args.blockBase = 0, args.gres = NULL, args.gresStride = 0, args.glyphMap = dGlyphMap, args.nMapped = nMapped;
-    args.workQueue = NULL, args.workItems = 0;
-    if (GRES && OVERLAP && plan.resBytes) {
-        stride = plan.resBytes/sizeof(double);
-        // More items than resident wavefront slots: a PERSISTENT launch -- one workgroup per slot draws tiles from a queue and keeps
-        // its slice of the workspace (3 072 x 30 KB = 92 MB for 20-contour glyphs: Infinity-Cache resident; as one slice per tile the
-        // same launch streamed 9 GB through HBM and had to be cut into chunks of 1 GB of workspace).
-        const size_t slots = (size_t) residentSlots(b->device)*4u*MSDF_DISTANCE_WAVES_PER_SIMD;
-        // (Only for launches of many rounds: a persistent workgroup never yields its slot, so next to the other glyph classes' launches
-        // it freezes the split of the device between them -- measured 2 % slower than the direct mapping at 5 rounds, 12 % faster at 96.)
-        const size_t minRounds = (size_t) tuning().persistentRounds;   // 8; MSDFHIP_PERSISTENT_ROUNDS, 0 = never
-        // shareGrid (round 4): a class that is a small share of a batch's work runs persistent on that share of the slots -- the launch is no
-        // longer (the other classes fill the device, it finishes inside the pass either way: 3.74 vs 3.77 ms) and its few workspace slices, rewritten by
-        // one tile after the other, stay in the L2s instead of being written once per tile: HBM bytes of the pass 922 -> 634 MB on the bench workload
-        // (2.2x -> 1.5x algorithmic; tools/persistent_grid_traffic.sh)
-        const bool byShare = shareGrid > 0 && shareGrid < slots && blocks > shareGrid;
-        if (((minRounds && blocks >= minRounds*slots) || byShare) && blocks < 0xffffffffull-8u*slots) {
-            chunk = byShare ? shareGrid : slots;
-            if (tuning().persistentGrid > 0 && (size_t) tuning().persistentGrid < chunk)
-                chunk = (size_t) tuning().persistentGrid;            // (A/B: a fixed grid)
-            rc = ensureGres(b, chunk*plan.resBytes, &gres);
-            if (rc == MSDFHIP_OK)
-                rc = ensureWorkQueue(b, &queue, stream);
-            if (rc != MSDFHIP_OK)
-                return rc;
-            // The parity is read and flipped under the batch's scratch mutex, and flipped only once the launch has been ISSUED: a launch that fails to
-            // be issued has neither dirtied its own set nor zeroed the other, so the next launch must draw from the same (still zero) set again --
-            // flipped up front, it would draw from the set the last successful launch left dirty and render no tile of the class.
-            // Launches on one batch are ordered by the caller (they share the batch's workspaces).
-            std::lock_guard<std::mutex> lock(b->work.mutex);
-            queue += b->work.queueParity ? 16 : 0;                    // (the kernel finds the other set at `queue ^ 64 bytes`)
-            args.gres = gres, args.gresStride = stride, args.workQueue = queue, args.workItems = (unsigned) blocks;
-            launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) chunk, plan.bytes, stream, args);
-            HIPCHK(hipGetLastError());
-            b->work.queueParity ^= 1u;
-            if (persistent)
-                *persistent = true;
-            return MSDFHIP_OK;
-        }
-        chunk = GRES_WORKSPACE_CAP/plan.resBytes;
-        if (chunk < 256)
-            chunk = 256;
-        if (chunk > blocks)
-            chunk = blocks;
-        rc = ensureGres(b, chunk*plan.resBytes, &gres);
+    args.batch = viewOf(b), args.glyphs = dGlyphs, args.width = w, args.height = h, args.tilesX = (w+TILE-1)/TILE, args.tilesPerGlyph = tilesOf(w, h);
+    args.maxEdges = l.lds.listStride, args.dst = dst, args.toScratch = toScratch, args.blockBase = 0, args.gres = NULL, args.gresStride = 0;
+    args.glyphMap = l.mapped ? b->work.bucket.ptr+l.offset : NULL, args.nMapped = l.mapped ? l.count : 0, args.workQueue = NULL, args.workItems = 0;
+    if (grid.gresBytes) {
+        rc = ensureGres(b, grid.gresBytes, &args.gres);
         if (rc != MSDFHIP_OK)
             return rc;
+        args.gresStride = l.lds.resBytes/sizeof(double);
     }
-    for (size_t base = 0; base < blocks; base += chunk) {
-        const size_t n = blocks-base < chunk ? blocks-base : chunk;
-        args.gres = gres, args.gresStride = stride, args.blockBase = (unsigned) base;
-        launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) n, plan.bytes, stream, args);
+    if (grid.persistent) {
+        unsigned *queue = NULL;
+        rc = ensureWorkQueue(b, &queue, stream);
+        if (rc != MSDFHIP_OK)
+            return rc;
+        // The parity is read and flipped under the batch's scratch mutex, and flipped only once the launch has been ISSUED: a launch that fails to
+        // be issued has neither dirtied its own set nor zeroed the other, so the next launch must draw from the same (still zero) set again --
+        // flipped up front, it would draw from the set the last successful launch left dirty and render no tile of the class.
+        // Launches on one batch are ordered by the caller (they share the batch's workspaces).
+        std::lock_guard<std::mutex> lock(b->work.mutex);
+        args.workQueue = queue+(b->work.queueParity ? 16 : 0);    // (the kernel finds the other set at `queue ^ 64 bytes`)
+        args.workItems = (unsigned) blocks;
+        launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) grid.chunk, l.lds.bytes, stream, args);
+        HIPCHK(hipGetLastError());
+        b->work.queueParity ^= 1u;
+    } else {
+        for (size_t base = 0; base < blocks; base += grid.chunk) {
+            args.blockBase = (unsigned) base;
+            launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) (blocks-base < grid.chunk ? blocks-base : grid.chunk), l.lds.bytes, stream, args);
+        }
+        HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipGetLastError());
+    countRoute(routeOf(l, grid));
     return MSDFHIP_OK;
+}
+
+// f(OVERLAP, GRES, TPW) with a planned launch's kernel variant as integral constants: the five instantiations of k_distance a selector has
+// (named in the order the code object has always held them: a reordering moves every kernel behind them in the device assembly).
+template <class F>
+int forDistanceVariant(const DistanceLaunch &l, F &&f) {
+    typedef std::integral_constant<int, 1> One;
+    typedef std::integral_constant<int, (int) QUAD> Quad;
+    if (!l.overlap)
+        return l.gres ? f(std::false_type(), std::true_type(), One()) : f(std::false_type(), std::false_type(), Quad());
+    if (l.gres)
+        return f(std::true_type(), std::true_type(), One());
+    return l.tpw != 1 ? f(std::true_type(), std::false_type(), Quad()) : f(std::true_type(), std::false_type(), One());
 }
 
 // Upload of a few KB from pinned host memory by a kernel instead of an SDMA copy (see k_upload_words; StreamFeeder::prepareChunk uses it the other way,
@@ -618,7 +583,7 @@ int uploadSmall(void *dst, const void *srcPinned, size_t bytes, hipStream_t stre
 int ensureBuckets(const MsdfHipBatch *b, int limit, hipStream_t stream) {
     Workspace &ws = b->work;
     std::lock_guard<std::mutex> lock(ws.mutex);
-    const int bucketKey = limit+(tuning().smallMaxEdges<<12);    // what the class lists depend on
+    const int bucketKey = limit+(tuning().plan.smallMaxEdges<<12);    // what the class lists depend on
     if (ws.bucketKey == bucketKey && ws.bucket.ptr)
         return MSDFHIP_OK;
     const int rcCounts = fetchGlyphCounts(b);
@@ -629,7 +594,7 @@ int ensureBuckets(const MsdfHipBatch *b, int limit, hipStream_t stream) {
     HIPCHK(ws.hBucket.ensure(cap));
     if (ws.bucketUploaded)                                       // an earlier upload from hBucket (same batch, other limit) must have left it
         HIPCHK(hipStreamSynchronize(stream));
-    const ClassPlan plan = planClasses(b->hContours.data(), b->hEdges.data(), b->nGlyphs, limit, tuning().smallMaxEdges, (size_t) gLdsLimit.load(), ws.hBucket.ptr);
+    const ClassPlan plan = planClasses(b->hContours.data(), b->hEdges.data(), b->nGlyphs, limit, tuning().plan.smallMaxEdges, (size_t) gLdsLimit.load(), ws.hBucket.ptr);
     const int rcUp = uploadSmall(ws.bucket.ptr, ws.hBucket.ptr, sizeof(int)*(size_t) b->nGlyphs, stream);   // (hBucket is pinned)
     if (rcUp != MSDFHIP_OK)
         return rcUp;
@@ -737,214 +702,70 @@ int launchUnculled(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
     return MSDFHIP_OK;
 }
 
-// rc of a launch, counted under `route` when it was issued (msdfhip_debug_route_counts)
-int counted(int rc, int route) {
-    if (rc == MSDFHIP_OK)
-        countRoute(route);
-    return rc;
-}
-
-// Contours up to which a glyph's combiner scratch fits the per-wavefront LDS budget next to the lists of a smallMaxEdges glyph (the LDS class's bound).
-int overlapClassLimit(int nch) {
-    const size_t perContourLds = (size_t) nch*WAVE*sizeof(double);
-    const int smallMaxEdges = tuning().smallMaxEdges, classTpw = tuning().ldsClassTpw == 1 ? 1 : (int) QUAD;
-    int limitAll = 0;
-    while ((size_t) (limitAll+1)*perContourLds+(size_t) classTpw*tileListBytes(smallMaxEdges, limitAll+1, false) <= ldsBudget())
-        ++limitAll;
-    return limitAll;
-}
-
-// How the distance pass of b at w x h takes its glyphs. hugeBatch: a glyph's survivor lists exceed a CU's LDS. smallLaunch: too few tiles to fill the
-// device -- one tile per wavefront, combiner scratch (overlap: nch channels per contour, bounded) in the global workspace.
-struct LaunchShape { bool hugeBatch, smallLaunch; };
-LaunchShape launchShape(const MsdfHipBatch *b, int w, int h, int nch, bool overlap) {
-    const size_t tilesAll = (size_t) b->nGlyphs*(size_t) (((w+TILE-1)/TILE)*((h+TILE-1)/TILE));
-    const size_t gresAll = tilesAll*(size_t) b->maxContours*nch*WAVE*sizeof(double);
-    LaunchShape l;
-    l.hugeBatch = tileListBytes(b->maxEdges, b->maxContours, true) > (size_t) gLdsLimit.load();
-    l.smallLaunch = !l.hugeBatch && tilesAll <= (size_t) tuning().smallLaunchTiles && (!overlap || gresAll <= ((size_t) 64<<20));
-    return l;
-}
-
 int runCorrection(const MsdfHipBatch *b, int channels, int w, int h, const MsdfHipGlyph *dGlyphs, const float *src, float *out, uint8_t *stencil,
                   const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call, bool paramsOnly = false);   // (below)
+// The distance pass: planned by planDistance (msdf_launchplan.hpp), executed here.
 // ecAhead: the config of the coming correction pass, whose k_ec_params may run next to the distance pass (NULL: not wanted); call.ecParamsQueued says whether it did.
 template <int SEL>
 int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, float *dst, int toScratch, bool overlap, hipStream_t stream,
                      const MsdfHipConfig *ecAhead, GenerateCall &call) {
-    // A glyph whose survivor lists exceed a CU's LDS takes the list-free kernel (the reference cannot fail on a large shape; neither may this) --
-    // alone: in a batch, the OTHER glyphs keep the culled kernels (ensureBuckets puts the oversized ones last in the class list; maxE / maxC below
-    // are the maxima of the rest). Round 3 sent the whole batch through the list-free kernel with it.
-    const LaunchShape shape = launchShape(b, w, h, SelTraits<SEL>::NCH, overlap);
-    const bool hugeBatch = shape.hugeBatch, smallLaunch = shape.smallLaunch;
-    if (hugeBatch && b->nGlyphs == 1) {
-        ScopedTimer timer(stream, 0);
-        return overlap && b->maxContours > 1 ? launchUnculled<SEL, true>(b, dGlyphs, w, h, dst, toScratch, stream)
-                                             : launchUnculled<SEL, false>(b, dGlyphs, w, h, dst, toScratch, stream);
-    }
-    int maxE = b->maxEdges, maxC = b->maxContours, nHuge = 0, rc = MSDFHIP_OK;
-    const int limitAll = overlapClassLimit(SelTraits<SEL>::NCH);   // contours whose combiner scratch fits the per-wavefront LDS budget next to the lists of a smallMaxEdges glyph
-    const int smallMaxEdges = tuning().smallMaxEdges, classTpw = tuning().ldsClassTpw == 1 ? 1 : (int) QUAD;
-    if (hugeBatch) {
-        rc = ensureBuckets(b, limitAll < 1 ? 1 : limitAll, stream);
+    const PlanEnv env = planEnv(b->device);
+    int rc = MSDFHIP_OK;
+    const int limit = classListLimit(env, countsOf(b), w, h, SelTraits<SEL>::NCH, overlap);
+    if (limit) {
+        rc = ensureBuckets(b, limit, stream);
         if (rc != MSDFHIP_OK)
             return rc;
-        nHuge = b->plan.nHuge;
-        maxE = b->plan.oneMaxE > b->plan.smallMaxE ? b->plan.oneMaxE : b->plan.smallMaxE, maxE = b->plan.restMaxE > maxE ? b->plan.restMaxE : maxE;
-        maxC = b->plan.smallMaxC > b->plan.restMaxC ? b->plan.smallMaxC : b->plan.restMaxC, maxC = b->plan.nOne > 0 && maxC < 1 ? 1 : maxC;
-        // (the lists are sized by the two maxima, which may come from different glyphs: if even those do not fit, or nothing is left, the whole batch goes list-free)
-        if (nHuge == b->nGlyphs || tileListBytes(maxE, maxC, true) > (size_t) gLdsLimit.load()) {
-            ScopedTimer timer(stream, 0);
-            return overlap && b->maxContours > 1 ? launchUnculled<SEL, true>(b, dGlyphs, w, h, dst, toScratch, stream)
-                                                 : launchUnculled<SEL, false>(b, dGlyphs, w, h, dst, toScratch, stream);
-        }
     }
-    const int nCulled = b->nGlyphs-nHuge;
-    LdsPlan plan;
-    rc = planLds(b, SelTraits<SEL>::NCH, overlap, plan, maxC, maxE);
-    if (rc != MSDFHIP_OK)
-        return rc;
+    const DistancePlan plan = planDistance(env, countsOf(b), w, h, SelTraits<SEL>::NCH, overlap, b->serialClasses, ecAhead != NULL, b->plan);
+    if (plan.tooComplex)
+        return failTooComplex(plan.refused, env);
+    const auto unculled = plan.unculledOverlap ? launchUnculled<SEL, true> : launchUnculled<SEL, false>;   // the list-free kernel's combiner, chosen once
     ScopedTimer timer(stream, 0);                                // the distance pass of one generate call (one or more launches)
-    // A launch too small to fill the device (a single-shape call, a micro-batched group) is latency bound: it takes one tile per
-    // wavefront instead of four -- four times the wavefronts, a quarter of the serial work each -- with the combiner scratch in the
-    // global workspace (single 64x64 glyph: 19 -> 8 us simple, ~100 -> ~30 us overlapping combiner).
-    const int tilesAll = ((w+TILE-1)/TILE)*((h+TILE-1)/TILE);
-    LdsPlan single = plan;                                       // one tile per wavefront: one survivor list, scratch (if any) in global memory
-    single.globalRes = true;
-    single.bytes = tileListBytes(maxE, maxC, true);
-    single.resBytes = overlap ? (size_t) maxC*SelTraits<SEL>::NCH*WAVE*sizeof(double) : 0;
-    if (!overlap || maxC <= 1) {
-        if (smallLaunch)
-            return counted(launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, single, stream), MSDFHIP_ROUTE_DIST_SMALL_SIMPLE);
-        if (overlap) {
-            rc = planLds(b, SelTraits<SEL>::NCH, false, plan, maxC, maxE);
-            if (rc != MSDFHIP_OK)
-                return rc;
-        }
-        if (!hugeBatch)
-            return counted(launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream), MSDFHIP_ROUTE_DIST_FULL_SIMPLE);
-        rc = nCulled > 0 ? counted(launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream, b->work.bucket.ptr, nCulled), MSDFHIP_ROUTE_DIST_FULL_SIMPLE)
-                         : MSDFHIP_OK;
-        if (rc == MSDFHIP_OK)                                    // (the oversized glyphs after the others on the same stream: they share the batch's workspace)
-            rc = overlap && b->maxContours > 1 ? launchUnculled<SEL, true>(b, dGlyphs, w, h, dst, toScratch, stream, b->work.bucket.ptr+nCulled, nHuge)
-                                               : launchUnculled<SEL, false>(b, dGlyphs, w, h, dst, toScratch, stream, b->work.bucket.ptr+nCulled, nHuge);
-        return rc;
-    }
-    if (smallLaunch && b->nGlyphs == 1)
-        return counted(launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, single, stream), MSDFHIP_ROUTE_DIST_SMALL_OVERLAP);
-    const int limit = limitAll;
-    bool persistent = false;                                     // (whether a global-scratch launch went persistent: route counters only)
-    if (b->nGlyphs == 1) {                                       // the class is known, no index map
-        if (maxC <= limit && maxE <= smallMaxEdges && !plan.globalRes)
-            return counted(launchDistance<SEL, true, false>(b, dGlyphs, w, h, dst, toScratch, plan, stream), MSDFHIP_ROUTE_DIST_LDS_QUAD);
-        rc = launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, NULL, 0, 0, &persistent);
-        return counted(rc, persistent ? MSDFHIP_ROUTE_DIST_GLOBAL_PERSISTENT : MSDFHIP_ROUTE_DIST_GLOBAL_DIRECT);
-    }
-    rc = ensureBuckets(b, limit < 1 ? 1 : limit, stream);
-    if (rc != MSDFHIP_OK)
-        return rc;
-    const int nRest = nCulled-b->plan.nOne-b->plan.nSmall;
-    if (smallLaunch) {
-        if (b->plan.nOne > 0) {
-            rc = counted(launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, b->work.bucket.ptr, b->plan.nOne), MSDFHIP_ROUTE_DIST_SMALL_SIMPLE);
-            if (rc != MSDFHIP_OK)
-                return rc;
-        }
-        if (b->nGlyphs > b->plan.nOne)
-            return counted(launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, single, stream, b->work.bucket.ptr+b->plan.nOne, b->nGlyphs-b->plan.nOne),
-                           MSDFHIP_ROUTE_DIST_SMALL_OVERLAP);
-        return MSDFHIP_OK;
-    }
-    // The classes are disjoint sets of glyphs: their launches run CONCURRENTLY (the long LDS-class launch on the caller's stream, the other
-    // two on the batch's side streams, forked and joined by events), so that the tail of one fills with the wavefronts of the others --
-    // two processes sharing the GPU had measured 12 % more throughput than one.
-    const int classes = (b->plan.nOne > 0)+(b->plan.nSmall > 0)+(nRest > 0);
-    const bool concurrent = classes > 1 && !tuning().serialClasses && !b->serialClasses;
-    hipStream_t sOne = stream, sRest = stream;
-    if (concurrent) {
+    hipStream_t streams[3] = { stream, stream, stream };         // by PLAN_STREAM_*
+    if (plan.concurrent) {
         rc = ensureSideStreams(b);
         if (rc != MSDFHIP_OK)
             return rc;
         HIPCHK(hipEventRecord(b->work.forkEvent, stream));
-        if (nRest > 0 && b->plan.nSmall > 0) {
-            sRest = b->work.sideStream[0];
-            HIPCHK(hipStreamWaitEvent(sRest, b->work.forkEvent, 0));
-        }
-        if (b->plan.nOne > 0 && (b->plan.nSmall > 0 || nRest > 0)) {
-            sOne = b->work.sideStream[1];
-            HIPCHK(hipStreamWaitEvent(sOne, b->work.forkEvent, 0));
+        for (int k = 0; k < plan.nLaunches; ++k) {
+            const int role = plan.launches[k].stream;
+            if (role != PLAN_STREAM_CALLER) {
+                streams[role] = b->work.sideStream[role-PLAN_STREAM_SIDE0];
+                HIPCHK(hipStreamWaitEvent(streams[role], b->work.forkEvent, 0));
+            }
         }
     }
     // (an error between fork and join must not leave side-stream kernels unordered with the caller's stream: the launches only set rc,
     // the join below always runs)
     int aheadRc = MSDFHIP_OK;
-    if (ecAhead && sOne != stream) {
-        // the correction pass's per-glyph constants (k_ec_params: 17 us + a dependent launch behind the join, round 6 timeline) depend on nothing the distance
-        // pass writes: ahead of the one-contour class on its side stream
-        aheadRc = runCorrection(b, SelTraits<SEL>::NCH, w, h, dGlyphs, NULL, NULL, NULL, *ecAhead, sOne, call, true);
-    }
-    if (nRest > 0) {                                             // first: few, heavy glyphs -- the longest tail
-        LdsPlan rest = plan;                                     // sized for the batch's largest glyph
-        rest.globalRes = true;
-        rest.bytes = tileListBytes(maxE, maxC, true);
-        size_t shareGrid = 0;
-        if (tuning().shareGridFactor > 0 && concurrent) {
-            const size_t slots = (size_t) residentSlots(b->device)*4u*MSDF_DISTANCE_WAVES_PER_SIMD;
-            shareGrid = (size_t) ((double) slots*b->plan.restShare*tuning().shareGridFactor);
-            shareGrid = shareGrid < 256 ? 256 : shareGrid;
-        }
-        rc = launchDistance<SEL, true, true>(b, dGlyphs, w, h, dst, toScratch, rest, sRest, b->work.bucket.ptr+b->plan.nOne+b->plan.nSmall, nRest, shareGrid, &persistent);
-        rc = counted(rc, persistent ? MSDFHIP_ROUTE_DIST_GLOBAL_PERSISTENT : MSDFHIP_ROUTE_DIST_GLOBAL_DIRECT);
-    }
-    if (rc == MSDFHIP_OK && b->plan.nSmall > 0) {
-        // A launch of few rounds of wavefronts (a shard of an atlas: BASELINE config 4 over 8 GPUs leaves 1 024 glyphs per device) ends when its
-        // last wavefronts do, and a wavefront of four tiles is four times as long: below shortRounds rounds the class takes one tile per wavefront.
-        const size_t slots = (size_t) residentSlots(b->device)*4u*MSDF_DISTANCE_WAVES_PER_SIMD;
-        const bool shortLaunch = classTpw == 1 || (size_t) b->plan.nSmall*(size_t) ((tilesAll+QUAD-1)/QUAD) < (size_t) tuning().shortRounds*slots;
-        LdsPlan small;
-        rc = planLds(b, SelTraits<SEL>::NCH, true, small, b->plan.smallMaxC, b->plan.smallMaxE, shortLaunch ? 1 : (int) QUAD);
-        if (rc == MSDFHIP_OK)
-            rc = shortLaunch ? counted(launchDistance<SEL, true, false, 1>(b, dGlyphs, w, h, dst, toScratch, small, stream, b->work.bucket.ptr+b->plan.nOne, b->plan.nSmall),
-                                       MSDFHIP_ROUTE_DIST_LDS_SINGLE)
-                             : counted(launchDistance<SEL, true, false>(b, dGlyphs, w, h, dst, toScratch, small, stream, b->work.bucket.ptr+b->plan.nOne, b->plan.nSmall),
-                                       MSDFHIP_ROUTE_DIST_LDS_QUAD);
-    }
-    if (rc == MSDFHIP_OK && b->plan.nOne > 0) {
-        const size_t slots = (size_t) residentSlots(b->device)*4u*MSDF_SIMPLE_WAVES_PER_SIMD;
-        const bool shortLaunch = (size_t) b->plan.nOne*(size_t) ((tilesAll+QUAD-1)/QUAD) < (size_t) tuning().shortRounds*slots;   // as for the LDS class above
-        LdsPlan simple;
-        rc = planLds(b, SelTraits<SEL>::NCH, false, simple, 1, b->plan.oneMaxE, shortLaunch ? 1 : (int) QUAD);
-        if (rc == MSDFHIP_OK && shortLaunch) {
-            simple.bytes = tileListBytes(b->plan.oneMaxE, 1, true);
-            rc = counted(launchDistance<SEL, false, true>(b, dGlyphs, w, h, dst, toScratch, simple, sOne, b->work.bucket.ptr, b->plan.nOne), MSDFHIP_ROUTE_DIST_ONE_SINGLE);
-        } else if (rc == MSDFHIP_OK)
-            rc = counted(launchDistance<SEL, false, false>(b, dGlyphs, w, h, dst, toScratch, simple, sOne, b->work.bucket.ptr, b->plan.nOne), MSDFHIP_ROUTE_DIST_ONE_QUAD);
+    if (plan.ecAhead)
+        aheadRc = runCorrection(b, SelTraits<SEL>::NCH, w, h, dGlyphs, NULL, NULL, NULL, *ecAhead, streams[PLAN_STREAM_SIDE1], call, true);
+    for (int k = 0; k < plan.nLaunches && rc == MSDFHIP_OK; ++k) {
+        const DistanceLaunch &l = plan.launches[k];
+        rc = forDistanceVariant(l, [&](auto o, auto g, auto t) {
+            return launchDistance<SEL, decltype(o)::value, decltype(g)::value, decltype(t)::value>(b, dGlyphs, w, h, dst, toScratch, l, env, streams[l.stream]);
+        });
     }
     hipError_t joinError = hipSuccess;
-    if (sRest != stream) {
-        hipError_t e = hipEventRecord(b->work.joinEvent[0], sRest);
-        if (e == hipSuccess)
-            e = hipStreamWaitEvent(stream, b->work.joinEvent[0], 0);
-        joinError = e != hipSuccess ? e : joinError;
-    }
-    if (sOne != stream) {
-        hipError_t e = hipEventRecord(b->work.joinEvent[1], sOne);
-        if (e == hipSuccess)
-            e = hipStreamWaitEvent(stream, b->work.joinEvent[1], 0);
-        joinError = e != hipSuccess ? e : joinError;
-    }
+    for (int k = 0; k < 2; ++k)
+        if (streams[PLAN_STREAM_SIDE0+k] != stream) {
+            hipError_t e = hipEventRecord(b->work.joinEvent[k], streams[PLAN_STREAM_SIDE0+k]);
+            if (e == hipSuccess)
+                e = hipStreamWaitEvent(stream, b->work.joinEvent[k], 0);
+            joinError = e != hipSuccess ? e : joinError;
+        }
     rc = aheadRc != MSDFHIP_OK ? aheadRc : rc;                   // (queued before the classes: its error is the call's first)
     if (joinError != hipSuccess) {                               // could not order the streams by events: fall back to waiting for them here
         (void) hipGetLastError();
-        if (sRest != stream)
-            (void) hipStreamSynchronize(sRest);
-        if (sOne != stream)
-            (void) hipStreamSynchronize(sOne);
+        for (int k = 0; k < 2; ++k)
+            if (streams[PLAN_STREAM_SIDE0+k] != stream)
+                (void) hipStreamSynchronize(streams[PLAN_STREAM_SIDE0+k]);
         if (rc == MSDFHIP_OK)
             rc = fail(MSDFHIP_ERR_HIP, "joining the glyph-class streams failed: %s", hipGetErrorString(joinError));
     }
-    if (rc == MSDFHIP_OK && nHuge > 0)                           // after the join: the list-free kernel shares the batch's workspace with the global-scratch class
-        rc = launchUnculled<SEL, true>(b, dGlyphs, w, h, dst, toScratch, stream, b->work.bucket.ptr+nCulled, nHuge);
+    if (rc == MSDFHIP_OK && plan.unculled)                       // after the join: the list-free kernel shares the batch's workspace with the global-scratch class
+        rc = unculled(b, dGlyphs, w, h, dst, toScratch, stream, plan.unculledMapped ? b->work.bucket.ptr+plan.unculledOffset : NULL, plan.unculledCount);
     return rc;
 }
 
@@ -969,137 +790,62 @@ int ensureDeferred(const MsdfHipBatch *b, size_t cap, EcCandidate **out) {
 template <int N, bool OVERLAP>
 unsigned queryResidentBlocks(int device, size_t lds) {
     enum { LDS_STEP = 2048, LDS_STEPS = 81 };
-    static std::atomic<int> cache[LDS_STEPS];                    // (one gfx950 is like another: not keyed by device)
+    static std::atomic<int> cache[LDS_STEPS];
     const size_t step = (lds+LDS_STEP-1)/LDS_STEP;
-    if (step >= LDS_STEPS)
-        return 0;
-    int v = cache[step].load();
-    if (!v) {
-        int perCu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void *>(k_ec_query<N, OVERLAP>), WAVE, step*LDS_STEP) != hipSuccess) {
-            (void) hipGetLastError();
-            perCu = 0;
-        }
-        v = perCu > 0 ? perCu*residentSlots(device) : -1;
-        cache[step].store(v);
-    }
-    return v > 0 ? (unsigned) v : 0u;
+    return step < LDS_STEPS ? (unsigned) residentBlocks(cache[step], device, reinterpret_cast<const void *>(k_ec_query<N, OVERLAP>), WAVE, step*LDS_STEP) : 0u;
 }
 
+// The correction pass as planCorrection (msdf_launchplan.hpp) laid it out; GRES is p.gres.
 template <int N, bool OVERLAP, bool GRES>
 int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, const float *src, float *out, uint8_t *stencil,
-             const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call, bool paramsOnly) {
+             const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call, bool paramsOnly, const EcPlan &p) {
     // paramsOnly (prepareAhead, dispatchDistance): only what does not depend on the distance field -- the work buffers and k_ec_params (per-glyph constants,
     // corner texels, zeroed candidate header) -- so that it is off the launch chain that follows the distance pass; call.ecParamsQueued says whether it
     // launched k_ec_params, and the full pass then skips that launch.
-    const int tilesX = (w+TILE-1)/TILE, tilesY = (h+TILE-1)/TILE, tiles = tilesX*tilesY;
+    const int tilesX = (w+TILE-1)/TILE, tiles = tilesOf(w, h);
     const unsigned blocks = (unsigned) b->nGlyphs*(unsigned) tiles;
-    const size_t allTexels = (size_t) b->nGlyphs*w*h;
-    if (allTexels >= 0xffffffffull)
-        return fail(MSDFHIP_ERR_INVALID, "batch of %zu texels exceeds the 32-bit texel index of the error-correction pass; split the batch", allTexels);
-    const size_t resBytes = OVERLAP ? (size_t) b->maxContours*WAVE*sizeof(double) : 0;   // combiner scratch of the PSDF distance checks
-    const size_t slowLds = GRES ? 0 : resBytes;
-    const unsigned slowGrid = (unsigned) (allTexels/WAVE < 64 ? 64 : allTexels/WAVE > 2048 ? 2048 : allTexels/WAVE);   // grid-stride over the texels
+    if (p.tooManyTexels)
+        return fail(MSDFHIP_ERR_INVALID, "batch of %zu texels exceeds the 32-bit texel index of the error-correction pass; split the batch", p.allTexels);
     double *gres = NULL;
     int rc;
     if (GRES) {
-        rc = ensureGres(b, (size_t) slowGrid*resBytes, &gres);
+        rc = ensureGres(b, (size_t) p.slowGrid*p.resBytes, &gres);
         if (rc != MSDFHIP_OK)
             return rc;
     }
-    const size_t gresStride = resBytes/sizeof(double);
-    rc = setLds(k_ec_slow<N, OVERLAP, GRES>, slowLds);
+    const size_t gresStride = p.resBytes/sizeof(double);
+    rc = setLds(k_ec_slow<N, OVERLAP, GRES>, p.slowLds);
     if (rc != MSDFHIP_OK)
         return rc;
     ScopedTimer timer(stream, 1, !paramsOnly);
-    if (cfg.ec_stage_limit != 0) {                               // test hook: stencil snapshots through the full pipeline for every texel
+    if (p.route == EC_ROUTE_STAGE_SNAPSHOT || p.route == EC_ROUTE_SLOW_ALL) {   // k_ec_slow takes every texel
         if (paramsOnly)
             return MSDFHIP_OK;
-        const unsigned cap = GRES ? slowGrid : 16384u;
-        const unsigned slowBlocks = (unsigned) ((allTexels+WAVE-1)/WAVE < cap ? (allTexels+WAVE-1)/WAVE : cap);
-        hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(slowBlocks), dim3(WAVE), slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
-                           (const EcCandidate *) NULL, 0u, 0, gres, gresStride);
+        hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(p.route == EC_ROUTE_SLOW_ALL ? p.slowGrid : p.snapshotBlocks), dim3(WAVE), p.slowLds, stream, viewOf(b),
+                           dGlyphs, w, h, src, out, stencil, cfg, (const EcCandidate *) NULL, 0u, 0, gres, gresStride);
         HIPCHK(hipGetLastError());
+        if (p.route == EC_ROUTE_SLOW_ALL)
+            countRoute(MSDFHIP_ROUTE_EC_SLOW_ALL);
         return MSDFHIP_OK;
     }
     const unsigned seg = ecSegment((size_t) w*h);                // candidate records per glyph
-    const size_t cap = deferredRecords(b->nGlyphs, (size_t) w*h, b->nEdges);
     EcCandidate *deferred = NULL;
-    rc = ensureDeferred(b, cap, &deferred);
+    rc = ensureDeferred(b, deferredRecords(b->nGlyphs, (size_t) w*h, b->nEdges), &deferred);
     if (rc != MSDFHIP_OK)
         return rc;
-    // k_ec_query parks the single-edge selector states of a glyph in LDS (40 B per edge) when the glyph has at most slotCap edges; its
-    // combiner scratch is one double per contour (wave-uniform query point)
-    // (both bounded so that the kernel's LDS does not cap its occupancy -- one 543-edge symbol in the batch had cost every wavefront
-    // 22 KB; measured: 2.67 -> 2.60 ms of correction on the distinct-glyph set)
-    const int slotCapWanted = tuning().querySlotCap, lpcContoursWanted = tuning().queryLpcContours;   // 160, 24 (MSDFHIP_QUERY_LDS)
-    int slotCap = b->maxEdges < slotCapWanted ? (b->maxEdges > 0 ? b->maxEdges : 1) : slotCapWanted;
-    bool wideSlots = false;
-    // A launch of few glyphs is a latency chain of its largest one (the 926-edge logo: one distance check per wavefront, 40 contours walked one
-    // after the other without the slots: correction 0.61 ms, with them 0.39): slots for up to 1024 edges there, LDS permitting.
-    if (b->nGlyphs < 256 && !tuning().hasQueryLds) {
-        const int wide = b->maxEdges < 1024 ? (b->maxEdges > 0 ? b->maxEdges : 1) : 1024;
-        const int wideMerged = b->maxContours < wide ? (b->maxContours > 0 ? b->maxContours : 1) : wide;
-        if ((size_t) b->maxContours*sizeof(double)+(size_t) (wide+wideMerged)*sizeof(PBSlot) <= (size_t) 64*1024 && wide > slotCap)
-            slotCap = wide, wideSlots = true;
-    }
-    // LDS of a query wavefront: the lane-per-candidate scratch [maxContours][64], or (cooperative) [maxContours] + the slots -- one or the other
-    EcQueryPolicy lpcMaxContours;
-    lpcMaxContours.lpcMaxContours = b->maxContours < lpcContoursWanted ? b->maxContours : lpcContoursWanted;     // beyond: cooperative only (one double per contour)
-    // Measured on MI355X (post-distance time in ms: Basic-Latin / CJK-like 48x48 / 8192 DejaVu glyphs / 1024x1024 logo):
-    //   cooperative only 1.98 / 5.35 / 2.83 / 4.60;  lane-per-candidate wherever the instruction count favours it 1.76 / 3.57 / 4.23 / 10.3;
-    //   lane-per-candidate only for glyphs of at most 48 edges 1.75 / 5.40 / 2.67 / 4.62  <- default: a chunk of a large glyph is one long
-    //   serial walk that the launch ends up waiting for.
-    // Round 2, after the records of the lane-per-candidate walk became scalar loads and the work list heavy-first: with the bound at 128
-    // edges for every launch the CJK-like set gains (4.42 -> 2.82) and the DejaVu set loses (2.33 -> 2.73: 55 k candidates are a latency
-    // chain, not a load) -- k_ec_scan therefore widens the bound only for launches whose cooperative cost exceeds wideLoad instructions.
-    // Round 3, after the chunk walk got batched scalar loads and the cooperative path its register records: the cost of an edge in a chunk
-    // relative to a cooperative round re-swept (340 / 200 / 120 / 60): 1.80 / 1.78 / 1.79 / 1.78 ms on the DejaVu set, 1.57 / 1.51 / 1.50 / 1.52 on
-    // Basic-Latin -- 150 (profiles/r03_ab_notes.md).
-    lpcMaxContours.lpcEdgeCost = tuning().qpEdgeCost, lpcMaxContours.lpcMaxEdges = tuning().qpMaxEdges, lpcMaxContours.lpcMinCount = tuning().qpMinCount;   // 150, 48, never
-    lpcMaxContours.wideMaxEdges = tuning().qpWideMaxEdges, lpcMaxContours.wideLoad = tuning().qpWideLoad, lpcMaxContours.wideMeanCount = tuning().qpWideMeanCount;                                                   // 128, 4e8 (MSDFHIP_QUERY_POLICY)
-    lpcMaxContours.gridSteps = tuning().queryGridSteps;
-    const size_t resLanes = OVERLAP ? (size_t) (lpcMaxContours.lpcMaxContours > 0 ? lpcMaxContours.lpcMaxContours : 1)*WAVE*sizeof(double) : 0;
-    const int slotOffset = OVERLAP ? (b->maxContours > 0 ? b->maxContours : 1) : 0;
-    const int mergedCap = b->maxContours < slotCap ? (b->maxContours > 0 ? b->maxContours : 1) : slotCap;   // per-contour merged states of a glyph that uses the slots
-    const size_t coopLds = (size_t) slotOffset*sizeof(double)+(size_t) (slotCap+mergedCap)*sizeof(PBSlot);
-    const size_t queryLds = resLanes > coopLds ? resLanes : coopLds;
-    const size_t fastLds = ecFastLdsBytes(b->maxEdges, N);
-    if (GRES && queryLds > (size_t) gLdsLimit.load() && fastLds <= (size_t) gLdsLimit.load()) {
-        // More contours than k_ec_query's per-contour LDS scratch holds (~19 000): the full per-texel pipeline with its scratch in the global
-        // workspace takes every texel -- slow, but a valid shape is corrected instead of refused (the reference cannot fail either).
-        if (paramsOnly)
-            return MSDFHIP_OK;
-        hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(slowGrid), dim3(WAVE), slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
-                           (const EcCandidate *) NULL, 0u, 0, gres, gresStride);
-        HIPCHK(hipGetLastError());
-        countRoute(MSDFHIP_ROUTE_EC_SLOW_ALL);
-        return MSDFHIP_OK;
-    }
-    if (fastLds > (size_t) gLdsLimit.load() || queryLds > (size_t) gLdsLimit.load())
+    if (p.route == EC_ROUTE_TOO_COMPLEX)
         return fail(MSDFHIP_ERR_TOO_COMPLEX, "a glyph has %d contours / %d edges: the error-correction pass needs %zu B of LDS per wavefront, device limit is %d B",
-                    b->maxContours, b->maxEdges, fastLds > queryLds ? fastLds : queryLds, gLdsLimit.load());
-    rc = setLds(k_ec_query<N, OVERLAP>, queryLds);
+                    b->maxContours, b->maxEdges, p.fastLds > p.queryLds ? p.fastLds : p.queryLds, gLdsLimit.load());
+    rc = setLds(k_ec_query<N, OVERLAP>, p.queryLds);
     if (rc != MSDFHIP_OK)
         return rc;
-    // the sweep's order (msdf_ec_fast.hpp: ecLazyProtect) is fixed per launch: an instantiation each
-    const bool lazyProtect = cfg.ec_mode == EC_MODE_EDGE_PRIORITY && cfg.ec_distance_check == EC_CHECK_AT_EDGE;
-    rc = lazyProtect ? setLds(k_ec_fast<N, true>, fastLds) : setLds(k_ec_fast<N, false>, fastLds);
+    rc = p.lazyProtect ? setLds(k_ec_fast<N, true>, p.fastLds) : setLds(k_ec_fast<N, false>, p.fastLds);
     if (rc != MSDFHIP_OK)
         return rc;
     int *offsets = reinterpret_cast<int *>(deferred+candidateRecords(b->nGlyphs, (size_t) w*h));
     int *corners = reinterpret_cast<int *>(deferred+candidateRecords(b->nGlyphs, (size_t) w*h)+offsetRecords(b->nGlyphs));
-    // the query kernel is a pool of wavefronts draining one work list: enough of them to fill the device, no more
-    // (a wavefront that finds the list empty leaves after one atomic; still, a single 64x64 glyph should not launch thousands of them)
-    const size_t wanted = allTexels/512;
-    unsigned queryBlocks = (unsigned) (wanted < 64 ? 64 : wanted > 8192 ? 8192 : wanted);
-    // ... dealt out statically (k_ec_query: no ticket counter) to as many workgroups as the device holds at once
-    const bool staticDeal = tuning().queryStatic != 0;
-    if (staticDeal) {
-        const unsigned resident = queryResidentBlocks<N, OVERLAP>(b->device, queryLds);
-        if (resident && queryBlocks > resident)
-            queryBlocks = resident;
-    }
+    const unsigned queryBlocks = p.residentQueryBlocks(p.staticDeal ? queryResidentBlocks<N, OVERLAP>(b->device, p.queryLds) : 0u);
+    const EcQueryPolicy policy = { p.lpcMaxContours, p.lpcEdgeCost, p.lpcMaxEdges, p.lpcMinCount, p.wideMaxEdges, p.wideLoad, p.wideMeanCount, p.gridSteps };
     if (!call.ecParamsQueued)
         hipLaunchKernelGGL(k_ec_params, dim3((unsigned) b->nGlyphs), dim3(WAVE), 0, stream, b->work.ecParams.ptr, viewOf(b), dGlyphs, cfg,
                            reinterpret_cast<unsigned *>(deferred), corners, offsets+ecSizesAt(b->nGlyphs));   // also zeroes the candidate header
@@ -1112,25 +858,25 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         call.ecParamsQueued = true;
         return MSDFHIP_OK;
     }
-    if (lazyProtect)
-        hipLaunchKernelGGL((k_ec_fast<N, true>), dim3(blocks), dim3(WAVE), fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
+    if (p.lazyProtect)
+        hipLaunchKernelGGL((k_ec_fast<N, true>), dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
                            (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
     else
-        hipLaunchKernelGGL((k_ec_fast<N, false>), dim3(blocks), dim3(WAVE), fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
+        hipLaunchKernelGGL((k_ec_fast<N, false>), dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
                            (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
-    hipLaunchKernelGGL(k_ec_scan, dim3(1), dim3(1024), 0, stream, b->nGlyphs, reinterpret_cast<const unsigned *>(deferred), seg, offsets, lpcMaxContours, ecOrder);
-    hipLaunchKernelGGL((k_ec_query<N, OVERLAP>), dim3(queryBlocks), dim3(WAVE), queryLds, stream, b->nGlyphs, b->dGlyphContourOffsets, b->dContourOffsets,
+    hipLaunchKernelGGL(k_ec_scan, dim3(1), dim3(1024), 0, stream, b->nGlyphs, reinterpret_cast<const unsigned *>(deferred), seg, offsets, policy, ecOrder);
+    hipLaunchKernelGGL((k_ec_query<N, OVERLAP>), dim3(queryBlocks), dim3(WAVE), p.queryLds, stream, b->nGlyphs, b->dGlyphContourOffsets, b->dContourOffsets,
                        (const EdgeRec *) viewOf(b).recs, viewOf(b).windings, dGlyphs, w, h, src, out, stencil, cfg,
-                       (const EcGlyphParams *) b->work.ecParams.ptr, (const EcCandidate *) deferred, seg, (const int *) offsets, offsets+2*(size_t) b->nGlyphs+2, tuning().queryBatch, slotCap, slotOffset, lpcMaxContours,
-                       call.overflowOut, ecOrder, staticDeal ? (tuning().queryStatic == 2 ? 5 : 1) : 0);
+                       (const EcGlyphParams *) b->work.ecParams.ptr, (const EcCandidate *) deferred, seg, (const int *) offsets, offsets+2*(size_t) b->nGlyphs+2, p.queryBatch,
+                       p.slotCap, p.slotOffset, policy, call.overflowOut, ecOrder, p.queryFlags);
     if (call.overflowOut)
         call.overflowMirrored = true;                            // the caller looks at the count after its copy back and reruns with the pass below if needed
     else
-        hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(slowGrid), dim3(WAVE), slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
+        hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(p.slowGrid), dim3(WAVE), p.slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
                            (const EcCandidate *) deferred, seg, 1, gres, gresStride);
     HIPCHK(hipGetLastError());
     countRoute(ecOrder ? MSDFHIP_ROUTE_EC_QUERY_HEAVIEST : MSDFHIP_ROUTE_EC_QUERY_BATCH);
-    if (wideSlots)
+    if (p.wideSlots)
         countRoute(MSDFHIP_ROUTE_EC_WIDE_SLOTS);
     return MSDFHIP_OK;
 }
@@ -1138,11 +884,12 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
 template <int N>
 int dispatchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, const float *src, float *out, uint8_t *stencil,
                const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call, bool paramsOnly) {
+    const EcPlan p = planCorrection(planEnv(b->device), countsOf(b), w, h, N, cfg.overlap_support != 0, cfg.ec_mode, cfg.ec_distance_check, cfg.ec_stage_limit,
+                                    ecFastLdsBytes(b->maxEdges, N));
     if (!cfg.overlap_support)
-        return launchEc<N, false, false>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly);
-    const bool globalRes = (size_t) b->maxContours*WAVE*sizeof(double) > 96*1024;
-    return globalRes ? launchEc<N, true, true>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly)
-                     : launchEc<N, true, false>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly);
+        return launchEc<N, false, false>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly, p);
+    return p.gres ? launchEc<N, true, true>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly, p)
+                  : launchEc<N, true, false>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly, p);
 }
 
 int checkConfig(const MsdfHipConfig *cfg) {
@@ -1175,12 +922,9 @@ int prepareAhead(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGly
     if (b->nGlyphs == 0 || w == 0 || h == 0)
         return MSDFHIP_OK;
     const int nch = channelsOf(mode);
-    const LaunchShape shape = launchShape(b, w, h, nch, false);  // (without dispatchDistance's bound on the combiner scratch: a launch of few tiles beyond it builds its class lists there, as before)
     int rc = MSDFHIP_OK;
-    if (cfg->overlap_support && b->maxContours > 1 && b->nGlyphs > 1 && !shape.hugeBatch && !shape.smallLaunch) {
-        const int limit = overlapClassLimit(nch);
-        rc = ensureBuckets(b, limit < 1 ? 1 : limit, stream);
-    }
+    if (const int limit = classListLimitAhead(planEnv(b->device), countsOf(b), w, h, nch, cfg->overlap_support != 0))
+        rc = ensureBuckets(b, limit, stream);
     if (rc == MSDFHIP_OK && mode >= 3 && cfg->ec_mode != MSDFHIP_EC_DISABLED)
         rc = runCorrection(b, nch, w, h, dGlyphs, NULL, NULL, NULL, *cfg, stream, call, true);
     return rc;
@@ -1190,32 +934,18 @@ int prepareAhead(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGly
 template <int N>
 int launchSign(const MsdfHipBatch *b, int w, int h, const MsdfHipGlyph *dGlyphs, const float *src, float *out, int dstPacked, float zero, int fillRule,
                int rasterizeOnly, hipStream_t stream) {
-    const int tilesX = (w+TILE-1)/TILE, tilesY = (h+TILE-1)/TILE;
-    // Tiles of one tile row share the per-row intersection lists: one wavefront takes `span` of them, as many as still leaves
-    // >= 16 wavefronts per CU in the launch (a single huge bitmap keeps span small, an atlas batch takes whole rows).
-    int span = tilesX;
-    while (span > 1 && (size_t) b->nGlyphs*tilesY*((tilesX+span-1)/span) < 4096)
-        span = (span+1)/2;
-    const int spansX = (tilesX+span-1)/span, spans = spansX*tilesY;
-    const size_t blocks = (size_t) b->nGlyphs*(size_t) spans;
-    if (blocks > 0x7fffffffull)
-        return fail(MSDFHIP_ERR_INVALID, "launch of %zu tile rows exceeds the grid limit; split the batch", blocks);
-    // Row-list capacity: every edge yields at most 3 intersections per row. Up to capLimit entries per row the lists of the
-    // whole shape fit; beyond, the kernel walks the edges in chunks of cap/3.
-    const size_t capLimit = tuning().signCap;                    // 192: 23 KB per wavefront at the limit (384: 46 KB = 3 wavefronts per CU; distinct-glyph set 2.95 -> 2.60 ms)
-    size_t cap = 3*(size_t) (b->maxEdges > 0 ? b->maxEdges : 1);
-    if (cap > capLimit)
-        cap = capLimit;
-    const size_t lds = SIGN_ROWS*cap*(sizeof(double)+sizeof(int))+SIGN_ROWS*sizeof(int);   // per-row intersection lists
-    int rc = setLds(k_sign_correction<N>, lds);
+    const SignPlan p = planSign(planEnv(b->device), b->nGlyphs, b->maxEdges, w, h);
+    if (p.blocks > 0x7fffffffull)
+        return fail(MSDFHIP_ERR_INVALID, "launch of %zu tile rows exceeds the grid limit; split the batch", p.blocks);
+    int rc = setLds(k_sign_correction<N>, p.lds);
     if (rc != MSDFHIP_OK)
         return rc;
     ScopedTimer timer(stream, 2);
-    hipLaunchKernelGGL((k_sign_correction<N>), dim3((unsigned) blocks), dim3(WAVE), lds, stream, viewOf(b), dGlyphs, w, h, spansX, span, spans, (int) cap,
+    hipLaunchKernelGGL((k_sign_correction<N>), dim3((unsigned) p.blocks), dim3(WAVE), p.lds, stream, viewOf(b), dGlyphs, w, h, p.spansX, p.span, p.spans, (int) p.cap,
                        src, out, dstPacked, zero, fillRule, rasterizeOnly);
     HIPCHK(hipGetLastError());
-    countRoute(span == tilesX ? MSDFHIP_ROUTE_SIGN_WHOLE_ROWS : MSDFHIP_ROUTE_SIGN_SPLIT);
-    if (cap < 3*(size_t) (b->maxEdges > 0 ? b->maxEdges : 1))
+    countRoute(p.wholeRows ? MSDFHIP_ROUTE_SIGN_WHOLE_ROWS : MSDFHIP_ROUTE_SIGN_SPLIT);
+    if (p.chunked)
         countRoute(MSDFHIP_ROUTE_SIGN_CHUNKED);
     return MSDFHIP_OK;
 }
@@ -3365,21 +3095,9 @@ static int fusedCapacity(int device, int variant, size_t lds) {  // variant = mo
     const size_t step = (lds+LDS_STEP-1)/LDS_STEP;
     if (variant < 2 || variant > 9 || step >= LDS_STEPS)
         return 0;
-    int v = cache[variant][step].load();
-    if (!v) {
-        const size_t rounded = step*LDS_STEP;
-        int perCu = 0;
-        forSingleCallVariant(variant, [&](auto sel, auto overlap) {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void *>(k_single_call<decltype(sel)::value, decltype(overlap)::value>),
-                                                             WAVE*SINGLE_TEAM, rounded) != hipSuccess) {
-                (void) hipGetLastError();
-                perCu = 0;
-            }
-        });
-        v = perCu > 0 ? perCu*residentSlots(device) : -1;
-        cache[variant][step].store(v);
-    }
-    return v > 0 ? v : 0;
+    const void *kernel = NULL;
+    forSingleCallVariant(variant, [&](auto sel, auto overlap) { kernel = reinterpret_cast<const void *>(k_single_call<decltype(sel)::value, decltype(overlap)::value>); });
+    return residentBlocks(cache[variant][step], device, kernel, WAVE*SINGLE_TEAM, step*LDS_STEP);
 }
 struct FusedReservation {                                        // the workgroups a fused launch holds of its device, released when the call is over
     std::atomic<int> *counter;

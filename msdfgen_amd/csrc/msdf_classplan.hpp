@@ -12,8 +12,8 @@ namespace msdfhip {
 // form, the per-contour channel bounds [C][3] (the LDS form keeps those in the combiner scratch's region)
 inline size_t tileListBytes(int maxEdges, int maxContours, bool withBounds) { return ((size_t) maxEdges+(withBounds ? 4 : 1)*(size_t) maxContours+2)*sizeof(int); }
 
-const int SMALL_MAX_EDGES = 128;                    // cost model only: the edge bound of the LDS-scratch class (tuning().smallMaxEdges is what the launches use)
-const int COST_LDS_MAX_CONTOURS = 5;                // cost model only: the LDS class's contour bound at the default LDS budget, msdf (overlapClassLimit derives the real one per launch)
+const int SMALL_MAX_EDGES = 128;                    // cost model only: the edge bound of the LDS-scratch class (PlanTuning::smallMaxEdges is what the launches use)
+const int COST_LDS_MAX_CONTOURS = 5;                // cost model only: the LDS class's contour bound at the default LDS budget, msdf (msdf_launchplan.hpp: overlapClassLimit derives the real one per launch)
 
 // Cost of one glyph in microseconds at 64x64 (only the ratios matter): a + b*E + c*C + d*E*C per kernel class, fitted to measured kernel
 // times (tools/fit_cost_model.py, profiles/r06_cost_model.json: refitted in round 6; the same table as msdfgen_amd/shard.py: COST_MODEL).

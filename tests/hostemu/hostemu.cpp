@@ -19,6 +19,7 @@
 #include "../../msdfgen_amd/csrc/msdf_shapeprep.hpp"
 #include "../../msdfgen_amd/csrc/msdf_classplan.hpp"
 #include "../../msdfgen_amd/csrc/msdf_hostplan.hpp"
+#include "../../msdfgen_amd/csrc/msdf_launchplan.hpp"
 
 using namespace msdfhip;
 
@@ -917,3 +918,87 @@ extern "C" void emu_shard_ranges(const int32_t *gco, const int32_t *co, int nGly
     memcpy(bounds, b.data(), sizeof(int)*b.size());
 }
 extern "C" double emu_glyph_cost(int contours, int edges) { return glyphCost(contours, edges); }
+
+// msdf_launchplan.hpp: the launch plans msdf_capi.hip executes (tests/test_launch_plan_host.py). env[EMU_ENV_FIELDS]: PlanTuning in the order below, the
+// LDS limit, the compute units.
+enum { EMU_ENV_FIELDS = 25 };
+static PlanEnv planEnvOf(const double *e) {
+    PlanEnv env;
+    PlanTuning &t = env.t;
+    t.resLdsBudget = (size_t) e[0], t.persistentRounds = (long) e[1], t.serialClasses = e[2] != 0, t.querySlotCap = (int) e[3], t.queryLpcContours = (int) e[4];
+    t.hasQueryLds = e[5] != 0, t.hasQueryPolicy = e[6] != 0, t.qpEdgeCost = (int) e[7], t.qpMaxEdges = (int) e[8], t.qpMinCount = (int) e[9];
+    t.qpWideMaxEdges = (int) e[10], t.qpWideLoad = (float) e[11], t.qpWideMeanCount = (float) e[12], t.signCap = (size_t) e[13], t.queryStatic = (int) e[14];
+    t.queryGridSteps = (int) e[15], t.queryBatch = (int) e[16], t.shareGridFactor = e[17], t.persistentGrid = (long) e[18], t.shortRounds = (long) e[19];
+    t.smallLaunchTiles = (long) e[20], t.smallMaxEdges = (int) e[21], t.ldsClassTpw = (int) e[22];
+    env.ldsLimit = (size_t) e[23], env.cus = (int) e[24];
+    return env;
+}
+extern "C" int emu_plan_env_defaults(double *e) {                // the defaults of PlanTuning; returns EMU_ENV_FIELDS
+    const PlanTuning t;
+    const double d[EMU_ENV_FIELDS] = { (double) t.resLdsBudget, (double) t.persistentRounds, (double) t.serialClasses, (double) t.querySlotCap, (double) t.queryLpcContours,
+                                       (double) t.hasQueryLds, (double) t.hasQueryPolicy, (double) t.qpEdgeCost, (double) t.qpMaxEdges, (double) t.qpMinCount,
+                                       (double) t.qpWideMaxEdges, t.qpWideLoad, t.qpWideMeanCount, (double) t.signCap, (double) t.queryStatic, (double) t.queryGridSteps,
+                                       (double) t.queryBatch, t.shareGridFactor, (double) t.persistentGrid, (double) t.shortRounds, (double) t.smallLaunchTiles,
+                                       (double) t.smallMaxEdges, (double) t.ldsClassTpw, 160*1024., 256. };
+    memcpy(e, d, sizeof(d));
+    return EMU_ENV_FIELDS;
+}
+extern "C" int emu_overlap_class_limit(const double *e, int nch) { return overlapClassLimit(planEnvOf(e), nch); }
+extern "C" int emu_launch_shape(const double *e, int nGlyphs, int maxC, int maxE, int w, int h, int nch, int boundScratch) {   // hugeBatch | smallLaunch<<1
+    const GlyphCounts b = { nGlyphs, maxC, maxE };
+    const LaunchShape l = launchShape(planEnvOf(e), b, w, h, nch, boundScratch != 0);
+    return (l.hugeBatch ? 1 : 0)|(l.smallLaunch ? 2 : 0);
+}
+extern "C" int emu_class_list_limit(const double *e, int nGlyphs, int maxC, int maxE, int w, int h, int nch, int overlap, int ahead) {
+    const GlyphCounts b = { nGlyphs, maxC, maxE };
+    return ahead ? classListLimitAhead(planEnvOf(e), b, w, h, nch, overlap != 0) : classListLimit(planEnvOf(e), b, w, h, nch, overlap != 0);
+}
+extern "C" void emu_plan_distance_grid(const double *e, long long blocks, long long resBytes, long long slots, long long shareGrid, long long *out3) {
+    const GridPlan g = planDistanceGrid((size_t) blocks, (size_t) resBytes, (size_t) slots, (size_t) shareGrid, planEnvOf(e));
+    out3[0] = g.persistent, out3[1] = (long long) g.chunk, out3[2] = (long long) g.gresBytes;
+}
+// The two steps of msdf_capi.hip's dispatchDistance over a glyph range given by its per-glyph counts: classListLimit, planClasses if it says so, planDistance.
+// order[n]: the class list (untouched if none was built). head[16]: tooComplex, launches, concurrent, ecAhead, unculled, unculledOverlap, unculledMapped,
+// unculledOffset, unculledCount, unculledAfterJoin, class limit, nOne, nSmall, nHuge, refused bytes. launches[4][20]: overlap, gres, tpw, LDS bytes, globalRes,
+// resBytes, idxBytes, LDS budget, mapped, offset, count, stream, shareGrid, route (resolved by the grid), blocks, persistent, chunk, gresBytes, listStride, maxContours.
+extern "C" void emu_plan_distance(const double *e, const int *contours, const int *edges, int n, int w, int h, int nch, int overlap, int serialBatch, int wantEcAhead,
+                                  int *order, long long *head, long long *launches) {
+    const PlanEnv env = planEnvOf(e);
+    GlyphCounts b = { n, 0, 0 };
+    for (int g = 0; g < n; ++g)
+        b.maxContours = std::max(b.maxContours, contours[g]), b.maxEdges = std::max(b.maxEdges, edges[g]);
+    const int limit = classListLimit(env, b, w, h, nch, overlap != 0);
+    ClassPlan classes;
+    if (limit)
+        classes = planClasses(contours, edges, n, limit, env.t.smallMaxEdges, env.ldsLimit, order);
+    const DistancePlan p = planDistance(env, b, w, h, nch, overlap != 0, serialBatch != 0, wantEcAhead != 0, classes);
+    const long long hd[16] = { p.tooComplex, p.nLaunches, p.concurrent, p.ecAhead, p.unculled, p.unculledOverlap, p.unculledMapped, p.unculledOffset, p.unculledCount,
+                               p.unculledAfterJoin, limit, classes.nOne, classes.nSmall, classes.nHuge, (long long) p.refused.bytes, 0 };
+    memcpy(head, hd, sizeof(hd));
+    for (int k = 0; k < p.nLaunches; ++k) {
+        const DistanceLaunch &l = p.launches[k];
+        const GridPlan g = gridOf(l, w, h, env);
+        const long long r[20] = { l.overlap, l.gres, l.tpw, (long long) l.lds.bytes, l.lds.globalRes, (long long) l.lds.resBytes, (long long) l.lds.idxBytes,
+                                  (long long) l.lds.ldsBudget, l.mapped, l.offset, l.count, l.stream, (long long) l.shareGrid, routeOf(l, g),
+                                  (long long) distanceBlocks(l.count, w, h, l.tpw), g.persistent, (long long) g.chunk, (long long) g.gresBytes, l.lds.listStride,
+                                  l.lds.maxContours };
+        memcpy(launches+20*k, r, sizeof(r));
+    }
+}
+// out[24]: tooManyTexels, gres, resBytes, slowLds, slowGrid, snapshotBlocks, route, slotCap, mergedCap, slotOffset, wideSlots, lpcMaxContours, lpcEdgeCost,
+// lpcMaxEdges, lpcMinCount, wideMaxEdges, gridSteps, queryLds, fastLds, lazyProtect, queryBlocks, queryBlocks clamped to `resident`, queryFlags, queryBatch.
+extern "C" void emu_plan_correction(const double *e, int nGlyphs, int maxC, int maxE, int w, int h, int n, int overlap, int ecMode, int ecCheck, int stageLimit,
+                                    long long fastLds, long long resident, long long *out) {
+    const GlyphCounts b = { nGlyphs, maxC, maxE };
+    const EcPlan p = planCorrection(planEnvOf(e), b, w, h, n, overlap != 0, ecMode, ecCheck, stageLimit, (size_t) fastLds);
+    const long long r[24] = { p.tooManyTexels, p.gres, (long long) p.resBytes, (long long) p.slowLds, p.slowGrid, p.snapshotBlocks, p.route, p.slotCap, p.mergedCap,
+                              p.slotOffset, p.wideSlots, p.lpcMaxContours, p.lpcEdgeCost, p.lpcMaxEdges, p.lpcMinCount, p.wideMaxEdges, p.gridSteps,
+                              (long long) p.queryLds, (long long) p.fastLds, p.lazyProtect, p.queryBlocks, p.residentQueryBlocks((unsigned) resident), p.queryFlags,
+                              p.queryBatch };
+    memcpy(out, r, sizeof(r));
+}
+extern "C" void emu_plan_sign(const double *e, int nGlyphs, int maxE, int w, int h, long long *out8) {   // span, spansX, spans, blocks, cap, lds, wholeRows, chunked
+    const SignPlan p = planSign(planEnvOf(e), nGlyphs, maxE, w, h);
+    const long long r[8] = { p.span, p.spansX, p.spans, (long long) p.blocks, (long long) p.cap, (long long) p.lds, p.wholeRows, p.chunked };
+    memcpy(out8, r, sizeof(r));
+}

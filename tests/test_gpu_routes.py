@@ -1,6 +1,7 @@
 """The launch routes a batched generate call takes by the size of its launch, against the oracle (tests/fuzzlib.py).
 
-dispatchDistance, launchEc and launchSign (msdfgen_amd/csrc/msdf_capi.hip) pick their kernels from the size of a launch: up to MSDFHIP_SMALL_LAUNCH_TILES
+planDistance, planCorrection and planSign (msdfgen_amd/csrc/msdf_launchplan.hpp; msdf_capi.hip's dispatchDistance, launchEc and launchSign execute their plans)
+pick the kernels from the size of a launch: up to MSDFHIP_SMALL_LAUNCH_TILES
 (8 192) tiles one tile per wavefront, beyond that three glyph classes on concurrent streams (one-contour, LDS scratch, global scratch; four tiles per
 wavefront or one; the global class direct or persistent), heaviest-first correction order from 256 glyphs, whole tile rows in the sign pass from
 nGlyphs x tilesY >= 4 096. The other sweeps are too small to leave the small route, so here (a) small groups run under MSDFHIP_* tables that force each
