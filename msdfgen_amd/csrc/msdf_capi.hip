@@ -28,6 +28,7 @@
 #include "msdf_hostplan.hpp"
 #include "msdf_kernels.hpp"
 #include "msdf_launchplan.hpp"
+#include "msdf_prepplan.hpp"
 #include "msdf_single.hpp"
 
 using namespace msdfhip;
@@ -1157,37 +1158,7 @@ int msdfhip_device_count(int *count) {
 
 namespace {
 
-// Host side of the preparation's sizes (the same arithmetic wherever raw outlines are prepared): co1 = the contour offsets after normalize, a prefix
-// of normalizedCount over the raw contour sizes; *bound2 = the upper bound of the coloured edge count (a contour of n1 < 3 edges may be split into 3*n1);
-// *longest = the longest normalized contour (it picks the colouring's LDS tier and says whether the `big` tables are needed).
-void prepOffsets(const int32_t *co, int nC, bool normalize, int32_t *co1, size_t *bound2, int *longest) {
-    size_t b2 = 0;
-    int lg = 0;
-    co1[0] = 0;
-    for (int c = 0; c < nC; ++c) {
-        const int n = co[c+1]-co[c];
-        const int n1 = normalize ? normalizedCount(n) : n;
-        co1[c+1] = co1[c]+n1;
-        b2 += n1 < 3 ? 3*(size_t) n1 : (size_t) n1;
-        lg = n1 > lg ? n1 : lg;
-    }
-    *bound2 = b2, *longest = lg;
-}
-
-// The device buffers of one preparation (every pointer the caller's: nothing is allocated here).
-struct PrepBuffers {
-    const int32_t *gco, *co, *co1;        // glyph -> contour offsets, raw contour offsets, contour offsets after normalize (prepOffsets)
-    EdgeArrays raw, norm, fin;            // raw edges (colors may be NULL = WHITE); normalized [co1[nC]]; coloured [bound2] (coloring != 0 only)
-    int32_t *cusp, *count, *co2;          // [nC+1] each: normalize's cusp flags; coloured edges per contour and their prefix (coloring != 0 only)
-    const unsigned long long *seeds;      // one per glyph, or NULL: cfg->seed for every glyph
-    ColourTables big;                     // the colouring's tables of contours beyond PREP_WAVE_MAX_EDGES (only when `longest` exceeds it)
-    int32_t *votes;                       // [nC] orientContours' votes of glyphs beyond PREP_ORIENT_LDS_CONTOURS contours (orient_contours only)
-    double *hitX;                         // [3 nE] + hitTag: scanline hits beyond PREP_ORIENT_LDS_HITS (only when orientHitsBig: see prepOrientScratch)
-    int32_t *hitTag;
-};
-
-// Does a glyph of maxRawEdges raw edges need k_prep_orient's global hit scratch (3 hits per edge at most)?
-bool orientHitsBig(long long maxRawEdges) { return 3*maxRawEdges > PREP_ORIENT_LDS_HITS; }
+static_assert(PREP_PLAN_WAVE_MAX_EDGES == PREP_WAVE_MAX_EDGES, "msdf_prepplan.hpp sizes the colouring's global tables from the kernels' LDS tier");
 
 // Shape preparation (row f3) as ONE queued sequence on `stream`, in the reference CLI's order: orientContours on the raw edges (orient.orient_contours),
 // normalize (k_prep_normalize_flat + the cusp repair), the winding step on the normalized edges (orient.winding), then with coloring the coloured
@@ -1332,80 +1303,41 @@ int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, c
         void release(void *p) { for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { ptrs.erase(ptrs.begin()+i); break; } }
     } dev;
     #define PREP_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(MSDFHIP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
-    int32_t *dGco = NULL, *dCo = NULL, *dCo1 = NULL, *dCo2 = NULL, *dCount = NULL, *dCusp = NULL, *dVotes = NULL, *dHitTag = NULL;
-    double *dHitX = NULL;
-    unsigned long long *dSeeds = NULL;
-    EdgeArrays raw = { NULL, NULL, NULL }, norm = { NULL, NULL, NULL }, fin = { NULL, NULL, NULL };
-    ColourTables big = { NULL, NULL, NULL, NULL, NULL, NULL };
-    const size_t eRaw = nE > 0 ? nE : 1, eNorm = nE1 > 0 ? nE1 : 1, eFin = bound2 > 0 ? bound2 : 1;
-    PREP_CHK(dev.alloc((void **) &dGco, sizeof(int32_t)*(size_t) (n_glyphs+1)));
-    PREP_CHK(dev.alloc((void **) &dCo, sizeof(int32_t)*(size_t) (nC+1)));
-    PREP_CHK(dev.alloc((void **) &dCo1, sizeof(int32_t)*(size_t) (nC+1)));
-    PREP_CHK(dev.alloc((void **) &dCusp, sizeof(int32_t)*(size_t) (nC+1)));
-    PREP_CHK(dev.alloc((void **) &raw.points, sizeof(double)*8*eRaw));
-    PREP_CHK(dev.alloc((void **) &raw.types, eRaw));
-    PREP_CHK(dev.alloc((void **) &norm.points, sizeof(double)*8*eNorm));
-    PREP_CHK(dev.alloc((void **) &norm.types, eNorm));
-    PREP_CHK(dev.alloc((void **) &norm.colors, eNorm));
-    PREP_CHK(hipMemcpy(dGco, gco, sizeof(int32_t)*(size_t) (n_glyphs+1), hipMemcpyHostToDevice));
-    PREP_CHK(hipMemcpy(dCo, co, sizeof(int32_t)*(size_t) (nC+1), hipMemcpyHostToDevice));
-    PREP_CHK(hipMemcpy(dCo1, co1.data(), sizeof(int32_t)*(size_t) (nC+1), hipMemcpyHostToDevice));
-    if (nE) {
-        PREP_CHK(hipMemcpy(raw.points, points, sizeof(double)*8*(size_t) nE, hipMemcpyHostToDevice));
-        PREP_CHK(hipMemcpy(raw.types, types, (size_t) nE, hipMemcpyHostToDevice));
-        if (colors) {
-            PREP_CHK(dev.alloc((void **) &raw.colors, eRaw));
-            PREP_CHK(hipMemcpy(raw.colors, colors, (size_t) nE, hipMemcpyHostToDevice));
-        }
-    }
+    // one allocation per region the configuration needs (msdf_prepplan.hpp), with the exact normalized count and the bound of the coloured one; the records
+    // and windings come with digest(), which sizes them from the final count
+    const PrepPlanConfig plan = { true, cfg->coloring, seeds != NULL, colors != NULL && nE > 0, orient.orient_contours != 0, orientHitsBig(maxRawEdges),
+                                  longest > PREP_WAVE_MAX_EDGES, true, false };
+    const PrepCounts counts = { (size_t) n_glyphs, (size_t) nC, (size_t) nE, (size_t) nE1, bound2 };
+    const PrepSizes sizes = prepRegionSizes(plan, counts);
+    void *region[PREP_REGIONS] = { NULL };
+    for (int r = 0; r < PREP_REGIONS; ++r)
+        if (sizes.bytes[r])
+            PREP_CHK(dev.alloc(&region[r], sizes.bytes[r]));
+    const size_t offsetBytes = sizeof(int32_t)*(size_t) (nC+1);
+    const struct { int region; const void *host; size_t bytes; } uploads[] = {
+        { PREP_GCO, gco, sizeof(int32_t)*(size_t) (n_glyphs+1) }, { PREP_CO, co, offsetBytes }, { PREP_CO1, co1.data(), offsetBytes },
+        { PREP_RAW_POINTS, points, sizeof(double)*8*(size_t) nE }, { PREP_RAW_TYPES, types, (size_t) nE }, { PREP_RAW_COLORS, colors, (size_t) nE },
+        { PREP_SEEDS, seeds, sizeof(unsigned long long)*(size_t) n_glyphs } };
+    for (size_t u = 0; u < sizeof(uploads)/sizeof(uploads[0]); ++u)
+        if (region[uploads[u].region] && uploads[u].bytes)
+            PREP_CHK(hipMemcpy(region[uploads[u].region], uploads[u].host, uploads[u].bytes, hipMemcpyHostToDevice));
     const double crossThreshold = cfg->coloring ? sin(cfg->angle_threshold) : 0.;   // edge-coloring.cpp:69, taken by the host's libm like the reference's
-    if (cfg->coloring) {
-        PREP_CHK(dev.alloc((void **) &dCount, sizeof(int32_t)*(size_t) (nC+1)));
-        PREP_CHK(dev.alloc((void **) &dCo2, sizeof(int32_t)*(size_t) (nC+1)));
-        PREP_CHK(dev.alloc((void **) &fin.points, sizeof(double)*8*eFin));
-        PREP_CHK(dev.alloc((void **) &fin.types, eFin));
-        PREP_CHK(dev.alloc((void **) &fin.colors, eFin));
-        if (seeds && n_glyphs) {
-            PREP_CHK(dev.alloc((void **) &dSeeds, sizeof(unsigned long long)*(size_t) n_glyphs));
-            PREP_CHK(hipMemcpy(dSeeds, seeds, sizeof(unsigned long long)*(size_t) n_glyphs, hipMemcpyHostToDevice));
-        }
-        // the colouring's per-contour tables live in LDS; a contour beyond PREP_WAVE_MAX_EDGES edges keeps them in global memory, indexed like the edges
-        if (longest > PREP_WAVE_MAX_EDGES) {
-            PREP_CHK(dev.alloc((void **) &big.cornerMask, sizeof(unsigned long long)*(eNorm/WAVE+(size_t) nC+2)));
-            PREP_CHK(dev.alloc((void **) &big.splineColor, eNorm));
-            if (cfg->coloring == 2) {
-                PREP_CHK(dev.alloc((void **) &big.edgeLength, sizeof(double)*eNorm));
-                PREP_CHK(dev.alloc((void **) &big.cornerLength, sizeof(double)*eNorm));
-                PREP_CHK(dev.alloc((void **) &big.cornerIndex, sizeof(int)*eNorm));
-                PREP_CHK(dev.alloc((void **) &big.minor, eNorm));
-            }
-        }
-    } else
-        fin = norm;
-    if (orient.orient_contours) {                                 // orientContours' scratch: votes of glyphs with many contours, hits beyond the LDS tier
-        PREP_CHK(dev.alloc((void **) &dVotes, sizeof(int32_t)*(size_t) (nC+1)));
-        if (orientHitsBig(maxRawEdges)) {
-            PREP_CHK(dev.alloc((void **) &dHitX, sizeof(double)*3*eRaw));
-            PREP_CHK(dev.alloc((void **) &dHitTag, sizeof(int32_t)*3*eRaw));
-        }
-    }
     // Every pass is queued without a host round trip; the coloured offsets come back once, at the end.
-    const PrepBuffers pb = { dGco, dCo, dCo1, raw, norm, fin, dCusp, dCount, dCo2, dSeeds, big, dVotes, dHitX, dHitTag };
+    const PrepBuffers pb = bindPrep(region);
     rc = queuePreparation(cfg, orient, n_glyphs, nC, nE1, longest, crossThreshold, pb, 0);
     if (rc != MSDFHIP_OK)
         return rc;
     // Shape::getBounds where the CLI takes it (main.cpp:1125-1132): of the normalized edges, which do not outlive this call when a colouring follows
-    double *dBounds = NULL;
-    PREP_CHK(dev.alloc((void **) &dBounds, sizeof(double)*4*(size_t) (n_glyphs > 0 ? n_glyphs : 1)));
-    rc = queueFrame(norm, dGco, dCo1, n_glyphs, dBounds, false, NULL, 0, 0, NULL, 0);
+    double *dBounds = (double *) region[PREP_BOUNDS];
+    rc = queueFrame(pb.norm, pb.gco, pb.co1, n_glyphs, dBounds, false, NULL, 0, 0, NULL, 0);
     if (rc != MSDFHIP_OK)
         return rc;
     const int32_t *finalCo = co1.data();
-    int32_t *dFinalCo = dCo1;
+    int32_t *dGco = (int32_t *) region[PREP_GCO], *dFinalCo = (int32_t *) region[PREP_CO1];
     if (cfg->coloring) {
-        PREP_CHK(hipMemcpy(co2.data(), dCo2, sizeof(int32_t)*(size_t) (nC+1), hipMemcpyDeviceToHost));   // in stream order after the kernels above
+        PREP_CHK(hipMemcpy(co2.data(), pb.co2, sizeof(int32_t)*(size_t) (nC+1), hipMemcpyDeviceToHost));   // in stream order after the kernels above
         finalCo = co2.data();
-        dFinalCo = dCo2;
+        dFinalCo = pb.co2;
     }
     PREP_CHK(hipGetLastError());
     PREP_CHK(hipDeviceSynchronize());
@@ -1421,9 +1353,9 @@ int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, c
     b->onDevice(currentDevice());
     b->nGlyphs = n_glyphs, b->nContours = nC, b->nEdges = finalCo[nC], b->maxContours = maxC, b->maxEdges = maxE;
     b->ownsInputs = true;                                        // the batch takes over the final arrays
-    b->dGlyphContourOffsets = dGco, b->dContourOffsets = dFinalCo, b->dPoints = fin.points, b->dTypes = fin.types, b->dColors = fin.colors;
+    b->dGlyphContourOffsets = dGco, b->dContourOffsets = dFinalCo, b->dPoints = pb.fin.points, b->dTypes = pb.fin.types, b->dColors = pb.fin.colors;
     b->dBounds = dBounds, b->boundsFixed = true;
-    dev.release(dGco), dev.release(dFinalCo), dev.release(fin.points), dev.release(fin.types), dev.release(fin.colors), dev.release(dBounds);
+    dev.release(dGco), dev.release(dFinalCo), dev.release(pb.fin.points), dev.release(pb.fin.types), dev.release(pb.fin.colors), dev.release(dBounds);
     rc = digest(b, NULL);
     if (rc == MSDFHIP_OK && hipStreamSynchronize(NULL) != hipSuccess)
         rc = fail(MSDFHIP_ERR_HIP, "edge digestion failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1986,7 +1918,8 @@ struct StreamFeeder : ChunkFeeder {
     int nG;
     std::vector<int> hContours, hEdges;                          // per glyph
     std::vector<long long> contourBase, edgeBase;                // prefix sums over the whole list (nG+1)
-    std::vector<int> chunkStart, chunkLen;
+    PrepPlanConfig planCfg;                                      // which regions a chunk's input area holds (msdf_prepplan.hpp); hitsBig / longContour per chunk
+    StreamPrepPlan plan;                                         // the chunks and what every slot must hold (begin)
     std::vector<std::shared_ptr<HostJob> > jobs;                 // flatten job of chunk k
     std::unique_ptr<std::atomic<int>[]> badType;                 // per chunk: a glyph whose fill produced an edge type outside 1..3 (-1: none); written by pool threads
     PipeSlot *slots;
@@ -1996,7 +1929,6 @@ struct StreamFeeder : ChunkFeeder {
     const uint64_t *seeds;                                       // one per glyph of the whole list, or NULL (prep->seed)
     MsdfHipOrientConfig orient;                                  // orientation around the preparation (checked; all 0: keep)
     double crossThreshold;                                       // sin(angle_threshold), by the host's libm (edge-coloring.cpp:69)
-    std::vector<char> mayHaveLong;                               // per chunk: a glyph whose normalized contours could exceed PREP_WAVE_MAX_EDGES (the `big` tables)
     const FrameParams *frame;                                    // raw outlines only: every chunk is framed between its preparation and its digest (k_frame); NULL: the caller's xf
     int frameW, frameH;
     enum { GRAIN = 32 };                                         // glyphs per flatten item
@@ -2006,6 +1938,8 @@ struct StreamFeeder : ChunkFeeder {
         : src(source), nG(n), slots(NULL), prep(prepCfg), seeds(glyphSeeds), crossThreshold(prepCfg && prepCfg->coloring ? sin(prepCfg->angle_threshold) : 0.),
           frame(prepCfg ? frameCfg : NULL), frameW(w), frameH(h) {
         orient.orient_contours = orientCfg ? orientCfg->orient_contours : 0, orient.winding = orientCfg ? orientCfg->winding : 0;
+        const PrepPlanConfig c = { prep != NULL, prep ? prep->coloring : 0, seeds != NULL, true, orient.orient_contours != 0, false, false, frame != NULL, true };
+        planCfg = c;
     }
     ~StreamFeeder() { drain(); }
     bool frames() const { return frame != NULL; }
@@ -2044,59 +1978,22 @@ struct StreamFeeder : ChunkFeeder {
         return MSDFHIP_OK;
     }
 
-    // layout of a chunk's inputs inside a slot's staging / device input area (offsets from the area's start); `bytes` are uploaded
-    struct Layout { size_t gco, co, points, types, colors, co1, seeds, bytes; };
-    Layout layout(size_t n, size_t nC, size_t nE) const {
-        Carver c;
-        Layout l;
-        l.gco = c.take((n+1)*sizeof(int32_t)), l.co = c.take((nC+1)*sizeof(int32_t)), l.points = c.take((nE ? nE : 1)*8*sizeof(double));
-        l.types = c.take(nE ? nE : 1), l.colors = c.take(nE ? nE : 1);
-        l.co1 = prep ? c.take((nC+1)*sizeof(int32_t)) : 0;     // (raw outlines) contour offsets after normalize, from the host (prepOffsets)
-        l.seeds = prep && seeds ? c.take(n*sizeof(uint64_t)) : 0;
-        l.bytes = c.off;
-        return l;
-    }
-
-    // (raw outlines) the device-only part of a chunk's input area behind the uploaded part: the preparation's buffers, then the records + windings of
-    // the PREPARED edges. nE1 / nE2: normalized / coloured edge counts. begin() sizes the slots with their bounds (nE + 2 nC, nE + 4 nC: a raw contour of
-    // one edge becomes three, one of two edges at most six), a chunk carves its exact counts -- the same pieces in the same order, so never beyond.
-    // With orient_contours: the votes (nC) and, when a glyph of the chunk can overflow k_prep_orient's LDS (hitsBig), 3 hits per raw edge (nE).
-    struct PrepLayout { size_t cusp, count, co2, norm[3], fin[3], bigMask, bigSpline, bigEdgeLength, bigCornerLength, bigCornerIndex, bigMinor, votes, hitX, hitTag,
-                        bounds, recs, windings, bytes; };
-    PrepLayout prepLayout(size_t at, size_t n, size_t nC, size_t nE, size_t nE1, size_t nE2, bool big, bool hitsBig) const {
-        Carver c;
-        c.off = (at+255)/256*256;
-        PrepLayout l = PrepLayout();
-        const size_t e1 = nE1 ? nE1 : 1, e2 = nE2 ? nE2 : 1;
-        l.cusp = c.take((nC+1)*sizeof(int32_t)), l.count = c.take((nC+1)*sizeof(int32_t)), l.co2 = c.take((nC+1)*sizeof(int32_t));
-        l.norm[0] = c.take(e1*8*sizeof(double)), l.norm[1] = c.take(e1), l.norm[2] = c.take(e1);
-        if (prep->coloring) {
-            l.fin[0] = c.take(e2*8*sizeof(double)), l.fin[1] = c.take(e2), l.fin[2] = c.take(e2);
-            if (big) {                                           // (msdfhip_batch_create_prepared's sizes)
-                l.bigMask = c.take(sizeof(unsigned long long)*(e1/WAVE+nC+2)), l.bigSpline = c.take(e1);
-                if (prep->coloring == 2)
-                    l.bigEdgeLength = c.take(sizeof(double)*e1), l.bigCornerLength = c.take(sizeof(double)*e1), l.bigCornerIndex = c.take(sizeof(int)*e1), l.bigMinor = c.take(e1);
-            }
-        }
-        if (orient.orient_contours) {
-            l.votes = c.take((nC+1)*sizeof(int32_t));
-            if (hitsBig)
-                l.hitX = c.take(3*(nE ? nE : 1)*sizeof(double)), l.hitTag = c.take(3*(nE ? nE : 1)*sizeof(int32_t));
-        }
-        if (frame)                                               // Shape::getBounds per glyph (k_frame)
-            l.bounds = c.take(4*(n ? n : 1)*sizeof(double));
-        l.recs = c.take(sizeof(EdgeRec)*(prep->coloring ? e2 : e1)), l.windings = c.take(nC ? nC : 1), l.bytes = c.off;
-        return l;
+    // A chunk's inputs inside a slot's pinned staging / device input area (msdf_prepplan.hpp): the uploaded regions, then on the device the preparation's
+    // buffers and the records + windings of the PREPARED edges. begin() sizes the slots from the plan's bounds; a chunk carves its exact counts.
+    PrepCarve carve(const StreamChunk &ch, size_t nE1 = 0, size_t nE2 = 0, bool longContour = false, bool hitsBig = false) const {
+        PrepPlanConfig c = planCfg;
+        c.longContour = longContour, c.hitsBig = hitsBig;
+        const PrepCounts counts = { (size_t) ch.length, ch.nC, ch.nE, nE1, nE2 };
+        return prepCarve(c, counts);
     }
 
     void flattenItem(size_t ci, int item) {
-        const int g0 = chunkStart[ci], n = chunkLen[ci];
-        PipeSlot &p = slots[ci%PIPE_SLOTS];
+        const int g0 = plan.chunks[ci].start, n = plan.chunks[ci].length;
         const long long c0 = contourBase[(size_t) g0], e0 = edgeBase[(size_t) g0];
-        const Layout l = layout((size_t) n, (size_t) (contourBase[(size_t) g0+n]-c0), (size_t) (edgeBase[(size_t) g0+n]-e0));
-        int32_t *gco = reinterpret_cast<int32_t *>(p.pinnedIn.ptr+l.gco), *co = reinterpret_cast<int32_t *>(p.pinnedIn.ptr+l.co);
-        double *points = reinterpret_cast<double *>(p.pinnedIn.ptr+l.points);
-        uint8_t *types = reinterpret_cast<uint8_t *>(p.pinnedIn.ptr+l.types), *colors = reinterpret_cast<uint8_t *>(p.pinnedIn.ptr+l.colors);
+        const PrepBuffers staged = bindPrep(slots[ci%PIPE_SLOTS].pinnedIn.ptr, carve(plan.chunks[ci]));   // (the uploaded regions alone)
+        int32_t *gco = const_cast<int32_t *>(staged.gco), *co = const_cast<int32_t *>(staged.co);
+        double *points = staged.raw.points;
+        uint8_t *types = staged.raw.types, *colors = staged.raw.colors;
         const int first = item*GRAIN, last = first+GRAIN < n ? first+GRAIN : n;
         if (item == 0)
             gco[0] = 0, co[0] = 0;
@@ -2119,43 +2016,24 @@ struct StreamFeeder : ChunkFeeder {
     }
 
     void startFlatten(size_t ci) {
-        if (ci >= chunkLen.size() || jobs[ci])
+        if (ci >= plan.chunks.size() || jobs[ci])
             return;
-        const int items = (chunkLen[ci]+GRAIN-1)/GRAIN;
+        const int items = (plan.chunks[ci].length+GRAIN-1)/GRAIN;
         jobs[ci] = hostPool().submit(items, [this, ci](int item) { flattenItem(ci, item); });
     }
 
     int begin(PipeSlot *pipeSlots, const std::vector<int> &lengths) {
         slots = pipeSlots;
-        chunkStart.clear(), chunkLen = lengths;
-        int g = 0;
-        size_t needIn = 0, needC = 0, needE = 0, prepPinned = 0, prepDev = 0;
-        mayHaveLong.assign(lengths.size(), 0);
-        for (size_t ci = 0; ci < lengths.size(); g += lengths[ci], ++ci) {
-            chunkStart.push_back(g);
-            const size_t nC = (size_t) (contourBase[(size_t) g+lengths[ci]]-contourBase[(size_t) g]), nE = (size_t) (edgeBase[(size_t) g+lengths[ci]]-edgeBase[(size_t) g]);
-            if (nE > 0x7fffffffull/8 || nC > 0x7fffffffull/8 || (prep && nE+4*nC > 0x7fffffffull/8))
-                return fail(MSDFHIP_ERR_INVALID, "a pipeline chunk of %d glyphs holds %zu edges / %zu contours: beyond the 32-bit offsets of a batch", lengths[ci], nE, nC);
-            const Layout l = layout((size_t) lengths[ci], nC, nE);
-            needIn = l.bytes > needIn ? l.bytes : needIn, needC = nC > needC ? nC : needC, needE = nE > needE ? nE : needE;
-            if (prep) {                                          // + the coloured offsets coming back behind the staging; the preparation's buffers
-                int maxRaw = 0;
-                for (int k = g; k < g+lengths[ci]; ++k) {
-                    mayHaveLong[ci] |= (long long) hEdges[(size_t) k]+2LL*hContours[(size_t) k] > PREP_WAVE_MAX_EDGES;
-                    maxRaw = hEdges[(size_t) k] > maxRaw ? hEdges[(size_t) k] : maxRaw;
-                }
-                const size_t pin = (l.bytes+255)/256*256+(nC+1)*sizeof(int32_t);
-                const size_t dev = prepLayout(l.bytes, (size_t) lengths[ci], nC, nE, nE+2*nC, nE+4*nC, mayHaveLong[ci] != 0, orientHitsBig(maxRaw)).bytes;
-                prepPinned = pin > prepPinned ? pin : prepPinned, prepDev = dev > prepDev ? dev : prepDev;
-            }
+        plan = planStreamPrep(hContours.data(), hEdges.data(), lengths, planCfg);
+        if (plan.refused >= 0) {
+            const StreamChunk &ch = plan.chunks[(size_t) plan.refused];
+            return fail(MSDFHIP_ERR_INVALID, "a pipeline chunk of %d glyphs holds %zu edges / %zu contours: beyond the 32-bit offsets of a batch", ch.length, ch.nE, ch.nC);
         }
-        if (prep)
-            needIn = prepPinned;
         jobs.assign(lengths.size(), std::shared_ptr<HostJob>());
         badType.reset(new std::atomic<int>[lengths.size() ? lengths.size() : 1]);
         for (size_t ci = 0; ci < lengths.size(); ++ci)
             badType[ci].store(-1);
-        const size_t recBytes = (sizeof(EdgeRec)*(needE ? needE : 1)+255)/256*256, devNeed = prep ? prepDev+256 : needIn+recBytes+(needC ? needC : 1)+256;
+        const size_t needIn = plan.pinnedBytes, devNeed = plan.devBytes+256;
         for (int k = 0; k < PIPE_SLOTS; ++k) {                   // every slot can take the largest chunk (grown once, kept with the pooled pipe)
             PipeSlot &p = slots[k];
             if (p.pinnedIn.cap < needIn)
@@ -2178,7 +2056,7 @@ struct StreamFeeder : ChunkFeeder {
         // keep the host threads two chunks ahead of the device: chunk ci+2 goes into the staging of the slot chunk ci+2-PIPE_SLOTS used -- that chunk's
         // upload (queued long ago) must have left it
         const size_t ahead = ci+2;
-        if (ahead < chunkLen.size()) {
+        if (ahead < plan.chunks.size()) {
             PipeSlot &q = slots[ahead%PIPE_SLOTS];
             if (&q != &p && q.inputsInFlight) {
                 HIPCHK(hipEventSynchronize(q.inputsUploaded));
@@ -2187,32 +2065,35 @@ struct StreamFeeder : ChunkFeeder {
             if (&q != &p)
                 startFlatten(ahead);
         }
-        const size_t nC = (size_t) (contourBase[(size_t) g0+n]-contourBase[(size_t) g0]), nE = (size_t) (edgeBase[(size_t) g0+n]-edgeBase[(size_t) g0]);
-        const Layout l = layout((size_t) n, nC, nE);
+        const StreamChunk &ch = plan.chunks[ci];
+        const int nC = (int) ch.nC;
+        const PrepBuffers staged = bindPrep(p.pinnedIn.ptr, carve(ch));
         size_t bound2 = 0;
         int longest = 0;
         if (prep) {                                              // the normalized offsets and the seeds travel with the chunk's upload
-            prepOffsets(reinterpret_cast<const int32_t *>(p.pinnedIn.ptr+l.co), (int) nC, prep->normalize != 0, reinterpret_cast<int32_t *>(p.pinnedIn.ptr+l.co1), &bound2, &longest);
-            if (seeds)
-                memcpy(p.pinnedIn.ptr+l.seeds, seeds+g0, sizeof(uint64_t)*(size_t) n);
+            prepOffsets(staged.co, nC, prep->normalize != 0, const_cast<int32_t *>(staged.co1), &bound2, &longest);
+            if (staged.seeds)
+                memcpy(const_cast<unsigned long long *>(staged.seeds), seeds+g0, sizeof(uint64_t)*(size_t) n);
         }
+        // the chunk's exact carve: inside the slot, which begin() sized from the bounds of these counts
+        const PrepCarve cv = carve(ch, prep ? (size_t) staged.co1[nC] : 0, bound2, longest > PREP_WAVE_MAX_EDGES, ch.hitsBig);
+        char *d = p.devIn.ptr;
+        const PrepBuffers pb = bindPrep(d, cv);
         // (a kernel reading the pinned staging: never queues behind another chunk's copy back)
-        const int rcUp = uploadSmall(p.devIn.ptr, p.pinnedIn.ptr, (l.bytes+15)/16*16, stream);
+        const int rcUp = uploadSmall(d, p.pinnedIn.ptr, cv.uploadBytes, stream);
         if (rcUp != MSDFHIP_OK)
             return rcUp;
         HIPCHK(hipEventRecord(p.inputsUploaded, stream));
         p.inputsInFlight = true;
         MsdfHipBatch &v = p.view;
         v.onDevice(currentDevice());
-        v.nGlyphs = n, v.nContours = (int) nC, v.nEdges = (int) nE;
-        v.dGlyphContourOffsets = reinterpret_cast<int32_t *>(p.devIn.ptr+l.gco), v.dContourOffsets = reinterpret_cast<int32_t *>(p.devIn.ptr+l.co);
-        v.dPoints = reinterpret_cast<double *>(p.devIn.ptr+l.points), v.dTypes = reinterpret_cast<uint8_t *>(p.devIn.ptr+l.types), v.dColors = reinterpret_cast<uint8_t *>(p.devIn.ptr+l.colors);
-        const size_t recOff = (l.bytes+255)/256*256;
-        v.dRecs = reinterpret_cast<EdgeRec *>(p.devIn.ptr+recOff);
-        v.dWindings = reinterpret_cast<int8_t *>(p.devIn.ptr+recOff+(sizeof(EdgeRec)*(nE ? nE : 1)+255)/256*256);
+        v.nGlyphs = n, v.nContours = nC, v.nEdges = (int) ch.nE;
+        v.dGlyphContourOffsets = const_cast<int32_t *>(pb.gco), v.dContourOffsets = const_cast<int32_t *>(pb.co);
+        v.dPoints = pb.raw.points, v.dTypes = pb.raw.types, v.dColors = pb.raw.colors;
+        v.dRecs = reinterpret_cast<EdgeRec *>(prepRegionAt(d, cv, PREP_RECS)), v.dWindings = reinterpret_cast<int8_t *>(prepRegionAt(d, cv, PREP_WINDINGS));
         v.setCounts(hContours.data()+g0, hEdges.data()+g0, n);
         if (prep) {
-            const int rcPrep = prepareChunk(p, l, n, (int) nC, bound2, longest, stream);
+            const int rcPrep = prepareChunk(p, cv, pb, staged.gco, staged.co1, n, nC, longest, stream);
             if (rcPrep != MSDFHIP_OK)
                 return rcPrep;
         }
@@ -2224,39 +2105,13 @@ struct StreamFeeder : ChunkFeeder {
     // (raw outlines) the chunk's preparation on its stream, behind its upload; then p.view is pointed at the prepared arrays. The per-glyph edge counts the
     // launches are planned from are the PREPARED ones, and the colouring may split a contour in a way only the device knows: its contour offsets come back
     // (one small copy + an event). runPipelineOnce calls this after the previous chunk's kernels are queued, so the device has work while the host waits.
-    int prepareChunk(PipeSlot &p, const Layout &l, int n, int nC, size_t bound2, int longest, hipStream_t stream) {
-        char *d = p.devIn.ptr;
-        const int32_t *hCo1 = reinterpret_cast<const int32_t *>(p.pinnedIn.ptr+l.co1), *hGco = reinterpret_cast<const int32_t *>(p.pinnedIn.ptr+l.gco);
-        const int nE1 = hCo1[nC];
-        const bool big = longest > PREP_WAVE_MAX_EDGES;
-        const int maxRaw = p.view.maxEdges;                      // (still of the raw counts)
-        const bool hitsBig = orient.orient_contours && orientHitsBig(maxRaw);
-        const PrepLayout pl = prepLayout(l.bytes, (size_t) n, (size_t) nC, (size_t) reinterpret_cast<const int32_t *>(p.pinnedIn.ptr+l.co)[nC], (size_t) nE1, bound2, big, hitsBig);
-        EdgeArrays raw = { reinterpret_cast<double *>(d+l.points), reinterpret_cast<uint8_t *>(d+l.types), reinterpret_cast<uint8_t *>(d+l.colors) };
-        EdgeArrays norm = { reinterpret_cast<double *>(d+pl.norm[0]), reinterpret_cast<uint8_t *>(d+pl.norm[1]), reinterpret_cast<uint8_t *>(d+pl.norm[2]) };
-        EdgeArrays fin = norm;
-        ColourTables tables = { NULL, NULL, NULL, NULL, NULL, NULL };
-        if (prep->coloring) {
-            fin.points = reinterpret_cast<double *>(d+pl.fin[0]), fin.types = reinterpret_cast<uint8_t *>(d+pl.fin[1]), fin.colors = reinterpret_cast<uint8_t *>(d+pl.fin[2]);
-            if (big) {
-                tables.cornerMask = reinterpret_cast<unsigned long long *>(d+pl.bigMask), tables.splineColor = reinterpret_cast<unsigned char *>(d+pl.bigSpline);
-                if (prep->coloring == 2) {
-                    tables.edgeLength = reinterpret_cast<double *>(d+pl.bigEdgeLength), tables.cornerLength = reinterpret_cast<double *>(d+pl.bigCornerLength);
-                    tables.cornerIndex = reinterpret_cast<int *>(d+pl.bigCornerIndex), tables.minor = reinterpret_cast<unsigned char *>(d+pl.bigMinor);
-                }
-            }
-        }
-        int32_t *dCo1 = reinterpret_cast<int32_t *>(d+l.co1), *dCo2 = reinterpret_cast<int32_t *>(d+pl.co2);
-        const PrepBuffers pb = { reinterpret_cast<const int32_t *>(d+l.gco), reinterpret_cast<const int32_t *>(d+l.co), dCo1, raw, norm, fin,
-                                 reinterpret_cast<int32_t *>(d+pl.cusp), reinterpret_cast<int32_t *>(d+pl.count), dCo2,
-                                 seeds ? reinterpret_cast<const unsigned long long *>(d+l.seeds) : NULL, tables,
-                                 orient.orient_contours ? reinterpret_cast<int32_t *>(d+pl.votes) : NULL,
-                                 hitsBig ? reinterpret_cast<double *>(d+pl.hitX) : NULL, hitsBig ? reinterpret_cast<int32_t *>(d+pl.hitTag) : NULL };
-        int rc = queuePreparation(prep, orient, n, nC, nE1, longest, crossThreshold, pb, stream);
+    // cv, pb: the chunk's carve and its buffers on the device; hGco, hCo1: the offsets in the pinned staging.
+    int prepareChunk(PipeSlot &p, const PrepCarve &cv, const PrepBuffers &pb, const int32_t *hGco, const int32_t *hCo1, int n, int nC, int longest, hipStream_t stream) {
+        int rc = queuePreparation(prep, orient, n, nC, hCo1[nC], longest, crossThreshold, pb, stream);
         if (rc != MSDFHIP_OK)
             return rc;
         if (frame) {                                             // bounds of the normalized edges -> xf of the chunk's descriptors, which are on the device already
-            rc = queueFrame(norm, pb.gco, dCo1, n, reinterpret_cast<double *>(d+pl.bounds), false, frame, frameW, frameH, p.frameGlyphs, stream);
+            rc = queueFrame(pb.norm, pb.gco, pb.co1, n, reinterpret_cast<double *>(prepRegionAt(p.devIn.ptr, cv, PREP_BOUNDS)), false, frame, frameW, frameH, p.frameGlyphs, stream);
             if (rc != MSDFHIP_OK)
                 return rc;
         }
@@ -2264,8 +2119,8 @@ struct StreamFeeder : ChunkFeeder {
         if (prep->coloring) {
             // the offsets come back by the word-copy kernel writing into the pinned staging rather than by a copy, which would share the copy engine with
             // the earlier chunks' tiles (measured the same either way on 8 192 glyphs, tools/stream_raw_bench.py: the wait is the preparation itself)
-            int32_t *hCo2 = reinterpret_cast<int32_t *>(p.pinnedIn.ptr+(l.bytes+255)/256*256);
-            rc = uploadSmall(hCo2, dCo2, sizeof(int32_t)*(size_t) (nC+1), stream);
+            int32_t *hCo2 = reinterpret_cast<int32_t *>(p.pinnedIn.ptr+cv.uploadBytes);
+            rc = uploadSmall(hCo2, pb.co2, sizeof(int32_t)*(size_t) (nC+1), stream);
             if (rc != MSDFHIP_OK)
                 return rc;
             HIPCHK(hipEventRecord(p.prepCounted, stream));
@@ -2274,9 +2129,8 @@ struct StreamFeeder : ChunkFeeder {
         }
         MsdfHipBatch &v = p.view;
         v.nEdges = hFinal[nC];
-        v.dContourOffsets = prep->coloring ? dCo2 : dCo1;
-        v.dPoints = fin.points, v.dTypes = fin.types, v.dColors = fin.colors;
-        v.dRecs = reinterpret_cast<EdgeRec *>(d+pl.recs), v.dWindings = reinterpret_cast<int8_t *>(d+pl.windings);
+        v.dContourOffsets = prep->coloring ? pb.co2 : const_cast<int32_t *>(pb.co1);
+        v.dPoints = pb.fin.points, v.dTypes = pb.fin.types, v.dColors = pb.fin.colors;
         for (int g = 0; g < n; ++g)
             v.hEdges[(size_t) g] = hFinal[hGco[g+1]]-hFinal[hGco[g]];
         v.countMaxima();

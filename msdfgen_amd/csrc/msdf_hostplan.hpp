@@ -1,6 +1,6 @@
 // msdf_hostplan.hpp -- the integer planning of the host-output pipeline (msdf_capi.hip: runPipelineOnce) and of the glyph-sharded entry point:
 // how a glyph list is cut into chunks, where a chunk's rectangles lie in the caller's buffer and whether they tile it, how a slot's device
-// buffer is laid out, which glyph range each device gets.
+// buffer is laid out, which glyph range each device gets. (A streamed call's INPUT areas -- staging, preparation buffers, records -- are msdf_prepplan.hpp's.)
 // Host code only (no HIP): msdf_capi.hip includes it, and tests/hostemu compiles it with the host compiler (tests/test_host_plan.py).
 
 #pragma once

@@ -20,6 +20,7 @@
 #include "../../msdfgen_amd/csrc/msdf_classplan.hpp"
 #include "../../msdfgen_amd/csrc/msdf_hostplan.hpp"
 #include "../../msdfgen_amd/csrc/msdf_launchplan.hpp"
+#include "../../msdfgen_amd/csrc/msdf_prepplan.hpp"
 
 using namespace msdfhip;
 
@@ -1001,4 +1002,49 @@ extern "C" void emu_plan_sign(const double *e, int nGlyphs, int maxE, int w, int
     const SignPlan p = planSign(planEnvOf(e), nGlyphs, maxE, w, h);
     const long long r[8] = { p.span, p.spansX, p.spans, (long long) p.blocks, (long long) p.cap, (long long) p.lds, p.wholeRows, p.chunked };
     memcpy(out8, r, sizeof(r));
+}
+
+// msdf_prepplan.hpp: the buffers of the raw-outline preparation (tests/test_prep_plan_host.py). cfg[9]: PrepPlanConfig in the order of its fields;
+// counts[5]: n, nC, nE, nE1, nE2.
+static PrepPlanConfig prepCfgOf(const int *c) {
+    const PrepPlanConfig cfg = { c[0] != 0, c[1], c[2] != 0, c[3] != 0, c[4] != 0, c[5] != 0, c[6] != 0, c[7] != 0, c[8] != 0 };
+    return cfg;
+}
+static PrepCounts prepCountsOf(const long long *k) {
+    const PrepCounts counts = { (size_t) k[0], (size_t) k[1], (size_t) k[2], (size_t) k[3], (size_t) k[4] };
+    return counts;
+}
+extern "C" int emu_prep_regions(int *uploaded) { *uploaded = PREP_UPLOADED; return PREP_REGIONS; }
+extern "C" int emu_prep_orient_hits_big(long long maxRawEdges) { return orientHitsBig(maxRawEdges) ? 1 : 0; }
+extern "C" void emu_prep_offsets(const int32_t *co, int nC, int normalize, int32_t *co1, long long *bound2, int *longest) {
+    size_t b2 = 0;
+    prepOffsets(co, nC, normalize != 0, co1, &b2, longest);
+    *bound2 = (long long) b2;
+}
+extern "C" void emu_prep_carve(const int *cfg, const long long *counts, long long *off, long long *bytes, long long *out3) {   // out3: uploadBytes, deviceBytes, pinnedBytes
+    const PrepCarve c = prepCarve(prepCfgOf(cfg), prepCountsOf(counts));
+    for (int r = 0; r < PREP_REGIONS; ++r)
+        off[r] = (long long) c.off[r], bytes[r] = (long long) c.bytes[r];
+    out3[0] = (long long) c.uploadBytes, out3[1] = (long long) c.deviceBytes, out3[2] = (long long) c.pinnedBytes;
+}
+// chunks[6 per chunk]: start, length, nC, nE, mayHaveLong, hitsBig; out3: pinnedBytes, devBytes, refused. Returns the number of chunks described.
+extern "C" int emu_plan_stream_prep(const int *contours, const int *edges, const int *lengths, int nChunks, const int *cfg, long long *chunks, long long *out3) {
+    const StreamPrepPlan p = planStreamPrep(contours, edges, std::vector<int>(lengths, lengths+nChunks), prepCfgOf(cfg));
+    for (size_t i = 0; i < p.chunks.size(); ++i) {
+        const StreamChunk &c = p.chunks[i];
+        const long long row[6] = { c.start, c.length, (long long) c.nC, (long long) c.nE, c.mayHaveLong, c.hitsBig };
+        memcpy(chunks+6*i, row, sizeof(row));
+    }
+    out3[0] = (long long) p.pinnedBytes, out3[1] = (long long) p.devBytes, out3[2] = p.refused;
+    return (int) p.chunks.size();
+}
+// The PrepBuffers of a carve at `base`, field by field: gco, co, co1, raw / norm / fin (points, types, colors), cusp, count, co2, seeds, big (cornerMask,
+// splineColor, edgeLength, cornerLength, cornerIndex, minor), votes, hitX, hitTag. Nothing is dereferenced.
+extern "C" void emu_bind_prep(unsigned long long base, const int *cfg, const long long *counts, unsigned long long *fields25) {
+    const PrepBuffers pb = bindPrep(reinterpret_cast<char *>((uintptr_t) base), prepCarve(prepCfgOf(cfg), prepCountsOf(counts)));
+    const void *f[25] = { pb.gco, pb.co, pb.co1, pb.raw.points, pb.raw.types, pb.raw.colors, pb.norm.points, pb.norm.types, pb.norm.colors, pb.fin.points, pb.fin.types,
+                          pb.fin.colors, pb.cusp, pb.count, pb.co2, pb.seeds, pb.big.cornerMask, pb.big.splineColor, pb.big.edgeLength, pb.big.cornerLength,
+                          pb.big.cornerIndex, pb.big.minor, pb.votes, pb.hitX, pb.hitTag };
+    for (int i = 0; i < 25; ++i)
+        fields25[i] = (unsigned long long) (uintptr_t) f[i];
 }
