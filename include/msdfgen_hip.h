@@ -142,6 +142,22 @@ int msdfhip_error_correction(int channels, float *pixels, int width, int height,
 int msdfhip_error_correction_shapeless(int channels, float *pixels, int width, int height, int row_stride, const double *xf,
                                        double min_deviation_ratio, int protect_all);
 
+/* The legacy generators: generateSDF_legacy / generatePSDF_legacy / generateMSDF_legacy / generateMTSDF_legacy(output, shape, range, scale, translate
+ * [, errorCorrectionConfig]), core/msdfgen.cpp:166-333 (declared msdfgen.h:72-76) -- the minimum over all edges in shape order, no contour combiner.
+ * Arguments as msdfhip_generate (xf built from scale, translate and range as there). Of `cfg` only ec_mode, the two ratios, the sign-pass fields
+ * (sign_correction, fill_rule, sdf_zero_value) and stencil_y_down are read: the correction of modes 3, 4 always runs without overlap support and with
+ * MSDFHIP_DO_NOT_CHECK_DISTANCE, as the reference's does (core/msdfgen.cpp:272-273). With sign_correction this is the reference CLI's -legacy flow
+ * (main.cpp:1223-1298). `stencil`: as msdfhip_generate. Set flip = (shape is Y-downward) xor (bitmap is Y-downward) and cfg->stencil_y_down = (bitmap
+ * is Y-downward), as for msdfhip_generate: the two together tell the shape's orientation, and the stencil's memory row r is then the reference's --
+ * row r of the SHAPE's rows for a Y-upward shape, row height-1-r for a Y-downward one, whatever the bitmap's own orientation (the legacy generators
+ * re-orient the bitmap to the shape before they correct it, core/msdfgen.cpp:223). */
+int msdfhip_generate_legacy(int mode, float *pixels, int width, int height, int row_stride, int flip,
+                            const int32_t *contour_offsets, int n_contours, const double *points, const uint8_t *types, const uint8_t *colors,
+                            const double *xf, const MsdfHipConfig *cfg, uint8_t *stencil);
+/* msdfErrorCorrection_legacy(output, threshold) on a 3- or 4-channel bitmap, in place: the clash detection between axial, then diagonal neighbours.
+ *   replaces core/msdf-error-correction.cpp:115-181 (declared core/msdf-error-correction.h:37-38). Any row stride (in floats, may be negative). */
+int msdfhip_error_correction_legacy(int channels, float *pixels, int width, int height, int row_stride, double threshold_x, double threshold_y);
+
 /* distanceSignCorrection(sdf, shape, projection, sdfZeroValue, fillRule) on an existing 1-, 3- or 4-channel bitmap, in place.
  *   replaces core/rasterization.cpp:19-92 (declared core/rasterization.h:17-19; the legacy overloads :21-27 forward).
  * xf: only the Projection part {sx, sy, tx, ty} is read. fill_rule: FillRule (core/Scanline.h:10-15). */
@@ -209,6 +225,14 @@ int msdfhip_batch_windings(const MsdfHipBatch *batch, int32_t *windings);
  * stream at a time. Different batches, and the single-shape entry points above, are independent of each other. */
 int msdfhip_batch_generate(const MsdfHipBatch *batch, int mode, int width, int height, const MsdfHipGlyph *d_glyphs,
                            float *d_out, uint8_t *d_stencil, float *d_scratch, const MsdfHipConfig *cfg, void *stream);
+/* The legacy generators (msdfhip_generate_legacy above) for every glyph of the batch; arguments, scratch size and stream as msdfhip_batch_generate,
+ * `cfg` read as msdfhip_generate_legacy reads it. The call leaves nothing on the batch that a later msdfhip_batch_generate would rely on. */
+int msdfhip_batch_generate_legacy(const MsdfHipBatch *batch, int mode, int width, int height, const MsdfHipGlyph *d_glyphs,
+                                  float *d_out, uint8_t *d_stencil, float *d_scratch, const MsdfHipConfig *cfg, void *stream);
+/* msdfErrorCorrection_legacy of n_glyphs packed device tiles d_tiles[g][h][w][channels] (channels 3 or 4), in place; d_scratch: device floats, as
+ * many as the tiles hold (the two passes run tiles -> scratch -> tiles). Asynchronous on `stream`. */
+int msdfhip_batch_error_correction_legacy(float *d_tiles, int n_glyphs, int width, int height, int channels, float *d_scratch,
+                                          double threshold_x, double threshold_y, void *stream);
 /* End to end into HOST memory (what replaces an atlas generator's loop of generate*() calls into caller-owned bitmaps,
  * core/msdfgen.cpp:52-76, README.md:133): HOST descriptors, HOST output. The glyph list is processed in chunks on two streams, so the
  * kernels of one chunk overlap the device-to-host copy of the previous one; synchronous for the caller.

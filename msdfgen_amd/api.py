@@ -4,6 +4,8 @@ on top of the C ABI.  Same names, argument meaning and defaults as the reference
 
     generate_sdf / generate_psdf / generate_msdf / generate_mtsdf (output, shape, transformation, config)
     msdf_error_correction(sdf, shape, transformation, config)
+    generate_sdf_legacy / generate_psdf_legacy / generate_msdf_legacy / generate_mtsdf_legacy (output, shape, range, scale, translate[, error_correction_config])
+    msdf_error_correction_legacy(output, threshold) / error_correction_legacy(tiles, threshold)    -- host bitmap / device tensor
     distance_sign_correction(sdf, shape, projection, sdf_zero_value, fill_rule)
     rasterize(output, shape, projection, fill_rule)
     render_sdf(sdf_tiles, out_width, out_height, out_channels, sdf_px_range, sd_threshold) / simulate_8bit(tiles)   -- device tensors
@@ -245,6 +247,83 @@ def msdf_error_correction(sdf, shape, transformation, config: Optional[MSDFGener
                                             _lib.ptr(stencil, _lib._bp) if stencil is not None else None))
     del keep
     return sdf
+
+
+# ---- the legacy generators (msdfgen.h:72-76, core/msdfgen.cpp:166-333) and the legacy correction (core/msdf-error-correction.h:37-38) ----
+
+
+def _pair(v):
+    return (float(v), float(v)) if np.isscalar(v) else (float(v[0]), float(v[1]))
+
+
+def _legacy_xf(range, scale, translate):
+    """(sx, sy, tx, ty, mapScale, mapTranslate) of the legacy signature's Range (a Range, a symmetrical width or a (lower, upper) pair), scale, translate."""
+    r = range if isinstance(range, Range) else Range(float(range)) if np.isscalar(range) else Range(float(range[0]), float(range[1]))
+    ms, mt = distance_mapping(r.lower, r.upper)
+    return np.array(_pair(scale)+_pair(translate)+(ms, mt), np.float64)
+
+
+def _generate_legacy(mode, output, shape, range, scale, translate, ec, y_orientation):
+    lib = _lib.load()
+    px, w, h, stride = _bitmap_args(output, CHANNELS[mode])
+    keep, sargs = _shape_args(shape)
+    xf = _legacy_xf(range, scale, translate)
+    cfg = _c_config(MSDFGeneratorConfig(error_correction=ec) if ec is not None else None, y_orientation)   # (the library fixes overlap support and the distance check)
+    flip = int(bool(shape.inverse_y) != (y_orientation == Y_DOWNWARD))
+    stencil = ec.buffer if ec is not None and mode >= 3 else None
+    if stencil is not None and (stencil.dtype != np.uint8 or stencil.size < w*h or not stencil.flags.c_contiguous):
+        raise ValueError("error_correction_config.buffer must be C-contiguous uint8 with at least width*height bytes")
+    _lib.check(lib.msdfhip_generate_legacy(mode, px, w, h, stride, flip, *sargs, _lib.ptr(xf, _lib._dp), C.byref(cfg),
+                                           _lib.ptr(stencil, _lib._bp) if stencil is not None else None))
+    del keep
+    return output
+
+
+def generate_sdf_legacy(output, shape, range, scale, translate, y_orientation=Y_UPWARD):
+    """generateSDF_legacy (msdfgen.h:72, core/msdfgen.cpp:166-186): the true distance to the nearest of ALL edges, no contour combiner."""
+    return _generate_legacy(MODE_SDF, output, shape, range, scale, translate, None, y_orientation)
+
+
+def generate_psdf_legacy(output, shape, range, scale, translate, y_orientation=Y_UPWARD):
+    """generatePSDF_legacy (msdfgen.h:73, core/msdfgen.cpp:188-215)."""
+    return _generate_legacy(MODE_PSDF, output, shape, range, scale, translate, None, y_orientation)
+
+
+generate_pseudo_sdf_legacy = generate_psdf_legacy      # generatePseudoSDF_legacy (msdfgen.h:74) forwards, core/msdfgen.cpp:217-219
+
+
+def generate_msdf_legacy(output, shape, range, scale, translate, error_correction_config: Optional[ErrorCorrectionConfig] = None, y_orientation=Y_UPWARD):
+    """generateMSDF_legacy (msdfgen.h:75, core/msdfgen.cpp:221-274), including its error correction: the configured mode without the distance check."""
+    return _generate_legacy(MODE_MSDF, output, shape, range, scale, translate, error_correction_config or ErrorCorrectionConfig(), y_orientation)
+
+
+def generate_mtsdf_legacy(output, shape, range, scale, translate, error_correction_config: Optional[ErrorCorrectionConfig] = None, y_orientation=Y_UPWARD):
+    """generateMTSDF_legacy (msdfgen.h:76, core/msdfgen.cpp:276-333), including its error correction."""
+    return _generate_legacy(MODE_MTSDF, output, shape, range, scale, translate, error_correction_config or ErrorCorrectionConfig(), y_orientation)
+
+
+def msdf_error_correction_legacy(output, threshold):
+    """msdfErrorCorrection_legacy(output, threshold) (core/msdf-error-correction.h:37-38), in place on a 3- or 4-channel host bitmap; threshold: a
+    Vector2 as an (x, y) pair, or one number for both."""
+    n = output.shape[2] if output.ndim == 3 else 0
+    px, w, h, stride = _bitmap_args(output, n)
+    tx, ty = _pair(threshold)
+    _lib.check(_lib.load().msdfhip_error_correction_legacy(n, px, w, h, stride, tx, ty))
+    return output
+
+
+def error_correction_legacy(tiles, threshold, stream=None):
+    """msdfErrorCorrection_legacy of every tile of a contiguous float32 device tensor (G, H, W, N), N = 3 or 4, in place (msdfhip_batch_error_correction_legacy)."""
+    import torch
+    g, h, w, n = tiles.shape
+    assert tiles.dtype == torch.float32 and tiles.is_contiguous()
+    tx, ty = _pair(threshold)
+    scratch = torch.empty_like(tiles)
+    s = (stream or torch.cuda.current_stream(tiles.device)).cuda_stream
+    _lib.check(_lib.load().msdfhip_batch_error_correction_legacy(tiles.data_ptr(), g, w, h, n, scratch.data_ptr(), tx, ty, s))
+    if stream is not None:
+        scratch.record_stream(stream)
+    return tiles
 
 
 def _fast_error_correction(sdf, transformation, min_deviation_ratio, protect_all):
@@ -550,6 +629,37 @@ class GlyphBatch:
             _lib.check(_lib.load().msdfhip_batch_frame(self._handle, C.byref(fc), int(width), int(height), descriptors.data_ptr(), s))
         _lib.check(_lib.load().msdfhip_batch_generate(self._handle, mode, width, height, descriptors.data_ptr(), out.data_ptr(),
                                                       stencil.data_ptr() if stencil is not None else None, scratch_ptr, C.byref(cfg), s))
+        return out
+
+    def generate_legacy(self, mode, width, height, xfs=None, config=None, out=None, stencil=None, descriptors=None, stream=None, y_orientation=Y_UPWARD,
+                        scanline_pass=False, fill_rule=FILL_NONZERO, sdf_zero_value=.5, frame: Optional["FrameConfig"] = None):
+        """The legacy generators (generateSDF_legacy ... generateMTSDF_legacy, core/msdfgen.cpp:166-333) for every glyph of the batch; arguments and result
+        as generate(). config: an MSDFGeneratorConfig or an ErrorCorrectionConfig -- only the correction mode and the two ratios are read: the
+        correction of modes 3, 4 runs without overlap support and without the distance check, as the reference's does.
+        scanline_pass=True is the reference CLI's default -legacy flow (main.cpp:1223-1298): legacy field -> distanceSignCorrection -> error correction."""
+        torch = self.torch
+        n = CHANNELS[mode]
+        if descriptors is None:
+            descriptors = self.descriptors(xfs, width, height, n, y_orientation)
+        if out is None:
+            out = torch.empty((self.n_glyphs, height, width, n), dtype=torch.float32, device=self.device)
+        if isinstance(config, ErrorCorrectionConfig):
+            config = MSDFGeneratorConfig(error_correction=config)
+        cfg = _c_config(config if config is not None else (MSDFGeneratorConfig() if mode >= 3 else GeneratorConfig()), y_orientation)
+        _with_scanline_pass(cfg, scanline_pass, fill_rule, sdf_zero_value)
+        scratch_ptr = None
+        stages = int(mode >= 3 and cfg.ec_mode != EC_DISABLED)+int(bool(scanline_pass))
+        if stages:
+            need = stages*self.n_glyphs*height*width*n
+            if self._scratch is None or self._scratch.numel() < need:
+                self._scratch = torch.empty(need, dtype=torch.float32, device=self.device)
+            scratch_ptr = self._scratch.data_ptr()
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        if frame is not None:
+            fc = frame.c_struct()
+            _lib.check(_lib.load().msdfhip_batch_frame(self._handle, C.byref(fc), int(width), int(height), descriptors.data_ptr(), s))
+        _lib.check(_lib.load().msdfhip_batch_generate_legacy(self._handle, mode, width, height, descriptors.data_ptr(), out.data_ptr(),
+                                                             stencil.data_ptr() if stencil is not None else None, scratch_ptr, C.byref(cfg), s))
         return out
 
 

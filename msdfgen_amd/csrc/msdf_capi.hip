@@ -963,6 +963,95 @@ int runSignCorrection(const MsdfHipBatch *b, int channels, int w, int h, const M
     return fail(MSDFHIP_ERR_INVALID, "channels %d (must be 1, 3 or 4)", channels);
 }
 
+// ---- the legacy generators and the legacy correction (msdf_legacy.hpp) ----------------------------------------------------------
+
+// What a legacy generator makes of the caller's config: generateMSDF_legacy / generateMTSDF_legacy take an ErrorCorrectionConfig only, switch its
+// distance check off and correct without overlap support (msdfgen.cpp:272-273, 331-332). Read from the caller: the correction mode, the two ratios,
+// the sign-pass fields and the row order of the optional stencil; everything else is fixed here.
+MsdfHipConfig legacyConfig(const MsdfHipConfig &in) {
+    MsdfHipConfig cfg;
+    msdfhip_default_config(&cfg);
+    cfg.overlap_support = 0;
+    cfg.ec_distance_check = MSDFHIP_DO_NOT_CHECK_DISTANCE;
+    cfg.ec_mode = in.ec_mode, cfg.min_deviation_ratio = in.min_deviation_ratio, cfg.min_improve_ratio = in.min_improve_ratio;
+    cfg.sign_correction = in.sign_correction, cfg.fill_rule = in.fill_rule, cfg.sdf_zero_value = in.sdf_zero_value;
+    cfg.stencil_y_down = in.stencil_y_down;
+    return cfg;
+}
+
+template <int MODE>
+int launchLegacyDistanceKernel(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, float *dst, int toScratch, hipStream_t stream) {
+    const LegacyDistancePlan p = planLegacyDistance(b->nGlyphs, w, h);
+    if (p.blocks == 0)
+        return MSDFHIP_OK;
+    if (p.tooManyBlocks)
+        return fail(MSDFHIP_ERR_INVALID, "launch of %zu tiles exceeds the grid limit; split the batch", p.blocks);
+    ScopedTimer timer(stream, 0);
+    hipLaunchKernelGGL(k_distance_legacy<MODE>, dim3((unsigned) p.blocks), dim3(WAVE), 0, stream, b->nGlyphs, (const int32_t *) b->dGlyphContourOffsets,
+                       (const int32_t *) b->dContourOffsets, (const EdgeRec *) b->dRecs, dGlyphs, w, h, (w+TILE-1)/TILE, tilesOf(w, h), dst, toScratch);
+    HIPCHK(hipGetLastError());
+    return MSDFHIP_OK;
+}
+
+int launchLegacyDistance(int mode, const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, float *dst, int toScratch, hipStream_t stream) {
+    switch (mode) {
+        case 1: return launchLegacyDistanceKernel<1>(b, dGlyphs, w, h, dst, toScratch, stream);
+        case 2: return launchLegacyDistanceKernel<2>(b, dGlyphs, w, h, dst, toScratch, stream);
+        case 3: return launchLegacyDistanceKernel<3>(b, dGlyphs, w, h, dst, toScratch, stream);
+    }
+    return launchLegacyDistanceKernel<4>(b, dGlyphs, w, h, dst, toScratch, stream);
+}
+
+// msdfErrorCorrection_legacy of nGlyphs packed tiles, in place: pass 0 tiles -> scratch, pass 1 scratch -> tiles (planLegacyCorrection).
+int launchLegacyCorrection(float *dTiles, float *dScratch, int nGlyphs, int w, int h, int channels, double thresholdX, double thresholdY, hipStream_t stream) {
+    const LegacyEcPlan p = planLegacyCorrection(nGlyphs, w, h, channels);
+    if (p.blocks == 0)
+        return MSDFHIP_OK;
+    for (int pass = 0; pass < 2; ++pass) {
+        const float *src = pass == 0 ? dTiles : dScratch;
+        float *dst = pass == 0 ? dScratch : dTiles;
+        if (channels == 3)
+            hipLaunchKernelGGL(k_ec_legacy<3>, dim3(p.blocks), dim3(PLAN_LEGACY_EC_THREADS), 0, stream, src, dst, nGlyphs, w, h, pass, thresholdX, thresholdY);
+        else
+            hipLaunchKernelGGL(k_ec_legacy<4>, dim3(p.blocks), dim3(PLAN_LEGACY_EC_THREADS), 0, stream, src, dst, nGlyphs, w, h, pass, thresholdX, thresholdY);
+        HIPCHK(hipGetLastError());                                   // (a pass that was not queued must not be followed by one that reads its output)
+    }
+    return MSDFHIP_OK;
+}
+
+// One legacy generate call on b (arguments checked, device bound, cfg = legacyConfig): legacy distance pass -> sign correction -> error correction
+// without the distance check. With the sign pass this is the reference CLI's -legacy flow (main.cpp:1223-1298). Nothing of the call stays on the batch:
+// like runGenerate it carries its state in `call`, and the legacy pass takes no class list, work queue or side stream of the batch.
+int runGenerateLegacy(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGlyph *dGlyphs, float *dOut, uint8_t *dStencil, float *dScratch,
+                      const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call) {
+    if (b->nGlyphs == 0 || w == 0 || h == 0)
+        return MSDFHIP_OK;
+    const int nch = channelsOf(mode);
+    const bool correct = mode >= 3 && cfg.ec_mode != MSDFHIP_EC_DISABLED;
+    const bool signPass = cfg.sign_correction != 0;
+    const int stages = (correct ? 1 : 0)+(signPass ? 1 : 0);
+    const size_t tileFloats = (size_t) b->nGlyphs*w*h*nch;
+    int rc = MSDFHIP_OK;
+    if (stages && !dScratch) {
+        rc = ensureScratch(b, tileFloats*stages, &dScratch);
+        if (rc != MSDFHIP_OK)
+            return rc;
+    }
+    float *stageA = stages ? dScratch : NULL, *stageB = stages == 2 ? dScratch+tileFloats : NULL;
+    float *dst = stages ? stageA : dOut;
+    rc = launchLegacyDistance(mode, b, dGlyphs, w, h, dst, stages != 0, stream);
+    if (rc != MSDFHIP_OK || !stages)
+        return rc;
+    const float *ecSrc = stageA;
+    if (signPass) {
+        rc = runSignCorrection(b, nch, w, h, dGlyphs, stageA, correct ? stageB : dOut, correct ? 1 : 0, cfg.sdf_zero_value, cfg.fill_rule, stream);
+        if (rc != MSDFHIP_OK || !correct)
+            return rc;
+        ecSrc = stageB;
+    }
+    return runCorrection(b, nch, w, h, dGlyphs, ecSrc, dOut, dStencil, cfg, stream, call);
+}
+
 } // namespace
 
 extern "C" {
@@ -1542,6 +1631,35 @@ int msdfhip_batch_generate(const MsdfHipBatch *b, int mode, int w, int h, const 
         return rc;
     GenerateCall call;
     return runGenerate(b, mode, w, h, dGlyphs, dOut, dStencil, dScratch, cfg, (hipStream_t) streamPtr, call);
+}
+
+int msdfhip_batch_generate_legacy(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGlyph *dGlyphs, float *dOut, uint8_t *dStencil,
+                                  float *dScratch, const MsdfHipConfig *cfg, void *streamPtr) {
+    if (!b || mode < 1 || mode > 4 || w < 0 || h < 0 || !dGlyphs || !dOut || !cfg)
+        return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_batch_generate_legacy");
+    const MsdfHipConfig legacy = legacyConfig(*cfg);
+    int rc = checkConfig(&legacy);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    rc = ensureDevice(b->device);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    GenerateCall call;
+    return runGenerateLegacy(b, mode, w, h, dGlyphs, dOut, dStencil, dScratch, legacy, (hipStream_t) streamPtr, call);
+}
+
+int msdfhip_batch_error_correction_legacy(float *dTiles, int nGlyphs, int w, int h, int channels, float *dScratch, double thresholdX, double thresholdY,
+                                          void *streamPtr) {
+    if (nGlyphs < 0 || w < 0 || h < 0 || (channels != 3 && channels != 4))
+        return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_batch_error_correction_legacy (channels must be 3 or 4)");
+    if (nGlyphs == 0 || w == 0 || h == 0)
+        return MSDFHIP_OK;
+    if (!dTiles || !dScratch)
+        return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_error_correction_legacy: NULL argument");
+    int rc = ensureDeviceOf(dTiles);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    return launchLegacyCorrection(dTiles, dScratch, nGlyphs, w, h, channels, thresholdX, thresholdY, (hipStream_t) streamPtr);
 }
 
 int msdfhip_tiles_to_bytes(const float *dTiles, int nGlyphs, int w, int h, int channels, const MsdfHipGlyph *dGlyphs, uint8_t *dAtlas, void *streamPtr) {
@@ -2849,7 +2967,7 @@ static void destroyPipe(Pipe *p) {
     (void) hipGetLastError();
 }
 
-enum SingleOp { OP_GENERATE = 0, OP_ERROR_CORRECTION = 1, OP_SIGN_CORRECTION = 2, OP_RASTERIZE = 3 };   // what the single-shape call does to `pixels`
+enum SingleOp { OP_GENERATE = 0, OP_ERROR_CORRECTION = 1, OP_SIGN_CORRECTION = 2, OP_RASTERIZE = 3, OP_GENERATE_LEGACY = 4 };   // what the single-shape call does to `pixels`
 
 // One host-pointer call (generate* / msdfErrorCorrection / distanceSignCorrection / rasterize on one shape and one bitmap).
 struct ShapeCall {
@@ -2997,8 +3115,9 @@ static GroupPlan planGroup(ShapeCall *const *calls, int n) {
     GroupPlan p;
     p.n = n;
     p.bitmapIsInput = op == OP_ERROR_CORRECTION || op == OP_SIGN_CORRECTION;
-    p.correct = op <= OP_ERROR_CORRECTION && channels >= 3 && cfg->ec_mode != MSDFHIP_EC_DISABLED;
-    p.stages = op == OP_GENERATE ? (p.correct ? 1 : 0)+(cfg->sign_correction ? 1 : 0) : 0;
+    const bool generates = op == OP_GENERATE || op == OP_GENERATE_LEGACY;
+    p.correct = (generates || op == OP_ERROR_CORRECTION) && channels >= 3 && cfg->ec_mode != MSDFHIP_EC_DISABLED;
+    p.stages = generates ? (p.correct ? 1 : 0)+(cfg->sign_correction ? 1 : 0) : 0;
     p.anyStencil = false;
     p.sumC = p.sumE = 0, p.maxC = p.maxE = 0;
     for (int g = 0; g < n; ++g) {
@@ -3257,6 +3376,8 @@ static int runBatched(const GroupPlan &p, ThreadArena &a, MsdfHipBatch &b, const
             rc = runSignCorrection(&b, c.channels, c.w, c.h, dGlyph, dSrc, dOut, 0, c.cfg.sdf_zero_value, c.cfg.fill_rule, a.stream);
         else if (c.op == OP_RASTERIZE)
             rc = runSignCorrection(&b, 1, c.w, c.h, dGlyph, NULL, dOut, 0, 0.f, c.cfg.fill_rule, a.stream);
+        else if (c.op == OP_GENERATE_LEGACY)                     // (c.cfg is a legacyConfig: msdfhip_generate_legacy)
+            rc = runGenerateLegacy(&b, c.mode, c.w, c.h, dGlyph, dOut, dStencil, p.stages ? reinterpret_cast<float *>(a.dev+p.dScratch) : NULL, c.cfg, a.stream, call);
         else
             rc = runGenerate(&b, c.mode, c.w, c.h, dGlyph, dOut, dStencil, p.stages ? reinterpret_cast<float *>(a.dev+p.dScratch) : NULL, &c.cfg, a.stream, call);
         if (rc == MSDFHIP_OK)
@@ -3552,6 +3673,54 @@ int msdfhip_generate(int mode, float *pixels, int w, int h, int rowStride, int f
     if (mode < 1 || mode > 4)
         return fail(MSDFHIP_ERR_INVALID, "mode %d (must be 1..4)", mode);
     return singleShape(mode, channelsOf(mode), OP_GENERATE, pixels, w, h, rowStride, flip, co, nC, points, types, colors, xf, cfg, stencil);
+}
+
+// The legacy generators on one shape. A group of them takes the batched launch sequence (runBatched: planGroup reserves k_single_call's areas for
+// OP_GENERATE only), and sameLaunch never puts a legacy call and a modern one into one group: their ops differ.
+int msdfhip_generate_legacy(int mode, float *pixels, int w, int h, int rowStride, int flip, const int32_t *co, int nC, const double *points,
+                            const uint8_t *types, const uint8_t *colors, const double *xf, const MsdfHipConfig *cfg, uint8_t *stencil) {
+    if (mode < 1 || mode > 4)
+        return fail(MSDFHIP_ERR_INVALID, "mode %d (must be 1..4)", mode);
+    if (!cfg)
+        return fail(MSDFHIP_ERR_INVALID, "cfg is NULL");
+    const MsdfHipConfig legacy = legacyConfig(*cfg);
+    return singleShape(mode, channelsOf(mode), OP_GENERATE_LEGACY, pixels, w, h, rowStride, flip, co, nC, points, types, colors, xf, &legacy, stencil);
+}
+
+// msdfErrorCorrection_legacy on a host bitmap: rows gathered into the calling thread's arena, one H2D copy, the two passes, one D2H copy.
+int msdfhip_error_correction_legacy(int channels, float *pixels, int w, int h, int rowStride, double thresholdX, double thresholdY) {
+    if (w < 0 || h < 0 || (channels != 3 && channels != 4))
+        return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_error_correction_legacy (channels must be 3 or 4)");
+    if (w == 0 || h == 0)
+        return MSDFHIP_OK;
+    if (!pixels)
+        return fail(MSDFHIP_ERR_INVALID, "NULL bitmap");
+    int rc = ensureDevice();
+    if (rc != MSDFHIP_OK)
+        return rc;
+    const size_t rowBytes = sizeof(float)*(size_t) w*channels, bytes = rowBytes*h;
+    Carver c;
+    const size_t offTiles = c.take(bytes), offScratch = c.take(bytes);
+    ArenaLease lease;
+    rc = lease.take(currentDevice());
+    if (rc != MSDFHIP_OK)
+        return rc;
+    ThreadArena &a = *lease.a;
+    rc = arenaReserve(a, c.off, bytes);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    for (int y = 0; y < h; ++y)
+        memcpy(a.pinned+rowBytes*y, pixels+(ptrdiff_t) rowStride*y, rowBytes);
+    HIPCHK(hipMemcpyAsync(a.dev+offTiles, a.pinned, bytes, hipMemcpyHostToDevice, a.stream));
+    rc = launchLegacyCorrection(reinterpret_cast<float *>(a.dev+offTiles), reinterpret_cast<float *>(a.dev+offScratch), 1, w, h, channels, thresholdX, thresholdY,
+                                a.stream);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    HIPCHK(hipMemcpyAsync(a.pinned, a.dev+offTiles, bytes, hipMemcpyDeviceToHost, a.stream));
+    HIPCHK(hipStreamSynchronize(a.stream));
+    for (int y = 0; y < h; ++y)
+        memcpy(pixels+(ptrdiff_t) rowStride*y, a.pinned+rowBytes*y, rowBytes);
+    return MSDFHIP_OK;
 }
 
 int msdfhip_generate_sdf(float *pixels, int w, int h, int rowStride, int flip, const int32_t *co, int nC, const double *points,
@@ -3912,4 +4081,3 @@ extern "C" int msdfhip_debug_wait_profile(unsigned long long *out24, int reset) 
     return MSDFHIP_OK;
 #endif
 }
-

@@ -25,6 +25,7 @@
 #include "msdf_scanline.hpp"
 #include "msdf_shapeprep.hpp"
 #include "msdf_frame.hpp"
+#include "msdf_legacy.hpp"
 #include "../../include/msdfgen_hip.h"
 
 namespace msdfhip {
@@ -2471,6 +2472,47 @@ k_shape_distance(BatchView batch, int nPoints, const double *pts, double *out, d
         shapeDistanceSimple<SEL>(batch.recs, edges, C, p, d);
     for (int ch = 0; ch < 4; ++ch)
         out[4*(size_t) i+ch] = ch < NCH ? d[ch] : 0.;
+}
+
+// ------------------------------------------------------------------------------------------------- legacy generators
+
+// generate*_legacy (msdf_legacy.hpp): one wavefront per 8x8 tile, lane = texel, blocks dealt to (glyph, tile) like k_distance's. The glyph's edges are
+// walked in shape order by every lane alike -- the contour offsets and the records of the walk are wave-uniform reads -- with no per-tile cull: a cull
+// would have to keep, among edges that tie, the first in shape order for every texel of the tile. Only the nearest edges' records after the walk are
+// fetched per lane. dst / toScratch: as k_distance.
+template <int MODE>
+__global__ void __launch_bounds__(WAVE)
+k_distance_legacy(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const int32_t *__restrict__ contourOffsets, const EdgeRec *__restrict__ recs,
+                  const MsdfHipGlyph *__restrict__ glyphs, int width, int height, int tilesX, int tilesPerGlyph, float *__restrict__ dst, int toScratch) {
+    enum { NCH = LegacyTraits<MODE>::NCH };
+    const GlyphWork wk = decodeBlock(nGlyphs, tilesPerGlyph);
+    if (!wk.valid)
+        return;
+    const int lane = threadIdx.x;
+    const int c0 = glyphContourOffsets[wk.g], C = glyphContourOffsets[wk.g+1]-c0;
+    const MsdfHipGlyph gd = glyphs[wk.g];
+    const Xform t = loadXform(gd);
+    const int tx = wk.tile%tilesX, ty = wk.tile/tilesX;
+    const int x = tx*TILE+(lane&(TILE-1)), y = ty*TILE+(lane>>3);
+    if (x >= width || y >= height)
+        return;
+    float texel[NCH];
+    legacyTexelMapped<MODE>(recs, contourOffsets+c0, C, t, x, y, texel);
+    const int yn = gd.flip ? height-1-y : y;                        // output.reorient(shape orientation), msdfgen.cpp:168
+    float *px = toScratch ? dst+(((size_t) wk.g*height+yn)*width+x)*NCH : dst+gd.out_offset+(ptrdiff_t) gd.row_stride*yn+(ptrdiff_t) NCH*x;
+    for (int ch = 0; ch < NCH; ++ch)
+        px[ch] = texel[ch];
+}
+
+// One pass of msdfErrorCorrection_legacy (msdf_legacy.hpp: legacyClashTexel) over nGlyphs packed tiles [g][h][w][N], src -> dst, a thread per texel.
+template <int N>
+__global__ void __launch_bounds__(256)
+k_ec_legacy(const float *__restrict__ src, float *__restrict__ dst, int nGlyphs, int width, int height, int pass, double thresholdX, double thresholdY) {
+    const size_t texels = (size_t) width*height, total = (size_t) nGlyphs*texels;
+    for (size_t i = (size_t) blockIdx.x*blockDim.x+threadIdx.x; i < total; i += (size_t) gridDim.x*blockDim.x) {
+        const size_t g = i/texels, rem = i%texels;
+        legacyClashTexel<N>(src+g*texels*N, dst+g*texels*N, width, height, (int) (rem%(size_t) width), (int) (rem/(size_t) width), pass, thresholdX, thresholdY);
+    }
 }
 
 } // namespace msdfhip

@@ -430,4 +430,31 @@ inline SignPlan planSign(const PlanEnv &env, int nGlyphs, int maxEdges, int w, i
     return p;
 }
 
+// The legacy generators (k_distance_legacy): a wavefront per tile of every glyph, dealt like k_distance's one-tile launches (decodeBlock).
+struct LegacyDistancePlan {
+    size_t blocks;
+    bool tooManyBlocks;               // beyond the grid limit: refused
+};
+inline LegacyDistancePlan planLegacyDistance(int nGlyphs, int w, int h) {
+    LegacyDistancePlan p;
+    p.blocks = distanceBlocks(nGlyphs, w, h, 1);
+    p.tooManyBlocks = p.blocks > 0x7fffffffull;
+    return p;
+}
+
+// The legacy correction (k_ec_legacy) of nGlyphs packed tiles of w x h texels with n channels: two out-of-place passes, tiles -> scratch -> tiles.
+enum { PLAN_LEGACY_EC_THREADS = 256, PLAN_LEGACY_EC_MAX_BLOCKS = 65536 };
+struct LegacyEcPlan {
+    size_t texels, scratchFloats;     // of all tiles; the scratch holds one copy of them
+    unsigned blocks;                  // workgroups of PLAN_LEGACY_EC_THREADS threads per pass, grid-stride over the texels (0: nothing to do)
+};
+inline LegacyEcPlan planLegacyCorrection(int nGlyphs, int w, int h, int n) {
+    LegacyEcPlan p;
+    p.texels = (size_t) (nGlyphs > 0 ? nGlyphs : 0)*(size_t) w*(size_t) h;
+    p.scratchFloats = p.texels*(size_t) n;
+    const size_t wanted = (p.texels+PLAN_LEGACY_EC_THREADS-1)/PLAN_LEGACY_EC_THREADS;
+    p.blocks = (unsigned) (wanted < PLAN_LEGACY_EC_MAX_BLOCKS ? wanted : PLAN_LEGACY_EC_MAX_BLOCKS);
+    return p;
+}
+
 } // namespace msdfhip

@@ -141,6 +141,10 @@ _PROTOS = {
     "msdfhip_set_host_threads": (C.c_int, [C.c_int]),
     "msdfhip_single_call_fallbacks": (C.c_int, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_int]),
     "msdfhip_debug_route_counts": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int, C.c_int]),
+    "msdfhip_generate_legacy": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int] + _SHAPE_ARGS + [_dp, C.POINTER(Config), _bp]),
+    "msdfhip_error_correction_legacy": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "msdfhip_batch_generate_legacy": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.POINTER(Config), _vp]),
+    "msdfhip_batch_error_correction_legacy": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_double, C.c_double, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_PROTOS))
