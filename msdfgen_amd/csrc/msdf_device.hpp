@@ -128,7 +128,8 @@ MSDF_HD double cross(V2 a, V2 b) { return a.x*b.y-a.y*b.x; }
 // Goldschmidt step on (g, h) and two Newton corrections of g (seven FMAs); scale back; patch x = 0 / inf. For 2^-767 <= x < inf the scaling
 // is the identity and the patch never applies: the SAME seven FMAs without them yield the same bits with 10 instead of 18 instructions.
 // The wavefront takes the compiler's sqrt whenever any lane is outside that range (a texel exactly on a control point: x = 0).
-// msdfhip_debug_sqrt_mismatches compares the two on the device (tests/test_gpu_parity.py).
+// tests/test_gpu_devmath.py runs both on the device against IEEE sqrt, bit for bit: wavefronts wholly in range (exponents -767..1023, 2^-767 itself,
+// perfect squares and their neighbours, all-ones significands) and wavefronts in which one lane is out of range.
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ inline double leanSqrtCore(double x) {
     const double y = __builtin_amdgcn_rsq(x);
@@ -208,7 +209,14 @@ MSDF_HD float mixf(float a, float b, double w) { return (float) ((1.-w)*a+w*b); 
 // System/6000 processor", 1990, Thm 4.? / Cornea-Harrison-Tang: q = RN(a*y), r = a-b*q exactly, q' = RN(q+r*y) == RN(a/b) when y
 // is the correctly rounded reciprocal, b's significand is not all ones, and nothing over/underflows). divSafe() is evaluated per
 // divisor at digestion time; edges with an unsafe divisor keep the IEEE division. ~3 instructions instead of ~28 on gfx950.
-// tests/test_device_logic_host.py fuzzes the identity against true division.
+// divSafe() guards the DIVISOR only (y is normal, 1e-100 < |b| < 1e100). The DIVIDEND has a domain of its own, which no call site checks:
+//   * 2^-969 <= |a| < inf. The residual r = a-b*q is a multiple of ulp(b)*ulp(q) = 2^(eb+eq-104) (eb, eq: the exponents of b and q), and
+//     a = b*q+r puts a's exponent at eb+eq or eb+eq+1: with |a| >= 2^-969 that grid is no finer than 2^-1074, the smallest subnormal, and the
+//     FMA delivers r exactly. Below, r is rounded and the quotient can be off in its last place (seen from |a| ~ 2^-1004 down).
+//   * 2^-1021 <= |a/b| <= 2^1023: q and the result are normal and finite. (A quotient that overflows gives NaN here, inf - inf.)
+//   * a == +-0 gives a zero, with IEEE's sign except for -0 over a positive divisor: +0 (r = fma(-b, -0, -0) is +0, and +0*y + -0 = +0).
+// DESIGN.md 4 argues from the call sites why neither a dividend outside that domain nor the sign of a zero quotient reaches an output.
+// tests/test_device_logic_host.py (host build) and tests/test_gpu_devmath.py (gfx950 build) assert exactly this: IEEE inside the domain, +0 for -0/b.
 MSDF_HD double divExact(double a, double b, double y) {
     const double q = a*y;
     const double r = fma(-b, q, a);

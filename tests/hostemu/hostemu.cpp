@@ -239,6 +239,18 @@ long emu_div_exact_violations(const double *a, const double *b, long n, long *sa
         *safeCount = safe;
     return bad;
 }
+// divSafe and divExact themselves (the reciprocal formed as buildRecord forms it), for tests that state divExact's domain input by input.
+void emu_div_exact(const double *a, const double *b, long n, int32_t *safe, double *q) {
+    for (long i = 0; i < n; ++i) {
+        safe[i] = divSafe(b[i]) ? 1 : 0;
+        q[i] = divExact(a[i], b[i], 1/b[i]);
+    }
+}
+// This machine's libm acos: what solveCubicNormed calls in the host build (the device build calls OCML's).
+void emu_libm_acos(const double *x, long n, double *out) {
+    for (long i = 0; i < n; ++i)
+        out[i] = acos(x[i]);
+}
 void emu_cull_stats(long *kept, long *total, int reset) { *kept = g_cullKept, *total = g_cullTotal; if (reset) g_cullKept = g_cullTotal = 0; }
 
 // Fuzz of the exact-skip prefilter of the diagonal test: returns the number of coefficient triples for which

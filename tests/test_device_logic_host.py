@@ -224,6 +224,32 @@ def test_reciprocal_fma_division_is_correctly_rounded(emu):
     assert n-1500 < safe.value < n
 
 
+def test_reciprocal_fma_division_has_a_stated_domain(emu):
+    """What the fuzz above cannot draw (tests/devmathcases.py: div_edge_inputs): quotients next to ties, divisors at both ends of divSafe's range, dividends
+    down to the subnormals and zero dividends of either sign. divExact equals IEEE division for every dividend inside the domain its comment states
+    (a zero, or 2^-969 <= |a| with a quotient that neither underflows nor overflows) -- except that a -0 dividend over a positive divisor gives +0; below
+    2^-969 the residual fma(-b, q, a) is no longer exact and the quotient does depart from IEEE. tests/test_gpu_devmath.py asserts the same on the device."""
+    import ctypes as C
+    import devmathcases as D
+    from devmathcases import check_division, check_zero_dividends
+
+    def div(a, b):
+        a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+        safe, q = np.zeros(len(a), np.int32), np.zeros(len(a))
+        emu.lib.emu_div_exact(a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.c_long(len(a)), safe.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p))
+        return safe != 0, q
+
+    departs = {}
+    for name, (a, b) in D.div_edge_inputs().items():
+        safe, q = div(a, b)
+        dom, bad_out = check_division(name, a, b, safe, q, print)
+        departs[name] = int(bad_out.sum())
+        if name == "ones":
+            assert not safe.any()
+    assert departs["small"] > 0
+    check_zero_dividends(lambda a, b: div(a, b)[1])
+
+
 def test_lean_transcendentals_are_within_one_ulp(emu):
     """The device build replaces OCML's generic cos/pow inside solveCubicNormed by range-specific kernels (msdf_device.hpp).
     Check them against 80-bit long double evaluations of exactly the reference's expressions: < 1 ulp, like glibc/OCML."""
