@@ -191,16 +191,41 @@ MSDF_HD int diagonalPairFast(const FastCtx &cx, float am, float dm, const float 
 // the edge reports" :335, :349) compare only these. A texel's value is computed ONCE -- k_ec_fast does it while it stages the halo in LDS (round 6:
 // every lane used to recompute the medians of all eight neighbours, twice: 18 medians of 8 instructions per texel, 15 % of the kernel's VALU stream by
 // tools/isa_bbcount.py) -- with the reference's own expression, so the comparisons see the same floats.
+// cls[dy+1][dx+1] = the texel's class word (ecTexelClassWord; 0 outside the bitmap): everything else the first-level tests derive from ONE texel -- is it
+// inside the bitmap, and the signs of its three channel differences -- is likewise computed once per texel (k_ec_fast: next to the deviation, while the halo
+// is staged) instead of in each of the up to five lanes that look at it. v and dev of a texel outside the bitmap are unspecified: no test reads them.
 struct Neighbourhood {
     float v[3][3][3];
     float dev[3][3];
-    unsigned valid;
+    unsigned cls[3][3];
+    unsigned valid;     // the nine inside bits (host walk; the kernel reads them in cls)
 };
 
 MSDF_HD float ecTexelDeviation(const float *t) { return fabsf(medianf(t[0], t[1], t[2])-.5f); }
 
+// Class word of a texel inside the bitmap. With D[j] = t[j+1 mod 3]-t[j] (channel pair j in the reference's minuend / subtrahend order, the float
+// subtraction of hasLinearArtifact / hasDiagonalArtifact): bit j: D[j] > 0, bit 3+j: D[j] < 0, bit 6+j: D[j] == 0 (a NaN sets none of the three),
+// bit 15: inside. The bits ARE the outcomes of the comparisons the first-level tests make on this texel's differences.
+enum { EC_CLS_INSIDE = 0x8000 };
+MSDF_HD unsigned ecTexelClassWord(const float *t) {
+    unsigned w = EC_CLS_INSIDE;
+    MSDF_UNROLL
+    for (int j = 0; j < 3; ++j) {
+        const float d = t[j == 2 ? 0 : j+1]-t[j];
+        w |= (d > 0 ? 1u<<j : 0u)|(d < 0 ? 8u<<j : 0u)|(d == 0 ? 64u<<j : 0u);
+    }
+    return w;
+}
+
+MSDF_HD unsigned ecValidFromWords(const Neighbourhood &nb) {
+    unsigned valid = 0;
+    MSDF_UNROLL
+    for (int m = 0; m < 9; ++m)
+        valid |= (nb.cls[m/3][m%3]&EC_CLS_INSIDE) ? 1u<<m : 0u;
+    return valid;
+}
+
 MSDF_HD void loadNeighbourhood(Neighbourhood &nb, const SdfView &sdf, int x, int yn) {
-    nb.valid = 0;
     MSDF_UNROLL
     for (int dy = -1; dy <= 1; ++dy) {
         MSDF_UNROLL
@@ -210,10 +235,10 @@ MSDF_HD void loadNeighbourhood(Neighbourhood &nb, const SdfView &sdf, int x, int
             const float *t = sdf.native(in ? nx : x, in ? ny : yn);
             nb.v[dy+1][dx+1][0] = t[0], nb.v[dy+1][dx+1][1] = t[1], nb.v[dy+1][dx+1][2] = t[2];
             nb.dev[dy+1][dx+1] = ecTexelDeviation(t);
-            if (in)
-                nb.valid |= 1u<<((dy+1)*3+(dx+1));
+            nb.cls[dy+1][dx+1] = in ? ecTexelClassWord(t) : 0u;
         }
     }
+    nb.valid = ecValidFromWords(nb);
 }
 
 // protectEdges (MSDFErrorCorrection.cpp:189-250) as a gather, from the register neighbourhood; see protectedByEdges in msdf_ec.hpp. Two
@@ -228,7 +253,7 @@ MSDF_HD void texelProtectPairs(const Neighbourhood &nb, const EcParams &p, Emit 
         for (int dx = -1; dx <= 1; ++dx) {
             if (!dx && !dy)
                 continue;
-            if (!(nb.valid&(1u<<((dy+1)*3+(dx+1)))))
+            if (!(nb.cls[dy+1][dx+1]&EC_CLS_INSIDE))
                 continue;
             const float radius = dy == 0 ? p.radiusH : dx == 0 ? p.radiusV : p.radiusD;
             const float odev = nb.dev[dy+1][dx+1];
@@ -274,44 +299,49 @@ MSDF_HD bool protectedByEdgesNb(const Neighbourhood &nb, const EcParams &p) {
 MSDF_HD int ecNeighbourDx(int k) { return k < 4 ? (k == 0 ? -1 : k == 2 ? 1 : 0) : ((k&1) ? 1 : -1); }
 MSDF_HD int ecNeighbourDy(int k) { return k < 4 ? (k == 1 ? -1 : k == 3 ? 1 : 0) : ((k&2) ? 1 : -1); }
 
-// Stage 1: emit(k, j) for every test of the centre texel of `nb` that the cheap conditions cannot settle. Exact skips only:
+// Stage 1: emit(k, j) for every test of the centre texel of `nb` (inside the bitmap) that the cheap conditions cannot settle. Exact skips only:
 //  * the neighbour must exist and the centre must be the texel farther from the edge (:335, :349);
 //  * linear: t = dA/(dA-dB) lies in (0, 1) only if dA and dB have strictly opposite signs;
 //  * diagonal: 0 == 0 has no usable root (equation-solver.cpp:13-17); Bernstein sign test (bernsteinMayHaveRoot).
+// What depends on one texel alone comes from the class words (Neighbourhood::cls): whether a neighbour exists, and the signs of dA and dB -- the three
+// linear tests of a neighbour are one mask, "positive here and negative there, or the reverse", and one branch on it. The diagonal tests read the
+// channels: dBC belongs to no single texel. They are spelled as the reference spells them (dBC left to right); the class words only tell where
+// dA == 0 && dD == 0, the one case in which dBC == 0 leaves nothing to solve.
 template <class Emit>
 MSDF_HD void texelCandidatePairs(const Neighbourhood &nb, Emit &emit) {
     const float *c = nb.v[1][1];
     const float cdev = nb.dev[1][1];
+    const unsigned cw = nb.cls[1][1];
     MSDF_UNROLL
     for (int k = 0; k < 4; ++k) {
         const int dx = k == 0 ? -1 : k == 2 ? 1 : 0, dy = k == 1 ? -1 : k == 3 ? 1 : 0;
-        if (!(nb.valid&(1u<<((dy+1)*3+(dx+1)))))
-            continue;
-        const float *b = nb.v[dy+1][dx+1];
-        if (!(cdev >= nb.dev[dy+1][dx+1]))
-            continue;
-        MSDF_UNROLL
-        for (int j = 0; j < 3; ++j) {
-            const int i0 = j, i1 = j == 2 ? 0 : j+1;
-            const float dA = c[i1]-c[i0], dB = b[i1]-b[i0];
-            if ((dA > 0 && dB < 0) || (dA < 0 && dB > 0))
-                emit(k, j);
+        const unsigned nw = nb.cls[dy+1][dx+1];
+        // bit j: D[j] > 0 here and < 0 there, or < 0 here and > 0 there; none for a neighbour outside the bitmap, whose word is 0
+        const unsigned opposite = ((cw&(nw>>3))|((cw>>3)&nw))&7u;
+        const unsigned m = cdev >= nb.dev[dy+1][dx+1] ? opposite : 0u;
+        if (m) {
+            if (m&1u)
+                emit(k, 0);
+            if (m&2u)
+                emit(k, 1);
+            if (m&4u)
+                emit(k, 2);
         }
     }
     MSDF_UNROLL
     for (int k = 4; k < 8; ++k) {
         const int dx = (k&1) ? 1 : -1, dy = (k&2) ? 1 : -1;
-        if (!(nb.valid&(1u<<((dy+1)*3+(dx+1)))))
+        const unsigned dw = nb.cls[dy+1][dx+1];
+        if (!(((dw&EC_CLS_INSIDE) != 0)&(cdev >= nb.dev[dy+1][dx+1])))      // (no short circuit: both are register values, one branch)
             continue;
         const float *d = nb.v[dy+1][dx+1];
-        if (!(cdev >= nb.dev[dy+1][dx+1]))
-            continue;
         const float *b = nb.v[1][dx+1], *cc = nb.v[dy+1][1];
+        const unsigned zeroAD = cw&dw;                          // bit 6+j: dA == 0 and dD == 0
         MSDF_UNROLL
         for (int j = 0; j < 3; ++j) {
             const int i0 = j, i1 = j == 2 ? 0 : j+1;
             const float dA = c[i1]-c[i0], dBC = b[i1]-b[i0]+cc[i1]-cc[i0], dD = d[i1]-d[i0];
-            if (dA == 0 && dBC == 0 && dD == 0)
+            if ((zeroAD&(64u<<j)) && dBC == 0)
                 continue;
             if (bernsteinMayHaveRoot(dA, dBC, dD))
                 emit(k, j);

@@ -1209,7 +1209,7 @@ k_ec_params(EcGlyphParams *out, BatchView batch, const MsdfHipGlyph *glyphs, Msd
 // the stencil byte [g][h][w] (native rows). Candidates whose verdict needs an exact shape-distance query are appended to `cands`
 // and judged by k_ec_query; a texel with a cheaply decided ERROR never needs them (the flag is an OR).
 #ifndef MSDF_EC_FAST_WAVES_PER_SIMD
-#define MSDF_EC_FAST_WAVES_PER_SIMD 7   // lazy instantiation 63 VGPRs / 17 scalar registers parked in vector lanes, eager 65 / 2; no vector spills, no scratch (tests/test_ec_fast_isa_budget.py); the kernel's 5.6 KB of LDS allow 7 wavefronts per SIMD anyway. Correction pass on the distinct-glyph set: 8 -> 1.94 ms, 7 -> 1.90, 6 -> 1.90
+#define MSDF_EC_FAST_WAVES_PER_SIMD 7   // lazy instantiation 67 VGPRs / 18 scalar registers parked in vector lanes, eager 63 / 1; no vector spills, no scratch (tests/test_ec_fast_isa_budget.py); the kernel's 5.6 KB of LDS allow 7 wavefronts per SIMD anyway. Correction pass on the distinct-glyph set: 8 -> 1.94 ms, 7 -> 1.90, 6 -> 1.90
 #endif
 // LDS of k_ec_fast per wavefront: 10x10 halo tile of the field | per-texel verdict words | item count | item queue (5.6 KB for msdf).
 enum { EC_HALO = TILE+2, EC_QUEUE_CAP = WAVE*24, EC_PROTECT_QUEUE_CAP = WAVE*8 };
@@ -1267,8 +1267,8 @@ struct EcPushProtect {
     __device__ void operator()(int m) { queue[atomicAdd(count, 1)] = (unsigned short) (lane|m<<6); }
 };
 
-// ORDER: 1 the lazy order, 0 the eager one -- k_ec_fast has an instantiation of each and the host picks by the configuration (63 / 65 VGPRs, 17 / 2 scalar
-// registers parked in vector lanes, all outside the queue loops; both orders in one body: 28) -- or -1: decided here, one body for k_single_call.
+// ORDER: 1 the lazy order, 0 the eager one -- k_ec_fast has an instantiation of each and the host picks by the configuration (67 / 63 VGPRs, 18 / 1 scalar
+// registers parked in vector lanes, all outside the queue loops) -- or -1: decided here, one body for k_single_call.
 template <int N, int ORDER = -1>
 __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHipGlyph *glyphs, int width, int height, int tilesX, int tilesPerGlyph,
           const float *src, float *out, uint8_t *stencilOut, const MsdfHipConfig &cfg, const EcGlyphParams *glyphParams, EcCandidate *cands, unsigned seg,
@@ -1283,11 +1283,17 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     int *itemCount = verdictLds+WAVE;
     unsigned short *queue = reinterpret_cast<unsigned short *>(itemCount+4);               // [EC_QUEUE_CAP]: lane | k<<6 | j<<9
     unsigned short *protectQueue = queue+EC_QUEUE_CAP;                                      // [EC_PROTECT_QUEUE_CAP]: lane | m<<6
-    // |median - .5| of every halo texel, computed once while the halo is staged (msdf_ec_fast.hpp: Neighbourhood::dev). The table overlays the TAIL of the
-    // item queue: every lane has its nine values in registers before the wavefront pushes its first item (one wavefront, LDS operations in program order, a
-    // wave barrier between the reads and the pushes) -- no LDS is added, the kernel keeps its seven wavefronts per SIMD.
-    float *devLds = reinterpret_cast<float *>(queue+EC_QUEUE_CAP)-EC_HALO*EC_HALO;
-    static_assert((EC_QUEUE_CAP*sizeof(unsigned short))%sizeof(float) == 0 && EC_QUEUE_CAP*sizeof(unsigned short) >= EC_HALO*EC_HALO*sizeof(float), "devLds overlays the queue's tail");
+    // |median - .5| and the class word of every halo texel, computed once while the halo is staged (msdf_ec_fast.hpp: Neighbourhood::dev, ::cls; a position
+    // outside the bitmap gets the word 0). The table overlays the TAIL of the item queue: every lane has its nine entries in registers before the wavefront
+    // pushes its first item (one wavefront, LDS operations in program order, a wave barrier between the reads and the pushes) -- no LDS is added, the kernel
+    // keeps its seven wavefronts per SIMD.
+    struct TexelClass {
+        float dev;
+        unsigned cls;
+    };
+    TexelClass *classLds = reinterpret_cast<TexelClass *>(queue+EC_QUEUE_CAP)-EC_HALO*EC_HALO;
+    static_assert((EC_QUEUE_CAP*sizeof(unsigned short))%sizeof(TexelClass) == 0 && EC_QUEUE_CAP*sizeof(unsigned short) >= EC_HALO*EC_HALO*sizeof(TexelClass)
+                  && 2*WAVE >= EC_HALO*EC_HALO && WAVE%EC_HALO == 4 && WAVE/EC_HALO == 6, "classLds overlays the queue's tail; the halo is staged in two rounds");
     const int lane = threadIdx.x;
     const MsdfHipGlyph gd = glyphs[wk.g];
     EcParams p;
@@ -1308,15 +1314,30 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
         cornerTexel = ecTileCornerTexel(corners+2*(size_t) gp.cornerBegin, gp.nCorners, tx, ty, height, gd.flip, lane);
 
     // ---- the tile and its one-texel halo go to LDS once (native rows); texels outside the bitmap are never read back
-    const float *field = src+(size_t) wk.g*height*width*N;
-    for (int idx = lane; idx < EC_HALO*EC_HALO; idx += WAVE) {
-        const int hx = tx*TILE+idx%EC_HALO-1, hy = ty*TILE+idx/EC_HALO-1;
-        if (hx >= 0 && hy >= 0 && hx < width && hy < height) {
-            const float *t = field+((size_t) hy*width+hx)*N;
-            float tv[N];
-            for (int ch = 0; ch < N; ++ch)
-                tv[ch] = t[ch], halo[idx*N+ch] = tv[ch];
-            devLds[idx] = ecTexelDeviation(tv);
+    // Two rounds, halo positions lane and lane+WAVE: column and row of the second follow from those of the first, and so does the texel's address (the tile's
+    // origin is wave-uniform, the second round's step as well).
+    const ptrdiff_t rowStep = (ptrdiff_t) width*N;
+    const ptrdiff_t origin = (((ptrdiff_t) wk.g*height+ty*TILE-1)*width+tx*TILE-1)*N;       // of halo position 0, in floats from src (outside the field where the tile touches a border)
+    const int hr0 = lane/EC_HALO, hc0 = lane-hr0*EC_HALO;
+    const ptrdiff_t laneStep0 = hr0*rowStep+hc0*N;
+    MSDF_UNROLL
+    for (int round = 0; round < 2; ++round) {
+        const int idx = lane+round*WAVE;
+        const bool wrap = round && hc0+WAVE%EC_HALO >= EC_HALO;
+        const int hc = hc0+round*(WAVE%EC_HALO)-(wrap ? EC_HALO : 0), hr = hr0+round*(WAVE/EC_HALO)+(wrap ? 1 : 0);
+        const ptrdiff_t laneStep = laneStep0+round*((WAVE/EC_HALO)*rowStep+(WAVE%EC_HALO)*N)+(wrap ? rowStep-EC_HALO*N : 0);
+        if (idx < EC_HALO*EC_HALO) {
+            const int hx = tx*TILE+hc-1, hy = ty*TILE+hr-1;
+            unsigned cls = 0;
+            if (hx >= 0 && hy >= 0 && hx < width && hy < height) {
+                const float *t = src+(origin+laneStep);
+                float tv[N];
+                for (int ch = 0; ch < N; ++ch)
+                    tv[ch] = t[ch], halo[idx*N+ch] = tv[ch];
+                classLds[idx].dev = ecTexelDeviation(tv);
+                cls = ecTexelClassWord(tv);
+            }
+            classLds[idx].cls = cls;
         }
     }
     if (lane < 2)
@@ -1324,30 +1345,33 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     waveSync();
 
     // ---- phase A (lane = texel): corner protection and the sign / radius stages of findErrors and protectEdges; survivors are queued
+    // The nine class entries and the nine texels are read at lane-constant offsets from the centre: a neighbour outside the bitmap is told by its word (0),
+    // its deviation and channels (whatever the LDS holds there) are read and never used.
     const int lx = lane&(TILE-1), ly = lane>>3;
     const int x = tx*TILE+lx, yn = ty*TILE+ly;
     const bool inside = x < width && yn < height;
     int st = 0;
     const bool classify = inside;
     Neighbourhood nb;
-    nb.valid = 0;
+    const int centre = (ly+1)*EC_HALO+lx+1;
+    MSDF_UNROLL
+    for (int dy = -1; dy <= 1; ++dy) {
+        MSDF_UNROLL
+        for (int dx = -1; dx <= 1; ++dx) {
+            const TexelClass tc = classLds[centre+dy*EC_HALO+dx];
+            nb.dev[dy+1][dx+1] = tc.dev, nb.cls[dy+1][dx+1] = tc.cls;
+        }
+    }
+    waveSync();                                                         // classLds is dead from here on: the queue may grow into it
     if (classify) {
         MSDF_UNROLL
         for (int dy = -1; dy <= 1; ++dy) {
             MSDF_UNROLL
             for (int dx = -1; dx <= 1; ++dx) {
-                const int nx = x+dx, ny = yn+dy;
-                const bool in = nx >= 0 && ny >= 0 && nx < width && ny < height;
-                const float *t = halo+((ly+1+(in ? dy : 0))*EC_HALO+lx+1+(in ? dx : 0))*N;
+                const float *t = halo+(centre+dy*EC_HALO+dx)*N;
                 nb.v[dy+1][dx+1][0] = t[0], nb.v[dy+1][dx+1][1] = t[1], nb.v[dy+1][dx+1][2] = t[2];
-                nb.dev[dy+1][dx+1] = devLds[(ly+1+(in ? dy : 0))*EC_HALO+lx+1+(in ? dx : 0)];
-                if (in)
-                    nb.valid |= 1u<<((dy+1)*3+(dx+1));
             }
         }
-    }
-    waveSync();                                                         // devLds is dead from here on: the queue may grow into it
-    if (classify) {
         if (p.mode == EC_MODE_EDGE_PRIORITY && !lazy) {
             if (cornerTexel)
                 st |= EC_PROTECTED;
@@ -1420,9 +1444,9 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
             if (cornerTexel)
                 verdictLds[lane] |= 0x100;
             else {
-                // |median - .5| of the 3x3 texels again, from the halo: the table of the staging loop lies under the item queue
+                // |median - .5| and the inside bit of the 3x3 texels again, from the halo and the coordinates: the table of the staging loop lies under the
+                // item queue (this round runs in a tenth of the tiles)
                 Neighbourhood nd;
-                nd.valid = 0;
                 MSDF_UNROLL
                 for (int dy = -1; dy <= 1; ++dy) {
                     MSDF_UNROLL
@@ -1430,8 +1454,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
                         const int nx = x+dx, ny = yn+dy;
                         const bool in = nx >= 0 && ny >= 0 && nx < width && ny < height;
                         nd.dev[dy+1][dx+1] = ecTexelDeviation(halo+((ly+1+(in ? dy : 0))*EC_HALO+lx+1+(in ? dx : 0))*N);
-                        if (in)
-                            nd.valid |= 1u<<((dy+1)*3+(dx+1));
+                        nd.cls[dy+1][dx+1] = in ? (unsigned) EC_CLS_INSIDE : 0u;
                     }
                 }
                 EcPushProtect pushProtect = { protectQueue, itemCount+1, lane };
