@@ -29,6 +29,7 @@
 #include "msdf_kernels.hpp"
 #include "msdf_launchplan.hpp"
 #include "msdf_prepplan.hpp"
+#include "msdf_resources.hpp"
 #include "msdf_single.hpp"
 
 using namespace msdfhip;
@@ -191,38 +192,6 @@ int currentDevice() {
 
 int channelsOf(int mode) { return mode <= 2 ? 1 : mode; }
 
-// hipHostMalloc for the library's own staging buffers. The HIP runtime recycles pinned address ranges without ThreadSanitizer seeing
-// the free / allocation pair (it is not instrumented), so under TSan the allocator's own synchronisation is stated explicitly (release at
-// the free, acquire at the allocation) -- otherwise writes of two threads to buffers that merely reuse an address are reported as races.
-// The pairing goes through ONE tag for all pinned memory, not through the block's base address: a recycled range may come back inside a
-// block with another base (seen once in four runs: staging writes of one call reported against the scatter reads of an earlier call of
-// another thread, same addresses, different owners) -- every allocation then acquires every earlier free, as a heap allocator would.
-#if defined(__has_feature)
-#if __has_feature(thread_sanitizer)
-#define MSDFHIP_TSAN 1
-extern "C" void __tsan_acquire(void *addr);
-extern "C" void __tsan_release(void *addr);
-#endif
-#endif
-#if defined(MSDFHIP_TSAN)
-static char gPinnedHeapTag;
-#endif
-hipError_t pinnedAlloc(void **p, size_t bytes, unsigned flags = hipHostMallocDefault) {
-    const hipError_t e = hipHostMalloc(p, bytes ? bytes : 1, flags);
-#if defined(MSDFHIP_TSAN)
-    if (e == hipSuccess)
-        __tsan_acquire(&gPinnedHeapTag);                         // pairs with the pinnedFree of whoever owned (any part of) the range before
-#endif
-    return e;
-}
-hipError_t pinnedFree(void *p) {
-#if defined(MSDFHIP_TSAN)
-    if (p)
-        __tsan_release(&gPinnedHeapTag);
-#endif
-    return hipHostFree(p);
-}
-
 struct TimedLaunch { hipEvent_t a, b; int kind; };
 std::mutex gTimingMutex;
 std::vector<TimedLaunch> gTimed;
@@ -247,38 +216,6 @@ struct ScopedTimer {
     }
 };
 
-// A grow-on-demand allocation of a workspace: device memory, or (PINNED) host staging through pinnedAlloc / pinnedFree. It is OWNED -- freed when it has
-// to grow and when it goes -- or BORROWED from a caller's arena (the single-shape calls carve theirs), and then only dropped. Freed on the thread's
-// current device: the launches are bound to the batch's device, and a Workspace binds to its device before its buffers go.
-template <class T, bool PINNED = false>
-struct WorkBuffer {
-    T *ptr = NULL;
-    size_t cap = 0;                   // elements
-    bool owned = false;
-    WorkBuffer() { }
-    WorkBuffer(const WorkBuffer &) = delete;
-    WorkBuffer &operator=(const WorkBuffer &) = delete;
-    ~WorkBuffer() { release(); }
-    void release() {
-        if (owned && ptr)
-            (void) (PINNED ? pinnedFree(ptr) : hipFree(ptr));
-        ptr = NULL, cap = 0, owned = false;
-    }
-    void borrow(T *p, size_t n) { release(); ptr = p, cap = n; }
-    hipError_t ensure(size_t n) {
-        if (cap >= n)
-            return hipSuccess;
-        release();
-        const hipError_t e = PINNED ? pinnedAlloc((void **) &ptr, n*sizeof(T)) : hipMalloc((void **) &ptr, n*sizeof(T));
-        if (e != hipSuccess) {
-            ptr = NULL;
-            return e;
-        }
-        cap = n, owned = true;
-        return hipSuccess;
-    }
-};
-
 // What the launches on one batch (or on one glyph range after the other: pipeline slots, single-shape groups) work in. Launches on one batch are
 // ordered by the caller; the mutex guards the buffers against concurrent callers that only size them.
 struct Workspace {
@@ -297,10 +234,10 @@ struct Workspace {
     bool bucketUploaded = false;      // an upload from hBucket may still be in flight
     WorkBuffer<int> ecOrder;          // glyph indices heaviest first (k_ec_scan / k_ec_query), built on first use; none: batch order
     WorkBuffer<int, true> hEcOrder;   // (pinned host copy it is uploaded from)
-    hipEvent_t ecOrderReady = NULL;   // (recorded behind that upload)
+    Event ecOrderReady;               // (recorded behind that upload)
     bool ecOrderTried = false;
-    hipStream_t sideStream[2] = { NULL, NULL };   // the three glyph classes of the distance pass run concurrently: two of them on these (fork / join by events)
-    hipEvent_t forkEvent = NULL, joinEvent[2] = { NULL, NULL };
+    Stream sideStream[2];             // the three glyph classes of the distance pass run concurrently: two of them on these (fork / join by events)
+    Event forkEvent, joinEvent[2];
 
     size_t reservedGlyphs = 0;        // the per-glyph buffers (bucket, hBucket, ecParams) are allocated for ranges of at least this many glyphs
 
@@ -314,32 +251,20 @@ struct Workspace {
         newGlyphRange();
     }
     size_t glyphCapacity(int nGlyphs) const { return std::max(std::max((size_t) (nGlyphs > 0 ? nGlyphs : 0), reservedGlyphs), (size_t) 1); }
-    ~Workspace() {
-        if (!(scratch.owned || deferred.owned || ecParams.owned || gres.owned || workQueue.owned || bucket.owned || hBucket.owned || ecOrder.owned || hEcOrder.owned ||
-              ecOrderReady || forkEvent || sideStream[0] || sideStream[1]))
-            return;                                              // (a view over an arena that never had to grow: no device call)
-        (void) hipSetDevice(device);
-        for (int k = 0; k < 2; ++k) {
-            if (sideStream[k])
-                hipStreamDestroy(sideStream[k]);
-            if (joinEvent[k])
-                hipEventDestroy(joinEvent[k]);
-        }
-        if (forkEvent)
-            hipEventDestroy(forkEvent);
-        if (ecOrderReady)
-            hipEventDestroy(ecOrderReady);
-    }                                                            // (then the buffers, on that device)
+    // No destructor of its own: the members release what they own on the thread's current device -- whoever destroys a batch or a pooled pipe binds
+    // `device` first -- and a view over an arena that never had to grow owns nothing: no device call at all.
 };
 
 // The shapes of a batch, fixed once it is digested: CSR arrays and edge records on the device, per-glyph counts on the host.
 struct ShapeData {
     int nGlyphs = 0, nContours = 0, nEdges = 0, maxContours = 0, maxEdges = 0;
-    int32_t *dGlyphContourOffsets = NULL, *dContourOffsets = NULL;
-    double *dPoints = NULL;
-    uint8_t *dTypes = NULL, *dColors = NULL;
-    EdgeRec *dRecs = NULL;
-    int8_t *dWindings = NULL;
+    // Each array is the batch's own (created from host arrays, prepared, digested) or borrowed: the caller's device arrays, the parent batch of a
+    // glyph range, a range of an arena or of a pipeline slot.
+    WorkBuffer<int32_t> dGlyphContourOffsets, dContourOffsets;
+    WorkBuffer<double> dPoints;
+    WorkBuffer<uint8_t> dTypes, dColors;
+    WorkBuffer<EdgeRec> dRecs;
+    WorkBuffer<int8_t> dWindings;
     mutable std::vector<int> hContours, hEdges;   // contours / edges per glyph (batches of device arrays: fetched on first need, fetchGlyphCounts)
     void countMaxima() {                          // maxContours / maxEdges of the per-glyph counts
         maxContours = maxEdges = 0;
@@ -356,9 +281,8 @@ struct ShapeData {
 
 struct MsdfHipBatch : ShapeData {
     int device = 0;                   // the HIP device the batch lives on; every call on the batch binds the calling thread to it
-    bool ownsInputs = false;          // the five input arrays are the batch's (dRecs / dWindings: a batch made with `new` owns them, a view never does)
     bool serialClasses = false;       // launch the glyph classes one after the other on the caller's stream (host-output pipeline: its chunks overlap instead)
-    mutable double *dBounds = NULL;   // [nGlyphs][4] l, b, r, t of Shape::getBounds (msdfhip_batch_bounds / _frame; allocated on first need, the batch's own)
+    mutable WorkBuffer<double> dBounds;   // [nGlyphs][4] l, b, r, t of Shape::getBounds (msdfhip_batch_bounds / _frame; allocated on first need, the batch's own)
     bool boundsFixed = false;         // dBounds were taken at creation from the normalized edges (batches prepared from raw outlines: the arrays they keep are the coloured ones)
     mutable Workspace work;
     mutable ClassPlan plan;           // the classes of work.bucket
@@ -378,32 +302,37 @@ struct GenerateCall {
 BatchView viewOf(const MsdfHipBatch *b) {
     BatchView v;
     v.nGlyphs = b->nGlyphs;
-    v.glyphContourOffsets = b->dGlyphContourOffsets;
-    v.contourOffsets = b->dContourOffsets;
-    v.recs = b->dRecs;
-    v.windings = b->dWindings;
+    v.glyphContourOffsets = b->dGlyphContourOffsets.ptr;
+    v.contourOffsets = b->dContourOffsets.ptr;
+    v.recs = b->dRecs.ptr;
+    v.windings = b->dWindings.ptr;
     return v;
 }
 
 int digest(MsdfHipBatch *b, hipStream_t stream) {
-    if (!b->dRecs)
-        HIPCHK(hipMalloc((void **) &b->dRecs, sizeof(EdgeRec)*(size_t) (b->nEdges > 0 ? b->nEdges : 1)));
-    if (!b->dWindings)
-        HIPCHK(hipMalloc((void **) &b->dWindings, (size_t) (b->nContours > 0 ? b->nContours : 1)));
+    HIPCHK(b->dRecs.ensure((size_t) (b->nEdges > 0 ? b->nEdges : 1)));          // (a view borrows room for them: nothing to do)
+    HIPCHK(b->dWindings.ensure((size_t) (b->nContours > 0 ? b->nContours : 1)));
     const int edgeBlocks = (b->nEdges+255)/256, contourBlocks = (b->nContours+255)/256;
     if (edgeBlocks+contourBlocks > 0)                            // records and windings in one launch
-        hipLaunchKernelGGL(k_prep_records, dim3(edgeBlocks+contourBlocks), dim3(256), 0, stream, b->dRecs, b->nEdges, b->nContours,
-                           b->dContourOffsets, b->dPoints, b->dTypes, b->dColors, b->dWindings, edgeBlocks);
+        hipLaunchKernelGGL(k_prep_records, dim3(edgeBlocks+contourBlocks), dim3(256), 0, stream, b->dRecs.ptr, b->nEdges, b->nContours,
+                           b->dContourOffsets.ptr, b->dPoints.ptr, b->dTypes.ptr, b->dColors.ptr, b->dWindings.ptr, edgeBlocks);
     HIPCHK(hipGetLastError());
     return MSDFHIP_OK;
+}
+
+// A batch's own copy of a host array: room for `alloc` elements (never none), the first `used` uploaded.
+template <class T>
+hipError_t uploadNew(WorkBuffer<T> &dst, const T *src, size_t alloc, size_t used) {
+    const hipError_t e = dst.ensure(alloc);
+    return e == hipSuccess && used ? hipMemcpy(dst.ptr, src, used*sizeof(T), hipMemcpyHostToDevice) : e;
 }
 
 int fetchGlyphCounts(const MsdfHipBatch *b) {             // device-array batches: the per-glyph counts are read back once
     if (!b->hContours.empty() || b->nGlyphs == 0)
         return MSDFHIP_OK;
     std::vector<int32_t> gco((size_t) b->nGlyphs+1), co((size_t) b->nContours+1);
-    HIPCHK(hipMemcpy(gco.data(), b->dGlyphContourOffsets, sizeof(int32_t)*gco.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(co.data(), b->dContourOffsets, sizeof(int32_t)*co.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(gco.data(), b->dGlyphContourOffsets.ptr, sizeof(int32_t)*gco.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(co.data(), b->dContourOffsets.ptr, sizeof(int32_t)*co.size(), hipMemcpyDeviceToHost));
     b->hContours.resize((size_t) b->nGlyphs);
     b->hEdges.resize((size_t) b->nGlyphs);
     for (int g = 0; g < b->nGlyphs; ++g) {
@@ -639,11 +568,9 @@ int ensureEcOrder(const MsdfHipBatch *b, const int **order, hipStream_t stream) 
         ws.ecOrder.release();
         return MSDFHIP_OK;
     }
-    if (hipEventCreateWithFlags(&ws.ecOrderReady, hipEventDisableTiming) != hipSuccess || hipEventRecord(ws.ecOrderReady, stream) != hipSuccess) {
+    if (ws.ecOrderReady.create(hipEventDisableTiming) != hipSuccess || hipEventRecord(ws.ecOrderReady, stream) != hipSuccess) {
         (void) hipGetLastError();
-        if (ws.ecOrderReady)
-            hipEventDestroy(ws.ecOrderReady);
-        ws.ecOrderReady = NULL;
+        ws.ecOrderReady.release();
         if (hipStreamSynchronize(stream) != hipSuccess) {        // no event for the other streams to wait on: the list must have landed before it is used
             (void) hipGetLastError();
             ws.ecOrder.release();
@@ -663,13 +590,10 @@ int ensureSideStreams(const MsdfHipBatch *b) {
     for (int k = 0; k < 2; ++k) {
         // The two side classes run at LOW queue priority: the long LDS-class launch on the caller's stream gets the slots first and the side
         // classes fill what it leaves, its tail included (distance pass 3.93 -> 3.80-3.88 ms; high: 4.01).
-        if (least != 0)
-            HIPCHK(hipStreamCreateWithPriority(&ws.sideStream[k], hipStreamNonBlocking, least));
-        else
-            HIPCHK(hipStreamCreateWithFlags(&ws.sideStream[k], hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&ws.joinEvent[k], hipEventDisableTiming));
+        HIPCHK(ws.sideStream[k].create(hipStreamNonBlocking, least));
+        HIPCHK(ws.joinEvent[k].create(hipEventDisableTiming));
     }
-    HIPCHK(hipEventCreateWithFlags(&ws.forkEvent, hipEventDisableTiming));
+    HIPCHK(ws.forkEvent.create(hipEventDisableTiming));
     return MSDFHIP_OK;
 }
 
@@ -866,7 +790,7 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         hipLaunchKernelGGL((k_ec_fast<N, false>), dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
                            (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
     hipLaunchKernelGGL(k_ec_scan, dim3(1), dim3(1024), 0, stream, b->nGlyphs, reinterpret_cast<const unsigned *>(deferred), seg, offsets, policy, ecOrder);
-    hipLaunchKernelGGL((k_ec_query<N, OVERLAP>), dim3(queryBlocks), dim3(WAVE), p.queryLds, stream, b->nGlyphs, b->dGlyphContourOffsets, b->dContourOffsets,
+    hipLaunchKernelGGL((k_ec_query<N, OVERLAP>), dim3(queryBlocks), dim3(WAVE), p.queryLds, stream, b->nGlyphs, b->dGlyphContourOffsets.ptr, b->dContourOffsets.ptr,
                        (const EdgeRec *) viewOf(b).recs, viewOf(b).windings, dGlyphs, w, h, src, out, stencil, cfg,
                        (const EcGlyphParams *) b->work.ecParams.ptr, (const EcCandidate *) deferred, seg, (const int *) offsets, offsets+2*(size_t) b->nGlyphs+2, p.queryBatch,
                        p.slotCap, p.slotOffset, policy, call.overflowOut, ecOrder, p.queryFlags);
@@ -987,8 +911,8 @@ int launchLegacyDistanceKernel(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyph
     if (p.tooManyBlocks)
         return fail(MSDFHIP_ERR_INVALID, "launch of %zu tiles exceeds the grid limit; split the batch", p.blocks);
     ScopedTimer timer(stream, 0);
-    hipLaunchKernelGGL(k_distance_legacy<MODE>, dim3((unsigned) p.blocks), dim3(WAVE), 0, stream, b->nGlyphs, (const int32_t *) b->dGlyphContourOffsets,
-                       (const int32_t *) b->dContourOffsets, (const EdgeRec *) b->dRecs, dGlyphs, w, h, (w+TILE-1)/TILE, tilesOf(w, h), dst, toScratch);
+    hipLaunchKernelGGL(k_distance_legacy<MODE>, dim3((unsigned) p.blocks), dim3(WAVE), 0, stream, b->nGlyphs, (const int32_t *) b->dGlyphContourOffsets.ptr,
+                       (const int32_t *) b->dContourOffsets.ptr, (const EdgeRec *) b->dRecs.ptr, dGlyphs, w, h, (w+TILE-1)/TILE, tilesOf(w, h), dst, toScratch);
     HIPCHK(hipGetLastError());
     return MSDFHIP_OK;
 }
@@ -1124,12 +1048,11 @@ int msdfhip_batch_create_device(MsdfHipBatch **batch, int n_glyphs, int n_contou
     b->onDevice(currentDevice());                                // ... not the process default
     b->nGlyphs = n_glyphs, b->nContours = n_contours, b->nEdges = n_edges;
     b->maxContours = max_contours_per_glyph, b->maxEdges = max_edges_per_glyph;
-    b->ownsInputs = false;
-    b->dGlyphContourOffsets = const_cast<int32_t *>(d_glyph_contour_offsets);
-    b->dContourOffsets = const_cast<int32_t *>(d_contour_offsets);
-    b->dPoints = const_cast<double *>(d_points);
-    b->dTypes = const_cast<uint8_t *>(d_types);
-    b->dColors = const_cast<uint8_t *>(d_colors);
+    b->dGlyphContourOffsets.borrow(const_cast<int32_t *>(d_glyph_contour_offsets), (size_t) n_glyphs+1);   // the caller's arrays: never freed here
+    b->dContourOffsets.borrow(const_cast<int32_t *>(d_contour_offsets), (size_t) n_contours+1);
+    b->dPoints.borrow(const_cast<double *>(d_points), 8*(size_t) n_edges);
+    b->dTypes.borrow(const_cast<uint8_t *>(d_types), (size_t) n_edges);
+    b->dColors.borrow(const_cast<uint8_t *>(d_colors), (size_t) n_edges);
     rc = digest(b, (hipStream_t) stream);
     if (rc != MSDFHIP_OK) {
         msdfhip_batch_destroy(b);
@@ -1195,20 +1118,18 @@ int msdfhip_batch_create_on(MsdfHipBatch **batch, int device, int n_glyphs, cons
     MsdfHipBatch *b = new MsdfHipBatch();
     b->onDevice(currentDevice());
     b->nGlyphs = n_glyphs, b->nContours = nC, b->nEdges = nE, b->maxContours = maxC, b->maxEdges = maxE;
-    b->ownsInputs = true;
     b->hContours.swap(hContours);
     b->hEdges.swap(hEdges);
     const size_t eAlloc = nE > 0 ? nE : 1;
-    #define ALLOC_COPY(dst, src, bytes, used) do { \
-        hipError_t e_ = hipMalloc((void **) &(dst), (bytes) ? (bytes) : 16); \
-        if (e_ == hipSuccess && (used)) e_ = hipMemcpy((dst), (src), (used), hipMemcpyHostToDevice); \
-        if (e_ != hipSuccess) { msdfhip_batch_destroy(b); return fail(MSDFHIP_ERR_HIP, "batch upload failed: %s", hipGetErrorString(e_)); } } while (0)
-    ALLOC_COPY(b->dGlyphContourOffsets, gco, sizeof(int32_t)*(size_t) (n_glyphs+1), sizeof(int32_t)*(size_t) (n_glyphs+1));
-    ALLOC_COPY(b->dContourOffsets, co, sizeof(int32_t)*(size_t) (nC+1), sizeof(int32_t)*(size_t) (nC+1));
-    ALLOC_COPY(b->dPoints, points, sizeof(double)*8*eAlloc, sizeof(double)*8*(size_t) nE);
-    ALLOC_COPY(b->dTypes, types, eAlloc, (size_t) nE);
-    ALLOC_COPY(b->dColors, colors, eAlloc, (size_t) nE);
-    #undef ALLOC_COPY
+    hipError_t e = uploadNew(b->dGlyphContourOffsets, gco, (size_t) n_glyphs+1, (size_t) n_glyphs+1);
+    if (e == hipSuccess) e = uploadNew(b->dContourOffsets, co, (size_t) nC+1, (size_t) nC+1);
+    if (e == hipSuccess) e = uploadNew(b->dPoints, points, 8*eAlloc, 8*(size_t) nE);
+    if (e == hipSuccess) e = uploadNew(b->dTypes, types, eAlloc, (size_t) nE);
+    if (e == hipSuccess) e = uploadNew(b->dColors, colors, eAlloc, (size_t) nE);
+    if (e != hipSuccess) {
+        msdfhip_batch_destroy(b);
+        return fail(MSDFHIP_ERR_HIP, "batch upload failed: %s", hipGetErrorString(e));
+    }
     rc = digest(b, NULL);
     if (rc == MSDFHIP_OK && hipStreamSynchronize(NULL) != hipSuccess)
         rc = fail(MSDFHIP_ERR_HIP, "edge digestion failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1247,6 +1168,8 @@ int msdfhip_device_count(int *count) {
 
 namespace {
 
+static_assert(PREP_FIN_TYPES == PREP_FIN_POINTS+1 && PREP_FIN_COLORS == PREP_FIN_POINTS+2 && PREP_NORM_TYPES == PREP_NORM_POINTS+1 && PREP_NORM_COLORS == PREP_NORM_POINTS+2,
+              "msdfhip_batch_create_prepared_oriented adopts an edge set's regions as points, types, colors");
 static_assert(PREP_PLAN_WAVE_MAX_EDGES == PREP_WAVE_MAX_EDGES, "msdf_prepplan.hpp sizes the colouring's global tables from the kernels' LDS tier");
 
 // Shape preparation (row f3) as ONE queued sequence on `stream`, in the reference CLI's order: orientContours on the raw edges (orient.orient_contours),
@@ -1385,12 +1308,6 @@ int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, c
     if (bound2 > 0x7fffffffull)
         return fail(MSDFHIP_ERR_INVALID, "too many edges");
     const int nE1 = co1[nC];
-    struct Dev {                                                  // scoped device allocations of this call
-        std::vector<void *> ptrs;
-        ~Dev() { for (size_t i = 0; i < ptrs.size(); ++i) hipFree(ptrs[i]); }
-        hipError_t alloc(void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 16); if (e == hipSuccess) ptrs.push_back(*p); return e; }
-        void release(void *p) { for (size_t i = 0; i < ptrs.size(); ++i) if (ptrs[i] == p) { ptrs.erase(ptrs.begin()+i); break; } }
-    } dev;
     #define PREP_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(MSDFHIP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
     // one allocation per region the configuration needs (msdf_prepplan.hpp), with the exact normalized count and the bound of the coloured one; the records
     // and windings come with digest(), which sizes them from the final count
@@ -1398,10 +1315,12 @@ int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, c
                                   longest > PREP_WAVE_MAX_EDGES, true, false };
     const PrepCounts counts = { (size_t) n_glyphs, (size_t) nC, (size_t) nE, (size_t) nE1, bound2 };
     const PrepSizes sizes = prepRegionSizes(plan, counts);
-    void *region[PREP_REGIONS] = { NULL };
-    for (int r = 0; r < PREP_REGIONS; ++r)
-        if (sizes.bytes[r])
-            PREP_CHK(dev.alloc(&region[r], sizes.bytes[r]));
+    WorkBuffer<char> owner[PREP_REGIONS];                        // scoped to this call, but for the six the batch adopts below
+    void *region[PREP_REGIONS];
+    for (int r = 0; r < PREP_REGIONS; ++r) {
+        PREP_CHK(owner[r].ensure(sizes.bytes[r]));
+        region[r] = owner[r].ptr;
+    }
     const size_t offsetBytes = sizeof(int32_t)*(size_t) (nC+1);
     const struct { int region; const void *host; size_t bytes; } uploads[] = {
         { PREP_GCO, gco, sizeof(int32_t)*(size_t) (n_glyphs+1) }, { PREP_CO, co, offsetBytes }, { PREP_CO1, co1.data(), offsetBytes },
@@ -1417,16 +1336,13 @@ int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, c
     if (rc != MSDFHIP_OK)
         return rc;
     // Shape::getBounds where the CLI takes it (main.cpp:1125-1132): of the normalized edges, which do not outlive this call when a colouring follows
-    double *dBounds = (double *) region[PREP_BOUNDS];
-    rc = queueFrame(pb.norm, pb.gco, pb.co1, n_glyphs, dBounds, false, NULL, 0, 0, NULL, 0);
+    rc = queueFrame(pb.norm, pb.gco, pb.co1, n_glyphs, (double *) region[PREP_BOUNDS], false, NULL, 0, 0, NULL, 0);
     if (rc != MSDFHIP_OK)
         return rc;
     const int32_t *finalCo = co1.data();
-    int32_t *dGco = (int32_t *) region[PREP_GCO], *dFinalCo = (int32_t *) region[PREP_CO1];
     if (cfg->coloring) {
         PREP_CHK(hipMemcpy(co2.data(), pb.co2, sizeof(int32_t)*(size_t) (nC+1), hipMemcpyDeviceToHost));   // in stream order after the kernels above
         finalCo = co2.data();
-        dFinalCo = pb.co2;
     }
     PREP_CHK(hipGetLastError());
     PREP_CHK(hipDeviceSynchronize());
@@ -1441,10 +1357,10 @@ int msdfhip_batch_create_prepared_oriented(MsdfHipBatch **batch, int n_glyphs, c
     MsdfHipBatch *b = new MsdfHipBatch();
     b->onDevice(currentDevice());
     b->nGlyphs = n_glyphs, b->nContours = nC, b->nEdges = finalCo[nC], b->maxContours = maxC, b->maxEdges = maxE;
-    b->ownsInputs = true;                                        // the batch takes over the final arrays
-    b->dGlyphContourOffsets = dGco, b->dContourOffsets = dFinalCo, b->dPoints = pb.fin.points, b->dTypes = pb.fin.types, b->dColors = pb.fin.colors;
-    b->dBounds = dBounds, b->boundsFixed = true;
-    dev.release(dGco), dev.release(dFinalCo), dev.release(pb.fin.points), dev.release(pb.fin.types), dev.release(pb.fin.colors), dev.release(dBounds);
+    const int fin = cfg->coloring ? PREP_FIN_POINTS : PREP_NORM_POINTS;   // the batch takes over the final arrays (bindPrep's pb.fin)
+    b->dGlyphContourOffsets.adopt(std::move(owner[PREP_GCO])), b->dContourOffsets.adopt(std::move(owner[cfg->coloring ? PREP_CO2 : PREP_CO1]));
+    b->dPoints.adopt(std::move(owner[fin])), b->dTypes.adopt(std::move(owner[fin+1])), b->dColors.adopt(std::move(owner[fin+2]));
+    b->dBounds.adopt(std::move(owner[PREP_BOUNDS])), b->boundsFixed = true;
     rc = digest(b, NULL);
     if (rc == MSDFHIP_OK && hipStreamSynchronize(NULL) != hipSuccess)
         rc = fail(MSDFHIP_ERR_HIP, "edge digestion failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1488,13 +1404,13 @@ int msdfhip_batch_download(const MsdfHipBatch *b, int32_t *co, double *points, u
         return rc;
     HIPCHK(hipDeviceSynchronize());
     if (co)
-        HIPCHK(hipMemcpy(co, b->dContourOffsets, sizeof(int32_t)*(size_t) (b->nContours+1), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(co, b->dContourOffsets.ptr, sizeof(int32_t)*(size_t) (b->nContours+1), hipMemcpyDeviceToHost));
     if (points && b->nEdges)
-        HIPCHK(hipMemcpy(points, b->dPoints, sizeof(double)*8*(size_t) b->nEdges, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(points, b->dPoints.ptr, sizeof(double)*8*(size_t) b->nEdges, hipMemcpyDeviceToHost));
     if (types && b->nEdges)
-        HIPCHK(hipMemcpy(types, b->dTypes, (size_t) b->nEdges, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(types, b->dTypes.ptr, (size_t) b->nEdges, hipMemcpyDeviceToHost));
     if (colors && b->nEdges)
-        HIPCHK(hipMemcpy(colors, b->dColors, (size_t) b->nEdges, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(colors, b->dColors.ptr, (size_t) b->nEdges, hipMemcpyDeviceToHost));
     return MSDFHIP_OK;
 }
 
@@ -1511,17 +1427,7 @@ void msdfhip_batch_destroy(MsdfHipBatch *b) {
     if (!b)
         return;
     (void) hipSetDevice(b->device);
-    if (b->ownsInputs) {
-        hipFree(b->dGlyphContourOffsets);
-        hipFree(b->dContourOffsets);
-        hipFree(b->dPoints);
-        hipFree(b->dTypes);
-        hipFree(b->dColors);
-    }
-    hipFree(b->dRecs);
-    hipFree(b->dWindings);
-    hipFree(b->dBounds);
-    delete b;                                                    // (its workspace releases itself)
+    delete b;                                                    // (what it owns of its arrays and its workspace goes with it, on that device)
 }
 
 int msdfhip_batch_windings(const MsdfHipBatch *b, int32_t *windings) {
@@ -1533,18 +1439,17 @@ int msdfhip_batch_windings(const MsdfHipBatch *b, int32_t *windings) {
     std::vector<int8_t> tmp((size_t) b->nContours+1);
     HIPCHK(hipDeviceSynchronize());
     if (b->nContours)
-        HIPCHK(hipMemcpy(tmp.data(), b->dWindings, (size_t) b->nContours, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(tmp.data(), b->dWindings.ptr, (size_t) b->nContours, hipMemcpyDeviceToHost));
     for (int c = 0; c < b->nContours; ++c)
         windings[c] = tmp[c];
     return MSDFHIP_OK;
 }
 
-// Shape::getBounds of the batch's glyphs into b->dBounds on `stream` (and, with `frame`, the framed xf into dGlyphs): one k_frame launch.
+// Shape::getBounds of the batch's glyphs into b->dBounds.ptr on `stream` (and, with `frame`, the framed xf into dGlyphs): one k_frame launch.
 static int frameBatch(const MsdfHipBatch *b, const FrameParams *frame, int w, int h, MsdfHipGlyph *dGlyphs, hipStream_t stream) {
-    if (!b->dBounds)
-        HIPCHK(hipMalloc((void **) &b->dBounds, sizeof(double)*4*(size_t) (b->nGlyphs > 0 ? b->nGlyphs : 1)));
-    const EdgeArrays edges = { b->dPoints, b->dTypes, b->dColors };
-    return queueFrame(edges, b->dGlyphContourOffsets, b->dContourOffsets, b->nGlyphs, b->dBounds, b->boundsFixed, frame, w, h, dGlyphs, stream);
+    HIPCHK(b->dBounds.ensure(4*(size_t) (b->nGlyphs > 0 ? b->nGlyphs : 1)));
+    const EdgeArrays edges = { b->dPoints.ptr, b->dTypes.ptr, b->dColors.ptr };
+    return queueFrame(edges, b->dGlyphContourOffsets.ptr, b->dContourOffsets.ptr, b->nGlyphs, b->dBounds.ptr, b->boundsFixed, frame, w, h, dGlyphs, stream);
 }
 
 int msdfhip_batch_bounds(const MsdfHipBatch *b, double *bounds) {
@@ -1561,7 +1466,7 @@ int msdfhip_batch_bounds(const MsdfHipBatch *b, double *bounds) {
     }
     HIPCHK(hipStreamSynchronize(NULL));
     if (b->nGlyphs)
-        HIPCHK(hipMemcpy(bounds, b->dBounds, sizeof(double)*4*(size_t) b->nGlyphs, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(bounds, b->dBounds.ptr, sizeof(double)*4*(size_t) b->nGlyphs, hipMemcpyDeviceToHost));
     return MSDFHIP_OK;
 }
 
@@ -1791,108 +1696,68 @@ int msdfhip_simulate_8bit(float *dPixels, size_t n, void *streamPtr) {
 
 enum { PIPE_SLOTS = 4 };
 struct PipeSlot {
-    hipStream_t stream;               // kernels and copy back of the slot's chunk
-    hipEvent_t done;                  // the slot's last device-to-host copy has finished
-    hipEvent_t kernelsDone;           // the kernels (and the small uploads before them) of the slot's last chunk have finished
-    hipEvent_t distanceDone;          // the distance pass of the slot's last chunk has finished (its correction pass may still run)
-    unsigned *pinnedOverflow;         // pinned, device-visible word: k_ec_query mirrors the chunk's candidate-overflow count here (no k_ec_slow launch per chunk)
-    bool busy;
+    Stream stream;                    // kernels and copy back of the slot's chunk (declared first: it goes last, after everything queued on it)
+    Event done;                       // the slot's last device-to-host copy has finished
+    Event kernelsDone;                // the kernels (and the small uploads before them) of the slot's last chunk have finished
+    Event distanceDone;               // the distance pass of the slot's last chunk has finished (its correction pass may still run)
+    WorkBuffer<unsigned, true> pinnedOverflow;   // pinned, device-visible word: k_ec_query mirrors the chunk's candidate-overflow count here (no k_ec_slow launch per chunk)
+    bool busy = false;
     WorkBuffer<char> dev;             // [descriptors | float tiles | stencil | byte tiles] (slotLayout)
     WorkBuffer<MsdfHipGlyph, true> pinnedGlyphs;   // pinned staging of the chunk's descriptors: the generators' in the first half, the byte conversion's in the second
     WorkBuffer<char, true> pinnedTiles;   // pinned staging of the chunk's output when the caller's layout is not packed (scattered on the host)
-    int pendingFirst, pendingCount;   // the chunk waiting in pinnedTiles for its scatter
+    int pendingFirst = 0, pendingCount = 0;   // the chunk waiting in pinnedTiles for its scatter
     MsdfHipBatch view;                // glyph range of the parent batch + this slot's own workspace (its per-glyph buffers hold a full chunk)
     // streamed calls (msdfhip_generate_stream): the chunk's own inputs
     WorkBuffer<char, true> pinnedIn;  // pinned staging the host threads flatten the chunk's shapes into: [gco | co | points | types | colors]
     WorkBuffer<char> devIn;           // the same on the device, followed by the chunk's records and windings
-    hipEvent_t inputsUploaded;        // the chunk's upload has left pinnedIn
-    bool inputsInFlight;
-    hipEvent_t prepCounted;           // streamed calls of raw outlines: the chunk's coloured contour offsets have reached pinnedIn (StreamFeeder::prepare)
-    MsdfHipGlyph *frameGlyphs;        // framed streamed calls: the chunk's descriptors on the device, uploaded BEFORE its shapes so that k_frame can write their xf
+    Event inputsUploaded;             // the chunk's upload has left pinnedIn
+    bool inputsInFlight = false;
+    Event prepCounted;                // streamed calls of raw outlines: the chunk's coloured contour offsets have reached pinnedIn (StreamFeeder::prepare)
+    MsdfHipGlyph *frameGlyphs = NULL; // framed streamed calls: the chunk's descriptors on the device, uploaded BEFORE its shapes so that k_frame can write their xf
+
+    hipError_t create() {
+        hipError_t e = stream.create(hipStreamNonBlocking);
+        Event *const events[] = { &done, &kernelsDone, &distanceDone, &inputsUploaded, &prepCounted };
+        for (size_t k = 0; e == hipSuccess && k < sizeof(events)/sizeof(events[0]); ++k)
+            e = events[k]->create(hipEventDisableTiming);
+        if (e == hipSuccess && (e = pinnedOverflow.ensure(64)) == hipSuccess)
+            pinnedOverflow.ptr[0] = 0;
+        return e;
+    }
 };
 
 // The slots of a pipeline in flight. Pipelines live in a process-wide pool per device (like the arenas of the single-shape calls):
 // a host-output call takes one and returns it, so that a caller that builds a fresh batch per atlas does not pay for 100+ MB of
 // device / pinned allocations every time; the pool is bounded by the peak number of concurrent host-output calls.
 struct Pipe {
-    int device;
+    int device = 0;
     PipeSlot slot[PIPE_SLOTS];
-};
-
-static std::mutex gPipeMutex;
-static std::vector<Pipe *> gPipePool;
-
-static void destroyPipe(Pipe *p);                                // (below, next to msdfhip_trim)
-
-struct PipeLease {
-    Pipe *p;
-    PipeLease() : p(NULL) { }
-    ~PipeLease() {
-        if (p) {
-            // Whatever exit the call took (an error return may leave copies into caller memory / kernels in flight on the slots' streams):
-            // nothing of this call is pending when the next caller takes the pipe. Idle streams answer at once.
-            for (int k = 0; k < PIPE_SLOTS; ++k)
-                if (p->slot[k].stream)
-                    (void) hipStreamSynchronize(p->slot[k].stream);
-            (void) hipGetLastError();
-            std::lock_guard<std::mutex> lock(gPipeMutex);
-            gPipePool.push_back(p);
+    hipError_t create(int d) {
+        device = d;
+        hipError_t e = hipSuccess;
+        for (int k = 0; e == hipSuccess && k < PIPE_SLOTS; ++k) {
+            slot[k].view.onDevice(d);
+            e = slot[k].create();
         }
+        return e;
     }
-    int take(int device) {
-        {
-            std::lock_guard<std::mutex> lock(gPipeMutex);
-            for (size_t i = gPipePool.size(); i-- > 0; )
-                if (gPipePool[i]->device == device) {
-                    p = gPipePool[i];
-                    gPipePool.erase(gPipePool.begin()+i);
-                    return MSDFHIP_OK;
-                }
-        }
-        Pipe *fresh = new Pipe();
-        fresh->device = device;
-        for (int k = 0; k < PIPE_SLOTS; ++k) {
-            PipeSlot &s = fresh->slot[k];
-            s.view.onDevice(device);
-            s.stream = NULL, s.done = NULL, s.kernelsDone = NULL, s.distanceDone = NULL, s.pinnedOverflow = NULL, s.busy = false;
-            s.pendingFirst = 0, s.pendingCount = 0;
-            s.inputsUploaded = NULL, s.inputsInFlight = false, s.prepCounted = NULL, s.frameGlyphs = NULL;
-        }
-        for (int k = 0; k < PIPE_SLOTS; ++k) {                   // a half-built pipe never reaches the pool
-            hipError_t e = hipStreamCreateWithFlags(&fresh->slot[k].stream, hipStreamNonBlocking);
-            if (e == hipSuccess)
-                e = hipEventCreateWithFlags(&fresh->slot[k].done, hipEventDisableTiming);
-            if (e == hipSuccess)
-                e = hipEventCreateWithFlags(&fresh->slot[k].kernelsDone, hipEventDisableTiming);
-            if (e == hipSuccess)
-                e = hipEventCreateWithFlags(&fresh->slot[k].distanceDone, hipEventDisableTiming);
-            if (e == hipSuccess) {
-                e = pinnedAlloc((void **) &fresh->slot[k].pinnedOverflow, 256);
-                if (e == hipSuccess)
-                    fresh->slot[k].pinnedOverflow[0] = 0;
-            }
-            if (e == hipSuccess)
-                e = hipEventCreateWithFlags(&fresh->slot[k].inputsUploaded, hipEventDisableTiming);
-            if (e == hipSuccess)
-                e = hipEventCreateWithFlags(&fresh->slot[k].prepCounted, hipEventDisableTiming);
-            if (e != hipSuccess) {
-                (void) hipGetLastError();
-                destroyPipe(fresh);
-                return fail(MSDFHIP_ERR_HIP, "host-output pipeline: creating a stream / event failed: %s", hipGetErrorString(e));
-            }
-        }
-        p = fresh;
-        return MSDFHIP_OK;
+    void quiesce() {                  // idle streams answer at once
+        for (int k = 0; k < PIPE_SLOTS; ++k)
+            if (slot[k].stream)
+                (void) hipStreamSynchronize(slot[k].stream);
     }
 };
+
+static DevicePool<Pipe> gPipePool;
 
 // Points slot.view at glyphs [g0, g0+n) of b (shared, read-only inputs; the slot keeps its own work buffers across chunks and calls).
 static void sliceBatch(const MsdfHipBatch *b, MsdfHipBatch &v, int g0, int n) {
     v.onDevice(b->device);
     v.nGlyphs = n, v.nContours = b->nContours, v.nEdges = b->nEdges;
-    v.dGlyphContourOffsets = b->dGlyphContourOffsets+g0;        // entries are absolute contour indices: valid from any starting glyph
-    v.dContourOffsets = b->dContourOffsets, v.dPoints = b->dPoints, v.dTypes = b->dTypes, v.dColors = b->dColors;
-    v.dRecs = b->dRecs, v.dWindings = b->dWindings;
+    v.dGlyphContourOffsets.borrow(b->dGlyphContourOffsets.ptr+g0, (size_t) n+1);   // entries are absolute contour indices: valid from any starting glyph
+    v.dContourOffsets.borrow(b->dContourOffsets.ptr, b->dContourOffsets.cap), v.dPoints.borrow(b->dPoints.ptr, b->dPoints.cap);
+    v.dTypes.borrow(b->dTypes.ptr, b->dTypes.cap), v.dColors.borrow(b->dColors.ptr, b->dColors.cap);
+    v.dRecs.borrow(b->dRecs.ptr, b->dRecs.cap), v.dWindings.borrow(b->dWindings.ptr, b->dWindings.cap);
     v.setCounts(b->hContours.data()+g0, b->hEdges.data()+g0, n);
     v.work.newGlyphRange();                                      // the class lists are per glyph range
     v.serialClasses = true;                                      // pipeline chunks overlap each other; side streams per chunk only alias the few hardware queues
@@ -2206,9 +2071,11 @@ struct StreamFeeder : ChunkFeeder {
         MsdfHipBatch &v = p.view;
         v.onDevice(currentDevice());
         v.nGlyphs = n, v.nContours = nC, v.nEdges = (int) ch.nE;
-        v.dGlyphContourOffsets = const_cast<int32_t *>(pb.gco), v.dContourOffsets = const_cast<int32_t *>(pb.co);
-        v.dPoints = pb.raw.points, v.dTypes = pb.raw.types, v.dColors = pb.raw.colors;
-        v.dRecs = reinterpret_cast<EdgeRec *>(prepRegionAt(d, cv, PREP_RECS)), v.dWindings = reinterpret_cast<int8_t *>(prepRegionAt(d, cv, PREP_WINDINGS));
+        v.dGlyphContourOffsets.borrow(const_cast<int32_t *>(pb.gco), (size_t) n+1), v.dContourOffsets.borrow(const_cast<int32_t *>(pb.co), (size_t) nC+1);
+        v.dPoints.borrow(pb.raw.points, cv.bytes[PREP_RAW_POINTS]/sizeof(double)), v.dTypes.borrow(pb.raw.types, cv.bytes[PREP_RAW_TYPES]);
+        v.dColors.borrow(pb.raw.colors, cv.bytes[PREP_RAW_COLORS]);
+        v.dRecs.borrow(reinterpret_cast<EdgeRec *>(prepRegionAt(d, cv, PREP_RECS)), cv.bytes[PREP_RECS]/sizeof(EdgeRec));   // (room for the final edges: digest has nothing to allocate)
+        v.dWindings.borrow(reinterpret_cast<int8_t *>(prepRegionAt(d, cv, PREP_WINDINGS)), cv.bytes[PREP_WINDINGS]);
         v.setCounts(hContours.data()+g0, hEdges.data()+g0, n);
         if (prep) {
             const int rcPrep = prepareChunk(p, cv, pb, staged.gco, staged.co1, n, nC, longest, stream);
@@ -2247,8 +2114,9 @@ struct StreamFeeder : ChunkFeeder {
         }
         MsdfHipBatch &v = p.view;
         v.nEdges = hFinal[nC];
-        v.dContourOffsets = prep->coloring ? pb.co2 : const_cast<int32_t *>(pb.co1);
-        v.dPoints = pb.fin.points, v.dTypes = pb.fin.types, v.dColors = pb.fin.colors;
+        const int fin = prep->coloring ? PREP_FIN_POINTS : PREP_NORM_POINTS;
+        v.dContourOffsets.borrow(prep->coloring ? pb.co2 : const_cast<int32_t *>(pb.co1), (size_t) nC+1);
+        v.dPoints.borrow(pb.fin.points, cv.bytes[fin]/sizeof(double)), v.dTypes.borrow(pb.fin.types, cv.bytes[fin+1]), v.dColors.borrow(pb.fin.colors, cv.bytes[fin+2]);
         for (int g = 0; g < n; ++g)
             v.hEdges[(size_t) g] = hFinal[hGco[g+1]]-hFinal[hGco[g]];
         v.countMaxima();
@@ -2290,7 +2158,7 @@ static void hintHwQueuesOnce() {
 
 // MSDFHIP_PIPELINE_TRACE: timed events per chunk (kernels enqueued / finished, copy finished) relative to the first enqueue; tools/pipeline_timeline.py reads the line
 struct PipeTrace {
-    struct Events { hipEvent_t start, kernels, copied; long long hostEnqueued; };
+    struct Events { Event start, kernels, copied; long long hostEnqueued; };   // (they go with the trace, on every exit of the call)
     std::vector<Events> chunks;
     const bool on;
     const long long t0;
@@ -2298,11 +2166,11 @@ struct PipeTrace {
     void chunkStarts(hipStream_t stream) {
         if (!on)
             return;
-        Events te;
-        hipEventCreate(&te.start), hipEventCreate(&te.kernels), hipEventCreate(&te.copied);
+        chunks.emplace_back();
+        Events &te = chunks.back();
+        te.start.create(hipEventDefault), te.kernels.create(hipEventDefault), te.copied.create(hipEventDefault);
         te.hostEnqueued = nowNsEarly()-t0;
         hipEventRecord(te.start, stream);
-        chunks.push_back(te);
     }
     void kernelsQueued(hipStream_t stream) {
         if (on)
@@ -2325,8 +2193,6 @@ struct PipeTrace {
                     lengths[i], chunks[i].hostEnqueued/1e6, a, k, c);
         }
         fprintf(stderr, "]}\n");
-        for (size_t i = 0; i < chunks.size(); ++i)
-            hipEventDestroy(chunks[i].start), hipEventDestroy(chunks[i].kernels), hipEventDestroy(chunks[i].copied);
     }
 };
 
@@ -2404,7 +2270,7 @@ static int queueChunkInputs(const PipeCall &pc, ChunkFeeder *feeder, PipeSlot &p
             return rc;
     }
     call.afterDistance = p.distanceDone;
-    call.overflowOut = pc.mirrorOverflow ? p.pinnedOverflow : NULL;
+    call.overflowOut = pc.mirrorOverflow ? p.pinnedOverflow.ptr : NULL;
     return prepareAhead(&p.view, pc.mode, w, h, dGlyphs, pc.cfg, compute, call);
 }
 
@@ -2420,7 +2286,7 @@ static int queueChunkWork(const PipeCall &pc, PipeSlot *pipe, int slot, size_t c
     uint8_t *dBytes = reinterpret_cast<uint8_t *>(p.dev.ptr+pc.at.offBytes);
     if (ci >= (size_t) pc.depth)                                 // at most `depth` (two) chunks' kernels at a time, in order: chunk k starts when chunk k-depth's KERNELS are done
         HIPCHK(hipStreamWaitEvent(compute, pipe[(slot+PIPE_SLOTS-pc.depth)%PIPE_SLOTS].kernelsDone, 0));
-    p.pinnedOverflow[0] = 0;                                     // (the slot's previous chunk is done: nothing on the device writes it any more)
+    p.pinnedOverflow.ptr[0] = 0;                                     // (the slot's previous chunk is done: nothing on the device writes it any more)
     int rc = runGenerate(&p.view, pc.mode, w, h, dGlyphs, dTiles, dStencil, NULL, pc.cfg, compute, call);
     if (rc != MSDFHIP_OK)
         return rc;
@@ -2466,9 +2332,11 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
     const int nG = b ? b->nGlyphs : nGlyphs, N = channelsOf(mode);
     if (nG == 0 || w == 0 || h == 0)
         return MSDFHIP_OK;
-    PipeLease lease;
-    rc = lease.take(currentDevice());
-    if (rc == MSDFHIP_OK && b)
+    DevicePool<Pipe>::Lease lease;
+    const hipError_t taken = gPipePool.take(currentDevice(), lease);
+    if (taken != hipSuccess)
+        return fail(MSDFHIP_ERR_HIP, "host-output pipeline: creating a stream / event failed: %s", hipGetErrorString(taken));
+    if (b)
         rc = fetchGlyphCounts(b);
     if (rc != MSDFHIP_OK)
         return rc;
@@ -2479,7 +2347,7 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
         ChunkFeeder *f;
         ~FeederDrain() { f->drain(); }
     } drainGuard = { feeder };
-    PipeSlot *pipe = lease.p->slot;
+    PipeSlot *pipe = lease->slot;
     PipeCall pc;
     pc.mode = mode, pc.w = w, pc.h = h, pc.N = N, pc.glyphs = glyphs, pc.cfg = cfg, pc.out = out, pc.atlas = atlas, pc.mirrorOverflow = mirrorOverflow;
     pc.texels = (size_t) w*h, pc.tile = pc.texels*N, pc.elem = out ? sizeof(float) : 1;
@@ -2529,7 +2397,7 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
         if (p.busy) {                                            // the slot's previous copy must have left its buffers
             HIPCHK(hipEventSynchronize(p.done));
             p.busy = false;
-            if (mirrorOverflow && p.pinnedOverflow[0] != 0)
+            if (mirrorOverflow && p.pinnedOverflow.ptr[0] != 0)
                 *overflowed = true;
             if (p.pendingCount)
                 scatterPending(p, glyphs, pc.dstBytes, pc.elem, w, h, N);
@@ -2548,7 +2416,7 @@ static int runPipelineOnce(const MsdfHipBatch *b, ChunkFeeder *feeder, int devic
         p.busy = false;
         if (e != hipSuccess && rc == MSDFHIP_OK)
             rc = fail(MSDFHIP_ERR_HIP, "host-output pipeline: %s", hipGetErrorString(e));
-        if (mirrorOverflow && e == hipSuccess && p.pinnedOverflow[0] != 0)
+        if (mirrorOverflow && e == hipSuccess && p.pinnedOverflow.ptr[0] != 0)
             *overflowed = true;
         if (rc == MSDFHIP_OK && p.pendingCount)
             scatterPending(p, glyphs, pc.dstBytes, pc.elem, w, h, N);
@@ -2859,112 +2727,49 @@ int msdfhip_generate_sharded(const int *devices, int n_devices, int mode, int w,
 // returns it, so short-lived worker threads (msdf-atlas-gen spawns a fresh team per Workload::finish()) reuse them instead of
 // leaking one per thread; the pool is bounded by the peak number of concurrent calls.
 struct ThreadArena {
-    int device;
-    hipStream_t stream;
-    char *dev, *pinned;
-    size_t devCap, pinnedCap;
-    unsigned *barrier;               // counters of k_single_call ([0] grid barrier, [16] finished workgroups): zeroed once, only ever counted up --
-    unsigned barrierEpoch, doneCount, doneEpoch;   // their values between calls, and the completion-flag value of the last call
-    char *pinnedDev;                 // the device's address of `pinned` (hipHostGetDevicePointer): k_single_call reads its inputs / writes its tile there
-};
+    int device = 0;
+    Stream stream;
+    WorkBuffer<char> dev;
+    WorkBuffer<char, true> pinned;
+    WorkBuffer<unsigned> barrier;     // counters of k_single_call ([0] grid barrier, [16] finished workgroups): zeroed once, only ever counted up --
+    unsigned barrierEpoch = 0, doneCount = 0, doneEpoch = 0;   // their values between calls, and the completion-flag value of the last call
+    char *pinnedDev = NULL;           // the device's address of `pinned` (hipHostGetDevicePointer): k_single_call reads its inputs / writes its tile there
 
-static std::mutex gArenaMutex;
-static std::vector<ThreadArena *> gArenaPool;
-
-struct ArenaLease {
-    ThreadArena *a;
-    bool quiescent;                                              // the call saw its own completion (stream sync or k_single_call's flag): nothing of it is in flight
-    ArenaLease() : a(NULL), quiescent(false) { }
-    ~ArenaLease() {
-        if (a) {
-            if (a->stream && !quiescent) {                       // (an error exit may leave copies / kernels of this call in flight)
-                (void) hipStreamSynchronize(a->stream);
-                (void) hipGetLastError();
-            }
-            std::lock_guard<std::mutex> lock(gArenaMutex);
-            gArenaPool.push_back(a);
-        }
-    }
-    int take(int device) {
-        {
-            std::lock_guard<std::mutex> lock(gArenaMutex);
-            for (size_t i = gArenaPool.size(); i-- > 0; )
-                if (gArenaPool[i]->device == device) {
-                    a = gArenaPool[i];
-                    gArenaPool.erase(gArenaPool.begin()+i);
-                    return MSDFHIP_OK;
-                }
-        }
-        ThreadArena *fresh = new ThreadArena();
-        fresh->device = device, fresh->stream = NULL, fresh->dev = fresh->pinned = NULL, fresh->devCap = fresh->pinnedCap = 0;
-        fresh->barrier = NULL, fresh->barrierEpoch = fresh->doneCount = fresh->doneEpoch = 0, fresh->pinnedDev = NULL;
-        if (hipStreamCreateWithFlags(&fresh->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete fresh;
-            return fail(MSDFHIP_ERR_HIP, "hipStreamCreate failed");
-        }
+    hipError_t create(int d) {
+        device = d;
+        hipError_t e = stream.create(hipStreamNonBlocking);
+        if (e == hipSuccess)
+            e = barrier.ensure(64);
         // (zeroed ON THE ARENA'S STREAM: hipMemset runs on the legacy default stream, which a non-blocking stream does not wait for -- the first
         // k_single_call of a fresh arena could start before it and have its counters zeroed under it; found by the TSan run of tests/sanitize)
-        if (hipMalloc((void **) &fresh->barrier, 256) != hipSuccess || hipMemsetAsync(fresh->barrier, 0, 256, fresh->stream) != hipSuccess) {
-            (void) hipGetLastError();
-            if (fresh->barrier)
-                hipFree(fresh->barrier);
-            hipStreamDestroy(fresh->stream);
-            delete fresh;
-            return fail(MSDFHIP_ERR_HIP, "hipMalloc failed (single-call barrier)");
-        }
-        a = fresh;
-        return MSDFHIP_OK;
+        return e == hipSuccess ? hipMemsetAsync(barrier.ptr, 0, 256, stream) : e;
+    }
+    void quiesce() {
+        if (stream)
+            (void) hipStreamSynchronize(stream);
     }
 };
 
+static DevicePool<ThreadArena> gArenaPool;
+typedef DevicePool<ThreadArena>::Lease ArenaHold;               // (quiescent: the call saw its own completion -- stream sync or k_single_call's flag)
+
+static int takeArena(ArenaHold &lease) {
+    const hipError_t e = gArenaPool.take(currentDevice(), lease);
+    return e == hipSuccess ? MSDFHIP_OK : fail(MSDFHIP_ERR_HIP, "single-shape call: creating its stream / barrier failed: %s", hipGetErrorString(e));
+}
+
 static int arenaReserve(ThreadArena &a, size_t devBytes, size_t pinnedBytes) {
-    if (a.devCap < devBytes) {
-        if (a.dev)
-            HIPCHK(hipFree(a.dev));
-        a.dev = NULL, a.devCap = 0;
-        const size_t cap = devBytes+devBytes/2+4096;
-        HIPCHK(hipMalloc((void **) &a.dev, cap));
-        a.devCap = cap;
-    }
-    if (a.pinnedCap < pinnedBytes) {
-        if (a.pinned)
-            HIPCHK(pinnedFree(a.pinned));
-        a.pinned = NULL, a.pinnedCap = 0;
-        const size_t cap = pinnedBytes+pinnedBytes/2+4096;
-        HIPCHK(pinnedAlloc((void **) &a.pinned, cap));
-        a.pinnedCap = cap;
+    if (a.dev.cap < devBytes)
+        HIPCHK(a.dev.ensure(devBytes+devBytes/2+4096));
+    if (a.pinned.cap < pinnedBytes) {
         a.pinnedDev = NULL;
-        if (hipHostGetDevicePointer((void **) &a.pinnedDev, a.pinned, 0) != hipSuccess) {   // not mapped: k_single_call then works on device copies
+        HIPCHK(a.pinned.ensure(pinnedBytes+pinnedBytes/2+4096));
+        if (hipHostGetDevicePointer((void **) &a.pinnedDev, a.pinned.ptr, 0) != hipSuccess) {   // not mapped: k_single_call then works on device copies
             (void) hipGetLastError();
             a.pinnedDev = NULL;
         }
     }
     return MSDFHIP_OK;
-}
-
-static void destroyPipe(Pipe *p) {
-    (void) hipSetDevice(p->device);
-    for (int k = 0; k < PIPE_SLOTS; ++k) {
-        PipeSlot &s = p->slot[k];
-        if (s.stream)
-            (void) hipStreamSynchronize(s.stream);
-        if (s.inputsUploaded)
-            hipEventDestroy(s.inputsUploaded);
-        if (s.prepCounted)
-            hipEventDestroy(s.prepCounted);
-        if (s.done)
-            hipEventDestroy(s.done);
-        if (s.kernelsDone)
-            hipEventDestroy(s.kernelsDone);
-        if (s.distanceDone)
-            hipEventDestroy(s.distanceDone);
-        if (s.pinnedOverflow)
-            pinnedFree(s.pinnedOverflow);
-        if (s.stream)
-            hipStreamDestroy(s.stream);
-    }
-    delete p;                                                    // (the slots' buffers and the views' workspaces release themselves)
-    (void) hipGetLastError();
 }
 
 enum SingleOp { OP_GENERATE = 0, OP_ERROR_CORRECTION = 1, OP_SIGN_CORRECTION = 2, OP_RASTERIZE = 3, OP_GENERATE_LEGACY = 4 };   // what the single-shape call does to `pixels`
@@ -3167,8 +2972,8 @@ static GroupPlan planGroup(ShapeCall *const *calls, int n) {
 static void stageGroup(const GroupPlan &p, ThreadArena &a, ShapeCall *const *calls, int n) {
     const ShapeCall &c0 = *calls[0];
     const int channels = c0.channels, w = c0.w, h = c0.h;
-    int32_t *gco = reinterpret_cast<int32_t *>(a.pinned+p.hGco), *co = reinterpret_cast<int32_t *>(a.pinned+p.hCo);
-    MsdfHipGlyph *gd = reinterpret_cast<MsdfHipGlyph *>(a.pinned+p.hGlyph);
+    int32_t *gco = reinterpret_cast<int32_t *>(a.pinned.ptr+p.hGco), *co = reinterpret_cast<int32_t *>(a.pinned.ptr+p.hCo);
+    MsdfHipGlyph *gd = reinterpret_cast<MsdfHipGlyph *>(a.pinned.ptr+p.hGlyph);
     size_t cAt = 0, eAt = 0;
     co[0] = 0;
     for (int g = 0; g < n; ++g) {
@@ -3178,9 +2983,9 @@ static void stageGroup(const GroupPlan &p, ThreadArena &a, ShapeCall *const *cal
         for (int k = 1; k <= c.nC; ++k)
             co[cAt+k] = (int32_t) (eAt+c.co[k]);
         if (nE) {
-            memcpy(a.pinned+p.hPts+eAt*8*sizeof(double), c.points, (size_t) nE*8*sizeof(double));
-            memcpy(a.pinned+p.hTypes+eAt, c.types, nE);
-            memcpy(a.pinned+p.hColors+eAt, c.colors, nE);
+            memcpy(a.pinned.ptr+p.hPts+eAt*8*sizeof(double), c.points, (size_t) nE*8*sizeof(double));
+            memcpy(a.pinned.ptr+p.hTypes+eAt, c.types, nE);
+            memcpy(a.pinned.ptr+p.hColors+eAt, c.colors, nE);
         }
         cAt += c.nC, eAt += nE;
         memcpy(gd[g].xf, c.xf, sizeof(gd[g].xf));
@@ -3189,7 +2994,7 @@ static void stageGroup(const GroupPlan &p, ThreadArena &a, ShapeCall *const *cal
         gd[g].flip = c.flip ? 1 : 0;
         if (p.bitmapIsInput)
             for (int y = 0; y < h; ++y)
-                memcpy(a.pinned+p.hSrc+((size_t) g*p.texels+(size_t) y*w)*channels*sizeof(float), c.pixels+(ptrdiff_t) c.rowStride*y, sizeof(float)*(size_t) w*channels);
+                memcpy(a.pinned.ptr+p.hSrc+((size_t) g*p.texels+(size_t) y*w)*channels*sizeof(float), c.pixels+(ptrdiff_t) c.rowStride*y, sizeof(float)*(size_t) w*channels);
     }
     gco[n] = (int32_t) cAt;
 }
@@ -3198,19 +3003,19 @@ static void stageGroup(const GroupPlan &p, ThreadArena &a, ShapeCall *const *cal
 static void buildView(const GroupPlan &p, ThreadArena &a, ShapeCall *const *calls, int n, MsdfHipBatch &b) {
     b.onDevice(a.device);
     b.nGlyphs = n, b.nContours = (int) p.sumC, b.nEdges = (int) p.sumE;
-    b.dGlyphContourOffsets = reinterpret_cast<int32_t *>(a.dev+p.hGco);
-    b.dContourOffsets = reinterpret_cast<int32_t *>(a.dev+p.hCo);
-    b.dPoints = reinterpret_cast<double *>(a.dev+p.hPts);
-    b.dTypes = reinterpret_cast<uint8_t *>(a.dev+p.hTypes);
-    b.dColors = reinterpret_cast<uint8_t *>(a.dev+p.hColors);
-    b.dRecs = reinterpret_cast<EdgeRec *>(a.dev+p.dRecs);
-    b.dWindings = reinterpret_cast<int8_t *>(a.dev+p.dWind);
+    b.dGlyphContourOffsets.borrow(reinterpret_cast<int32_t *>(a.dev.ptr+p.hGco), (size_t) n+1);
+    b.dContourOffsets.borrow(reinterpret_cast<int32_t *>(a.dev.ptr+p.hCo), p.sumC+1);
+    b.dPoints.borrow(reinterpret_cast<double *>(a.dev.ptr+p.hPts), 8*p.eAlloc);
+    b.dTypes.borrow(reinterpret_cast<uint8_t *>(a.dev.ptr+p.hTypes), p.eAlloc);
+    b.dColors.borrow(reinterpret_cast<uint8_t *>(a.dev.ptr+p.hColors), p.eAlloc);
+    b.dRecs.borrow(reinterpret_cast<EdgeRec *>(a.dev.ptr+p.dRecs), p.eAlloc);
+    b.dWindings.borrow(reinterpret_cast<int8_t *>(a.dev.ptr+p.dWind), p.cAlloc);
     if (p.correct)
-        b.work.deferred.borrow(reinterpret_cast<EcCandidate *>(a.dev+p.dCands), p.candCap);
-    b.work.ecParams.borrow(reinterpret_cast<EcGlyphParams *>(a.dev+p.dParams), (size_t) n);
-    b.work.bucket.borrow(reinterpret_cast<int *>(a.dev+p.hBucket), (size_t) n), b.work.hBucket.borrow(reinterpret_cast<int *>(a.pinned+p.hBucket), (size_t) n);
+        b.work.deferred.borrow(reinterpret_cast<EcCandidate *>(a.dev.ptr+p.dCands), p.candCap);
+    b.work.ecParams.borrow(reinterpret_cast<EcGlyphParams *>(a.dev.ptr+p.dParams), (size_t) n);
+    b.work.bucket.borrow(reinterpret_cast<int *>(a.dev.ptr+p.hBucket), (size_t) n), b.work.hBucket.borrow(reinterpret_cast<int *>(a.pinned.ptr+p.hBucket), (size_t) n);
     if (p.gresNeed)
-        b.work.gres.borrow(reinterpret_cast<double *>(a.dev+p.dGres), p.gresNeed/sizeof(double));
+        b.work.gres.borrow(reinterpret_cast<double *>(a.dev.ptr+p.dGres), p.gresNeed/sizeof(double));
     b.hContours.resize((size_t) n);
     b.hEdges.resize((size_t) n);
     for (int g = 0; g < n; ++g) {
@@ -3222,20 +3027,20 @@ static void buildView(const GroupPlan &p, ThreadArena &a, ShapeCall *const *call
 
 // The status words and the results (with the stencils only where one is wanted) -> pinned staging, and the end of everything queued on the arena's stream.
 static int copyBackAndWait(const GroupPlan &p, ThreadArena &a) {
-    HIPCHK(hipMemcpyAsync(a.pinned+p.hStatus, a.dev+p.hStatus, 256+(p.anyStencil ? p.resultBytes : p.n*p.tileBytes), hipMemcpyDeviceToHost, a.stream));
+    HIPCHK(hipMemcpyAsync(a.pinned.ptr+p.hStatus, a.dev.ptr+p.hStatus, 256+(p.anyStencil ? p.resultBytes : p.n*p.tileBytes), hipMemcpyDeviceToHost, a.stream));
     HIPCHK(waitStream(a.stream));
     return MSDFHIP_OK;
 }
 
 // k_single_call's arguments. Zero copy: the kernel reads the staged CSR arrays straight from pinned host memory (phase 0) and writes the result tile and
-// its status words there; else a.dev holds the inputs already.
+// its status words there; else a.dev.ptr holds the inputs already.
 static void fillSingleArgs(SingleArgs &sa, const GroupPlan &p, const SinglePlan &single, ThreadArena &a, const MsdfHipBatch &b, const ShapeCall &c, bool overlapEff, bool zeroCopy) {
     const size_t sumC = p.sumC, sumE = p.sumE;
-    char *in = zeroCopy ? a.pinnedDev : a.dev;
+    char *in = zeroCopy ? a.pinnedDev : a.dev.ptr;
     sa.srcContourOffsets = reinterpret_cast<const int32_t *>(in+p.hCo), sa.points = reinterpret_cast<const double *>(in+p.hPts);
     sa.types = reinterpret_cast<const uint8_t *>(in+p.hTypes), sa.colors = reinterpret_cast<const uint8_t *>(in+p.hColors);
     sa.srcGlyph = reinterpret_cast<const MsdfHipGlyph *>(in+p.hGlyph);
-    sa.priv = a.dev+p.dPriv, sa.privStride = p.pvStride, sa.privWindings = p.pvWind, sa.privOffsets = p.pvOff, sa.privGlyphOffsets = p.pvGco, sa.privGlyph = p.pvGlyph;
+    sa.priv = a.dev.ptr+p.dPriv, sa.privStride = p.pvStride, sa.privWindings = p.pvWind, sa.privOffsets = p.pvOff, sa.privGlyphOffsets = p.pvGco, sa.privGlyph = p.pvGlyph;
     sa.nContours = (int) sumC, sa.nEdges = (int) sumE;
     {   // small shapes inside the kernel arguments (msdf_single.hpp)
         Carver pc;
@@ -3245,31 +3050,31 @@ static void fillSingleArgs(SingleArgs &sa, const GroupPlan &p, const SinglePlan 
         if (pc.off <= sizeof(sa.payload) && !tuning().noArgPayloadSingle) {
             sa.payloadBytes = (unsigned) pc.off, sa.payOffsets = (unsigned) pCo, sa.payPoints = (unsigned) pPts, sa.payTypes = (unsigned) pTypes;
             sa.payColors = (unsigned) pColors, sa.payGlyph = (unsigned) pGlyph;
-            memcpy(sa.payload+pCo, a.pinned+p.hCo, (sumC+1)*sizeof(int32_t));
-            memcpy(sa.payload+pPts, a.pinned+p.hPts, sumE*8*sizeof(double));
-            memcpy(sa.payload+pTypes, a.pinned+p.hTypes, sumE);
-            memcpy(sa.payload+pColors, a.pinned+p.hColors, sumE);
-            memcpy(sa.payload+pGlyph, a.pinned+p.hGlyph, sizeof(MsdfHipGlyph));
+            memcpy(sa.payload+pCo, a.pinned.ptr+p.hCo, (sumC+1)*sizeof(int32_t));
+            memcpy(sa.payload+pPts, a.pinned.ptr+p.hPts, sumE*8*sizeof(double));
+            memcpy(sa.payload+pTypes, a.pinned.ptr+p.hTypes, sumE);
+            memcpy(sa.payload+pColors, a.pinned.ptr+p.hColors, sumE);
+            memcpy(sa.payload+pGlyph, a.pinned.ptr+p.hGlyph, sizeof(MsdfHipGlyph));
         }
     }
     sa.width = c.w, sa.height = c.h, sa.tilesX = (c.w+TILE-1)/TILE, sa.tiles = (int) p.tilesAll, sa.listStride = p.maxE;
-    sa.scratch = p.correct ? reinterpret_cast<float *>(a.dev+p.dScratch) : NULL;
-    sa.out = reinterpret_cast<float *>((zeroCopy ? a.pinnedDev : a.dev)+p.hOut);
-    sa.stencil = p.anyStencil ? reinterpret_cast<uint8_t *>(a.dev+p.hStencil) : NULL;
-    sa.gres = overlapEff && !single.resInLds ? reinterpret_cast<double *>(a.dev+p.dGres) : NULL, sa.gresStride = single.resBytes/sizeof(double);
+    sa.scratch = p.correct ? reinterpret_cast<float *>(a.dev.ptr+p.dScratch) : NULL;
+    sa.out = reinterpret_cast<float *>((zeroCopy ? a.pinnedDev : a.dev.ptr)+p.hOut);
+    sa.stencil = p.anyStencil ? reinterpret_cast<uint8_t *>(a.dev.ptr+p.hStencil) : NULL;
+    sa.gres = overlapEff && !single.resInLds ? reinterpret_cast<double *>(a.dev.ptr+p.dGres) : NULL, sa.gresStride = single.resBytes/sizeof(double);
     // candidates: a counter and a segment of SINGLE_TILE_SEGMENT records per TILE (the tile's workgroup judges them itself), then the corner list
     sa.cfg = c.cfg, sa.correct = p.correct ? 1 : 0, sa.ecParams = b.work.ecParams.ptr, sa.cands = b.work.deferred.ptr, sa.seg = SINGLE_TILE_SEGMENT;
     sa.corners = p.correct ? reinterpret_cast<int *>(b.work.deferred.ptr+ecHeaderRecords((int) p.tilesAll)+p.tilesAll*SINGLE_TILE_SEGMENT) : NULL;
     sa.sizes = NULL;
     sa.slotCap = single.slotCap, sa.slotOffset = single.slotOffset;
     sa.teamXchgOffset = (unsigned) single.teamXchgOffset;
-    sa.barrier = a.barrier, sa.barrierBase = a.barrierEpoch, sa.doneBase = a.doneCount;
+    sa.barrier = a.barrier.ptr, sa.barrierBase = a.barrierEpoch, sa.doneBase = a.doneCount;
     sa.doneValue = a.doneEpoch+1u ? a.doneEpoch+1u : 1u;
     {   // ~70 ns per iteration: 2-3 ms for a font glyph, growing with the edges a tile may have to walk, at most the old 0.3 s
         const unsigned long long limit = (1ull<<15)+((unsigned long long) sumE<<8);
         sa.spinLimit = tuning().singleSpinLimit ? (unsigned) tuning().singleSpinLimit : (unsigned) (limit < (1ull<<22) ? limit : (1ull<<22));
     }
-    sa.status = reinterpret_cast<unsigned *>((zeroCopy ? a.pinnedDev : a.dev)+p.hStatus);
+    sa.status = reinterpret_cast<unsigned *>((zeroCopy ? a.pinnedDev : a.dev.ptr)+p.hStatus);
 }
 
 // ---- one launch for the whole call (msdf_single.hpp) where it applies: ONE shape, a generate*() call without the scanline pass, a bitmap of
@@ -3280,17 +3085,17 @@ static void fillSingleArgs(SingleArgs &sa, const GroupPlan &p, const SinglePlan 
 // word the last workgroup writes instead of a stream synchronisation. With a stencil (rare) the results take the device buffers and one copy, as the
 // batched path does.
 enum FusedOutcome { FUSED_DONE, FUSED_RERUN };
-static int runFused(const GroupPlan &p, const SinglePlan &single, ThreadArena &a, ArenaLease &lease, const MsdfHipBatch &b, FusedReservation &fusedSlots, const ShapeCall &c,
+static int runFused(const GroupPlan &p, const SinglePlan &single, ThreadArena &a, ArenaHold &lease, const MsdfHipBatch &b, FusedReservation &fusedSlots, const ShapeCall &c,
                     bool overlapEff, bool zeroCopy, FusedOutcome &outcome) {
     outcome = FUSED_RERUN;
     SingleArgs sa;
     fillSingleArgs(sa, p, single, a, b, c, overlapEff, zeroCopy);
     const unsigned groups = (unsigned) p.tilesAll+(p.correct ? 1u : 0u);
-    volatile unsigned *hostStatus = reinterpret_cast<volatile unsigned *>(a.pinned+p.hStatus);
+    volatile unsigned *hostStatus = reinterpret_cast<volatile unsigned *>(a.pinned.ptr+p.hStatus);
     if (zeroCopy)
         hostStatus[0] = hostStatus[1] = hostStatus[2] = 0;       // overflow / barrier flags are only ever RAISED by the kernel; [2]: the staging area is recycled, whatever sits there is not this call's flag
     else
-        HIPCHK(hipMemsetAsync(a.dev+p.hStatus, 0, 64, a.stream));
+        HIPCHK(hipMemsetAsync(a.dev.ptr+p.hStatus, 0, 64, a.stream));
     forSingleCallVariant(c.mode*2+(overlapEff ? 1 : 0), [&](auto sel, auto overlap) {
         hipLaunchKernelGGL((k_single_call<decltype(sel)::value, decltype(overlap)::value>), dim3(groups), dim3(WAVE*SINGLE_TEAM), single.lds, a.stream, sa);
     });
@@ -3316,7 +3121,7 @@ static int runFused(const GroupPlan &p, const SinglePlan &single, ThreadArena &a
             HIPCHK(hipStreamSynchronize(a.stream));
             if (hostStatus[2] != sa.doneValue) {
                 unsigned counters[32] = { 0 };
-                (void) hipMemcpy(counters, a.barrier, sizeof(counters), hipMemcpyDeviceToHost);
+                (void) hipMemcpy(counters, a.barrier.ptr, sizeof(counters), hipMemcpyDeviceToHost);
                 gSingleLost += 1;
                 if (tuning().singleVerbose)
                     fprintf(stderr, "msdfgen_hip: k_single_call ended without raising its completion flag (flag %u, expected %u; status %u %u; finished-workgroup "
@@ -3340,7 +3145,7 @@ static int runFused(const GroupPlan &p, const SinglePlan &single, ThreadArena &a
     if (abandoned) {                                             // the values on the device no longer match the epochs kept here: leave the counters as a fresh arena has them
         lease.quiescent = false;
         HIPCHK(hipStreamSynchronize(a.stream));
-        HIPCHK(hipMemsetAsync(a.barrier, 0, 256, a.stream));
+        HIPCHK(hipMemsetAsync(a.barrier.ptr, 0, 256, a.stream));
         a.barrierEpoch = a.doneCount = 0;
     }
     if (!abandoned && hostStatus[0] == 0)
@@ -3353,7 +3158,7 @@ static int runFused(const GroupPlan &p, const SinglePlan &single, ThreadArena &a
         ++gSingleCalls;
     }
     if (outcome == FUSED_RERUN && zeroCopy)                      // rerun through the batched sequence: it expects the inputs on the device
-        HIPCHK(hipMemcpyAsync(a.dev, a.pinned, p.inputBytes, hipMemcpyHostToDevice, a.stream));
+        HIPCHK(hipMemcpyAsync(a.dev.ptr, a.pinned.ptr, p.inputBytes, hipMemcpyHostToDevice, a.stream));
     return MSDFHIP_OK;
 }
 
@@ -3362,14 +3167,14 @@ static int runFused(const GroupPlan &p, const SinglePlan &single, ThreadArena &a
 // a distance check: pathological inputs only) the operation runs once more, with the per-texel overflow pass in its launch sequence -- an in-place correction
 // too: the input copy on the device is intact.
 static int runBatched(const GroupPlan &p, ThreadArena &a, MsdfHipBatch &b, const ShapeCall &c) {
-    const MsdfHipGlyph *dGlyph = reinterpret_cast<const MsdfHipGlyph *>(a.dev+p.hGlyph);
-    const float *dSrc = reinterpret_cast<const float *>(a.dev+p.hSrc);
-    float *dOut = reinterpret_cast<float *>(a.dev+p.hOut);
-    uint8_t *dStencil = p.anyStencil ? reinterpret_cast<uint8_t *>(a.dev+p.hStencil) : NULL;
+    const MsdfHipGlyph *dGlyph = reinterpret_cast<const MsdfHipGlyph *>(a.dev.ptr+p.hGlyph);
+    const float *dSrc = reinterpret_cast<const float *>(a.dev.ptr+p.hSrc);
+    float *dOut = reinterpret_cast<float *>(a.dev.ptr+p.hOut);
+    uint8_t *dStencil = p.anyStencil ? reinterpret_cast<uint8_t *>(a.dev.ptr+p.hStencil) : NULL;
     int rc = digest(&b, a.stream);
     for (int attempt = 0; rc == MSDFHIP_OK && attempt < 2; ++attempt) {   // mirrored, then with the overflow pass
         GenerateCall call;
-        call.overflowOut = attempt == 0 ? reinterpret_cast<unsigned *>(a.dev+p.hStatus) : NULL;
+        call.overflowOut = attempt == 0 ? reinterpret_cast<unsigned *>(a.dev.ptr+p.hStatus) : NULL;
         if (c.op == OP_ERROR_CORRECTION)
             rc = runCorrection(&b, c.channels, c.w, c.h, dGlyph, dSrc, dOut, dStencil, c.cfg, a.stream, call);
         else if (c.op == OP_SIGN_CORRECTION)
@@ -3377,12 +3182,12 @@ static int runBatched(const GroupPlan &p, ThreadArena &a, MsdfHipBatch &b, const
         else if (c.op == OP_RASTERIZE)
             rc = runSignCorrection(&b, 1, c.w, c.h, dGlyph, NULL, dOut, 0, 0.f, c.cfg.fill_rule, a.stream);
         else if (c.op == OP_GENERATE_LEGACY)                     // (c.cfg is a legacyConfig: msdfhip_generate_legacy)
-            rc = runGenerateLegacy(&b, c.mode, c.w, c.h, dGlyph, dOut, dStencil, p.stages ? reinterpret_cast<float *>(a.dev+p.dScratch) : NULL, c.cfg, a.stream, call);
+            rc = runGenerateLegacy(&b, c.mode, c.w, c.h, dGlyph, dOut, dStencil, p.stages ? reinterpret_cast<float *>(a.dev.ptr+p.dScratch) : NULL, c.cfg, a.stream, call);
         else
-            rc = runGenerate(&b, c.mode, c.w, c.h, dGlyph, dOut, dStencil, p.stages ? reinterpret_cast<float *>(a.dev+p.dScratch) : NULL, &c.cfg, a.stream, call);
+            rc = runGenerate(&b, c.mode, c.w, c.h, dGlyph, dOut, dStencil, p.stages ? reinterpret_cast<float *>(a.dev.ptr+p.dScratch) : NULL, &c.cfg, a.stream, call);
         if (rc == MSDFHIP_OK)
             rc = copyBackAndWait(p, a);
-        if (!(call.overflowMirrored && *reinterpret_cast<const unsigned *>(a.pinned+p.hStatus) != 0))
+        if (!(call.overflowMirrored && *reinterpret_cast<const unsigned *>(a.pinned.ptr+p.hStatus) != 0))
             break;
     }
     return rc;
@@ -3393,11 +3198,11 @@ static void scatterGroup(const GroupPlan &p, ThreadArena &a, ShapeCall *const *c
     const int channels = calls[0]->channels, w = calls[0]->w, h = calls[0]->h;
     for (int g = 0; g < n; ++g) {
         const ShapeCall &c = *calls[g];
-        const float *tile = reinterpret_cast<const float *>(a.pinned+p.hOut)+(size_t) g*p.texels*channels;
+        const float *tile = reinterpret_cast<const float *>(a.pinned.ptr+p.hOut)+(size_t) g*p.texels*channels;
         for (int y = 0; y < h; ++y)
             memcpy(c.pixels+(ptrdiff_t) c.rowStride*y, tile+(size_t) y*w*channels, sizeof(float)*(size_t) w*channels);
         if (c.stencil && p.anyStencil)
-            memcpy(c.stencil, a.pinned+p.hStencil+(size_t) g*p.texels, p.texels);
+            memcpy(c.stencil, a.pinned.ptr+p.hStencil+(size_t) g*p.texels, p.texels);
     }
 }
 
@@ -3408,11 +3213,11 @@ static int runGroup(ShapeCall *const *calls, int n) {
     if (rc != MSDFHIP_OK)
         return rc;
     const GroupPlan plan = planGroup(calls, n);
-    ArenaLease lease;
-    rc = lease.take(currentDevice());
+    ArenaHold lease;
+    rc = takeArena(lease);
     if (rc != MSDFHIP_OK)
         return rc;
-    ThreadArena &a = *lease.a;
+    ThreadArena &a = *lease;
     rc = arenaReserve(a, plan.devBytes, plan.pinnedBytes);
     if (rc != MSDFHIP_OK)
         return rc;
@@ -3437,11 +3242,11 @@ static int runGroup(ShapeCall *const *calls, int n) {
     if (zeroCopy) {
         // (nothing to upload)
     } else if (plan.inputBytes <= ((size_t) 1<<20)) {            // a few KB: read from the pinned staging by a kernel -- no SDMA submission on the latency path
-        rc = uploadSmall(a.dev, a.pinned, plan.inputBytes, a.stream);
+        rc = uploadSmall(a.dev.ptr, a.pinned.ptr, plan.inputBytes, a.stream);
         if (rc != MSDFHIP_OK)
             return rc;
     } else
-        HIPCHK(hipMemcpyAsync(a.dev, a.pinned, plan.inputBytes, hipMemcpyHostToDevice, a.stream));
+        HIPCHK(hipMemcpyAsync(a.dev.ptr, a.pinned.ptr, plan.inputBytes, hipMemcpyHostToDevice, a.stream));
 
     MsdfHipBatch b;
     buildView(plan, a, calls, n, b);
@@ -3614,25 +3419,25 @@ int msdfhip_render_sdf_host(float *out, int ow, int oh, int outStride, int no, c
     const size_t inBytes = sizeof(float)*(size_t) sw*sh*ns, outBytes = sizeof(float)*(size_t) ow*oh*no;
     Carver c;
     const size_t offIn = c.take(inBytes), offOut = c.take(outBytes);
-    ArenaLease lease;
-    rc = lease.take(currentDevice());
+    ArenaHold lease;
+    rc = takeArena(lease);
     if (rc != MSDFHIP_OK)
         return rc;
-    ThreadArena &a = *lease.a;
+    ThreadArena &a = *lease;
     rc = arenaReserve(a, c.off, c.off);
     if (rc != MSDFHIP_OK)
         return rc;
     for (int y = 0; y < sh; ++y)
-        memcpy(a.pinned+offIn+sizeof(float)*(size_t) y*sw*ns, sdf+(ptrdiff_t) sdfStride*y, sizeof(float)*(size_t) sw*ns);
-    HIPCHK(hipMemcpyAsync(a.dev+offIn, a.pinned+offIn, inBytes, hipMemcpyHostToDevice, a.stream));
-    rc = msdfhip_render_sdf(reinterpret_cast<const float *>(a.dev+offIn), 1, sw, sh, ns, reinterpret_cast<float *>(a.dev+offOut), ow, oh, no,
+        memcpy(a.pinned.ptr+offIn+sizeof(float)*(size_t) y*sw*ns, sdf+(ptrdiff_t) sdfStride*y, sizeof(float)*(size_t) sw*ns);
+    HIPCHK(hipMemcpyAsync(a.dev.ptr+offIn, a.pinned.ptr+offIn, inBytes, hipMemcpyHostToDevice, a.stream));
+    rc = msdfhip_render_sdf(reinterpret_cast<const float *>(a.dev.ptr+offIn), 1, sw, sh, ns, reinterpret_cast<float *>(a.dev.ptr+offOut), ow, oh, no,
                             rangeLower, rangeUpper, sdThreshold, a.stream);
     if (rc != MSDFHIP_OK)
         return rc;
-    HIPCHK(hipMemcpyAsync(a.pinned+offOut, a.dev+offOut, outBytes, hipMemcpyDeviceToHost, a.stream));
+    HIPCHK(hipMemcpyAsync(a.pinned.ptr+offOut, a.dev.ptr+offOut, outBytes, hipMemcpyDeviceToHost, a.stream));
     HIPCHK(hipStreamSynchronize(a.stream));
     for (int y = 0; y < oh; ++y)
-        memcpy(out+(ptrdiff_t) outStride*y, a.pinned+offOut+sizeof(float)*(size_t) y*ow*no, sizeof(float)*(size_t) ow*no);
+        memcpy(out+(ptrdiff_t) outStride*y, a.pinned.ptr+offOut+sizeof(float)*(size_t) y*ow*no, sizeof(float)*(size_t) ow*no);
     return MSDFHIP_OK;
 }
 
@@ -3647,24 +3452,24 @@ int msdfhip_simulate_8bit_host(float *pixels, int w, int h, int rowStride, int c
     if (rc != MSDFHIP_OK)
         return rc;
     const size_t bytes = sizeof(float)*(size_t) w*h*channels;
-    ArenaLease lease;
-    rc = lease.take(currentDevice());
+    ArenaHold lease;
+    rc = takeArena(lease);
     if (rc != MSDFHIP_OK)
         return rc;
-    ThreadArena &a = *lease.a;
+    ThreadArena &a = *lease;
     rc = arenaReserve(a, bytes, bytes);
     if (rc != MSDFHIP_OK)
         return rc;
     for (int y = 0; y < h; ++y)
-        memcpy(a.pinned+sizeof(float)*(size_t) y*w*channels, pixels+(ptrdiff_t) rowStride*y, sizeof(float)*(size_t) w*channels);
-    HIPCHK(hipMemcpyAsync(a.dev, a.pinned, bytes, hipMemcpyHostToDevice, a.stream));
-    rc = msdfhip_simulate_8bit(reinterpret_cast<float *>(a.dev), (size_t) w*h*channels, a.stream);
+        memcpy(a.pinned.ptr+sizeof(float)*(size_t) y*w*channels, pixels+(ptrdiff_t) rowStride*y, sizeof(float)*(size_t) w*channels);
+    HIPCHK(hipMemcpyAsync(a.dev.ptr, a.pinned.ptr, bytes, hipMemcpyHostToDevice, a.stream));
+    rc = msdfhip_simulate_8bit(reinterpret_cast<float *>(a.dev.ptr), (size_t) w*h*channels, a.stream);
     if (rc != MSDFHIP_OK)
         return rc;
-    HIPCHK(hipMemcpyAsync(a.pinned, a.dev, bytes, hipMemcpyDeviceToHost, a.stream));
+    HIPCHK(hipMemcpyAsync(a.pinned.ptr, a.dev.ptr, bytes, hipMemcpyDeviceToHost, a.stream));
     HIPCHK(hipStreamSynchronize(a.stream));
     for (int y = 0; y < h; ++y)
-        memcpy(pixels+(ptrdiff_t) rowStride*y, a.pinned+sizeof(float)*(size_t) y*w*channels, sizeof(float)*(size_t) w*channels);
+        memcpy(pixels+(ptrdiff_t) rowStride*y, a.pinned.ptr+sizeof(float)*(size_t) y*w*channels, sizeof(float)*(size_t) w*channels);
     return MSDFHIP_OK;
 }
 
@@ -3701,25 +3506,25 @@ int msdfhip_error_correction_legacy(int channels, float *pixels, int w, int h, i
     const size_t rowBytes = sizeof(float)*(size_t) w*channels, bytes = rowBytes*h;
     Carver c;
     const size_t offTiles = c.take(bytes), offScratch = c.take(bytes);
-    ArenaLease lease;
-    rc = lease.take(currentDevice());
+    ArenaHold lease;
+    rc = takeArena(lease);
     if (rc != MSDFHIP_OK)
         return rc;
-    ThreadArena &a = *lease.a;
+    ThreadArena &a = *lease;
     rc = arenaReserve(a, c.off, bytes);
     if (rc != MSDFHIP_OK)
         return rc;
     for (int y = 0; y < h; ++y)
-        memcpy(a.pinned+rowBytes*y, pixels+(ptrdiff_t) rowStride*y, rowBytes);
-    HIPCHK(hipMemcpyAsync(a.dev+offTiles, a.pinned, bytes, hipMemcpyHostToDevice, a.stream));
-    rc = launchLegacyCorrection(reinterpret_cast<float *>(a.dev+offTiles), reinterpret_cast<float *>(a.dev+offScratch), 1, w, h, channels, thresholdX, thresholdY,
+        memcpy(a.pinned.ptr+rowBytes*y, pixels+(ptrdiff_t) rowStride*y, rowBytes);
+    HIPCHK(hipMemcpyAsync(a.dev.ptr+offTiles, a.pinned.ptr, bytes, hipMemcpyHostToDevice, a.stream));
+    rc = launchLegacyCorrection(reinterpret_cast<float *>(a.dev.ptr+offTiles), reinterpret_cast<float *>(a.dev.ptr+offScratch), 1, w, h, channels, thresholdX, thresholdY,
                                 a.stream);
     if (rc != MSDFHIP_OK)
         return rc;
-    HIPCHK(hipMemcpyAsync(a.pinned, a.dev+offTiles, bytes, hipMemcpyDeviceToHost, a.stream));
+    HIPCHK(hipMemcpyAsync(a.pinned.ptr, a.dev.ptr+offTiles, bytes, hipMemcpyDeviceToHost, a.stream));
     HIPCHK(hipStreamSynchronize(a.stream));
     for (int y = 0; y < h; ++y)
-        memcpy(pixels+(ptrdiff_t) rowStride*y, a.pinned+rowBytes*y, rowBytes);
+        memcpy(pixels+(ptrdiff_t) rowStride*y, a.pinned.ptr+rowBytes*y, rowBytes);
     return MSDFHIP_OK;
 }
 
@@ -3831,12 +3636,12 @@ int msdfhip_shape_distance(int selector, int overlap, const int32_t *co, int nC,
     int rc = msdfhip_batch_create(&b, 1, gco, co, points, types, colors);
     if (rc != MSDFHIP_OK)
         return rc;
+    const std::unique_ptr<MsdfHipBatch, void (*)(MsdfHipBatch *)> batch(b, msdfhip_batch_destroy);
     const int nch = channelsOf(selector);
     size_t lds = overlap ? (size_t) b->maxContours*nch*WAVE*sizeof(double) : 0;
-    double *dPts = NULL, *dOut = NULL, *gres = NULL;
+    double *gres = NULL;
     size_t gresStride = 0;
     int chunkPoints = nPoints;
-    hipError_t e = hipSuccess;
     if (lds > (size_t) gLdsLimit.load()) {                       // more contours than a CU's LDS holds scratch for: a global workspace slice per workgroup
         gresStride = lds/sizeof(double);
         size_t groups = (size_t) (nPoints+WAVE-1)/WAVE;
@@ -3844,20 +3649,21 @@ int msdfhip_shape_distance(int selector, int overlap, const int32_t *co, int nC,
             groups = ((size_t) 2<<30)/lds > 0 ? ((size_t) 2<<30)/lds : 1;
         chunkPoints = (int) (groups*WAVE < (size_t) nPoints ? groups*WAVE : (size_t) nPoints);
         rc = ensureGres(b, groups*lds, &gres);
+        if (rc != MSDFHIP_OK)
+            return rc;
         lds = 0;
     }
-    if (rc == MSDFHIP_OK) {
-        e = hipMalloc((void **) &dPts, sizeof(double)*2*(size_t) nPoints);
-        if (e == hipSuccess) e = hipMalloc((void **) &dOut, sizeof(double)*4*(size_t) nPoints);
-        if (e == hipSuccess) e = hipMemcpy(dPts, pts, sizeof(double)*2*(size_t) nPoints, hipMemcpyHostToDevice);
-    }
-    if (rc == MSDFHIP_OK && e == hipSuccess) {
+    WorkBuffer<double> dPts, dOut;                               // (freed before the batch, on its device)
+    hipError_t e = dPts.ensure(2*(size_t) nPoints);
+    if (e == hipSuccess) e = dOut.ensure(4*(size_t) nPoints);
+    if (e == hipSuccess) e = hipMemcpy(dPts.ptr, pts, sizeof(double)*2*(size_t) nPoints, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
         const dim3 block(WAVE);
         const BatchView v = viewOf(b);
         #define LAUNCH_SD(S, O) do { rc = setLds(k_shape_distance<S, O>, lds); \
             for (int base = 0; rc == MSDFHIP_OK && base < nPoints; base += chunkPoints) { \
                 const int n = nPoints-base < chunkPoints ? nPoints-base : chunkPoints; \
-                hipLaunchKernelGGL((k_shape_distance<S, O>), dim3((n+WAVE-1)/WAVE), block, lds, 0, v, n, dPts+2*(size_t) base, dOut+4*(size_t) base, gres, gresStride); \
+                hipLaunchKernelGGL((k_shape_distance<S, O>), dim3((n+WAVE-1)/WAVE), block, lds, 0, v, n, dPts.ptr+2*(size_t) base, dOut.ptr+4*(size_t) base, gres, gresStride); \
             } } while (0)
         switch (selector*2+(overlap ? 1 : 0)) {
             case 2: LAUNCH_SD(1, false); break;
@@ -3870,17 +3676,15 @@ int msdfhip_shape_distance(int selector, int overlap, const int32_t *co, int nC,
             default: LAUNCH_SD(4, true); break;
         }
         #undef LAUNCH_SD
-        if (rc == MSDFHIP_OK) {
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(NULL);
-            if (e == hipSuccess) e = hipMemcpy(out, dOut, sizeof(double)*4*(size_t) nPoints, hipMemcpyDeviceToHost);
-        }
+        if (rc != MSDFHIP_OK)
+            return rc;
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(NULL);
+        if (e == hipSuccess) e = hipMemcpy(out, dOut.ptr, sizeof(double)*4*(size_t) nPoints, hipMemcpyDeviceToHost);
     }
-    hipFree(dPts), hipFree(dOut);
-    msdfhip_batch_destroy(b);
     if (e != hipSuccess)
         return fail(MSDFHIP_ERR_HIP, "msdfhip_shape_distance: %s", hipGetErrorString(e));
-    return rc;
+    return MSDFHIP_OK;
 }
 
 // -------------------------------------------------------------------------------------------------------- timing hook
@@ -3889,35 +3693,8 @@ int msdfhip_shape_distance(int selector, int overlap, const int32_t *co, int nC,
 // call: ~100-200 MB of device + pinned memory each) only ever grow to the PEAK concurrency. A long-lived process that is done with a
 // burst returns them here; resources of calls in flight are not in the pools and stay untouched.
 int msdfhip_trim(void) {
-    std::vector<ThreadArena *> arenas;
-    std::vector<Pipe *> pipes;
-    {
-        std::lock_guard<std::mutex> lock(gArenaMutex);
-        arenas.swap(gArenaPool);
-    }
-    {
-        std::lock_guard<std::mutex> lock(gPipeMutex);
-        pipes.swap(gPipePool);
-    }
-    int prev = 0;
-    (void) hipGetDevice(&prev);
-    for (size_t i = 0; i < arenas.size(); ++i) {
-        ThreadArena *a = arenas[i];
-        (void) hipSetDevice(a->device);
-        if (a->stream)
-            (void) hipStreamSynchronize(a->stream);
-        hipFree(a->dev);
-        hipFree(a->barrier);
-        if (a->pinned)
-            pinnedFree(a->pinned);
-        if (a->stream)
-            hipStreamDestroy(a->stream);
-        delete a;
-    }
-    for (size_t i = 0; i < pipes.size(); ++i)
-        destroyPipe(pipes[i]);
-    (void) hipSetDevice(prev);
-    (void) hipGetLastError();
+    gArenaPool.drain();
+    gPipePool.drain();
     return MSDFHIP_OK;
 }
 
