@@ -225,6 +225,18 @@ int msdfhip_batch_windings(const MsdfHipBatch *batch, int32_t *windings);
  * stream at a time. Different batches, and the single-shape entry points above, are independent of each other. */
 int msdfhip_batch_generate(const MsdfHipBatch *batch, int mode, int width, int height, const MsdfHipGlyph *d_glyphs,
                            float *d_out, uint8_t *d_stencil, float *d_scratch, const MsdfHipConfig *cfg, void *stream);
+/* msdfhip_batch_generate with a bitmap size PER GLYPH (a tightly packed atlas: every glyph's box is its bounds plus the pixel range).
+ * sizes: HOST int32[n_glyphs*2] = w_g, h_g, each >= 1. Glyph g is generated as a w_g x h_g bitmap at d_out + d_glyphs[g].out_offset with
+ * d_glyphs[g].row_stride; flip reverses ITS h_g rows. With W = max w_g, H = max h_g, "slot" = W*H texels:
+ *   d_scratch  as msdfhip_batch_generate for a W x H call (n_glyphs*slot*N floats per intermediate field); glyph g's intermediate field is PACKED
+ *              [h_g][w_g][N] at the start of slot g
+ *   d_stencil  NULL or n_glyphs*slot bytes; glyph g's stencil is w_g*h_g bytes packed at g*slot, rows as msdfhip_batch_generate defines them
+ * The result per glyph is what msdfhip_batch_generate writes for that glyph at width = w_g, height = h_g, the behaviour of the correction and sign
+ * passes at the box's own borders included; the launches are those of a W x H call (same routes), workgroups outside a glyph's box leave at once.
+ * The sizes are read before the call returns (the batch keeps its own device copy, ordered on `stream` in front of the first launch).
+ * Fails with MSDFHIP_ERR_INVALID before the device is touched on sizes == NULL, any w_g, h_g < 1, or n_glyphs*slot beyond the 32-bit texel index. */
+int msdfhip_batch_generate_sized(const MsdfHipBatch *batch, int mode, const int32_t *sizes, const MsdfHipGlyph *d_glyphs,
+                                 float *d_out, uint8_t *d_stencil, float *d_scratch, const MsdfHipConfig *cfg, void *stream);
 /* The legacy generators (msdfhip_generate_legacy above) for every glyph of the batch; arguments, scratch size and stream as msdfhip_batch_generate,
  * `cfg` read as msdfhip_generate_legacy reads it. The call leaves nothing on the batch that a later msdfhip_batch_generate would rely on. */
 int msdfhip_batch_generate_legacy(const MsdfHipBatch *batch, int mode, int width, int height, const MsdfHipGlyph *d_glyphs,
@@ -399,6 +411,11 @@ int msdfhip_batch_download(const MsdfHipBatch *batch, int32_t *contour_offsets, 
  * Asynchronous on `stream`. The device-to-host copy of an 8-bit atlas is a quarter of the float tiles'. */
 int msdfhip_tiles_to_bytes(const float *d_tiles, int n_glyphs, int width, int height, int channels, const MsdfHipGlyph *d_glyphs,
                            uint8_t *d_atlas, void *stream);
+/* msdfhip_tiles_to_bytes for boxes: d_tiles holds glyph g packed [h_g][w_g][channels] at float offset tile_offsets[g] (HOST int64[n_glyphs]);
+ * sizes as msdfhip_batch_generate_sized (HOST int32[n_glyphs*2], validated the same way before the device is touched). The conversion is ordered on
+ * `stream`; the call returns when it has run (the device copy of the two host arrays lives for the call: there is no batch to keep it). */
+int msdfhip_tiles_to_bytes_sized(const float *d_tiles, int n_glyphs, const int32_t *sizes, const int64_t *tile_offsets, int channels,
+                                 const MsdfHipGlyph *d_glyphs, uint8_t *d_atlas, void *stream);
 
 /* estimateSDFError(sdf, shape, projection, scanlinesPerRow, fillRule) for every glyph of a batch: d_errors[g] from the
  * packed tiles d_tiles[g][h][w][channels] (memory rows; what msdfhip_batch_generate wrote), without leaving the device.

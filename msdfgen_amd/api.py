@@ -631,6 +631,94 @@ class GlyphBatch:
                                                       stencil.data_ptr() if stencil is not None else None, scratch_ptr, C.byref(cfg), s))
         return out
 
+    # ---- a bitmap size per glyph (msdfhip_batch_generate_sized): the boxes of a tightly packed atlas in ONE call
+
+    def _sizes(self, sizes):
+        sizes = np.ascontiguousarray(sizes, np.int32).reshape(self.n_glyphs, 2)
+        if self.n_glyphs and sizes.min() < 1:
+            raise ValueError("every box must be at least 1 x 1")
+        return sizes
+
+    @staticmethod
+    def packed_offsets(sizes, channels):
+        """Float offsets of tiles packed one after another: glyph g at sum_{k<g} w_k*h_k*channels; (G+1,) int64, the last entry = all floats."""
+        sizes = np.asarray(sizes, np.int64).reshape(-1, 2)
+        return np.concatenate([[0], np.cumsum(sizes[:, 0]*sizes[:, 1]*channels)]).astype(np.int64)
+
+    def descriptors_sized(self, xfs, sizes, channels, y_orientation=Y_UPWARD, out_offsets=None, row_strides=None):
+        """descriptors() for per-glyph boxes: sizes (G, 2) rows w_g, h_g. Default placement: tiles packed one after another, glyph g [h_g][w_g][N] at
+        packed_offsets(sizes, channels)[g] with row stride w_g*N; or an atlas placement via out_offsets / row_strides (per glyph, in floats, may be negative)."""
+        sizes = self._sizes(sizes)
+        d = np.zeros(self.n_glyphs, _lib.GLYPH_DTYPE)
+        if xfs is not None:
+            xfs = np.ascontiguousarray(xfs, np.float64).reshape(self.n_glyphs, 6)
+            d["xf"][:, :4] = xfs[:, :4]
+            d["xf"][:, 4] = np.float64(1)/(xfs[:, 5]-xfs[:, 4])  # DistanceMapping.cpp:13
+            d["xf"][:, 5] = -xfs[:, 4]
+        d["out_offset"] = self.packed_offsets(sizes, channels)[:-1] if out_offsets is None else np.asarray(out_offsets, np.int64)
+        d["row_stride"] = sizes[:, 0].astype(np.int64)*channels if row_strides is None else np.asarray(row_strides, np.int64)
+        d["flip"] = (self.shapes.inverse_y.astype(bool) != (y_orientation == Y_DOWNWARD)).astype(np.int32)
+        return self.torch.from_numpy(d.view(np.uint8).reshape(self.n_glyphs, 64)).to(self.device)
+
+    def generate_sized(self, mode, sizes, xfs=None, config=None, out=None, stencil=None, descriptors=None, stream=None, y_orientation=Y_UPWARD,
+                       scanline_pass=False, fill_rule=FILL_NONZERO, sdf_zero_value=.5):
+        """generate() with a bitmap size per glyph: sizes (G, 2) rows w_g, h_g; glyph g comes out as the reference renders it into a w_g x h_g bitmap.
+        Returns (out, offsets): the flat float32 device tensor and the (G+1,) packed float offsets -- glyph g is out[offsets[g]:offsets[g+1]] viewed
+        (h_g, w_g, N) -- unless `descriptors` place the boxes elsewhere in `out` (then `out` must be given; the offsets are still the packed ones).
+        stencil: a uint8 device tensor of G*W*H bytes with W, H the largest width and height; glyph g's w_g*h_g bytes are packed at g*W*H."""
+        torch = self.torch
+        n = CHANNELS[mode]
+        sizes = self._sizes(sizes)
+        offsets = self.packed_offsets(sizes, n)
+        if descriptors is None:
+            descriptors = self.descriptors_sized(xfs, sizes, n, y_orientation)
+        elif out is None:
+            raise ValueError("descriptors place the boxes in `out`: pass it")
+        if out is None:
+            out = torch.empty(int(offsets[-1]), dtype=torch.float32, device=self.device)
+        cfg = _c_config(config if config is not None else (MSDFGeneratorConfig() if mode >= 3 else GeneratorConfig()), y_orientation)
+        _with_scanline_pass(cfg, scanline_pass, fill_rule, sdf_zero_value)
+        slot = int(sizes[:, 0].max())*int(sizes[:, 1].max()) if self.n_glyphs else 0
+        if stencil is not None and (stencil.dtype != torch.uint8 or stencil.numel() < self.n_glyphs*slot):
+            raise ValueError("stencil must hold G*W*H bytes (W, H: the largest width and height)")
+        scratch_ptr = None
+        stages = int(mode >= 3 and cfg.ec_mode != EC_DISABLED)+int(bool(scanline_pass))   # intermediate fields: slots of W*H texels, msdfgen_hip.h
+        if stages:
+            need = stages*self.n_glyphs*slot*n
+            if self._scratch is None or self._scratch.numel() < need:
+                self._scratch = torch.empty(need, dtype=torch.float32, device=self.device)
+            scratch_ptr = self._scratch.data_ptr()
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        _lib.check(_lib.load().msdfhip_batch_generate_sized(self._handle, mode, _lib.ptr(sizes, _lib._ip), descriptors.data_ptr(), out.data_ptr(),
+                                                            stencil.data_ptr() if stencil is not None else None, scratch_ptr, C.byref(cfg), s))
+        return out, offsets
+
+    def to_bytes_sized(self, tiles, sizes, channels, atlas, out_offsets, row_strides, tile_offsets=None, stream=None):
+        """to_bytes() for boxes: `tiles` is the flat float32 device tensor of generate_sized (glyph g packed [h_g][w_g][channels] at tile_offsets[g],
+        default the packed offsets); glyph g's rectangle goes to the uint8 device tensor `atlas` at byte offset out_offsets[g] with row_strides[g]
+        bytes per row (a scalar or one per glyph; may be negative). Returns `atlas`."""
+        torch = self.torch
+        sizes = self._sizes(sizes)
+        g = self.n_glyphs
+        assert tiles.dtype == torch.float32 and tiles.is_contiguous() and atlas.dtype == torch.uint8
+        toff = np.ascontiguousarray(self.packed_offsets(sizes, channels)[:-1] if tile_offsets is None else tile_offsets, np.int64)
+        d = np.zeros(g, _lib.GLYPH_DTYPE)
+        d["out_offset"] = np.asarray(out_offsets, np.int64)
+        d["row_stride"] = np.asarray(row_strides, np.int64)
+        if g:
+            w, h = sizes[:, 0].astype(np.int64), sizes[:, 1].astype(np.int64)
+            last = d["out_offset"]+d["row_stride"].astype(np.int64)*(h-1)
+            lo, hi = np.minimum(d["out_offset"], last), np.maximum(d["out_offset"], last)+w*channels
+            if int(lo.min()) < 0 or int(hi.max()) > atlas.numel():
+                raise ValueError("a glyph rectangle lies outside the atlas")
+            if int(toff.min()) < 0 or int((toff+w*h*channels).max()) > tiles.numel():
+                raise ValueError("a glyph's tile lies outside `tiles`")
+        desc = torch.from_numpy(d.view(np.uint8).reshape(g, 64)).to(self.device)
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        _lib.check(_lib.load().msdfhip_tiles_to_bytes_sized(tiles.data_ptr(), g, _lib.ptr(sizes, _lib._ip), toff.ctypes.data_as(C.POINTER(C.c_int64)), int(channels),
+                                                            desc.data_ptr(), atlas.data_ptr(), s))
+        return atlas
+
     def generate_legacy(self, mode, width, height, xfs=None, config=None, out=None, stencil=None, descriptors=None, stream=None, y_orientation=Y_UPWARD,
                         scanline_pass=False, fill_rule=FILL_NONZERO, sdf_zero_value=.5, frame: Optional["FrameConfig"] = None):
         """The legacy generators (generateSDF_legacy ... generateMTSDF_legacy, core/msdfgen.cpp:166-333) for every glyph of the batch; arguments and result

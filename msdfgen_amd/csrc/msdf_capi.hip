@@ -31,6 +31,7 @@
 #include "msdf_prepplan.hpp"
 #include "msdf_resources.hpp"
 #include "msdf_single.hpp"
+#include "msdf_sizedplan.hpp"
 
 using namespace msdfhip;
 
@@ -236,6 +237,9 @@ struct Workspace {
     WorkBuffer<int, true> hEcOrder;   // (pinned host copy it is uploaded from)
     Event ecOrderReady;               // (recorded behind that upload)
     bool ecOrderTried = false;
+    WorkBuffer<int32_t> boxDims;      // msdfhip_batch_generate_sized: w_g, h_g per glyph, uploaded per call on the call's stream in front of its first launch
+    WorkBuffer<int32_t, true> hBoxDims;   // (pinned host copy it is uploaded from)
+    Event boxDimsRead;                // (recorded behind that upload: the next call waits for it before it rewrites hBoxDims)
     Stream sideStream[2];             // the three glyph classes of the distance pass run concurrently: two of them on these (fork / join by events)
     Event forkEvent, joinEvent[2];
 
@@ -297,6 +301,7 @@ struct GenerateCall {
     hipEvent_t afterDistance = NULL;  // host-output pipeline: recorded on the call's stream between the distance pass and what follows it (NULL: not wanted)
     unsigned *overflowOut = NULL;     // pipeline chunks, single-shape calls: where k_ec_query mirrors the candidate-overflow count (then no k_ec_slow launch)
     bool overflowMirrored = false;    // out: the correction pass did so
+    const int32_t *boxDims = NULL;    // msdfhip_batch_generate_sized: the device copy of the per-glyph box sizes (w, h below are then the slot's W, H); the sized kernels launch
 };
 
 BatchView viewOf(const MsdfHipBatch *b) {
@@ -428,8 +433,36 @@ int ensureGres(const MsdfHipBatch *b, size_t bytes, double **out) {
     return MSDFHIP_OK;
 }
 
+// The sized twins of the generate kernels (msdfhip_batch_generate_sized), by the template arguments of their uniform siblings as plain integers. Plain functions
+// defined at the END of this file: nothing in front of them names a twin, so the twins are instantiated behind every kernel the code object has always held
+// (forDistanceVariant: the order of the instantiations matters). All instantiations of one kernel template share a signature, hence one pointer type each.
+typedef void (*DistanceSizedKernel)(int, const int32_t *, const int32_t *, const EdgeRec *, const int8_t *, const MsdfHipGlyph *, int, int, int, int, int, float *, int, unsigned,
+                                    double *, size_t, const int *, int, unsigned *, unsigned, const int32_t *);
+typedef void (*UnculledSizedKernel)(int, const int32_t *, const int32_t *, const EdgeRec *, const int8_t *, const MsdfHipGlyph *, int, int, int, int, float *, int, double *, size_t,
+                                    unsigned *, unsigned, const int *, const int32_t *);
+typedef void (*EcSlowSizedKernel)(BatchView, const MsdfHipGlyph *, int, int, const float *, float *, uint8_t *, MsdfHipConfig, const EcCandidate *, unsigned, int, double *, size_t,
+                                  const int32_t *);
+typedef void (*EcFastSizedKernel)(BatchView, const MsdfHipGlyph *, int, int, int, int, const float *, float *, uint8_t *, MsdfHipConfig, const EcGlyphParams *, EcCandidate *,
+                                  unsigned, int, const int *, const int32_t *);
+typedef void (*EcQuerySizedKernel)(int, const int32_t *, const int32_t *, const EdgeRec *, const int8_t *, const MsdfHipGlyph *, int, int, const float *, float *, uint8_t *,
+                                   MsdfHipConfig, const EcGlyphParams *, const EcCandidate *, unsigned, const int *, int *, int, int, int, EcQueryPolicy, unsigned *, const int *,
+                                   int, const int32_t *);
+typedef void (*SignSizedKernel)(BatchView, const MsdfHipGlyph *, int, int, int, int, int, int, const float *, float *, int, float, int, int, const int32_t *);
+DistanceSizedKernel distanceSizedKernel(int sel, bool overlap, bool gres, int tpw);
+UnculledSizedKernel unculledSizedKernel(int sel, bool overlap);
+EcSlowSizedKernel ecSlowSizedKernel(int n, bool overlap, bool gres);
+EcFastSizedKernel ecFastSizedKernel(int n, bool lazy);
+EcQuerySizedKernel ecQuerySizedKernel(int n, bool overlap);
+SignSizedKernel signSizedKernel(int n);
+
 template <int SEL, bool OVERLAP, bool GRES, int TPW_>
-void launchDistanceKernel(unsigned grid, size_t lds, hipStream_t stream, const DistanceArgs &a) {
+void launchDistanceKernel(unsigned grid, size_t lds, hipStream_t stream, const DistanceArgs &a, const int32_t *dDims = NULL) {
+    if (dDims) {
+        hipLaunchKernelGGL(distanceSizedKernel(SEL, OVERLAP, GRES, TPW_), dim3(grid), dim3(WAVE), lds, stream, a.batch.nGlyphs, a.batch.glyphContourOffsets, a.batch.contourOffsets,
+                           a.batch.recs, a.batch.windings, a.glyphs, a.width, a.height, a.tilesX, a.tilesPerGlyph, a.maxEdges, a.dst, a.toScratch, a.blockBase, a.gres,
+                           a.gresStride, a.glyphMap, a.nMapped, a.workQueue, a.workItems, dDims);
+        return;
+    }
     hipLaunchKernelGGL((k_distance<SEL, OVERLAP, GRES, TPW_>), dim3(grid), dim3(WAVE), lds, stream, a.batch.nGlyphs, a.batch.glyphContourOffsets, a.batch.contourOffsets,
                        a.batch.recs, a.batch.windings, a.glyphs, a.width, a.height, a.tilesX, a.tilesPerGlyph, a.maxEdges, a.dst, a.toScratch, a.blockBase, a.gres,
                        a.gresStride, a.glyphMap, a.nMapped, a.workQueue, a.workItems);
@@ -438,13 +471,13 @@ void launchDistanceKernel(unsigned grid, size_t lds, hipStream_t stream, const D
 // One planned launch of the distance pass (msdf_launchplan.hpp: planDistance); counts its route once it is issued.
 template <int SEL, bool OVERLAP, bool GRES, int TPW_>
 int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, float *dst, int toScratch, const DistanceLaunch &l, const PlanEnv &env,
-                   hipStream_t stream) {
+                   hipStream_t stream, const int32_t *dDims = NULL) {
     const size_t blocks = distanceBlocks(l.count, w, h, TPW_);
     if (blocks == 0)
         return MSDFHIP_OK;
     if (blocks > 0x7fffffffull)
         return fail(MSDFHIP_ERR_INVALID, "launch of %zu tile quads exceeds the grid limit; split the batch", blocks);
-    int rc = setLds(k_distance<SEL, OVERLAP, GRES, TPW_>, l.lds.bytes);
+    int rc = dDims ? setLds(distanceSizedKernel(SEL, OVERLAP, GRES, TPW_), l.lds.bytes) : setLds(k_distance<SEL, OVERLAP, GRES, TPW_>, l.lds.bytes);
     if (rc != MSDFHIP_OK)
         return rc;
     const GridPlan grid = gridOf(l, w, h, env);
@@ -470,13 +503,13 @@ int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
         std::lock_guard<std::mutex> lock(b->work.mutex);
         args.workQueue = queue+(b->work.queueParity ? 16 : 0);    // (the kernel finds the other set at `queue ^ 64 bytes`)
         args.workItems = (unsigned) blocks;
-        launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) grid.chunk, l.lds.bytes, stream, args);
+        launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) grid.chunk, l.lds.bytes, stream, args, dDims);
         HIPCHK(hipGetLastError());
         b->work.queueParity ^= 1u;
     } else {
         for (size_t base = 0; base < blocks; base += grid.chunk) {
             args.blockBase = (unsigned) base;
-            launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) (blocks-base < grid.chunk ? blocks-base : grid.chunk), l.lds.bytes, stream, args);
+            launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) (blocks-base < grid.chunk ? blocks-base : grid.chunk), l.lds.bytes, stream, args, dDims);
         }
         HIPCHK(hipGetLastError());
     }
@@ -600,7 +633,7 @@ int ensureSideStreams(const MsdfHipBatch *b) {
 // The glyphs whose survivor lists exceed a CU's LDS take the list-free kernel (see k_distance_unculled): all of the batch, or those of dGlyphMap.
 template <int SEL, bool OVERLAP>
 int launchUnculled(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, float *dst, int toScratch, hipStream_t stream, const int *dGlyphMap = NULL,
-                   int nMapped = 0) {
+                   int nMapped = 0, const int32_t *dDims = NULL) {
     const int tilesX = (w+TILE-1)/TILE, tiles = tilesX*((h+TILE-1)/TILE);
     const size_t items = (size_t) (dGlyphMap ? nMapped : b->nGlyphs)*(size_t) tiles;
     if (items == 0)
@@ -620,8 +653,12 @@ int launchUnculled(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
     unsigned *counter = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(gres)+groups*resBytes);
     HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned), stream));
     const BatchView v = viewOf(b);
-    hipLaunchKernelGGL((k_distance_unculled<SEL, OVERLAP>), dim3((unsigned) groups), dim3(WAVE), 0, stream, v.nGlyphs, v.glyphContourOffsets, v.contourOffsets, v.recs,
-                       v.windings, dGlyphs, w, h, tilesX, tiles, dst, toScratch, gres, resBytes/sizeof(double), counter, (unsigned) items, dGlyphMap);
+    if (dDims)
+        hipLaunchKernelGGL(unculledSizedKernel(SEL, OVERLAP), dim3((unsigned) groups), dim3(WAVE), 0, stream, v.nGlyphs, v.glyphContourOffsets, v.contourOffsets, v.recs,
+                           v.windings, dGlyphs, w, h, tilesX, tiles, dst, toScratch, gres, resBytes/sizeof(double), counter, (unsigned) items, dGlyphMap, dDims);
+    else
+        hipLaunchKernelGGL((k_distance_unculled<SEL, OVERLAP>), dim3((unsigned) groups), dim3(WAVE), 0, stream, v.nGlyphs, v.glyphContourOffsets, v.contourOffsets, v.recs,
+                           v.windings, dGlyphs, w, h, tilesX, tiles, dst, toScratch, gres, resBytes/sizeof(double), counter, (unsigned) items, dGlyphMap);
     HIPCHK(hipGetLastError());
     countRoute(MSDFHIP_ROUTE_DIST_UNCULLED);
     return MSDFHIP_OK;
@@ -669,7 +706,7 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
     for (int k = 0; k < plan.nLaunches && rc == MSDFHIP_OK; ++k) {
         const DistanceLaunch &l = plan.launches[k];
         rc = forDistanceVariant(l, [&](auto o, auto g, auto t) {
-            return launchDistance<SEL, decltype(o)::value, decltype(g)::value, decltype(t)::value>(b, dGlyphs, w, h, dst, toScratch, l, env, streams[l.stream]);
+            return launchDistance<SEL, decltype(o)::value, decltype(g)::value, decltype(t)::value>(b, dGlyphs, w, h, dst, toScratch, l, env, streams[l.stream], call.boxDims);
         });
     }
     hipError_t joinError = hipSuccess;
@@ -690,7 +727,7 @@ int dispatchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, 
             rc = fail(MSDFHIP_ERR_HIP, "joining the glyph-class streams failed: %s", hipGetErrorString(joinError));
     }
     if (rc == MSDFHIP_OK && plan.unculled)                       // after the join: the list-free kernel shares the batch's workspace with the global-scratch class
-        rc = unculled(b, dGlyphs, w, h, dst, toScratch, stream, plan.unculledMapped ? b->work.bucket.ptr+plan.unculledOffset : NULL, plan.unculledCount);
+        rc = unculled(b, dGlyphs, w, h, dst, toScratch, stream, plan.unculledMapped ? b->work.bucket.ptr+plan.unculledOffset : NULL, plan.unculledCount, call.boxDims);
     return rc;
 }
 
@@ -739,15 +776,20 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
             return rc;
     }
     const size_t gresStride = p.resBytes/sizeof(double);
-    rc = setLds(k_ec_slow<N, OVERLAP, GRES>, p.slowLds);
+    const int32_t *dDims = call.boxDims;                         // (a sized call: the twins of the kernels below, same grids, same LDS)
+    rc = dDims ? setLds(ecSlowSizedKernel(N, OVERLAP, GRES), p.slowLds) : setLds(k_ec_slow<N, OVERLAP, GRES>, p.slowLds);
     if (rc != MSDFHIP_OK)
         return rc;
     ScopedTimer timer(stream, 1, !paramsOnly);
     if (p.route == EC_ROUTE_STAGE_SNAPSHOT || p.route == EC_ROUTE_SLOW_ALL) {   // k_ec_slow takes every texel
         if (paramsOnly)
             return MSDFHIP_OK;
-        hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(p.route == EC_ROUTE_SLOW_ALL ? p.slowGrid : p.snapshotBlocks), dim3(WAVE), p.slowLds, stream, viewOf(b),
-                           dGlyphs, w, h, src, out, stencil, cfg, (const EcCandidate *) NULL, 0u, 0, gres, gresStride);
+        if (dDims)
+            hipLaunchKernelGGL(ecSlowSizedKernel(N, OVERLAP, GRES), dim3(p.route == EC_ROUTE_SLOW_ALL ? p.slowGrid : p.snapshotBlocks), dim3(WAVE), p.slowLds, stream, viewOf(b),
+                               dGlyphs, w, h, src, out, stencil, cfg, (const EcCandidate *) NULL, 0u, 0, gres, gresStride, dDims);
+        else
+            hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(p.route == EC_ROUTE_SLOW_ALL ? p.slowGrid : p.snapshotBlocks), dim3(WAVE), p.slowLds, stream, viewOf(b),
+                               dGlyphs, w, h, src, out, stencil, cfg, (const EcCandidate *) NULL, 0u, 0, gres, gresStride);
         HIPCHK(hipGetLastError());
         if (p.route == EC_ROUTE_SLOW_ALL)
             countRoute(MSDFHIP_ROUTE_EC_SLOW_ALL);
@@ -761,10 +803,10 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
     if (p.route == EC_ROUTE_TOO_COMPLEX)
         return fail(MSDFHIP_ERR_TOO_COMPLEX, "a glyph has %d contours / %d edges: the error-correction pass needs %zu B of LDS per wavefront, device limit is %d B",
                     b->maxContours, b->maxEdges, p.fastLds > p.queryLds ? p.fastLds : p.queryLds, gLdsLimit.load());
-    rc = setLds(k_ec_query<N, OVERLAP>, p.queryLds);
+    rc = dDims ? setLds(ecQuerySizedKernel(N, OVERLAP), p.queryLds) : setLds(k_ec_query<N, OVERLAP>, p.queryLds);
     if (rc != MSDFHIP_OK)
         return rc;
-    rc = p.lazyProtect ? setLds(k_ec_fast<N, true>, p.fastLds) : setLds(k_ec_fast<N, false>, p.fastLds);
+    rc = dDims ? setLds(ecFastSizedKernel(N, p.lazyProtect), p.fastLds) : p.lazyProtect ? setLds(k_ec_fast<N, true>, p.fastLds) : setLds(k_ec_fast<N, false>, p.fastLds);
     if (rc != MSDFHIP_OK)
         return rc;
     int *offsets = reinterpret_cast<int *>(deferred+candidateRecords(b->nGlyphs, (size_t) w*h));
@@ -783,19 +825,31 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         call.ecParamsQueued = true;
         return MSDFHIP_OK;
     }
-    if (p.lazyProtect)
+    if (dDims)
+        hipLaunchKernelGGL(ecFastSizedKernel(N, p.lazyProtect), dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
+                           (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners, dDims);
+    else if (p.lazyProtect)
         hipLaunchKernelGGL((k_ec_fast<N, true>), dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
                            (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
     else
         hipLaunchKernelGGL((k_ec_fast<N, false>), dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
                            (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
     hipLaunchKernelGGL(k_ec_scan, dim3(1), dim3(1024), 0, stream, b->nGlyphs, reinterpret_cast<const unsigned *>(deferred), seg, offsets, policy, ecOrder);
-    hipLaunchKernelGGL((k_ec_query<N, OVERLAP>), dim3(queryBlocks), dim3(WAVE), p.queryLds, stream, b->nGlyphs, b->dGlyphContourOffsets.ptr, b->dContourOffsets.ptr,
-                       (const EdgeRec *) viewOf(b).recs, viewOf(b).windings, dGlyphs, w, h, src, out, stencil, cfg,
-                       (const EcGlyphParams *) b->work.ecParams.ptr, (const EcCandidate *) deferred, seg, (const int *) offsets, offsets+2*(size_t) b->nGlyphs+2, p.queryBatch,
-                       p.slotCap, p.slotOffset, policy, call.overflowOut, ecOrder, p.queryFlags);
+    if (dDims)
+        hipLaunchKernelGGL(ecQuerySizedKernel(N, OVERLAP), dim3(queryBlocks), dim3(WAVE), p.queryLds, stream, b->nGlyphs, (const int32_t *) b->dGlyphContourOffsets.ptr,
+                           (const int32_t *) b->dContourOffsets.ptr, (const EdgeRec *) viewOf(b).recs, viewOf(b).windings, dGlyphs, w, h, src, out, stencil, cfg,
+                           (const EcGlyphParams *) b->work.ecParams.ptr, (const EcCandidate *) deferred, seg, (const int *) offsets, offsets+2*(size_t) b->nGlyphs+2, p.queryBatch,
+                           p.slotCap, p.slotOffset, policy, call.overflowOut, ecOrder, p.queryFlags, dDims);
+    else
+        hipLaunchKernelGGL((k_ec_query<N, OVERLAP>), dim3(queryBlocks), dim3(WAVE), p.queryLds, stream, b->nGlyphs, b->dGlyphContourOffsets.ptr, b->dContourOffsets.ptr,
+                           (const EdgeRec *) viewOf(b).recs, viewOf(b).windings, dGlyphs, w, h, src, out, stencil, cfg,
+                           (const EcGlyphParams *) b->work.ecParams.ptr, (const EcCandidate *) deferred, seg, (const int *) offsets, offsets+2*(size_t) b->nGlyphs+2, p.queryBatch,
+                           p.slotCap, p.slotOffset, policy, call.overflowOut, ecOrder, p.queryFlags);
     if (call.overflowOut)
         call.overflowMirrored = true;                            // the caller looks at the count after its copy back and reruns with the pass below if needed
+    else if (dDims)
+        hipLaunchKernelGGL(ecSlowSizedKernel(N, OVERLAP, GRES), dim3(p.slowGrid), dim3(WAVE), p.slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
+                           (const EcCandidate *) deferred, seg, 1, gres, gresStride, dDims);
     else
         hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(p.slowGrid), dim3(WAVE), p.slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
                            (const EcCandidate *) deferred, seg, 1, gres, gresStride);
@@ -858,16 +912,20 @@ int prepareAhead(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGly
 // distanceSignCorrection: src (packed tiles) -> out (packed if dstPacked, else the caller's bitmaps).
 template <int N>
 int launchSign(const MsdfHipBatch *b, int w, int h, const MsdfHipGlyph *dGlyphs, const float *src, float *out, int dstPacked, float zero, int fillRule,
-               int rasterizeOnly, hipStream_t stream) {
+               int rasterizeOnly, hipStream_t stream, const int32_t *dDims = NULL) {
     const SignPlan p = planSign(planEnv(b->device), b->nGlyphs, b->maxEdges, w, h);
     if (p.blocks > 0x7fffffffull)
         return fail(MSDFHIP_ERR_INVALID, "launch of %zu tile rows exceeds the grid limit; split the batch", p.blocks);
-    int rc = setLds(k_sign_correction<N>, p.lds);
+    int rc = dDims ? setLds(signSizedKernel(N), p.lds) : setLds(k_sign_correction<N>, p.lds);
     if (rc != MSDFHIP_OK)
         return rc;
     ScopedTimer timer(stream, 2);
-    hipLaunchKernelGGL((k_sign_correction<N>), dim3((unsigned) p.blocks), dim3(WAVE), p.lds, stream, viewOf(b), dGlyphs, w, h, p.spansX, p.span, p.spans, (int) p.cap,
-                       src, out, dstPacked, zero, fillRule, rasterizeOnly);
+    if (dDims)
+        hipLaunchKernelGGL(signSizedKernel(N), dim3((unsigned) p.blocks), dim3(WAVE), p.lds, stream, viewOf(b), dGlyphs, w, h, p.spansX, p.span, p.spans, (int) p.cap,
+                           src, out, dstPacked, zero, fillRule, rasterizeOnly, dDims);
+    else
+        hipLaunchKernelGGL((k_sign_correction<N>), dim3((unsigned) p.blocks), dim3(WAVE), p.lds, stream, viewOf(b), dGlyphs, w, h, p.spansX, p.span, p.spans, (int) p.cap,
+                           src, out, dstPacked, zero, fillRule, rasterizeOnly);
     HIPCHK(hipGetLastError());
     countRoute(p.wholeRows ? MSDFHIP_ROUTE_SIGN_WHOLE_ROWS : MSDFHIP_ROUTE_SIGN_SPLIT);
     if (p.chunked)
@@ -876,13 +934,13 @@ int launchSign(const MsdfHipBatch *b, int w, int h, const MsdfHipGlyph *dGlyphs,
 }
 
 int runSignCorrection(const MsdfHipBatch *b, int channels, int w, int h, const MsdfHipGlyph *dGlyphs, const float *src, float *out, int dstPacked,
-                      float zero, int fillRule, hipStream_t stream) {
+                      float zero, int fillRule, hipStream_t stream, const int32_t *dDims = NULL) {
     if (fillRule < 0 || fillRule > 3)
         return fail(MSDFHIP_ERR_INVALID, "fill rule %d (must be 0..3)", fillRule);
     switch (channels) {
-        case 1: return launchSign<1>(b, w, h, dGlyphs, src, out, dstPacked, zero, fillRule, src == NULL, stream);   // no source field: rasterize()
-        case 3: return launchSign<3>(b, w, h, dGlyphs, src, out, dstPacked, zero, fillRule, 0, stream);
-        case 4: return launchSign<4>(b, w, h, dGlyphs, src, out, dstPacked, zero, fillRule, 0, stream);
+        case 1: return launchSign<1>(b, w, h, dGlyphs, src, out, dstPacked, zero, fillRule, src == NULL, stream, dDims);   // no source field: rasterize()
+        case 3: return launchSign<3>(b, w, h, dGlyphs, src, out, dstPacked, zero, fillRule, 0, stream, dDims);
+        case 4: return launchSign<4>(b, w, h, dGlyphs, src, out, dstPacked, zero, fillRule, 0, stream, dDims);
     }
     return fail(MSDFHIP_ERR_INVALID, "channels %d (must be 1, 3 or 4)", channels);
 }
@@ -1516,7 +1574,7 @@ static int runGenerate(const MsdfHipBatch *b, int mode, int w, int h, const Msdf
         return rc;
     const float *ecSrc = stageA;
     if (signPass) {
-        rc = runSignCorrection(b, channelsOf(mode), w, h, dGlyphs, stageA, correct ? stageB : dOut, correct ? 1 : 0, cfg->sdf_zero_value, cfg->fill_rule, stream);
+        rc = runSignCorrection(b, channelsOf(mode), w, h, dGlyphs, stageA, correct ? stageB : dOut, correct ? 1 : 0, cfg->sdf_zero_value, cfg->fill_rule, stream, call.boxDims);
         if (rc != MSDFHIP_OK || !correct)
             return rc;
         ecSrc = stageB;
@@ -3858,3 +3916,150 @@ extern "C" int msdfhip_debug_wait_profile(unsigned long long *out24, int reset) 
     return MSDFHIP_OK;
 #endif
 }
+
+// ---- per-glyph box sizes: msdfhip_batch_generate_sized, msdfhip_tiles_to_bytes_sized ---------------------------------------------------------------
+//
+// The launch chain is that of a uniform call at W x H = the batch's largest box (msdf_sizedplan.hpp): runGenerate with GenerateCall::boxDims set plans with the
+// same planners, takes the same routes and counts them in the same counters; where it would launch a kernel it launches the kernel's sized twin, which it gets from
+// one of the functions below. They are the ONLY code that names the twins and they come last in this file, so that the twins are instantiated behind every
+// kernel the code object has always held (forDistanceVariant).
+
+namespace {
+
+DistanceSizedKernel distanceSizedKernel(int sel, bool overlap, bool gres, int tpw) {
+    // (the five variants of forDistanceVariant per selector)
+#define MSDF_SIZED_VARIANTS(SEL) \
+    case SEL: return !overlap ? (gres ? k_distance_sized<SEL, false, true, 1> : k_distance_sized<SEL, false, false, (int) QUAD>) \
+                     : gres ? k_distance_sized<SEL, true, true, 1> : tpw != 1 ? k_distance_sized<SEL, true, false, (int) QUAD> : k_distance_sized<SEL, true, false, 1>;
+    switch (sel) {
+        MSDF_SIZED_VARIANTS(1)
+        MSDF_SIZED_VARIANTS(2)
+        MSDF_SIZED_VARIANTS(3)
+        MSDF_SIZED_VARIANTS(4)
+    }
+#undef MSDF_SIZED_VARIANTS
+    return NULL;
+}
+UnculledSizedKernel unculledSizedKernel(int sel, bool overlap) {
+    switch (sel) {
+        case 1: return overlap ? k_distance_unculled_sized<1, true> : k_distance_unculled_sized<1, false>;
+        case 2: return overlap ? k_distance_unculled_sized<2, true> : k_distance_unculled_sized<2, false>;
+        case 3: return overlap ? k_distance_unculled_sized<3, true> : k_distance_unculled_sized<3, false>;
+    }
+    return overlap ? k_distance_unculled_sized<4, true> : k_distance_unculled_sized<4, false>;
+}
+EcSlowSizedKernel ecSlowSizedKernel(int n, bool overlap, bool gres) {      // (the three of dispatchEc per channel count)
+    if (n == 3)
+        return !overlap ? k_ec_slow_sized<3, false, false> : gres ? k_ec_slow_sized<3, true, true> : k_ec_slow_sized<3, true, false>;
+    return !overlap ? k_ec_slow_sized<4, false, false> : gres ? k_ec_slow_sized<4, true, true> : k_ec_slow_sized<4, true, false>;
+}
+EcFastSizedKernel ecFastSizedKernel(int n, bool lazy) {
+    if (n == 3)
+        return lazy ? k_ec_fast_sized<3, true> : k_ec_fast_sized<3, false>;
+    return lazy ? k_ec_fast_sized<4, true> : k_ec_fast_sized<4, false>;
+}
+EcQuerySizedKernel ecQuerySizedKernel(int n, bool overlap) {
+    if (n == 3)
+        return overlap ? k_ec_query_sized<3, true> : k_ec_query_sized<3, false>;
+    return overlap ? k_ec_query_sized<4, true> : k_ec_query_sized<4, false>;
+}
+SignSizedKernel signSizedKernel(int n) {
+    return n == 1 ? k_sign_correction_sized<1> : n == 3 ? k_sign_correction_sized<3> : k_sign_correction_sized<4>;
+}
+
+// The sizes of a sized call, validated (msdf_sizedplan.hpp). No device call.
+int checkSizes(const char *who, int nGlyphs, const int32_t *sizes, SizedLayout &layout) {
+    switch (sizedLayout(nGlyphs, sizes, layout)) {
+        case SIZED_NO_SIZES: return fail(MSDFHIP_ERR_INVALID, "%s: sizes is NULL", who);
+        case SIZED_BAD_BOX: return fail(MSDFHIP_ERR_INVALID, "%s: glyph %d has a %d x %d box (each side must be at least 1)", who, layout.badGlyph, (int) sizes[2*(size_t) layout.badGlyph],
+                                        (int) sizes[2*(size_t) layout.badGlyph+1]);
+        case SIZED_TOO_MANY_TEXELS: return fail(MSDFHIP_ERR_INVALID, "%s: %d slots of %d x %d texels exceed the 32-bit texel index; split the batch", who, nGlyphs, layout.W, layout.H);
+    }
+    return MSDFHIP_OK;
+}
+
+// The device copy of n (w, h) pairs in the workspace of `ws`, uploaded from its pinned host copy on `stream`: ordered in front of whatever the caller
+// launches on that stream next. (The device copy is shared by the calls on one batch like every other work buffer: they are ordered by the caller.)
+int uploadBoxDims(Workspace &ws, int n, const int32_t *sizes, hipStream_t stream, const int32_t **out) {
+    std::lock_guard<std::mutex> lock(ws.mutex);
+    const size_t ints = 2*ws.glyphCapacity(n);
+    if (ws.boxDimsRead && ws.hBoxDims.ptr)                       // the previous call's upload has read the pinned copy before it is rewritten
+        HIPCHK(hipEventSynchronize(ws.boxDimsRead));
+    HIPCHK(ws.boxDims.ensure(ints));
+    HIPCHK(ws.hBoxDims.ensure(ints));
+    memcpy(ws.hBoxDims.ptr, sizes, sizeof(int32_t)*2*(size_t) n);
+    const int rc = uploadSmall(ws.boxDims.ptr, ws.hBoxDims.ptr, sizeof(int32_t)*2*(size_t) n, stream);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    if (!ws.boxDimsRead)
+        HIPCHK(ws.boxDimsRead.create(hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ws.boxDimsRead, stream));
+    *out = ws.boxDims.ptr;
+    return MSDFHIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int msdfhip_batch_generate_sized(const MsdfHipBatch *b, int mode, const int32_t *sizes, const MsdfHipGlyph *dGlyphs, float *dOut, uint8_t *dStencil, float *dScratch,
+                                 const MsdfHipConfig *cfg, void *streamPtr) {
+    if (!b || mode < 1 || mode > 4 || !dGlyphs || !dOut)
+        return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_batch_generate_sized");
+    SizedLayout layout;
+    int rc = checkSizes("msdfhip_batch_generate_sized", b->nGlyphs, sizes, layout);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    rc = checkConfig(cfg);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    if (b->nGlyphs == 0)
+        return MSDFHIP_OK;
+    rc = ensureDevice(b->device);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    GenerateCall call;
+    rc = uploadBoxDims(b->work, b->nGlyphs, sizes, (hipStream_t) streamPtr, &call.boxDims);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    return runGenerate(b, mode, layout.W, layout.H, dGlyphs, dOut, dStencil, dScratch, cfg, (hipStream_t) streamPtr, call);
+}
+
+int msdfhip_tiles_to_bytes_sized(const float *dTiles, int nGlyphs, const int32_t *sizes, const int64_t *tileOffsets, int channels, const MsdfHipGlyph *dGlyphs, uint8_t *dAtlas,
+                                 void *streamPtr) {
+    if (nGlyphs < 0 || (channels != 1 && channels != 3 && channels != 4))
+        return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_tiles_to_bytes_sized");
+    SizedLayout layout;
+    int rc = checkSizes("msdfhip_tiles_to_bytes_sized", nGlyphs, sizes, layout);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    if (nGlyphs == 0)
+        return MSDFHIP_OK;
+    if (!dTiles || !tileOffsets || !dGlyphs || !dAtlas)
+        return fail(MSDFHIP_ERR_INVALID, "msdfhip_tiles_to_bytes_sized: NULL argument");
+    rc = ensureDeviceOf(dTiles);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    hipStream_t stream = (hipStream_t) streamPtr;
+    // The two host arrays go to a device buffer of this call (sizes, then offsets), freed once the conversion has run: no batch whose workspace could hold them.
+    WorkBuffer<long long> dMeta;
+    HIPCHK(dMeta.ensure(2*(size_t) nGlyphs));
+    std::vector<long long> meta(2*(size_t) nGlyphs);
+    memcpy(meta.data(), sizes, sizeof(int32_t)*2*(size_t) nGlyphs);
+    for (int g = 0; g < nGlyphs; ++g)
+        meta[(size_t) nGlyphs+g] = (long long) tileOffsets[g];
+    HIPCHK(hipMemcpyAsync(dMeta.ptr, meta.data(), sizeof(long long)*meta.size(), hipMemcpyHostToDevice, stream));
+    const unsigned gx = (unsigned) ((layout.slot+255)/256 < 64 ? (layout.slot+255)/256 : 64), gy = (unsigned) (nGlyphs < 65535 ? nGlyphs : 65535);
+    const int32_t *dDims = reinterpret_cast<const int32_t *>(dMeta.ptr);
+    const long long *dOffsets = dMeta.ptr+nGlyphs;
+    switch (channels) {
+        case 1: hipLaunchKernelGGL(k_tiles_to_bytes_sized<1>, dim3(gx, gy), dim3(256), 0, stream, dTiles, dGlyphs, nGlyphs, dDims, dOffsets, dAtlas); break;
+        case 3: hipLaunchKernelGGL(k_tiles_to_bytes_sized<3>, dim3(gx, gy), dim3(256), 0, stream, dTiles, dGlyphs, nGlyphs, dDims, dOffsets, dAtlas); break;
+        default: hipLaunchKernelGGL(k_tiles_to_bytes_sized<4>, dim3(gx, gy), dim3(256), 0, stream, dTiles, dGlyphs, nGlyphs, dDims, dOffsets, dAtlas); break;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(stream));                        // (the staging vector and the device buffer of this call go with it)
+    return MSDFHIP_OK;
+}
+
+} // extern "C"

@@ -623,12 +623,14 @@ struct DistanceArgs {
 
 // The body of k_distance as a device function: k_distance is its only caller per instantiation (inlined: the kernel's code is what it was);
 // k_single_call (msdf_single.hpp) runs the same body as one phase of a fused launch. blockId = the workgroup's index in the launch.
-template <int SEL, bool OVERLAP, bool GRES, int TPW_ = (GRES ? 1 : (int) QUAD), int TEAM = 1>
+// SIZED (k_distance_sized): glyph g is a dims[2g] x dims[2g+1] box inside the launch's width x height slot -- see the sized kernels at the end of this file.
+template <int SEL, bool OVERLAP, bool GRES, int TPW_ = (GRES ? 1 : (int) QUAD), int TEAM = 1, bool SIZED = false>
 __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const int32_t *__restrict__ contourOffsets, const EdgeRec *__restrict__ recs,
            const int8_t *__restrict__ windings, const MsdfHipGlyph *__restrict__ glyphs, int width, int height, int tilesX, int tilesPerGlyph, int maxEdges,
            float *__restrict__ dst, int toScratch, unsigned blockBase, double *__restrict__ gres, size_t gresStride, const int *__restrict__ glyphMap, int nMapped,
            unsigned *__restrict__ workQueue, unsigned workItems, const unsigned blockId, double *smem, const int knownContours = -1, const int knownEdges = -1,
-           double *teamXchg = NULL) {
+           double *teamXchg = NULL, const int32_t *__restrict__ dims = NULL) {
+    static_assert(!SIZED || TEAM == 1, "the sized form has no teams");
     // (TEAM > 1: a workgroup of TEAM wavefronts on ONE tile -- see TeamExchange; the leader culls, every member walks its share, the leader stores)
     static_assert(TEAM == 1 || (TPW_ == 1 && !GRES), "teams take one tile, combiner scratch in LDS");
     const int teamRank = TEAM > 1 ? MSDF_UNIFORM((int) (threadIdx.x>>6)) : 0;   // (wave-uniform, and said so: the walk's record pointers must be scalar)
@@ -664,6 +666,21 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
         return;                                                         // (direct mapping only: every queued item is valid)
     if (glyphMap)
         wk.g = MSDF_UNIFORM(glyphMap[wk.g]);                            // this launch covers a subset of the batch (bucketed by contour count)
+    // The glyph's own box (wave-uniform, scalar loads: `dims` is read-only and __restrict__ like the records). A quad whose tiles all lie outside it leaves
+    // here -- in the persistent form for its next item: a return would end the workgroup's queue walk.
+    const int boxW = SIZED ? MSDF_UNIFORM(dims[2*wk.g]) : width, boxH = SIZED ? MSDF_UNIFORM(dims[2*wk.g+1]) : height;
+    if (SIZED) {
+        bool some = false;
+        for (int q = 0; q < TPW_; ++q) {
+            const int tileQ = wk.tile*TPW_+q;
+            some = some || (tileQ < tilesPerGlyph && (tileQ%tilesX)*TILE < boxW && (tileQ/tilesX)*TILE < boxH);
+        }
+        if (!some) {
+            if (!persistent)
+                return;
+            continue;
+        }
+    }
     // (wave-uniform values; made scalar explicitly: inside k_single_call the offsets are memory the launch itself wrote, which the compiler
     // reads with vector loads -- the record pointer of the hand-placed s_load batches has to live in SGPRs)
     const int c0 = knownContours >= 0 ? 0 : MSDF_UNIFORM(batch.glyphContourOffsets[wk.g]), C = knownContours >= 0 ? knownContours : MSDF_UNIFORM(batch.glyphContourOffsets[wk.g+1])-c0;
@@ -700,8 +717,9 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
     if (TEAM == 1 || teamRank == 0) {
         const int q = lane/ROW, col = lane%ROW;
         const int tileQ = wk.tile*TPW+q;
-        const bool tileValid = tileQ < tilesPerGlyph;
+        const bool tileInGrid = tileQ < tilesPerGlyph;
         const int txq = tileQ%tilesX, tyq = tileQ/tilesX;
+        const bool tileValid = tileInGrid && (!SIZED || (txq*TILE < boxW && tyq*TILE < boxH));   // (SIZED: a tile outside the glyph's box keeps empty lists)
         const V2 tc = mk((txq*TILE+.5*TILE)*rsx-t.tx, (tyq*TILE+.5*TILE)*rsy-t.ty);   // tile centre: only has to be accurate to within the cull slack
         int *list = lists+(size_t) q*maxEdges, *cstart = cstarts+(size_t) q*(C+1);
         int nSurv = 0;
@@ -846,7 +864,7 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
             break;
         const int tx = tile%tilesX, ty = tile/tilesX;
         const int x = tx*TILE+(lane&(TILE-1)), y = ty*TILE+(lane>>3);
-        if (x >= width || y >= height)
+        if (x >= boxW || y >= boxH)
             continue;
         const V2 p = fastXf ? mk(divExact(x+.5, t.sx, rsx)-t.tx, divExact(y+.5, t.sy, rsy)-t.ty)
                             : unproject(t, mk(x+.5, y+.5));         // msdfgen.cpp:68 (coord/scale-translate, correctly rounded either way)
@@ -883,8 +901,8 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
         asm volatile("" : "+v"(laneAfter));
 #endif
         const int xo = tx*TILE+(laneAfter&(TILE-1)), yo = ty*TILE+(laneAfter>>3);
-        const int yn = gd.flip ? height-1-yo : yo;                  // output.reorient(shape orientation), msdfgen.cpp:55
-        float *px = toScratch ? dst+(((size_t) wk.g*height+yn)*width+xo)*NCH
+        const int yn = gd.flip ? boxH-1-yo : yo;                    // output.reorient(shape orientation), msdfgen.cpp:55
+        float *px = toScratch ? dst+(SIZED ? (size_t) wk.g*width*height+(size_t) yn*boxW+xo : ((size_t) wk.g*height+yn)*width+xo)*NCH
                               : dst+gd.out_offset+(ptrdiff_t) gd.row_stride*yn+(ptrdiff_t) NCH*xo;
         for (int ch = 0; ch < NCH; ++ch) {
             // streaming (nontemporal) stores: 400 MB of tiles per pass otherwise push the 128-VGPR kernels' scratch lines out of L2 (round 5, A/B: the pass's
@@ -1269,14 +1287,18 @@ struct EcPushProtect {
 
 // ORDER: 1 the lazy order, 0 the eager one -- k_ec_fast has an instantiation of each and the host picks by the configuration (67 / 63 VGPRs, 18 / 1 scalar
 // registers parked in vector lanes, all outside the queue loops) -- or -1: decided here, one body for k_single_call.
-template <int N, int ORDER = -1>
+template <int N, int ORDER = -1, bool SIZED = false>
 __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHipGlyph *glyphs, int width, int height, int tilesX, int tilesPerGlyph,
           const float *src, float *out, uint8_t *stencilOut, const MsdfHipConfig &cfg, const EcGlyphParams *glyphParams, EcCandidate *cands, unsigned seg,
-          int maxEdges, const int *corners, const unsigned blockId, int *smemFast, const int sinkSlots = 0, const int sinkSlot = 0) {
+          int maxEdges, const int *corners, const unsigned blockId, int *smemFast, const int sinkSlots = 0, const int sinkSlot = 0, const int32_t *__restrict__ dims = NULL) {
     // (sinkSlots > 0: the distance-check candidates go to segment sinkSlot of sinkSlots instead of the glyph's -- k_single_call gives every TILE its own
     // segment and lets the tile's workgroup judge them itself)
     const GlyphWork wk = decodeItem(blockId, batch.nGlyphs, tilesPerGlyph);
     if (!wk.valid)
+        return;
+    // (SIZED: the glyph's own box inside the width x height slot; a tile wholly outside it has no texel -- wave-uniform)
+    const int boxW = SIZED ? MSDF_UNIFORM(dims[2*wk.g]) : width, boxH = SIZED ? MSDF_UNIFORM(dims[2*wk.g+1]) : height;
+    if (SIZED && ((wk.tile%tilesX)*TILE >= boxW || (wk.tile/tilesX)*TILE >= boxH))
         return;
     float *halo = reinterpret_cast<float *>(smemFast);                                      // [EC_HALO*EC_HALO][N]
     int *verdictLds = reinterpret_cast<int *>(halo+EC_HALO*EC_HALO*N);                      // [WAVE]: bits 0-3 EC_V_*, bit 8 protected
@@ -1311,13 +1333,13 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     const bool lazy = ORDER < 0 ? ecLazyProtect(p) : ORDER != 0;
     bool cornerTexel = false;
     if (p.mode == EC_MODE_EDGE_PRIORITY && !lazy)
-        cornerTexel = ecTileCornerTexel(corners+2*(size_t) gp.cornerBegin, gp.nCorners, tx, ty, height, gd.flip, lane);
+        cornerTexel = ecTileCornerTexel(corners+2*(size_t) gp.cornerBegin, gp.nCorners, tx, ty, boxH, gd.flip, lane);
 
     // ---- the tile and its one-texel halo go to LDS once (native rows); texels outside the bitmap are never read back
     // Two rounds, halo positions lane and lane+WAVE: column and row of the second follow from those of the first, and so does the texel's address (the tile's
     // origin is wave-uniform, the second round's step as well).
-    const ptrdiff_t rowStep = (ptrdiff_t) width*N;
-    const ptrdiff_t origin = (((ptrdiff_t) wk.g*height+ty*TILE-1)*width+tx*TILE-1)*N;       // of halo position 0, in floats from src (outside the field where the tile touches a border)
+    const ptrdiff_t rowStep = (ptrdiff_t) boxW*N;
+    const ptrdiff_t origin = SIZED ? ((ptrdiff_t) wk.g*width*height+(ptrdiff_t) (ty*TILE-1)*boxW+tx*TILE-1)*N : (((ptrdiff_t) wk.g*height+ty*TILE-1)*width+tx*TILE-1)*N;       // of halo position 0, in floats from src (outside the field where the tile touches a border)
     const int hr0 = lane/EC_HALO, hc0 = lane-hr0*EC_HALO;
     const ptrdiff_t laneStep0 = hr0*rowStep+hc0*N;
     MSDF_UNROLL
@@ -1329,7 +1351,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
         if (idx < EC_HALO*EC_HALO) {
             const int hx = tx*TILE+hc-1, hy = ty*TILE+hr-1;
             unsigned cls = 0;
-            if (hx >= 0 && hy >= 0 && hx < width && hy < height) {
+            if (hx >= 0 && hy >= 0 && hx < boxW && hy < boxH) {
                 const float *t = src+(origin+laneStep);
                 float tv[N];
                 for (int ch = 0; ch < N; ++ch)
@@ -1349,7 +1371,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     // its deviation and channels (whatever the LDS holds there) are read and never used.
     const int lx = lane&(TILE-1), ly = lane>>3;
     const int x = tx*TILE+lx, yn = ty*TILE+ly;
-    const bool inside = x < width && yn < height;
+    const bool inside = x < boxW && yn < boxH;
     int st = 0;
     const bool classify = inside;
     Neighbourhood nb;
@@ -1419,7 +1441,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
             sink.header = reinterpret_cast<unsigned *>(cands);
             sink.segment = sinkSlots > 0 ? cands+ecHeaderRecords(sinkSlots)+(size_t) sinkSlot*seg : cands+ecHeaderRecords(batch.nGlyphs)+(size_t) wk.g*seg;
             sink.seg = seg, sink.g = sinkSlots > 0 ? sinkSlot : wk.g;
-            sink.texel = (unsigned) (((size_t) wk.g*height+ty*TILE+sy)*width+tx*TILE+sx);
+            sink.texel = (unsigned) (SIZED ? (size_t) wk.g*width*height+(size_t) (ty*TILE+sy)*boxW+tx*TILE+sx : ((size_t) wk.g*height+ty*TILE+sy)*width+tx*TILE+sx);
             const int v = evaluatePair(c, n, hb, vc, p, (word&0x100) != 0, gd.flip, k, jp, sink, order);
             if (v && order != EC_ORDER_LAZY_HELD)
                 atomicOr(&verdictLds[s], v);
@@ -1439,7 +1461,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
         const EcGlyphParams gl = glyphParams[wk.g];
         EcParams pr = p;
         pr.radiusH = gl.radiusH, pr.radiusV = gl.radiusV, pr.radiusD = gl.radiusD;
-        cornerTexel = ecTileCornerTexel(corners+2*(size_t) gl.cornerBegin, gl.nCorners, tx, ty, height, gd.flip, lane);
+        cornerTexel = ecTileCornerTexel(corners+2*(size_t) gl.cornerBegin, gl.nCorners, tx, ty, boxH, gd.flip, lane);
         if (need) {
             if (cornerTexel)
                 verdictLds[lane] |= 0x100;
@@ -1452,7 +1474,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
                     MSDF_UNROLL
                     for (int dx = -1; dx <= 1; ++dx) {
                         const int nx = x+dx, ny = yn+dy;
-                        const bool in = nx >= 0 && ny >= 0 && nx < width && ny < height;
+                        const bool in = nx >= 0 && ny >= 0 && nx < boxW && ny < boxH;
                         nd.dev[dy+1][dx+1] = ecTexelDeviation(halo+((ly+1+(in ? dy : 0))*EC_HALO+lx+1+(in ? dx : 0))*N);
                         nd.cls[dy+1][dx+1] = in ? (unsigned) EC_CLS_INSIDE : 0u;
                     }
@@ -1484,7 +1506,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
         st |= EC_PROTECTED;                                         // protectEdges hit (phase B) / protectAll (:38-39)
     if (verdict&EC_V_ERROR)
         st |= EC_ERROR;
-    const size_t texel = ((size_t) wk.g*height+yn)*width+x;
+    const size_t texel = SIZED ? (size_t) wk.g*width*height+(size_t) yn*boxW+x : ((size_t) wk.g*height+yn)*width+x;
     const float *in = halo+((ly+1)*EC_HALO+lx+1)*N;
     float v[N];
     for (int i = 0; i < N; ++i)
@@ -1497,7 +1519,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     for (int i = 0; i < N; ++i)
         px[i] = v[i];
     if (stencilOut)
-        stencilOut[stencilIndex(texel, yn, width, height, cfg.stencil_y_down)] = (uint8_t) st;
+        stencilOut[stencilIndex(texel, yn, boxW, boxH, cfg.stencil_y_down)] = (uint8_t) st;
 }
 template <int N, bool LAZY>
 __global__ void __launch_bounds__(WAVE, MSDF_EC_FAST_WAVES_PER_SIMD)
@@ -1695,13 +1717,13 @@ __device__ unsigned long long gQueryProfile[24];
 #define MSDF_QSTAMP(x) const unsigned long long x = __builtin_readcyclecounter()
 #endif
 #endif
-template <int N, bool OVERLAP>
-__global__ void __launch_bounds__(WAVE, MSDF_EC_QUERY_WAVES_PER_SIMD)
-k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const int32_t *__restrict__ contourOffsets, const EdgeRec *__restrict__ recs,
+// (the body of k_ec_query as a device function, inlined into its one caller per instantiation: k_ec_query, and with SIZED its twin k_ec_query_sized)
+template <int N, bool OVERLAP, bool SIZED = false>
+__device__ __forceinline__ void ecQueryBody(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const int32_t *__restrict__ contourOffsets, const EdgeRec *__restrict__ recs,
            const int8_t *__restrict__ windings, const MsdfHipGlyph *__restrict__ glyphs, int width, int height, const float *__restrict__ src, float *__restrict__ out,
            uint8_t *__restrict__ stencilOut, MsdfHipConfig cfg, const EcGlyphParams *__restrict__ glyphParams, const EcCandidate *__restrict__ cands, unsigned seg,
            const int *__restrict__ offsets, int *__restrict__ counter, int itemsPerTicket, int slotCap, int slotOffset, EcQueryPolicy lpcMaxContours,
-           unsigned *__restrict__ overflowOut, const int *__restrict__ order, int queryFlags) {   // queryFlags: 1 tickets dealt statically | 4 ... only the first, the others drawn from eight counters
+           unsigned *__restrict__ overflowOut, const int *__restrict__ order, int queryFlags, double *smemLds, const int32_t *__restrict__ dims = NULL) {   // queryFlags: 1 tickets dealt statically | 4 ... only the first, the others drawn from eight counters
     // overflowOut (single-shape host calls): the candidate-overflow count is mirrored next to the results, so that the host sees it with the
     // copy back instead of a k_ec_slow launch that does nothing in all but pathological cases (one launch less on a latency-bound path)
     if (overflowOut && blockIdx.x == 0 && threadIdx.x == 0)
@@ -1710,7 +1732,7 @@ k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const i
     // own stores -- corrected texels, stencil bytes, the work counter -- provably do not touch them)
     BatchView batch;
     batch.nGlyphs = nGlyphs, batch.glyphContourOffsets = glyphContourOffsets, batch.contourOffsets = contourOffsets, batch.recs = recs, batch.windings = windings;
-    extern __shared__ double smemLds[];                             // combiner scratch ([maxContours][64] or [maxContours]) | slotCap PBSlots at slotOffset
+    // smemLds: combiner scratch ([maxContours][64] or [maxContours]) | slotCap PBSlots at slotOffset
     PBSlot *slotBuf = reinterpret_cast<PBSlot *>(smemLds+slotOffset);
     const unsigned *header = reinterpret_cast<const unsigned *>(cands);
     const size_t texelsPerGlyph = (size_t) width*height;
@@ -1800,9 +1822,10 @@ k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const i
         const EcGlyphParams gp = glyphParams[g];
         p.hSpan = gp.hSpan, p.vSpan = gp.vSpan, p.dSpan = gp.dSpan, p.texelX = gp.texelX, p.texelY = gp.texelY;
         p.radiusH = gp.radiusH, p.radiusV = gp.radiusV, p.radiusD = gp.radiusD;
+        const int boxW = SIZED ? dims[2*g] : width, boxH = SIZED ? dims[2*g+1] : height;   // (SIZED: the glyph's field is packed [boxH][boxW][N] at the start of its slot)
         SdfView sdf;
         sdf.px = src+(size_t) g*texelsPerGlyph*N;
-        sdf.w = width, sdf.h = height, sdf.N = N, sdf.flip = gd.flip;
+        sdf.w = boxW, sdf.h = boxH, sdf.N = N, sdf.flip = gd.flip;
         const int nE = coff[C]-coff[0];
         WindingMasks wind;                                          // one vector load + two ballots per item instead of up to 4 C dependent byte loads
         wind.mem = batch.windings+c0;
@@ -1827,8 +1850,8 @@ k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const i
                 const EcCandidate cand = segment[k];
                 const size_t texel = cand.texel;
                 const int rem = (int) (texel-(size_t) g*texelsPerGlyph);
-                const int yn = rem/width, x = rem%width;
-                const int ys = gd.flip ? height-1-yn : yn;
+                const int yn = rem/boxW, x = rem%boxW;
+                const int ys = gd.flip ? boxH-1-yn : yn;
                 const bool artifact = ecEvaluateCandidate(sdf, p, x, ys, cand.t, (cand.dir&3)-1, ((cand.dir>>2)&3)-1, query);
                 if (artifact && query.slice == 0) {
                     const float *in = sdf.native(x, yn);
@@ -1836,7 +1859,7 @@ k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const i
                     float *px = out+gd.out_offset+(ptrdiff_t) gd.row_stride*yn+(ptrdiff_t) N*x;
                     px[0] = m, px[1] = m, px[2] = m;
                     if (stencilOut)
-                        stencilOut[stencilIndex(texel, yn, width, height, cfg.stencil_y_down)] |= (uint8_t) EC_ERROR;
+                        stencilOut[stencilIndex(texel, yn, boxW, boxH, cfg.stencil_y_down)] |= (uint8_t) EC_ERROR;
                 }
             }
         } else if (ecQueryLanePerCandidate(count, nE, C, lpcMaxContours)) {
@@ -1847,8 +1870,8 @@ k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const i
                 const EcCandidate cand = segment[k];
                 const size_t texel = cand.texel;
                 const int rem = (int) (texel-(size_t) g*texelsPerGlyph);
-                const int yn = rem/width, x = rem%width;
-                const int ys = gd.flip ? height-1-yn : yn;
+                const int yn = rem/boxW, x = rem%boxW;
+                const int ys = gd.flip ? boxH-1-yn : yn;
                 const bool artifact = ecEvaluateCandidate(sdf, p, x, ys, cand.t, (cand.dir&3)-1, ((cand.dir>>2)&3)-1, query);
                 if (artifact) {
                     const float *in = sdf.native(x, yn);
@@ -1856,7 +1879,7 @@ k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const i
                     float *px = out+gd.out_offset+(ptrdiff_t) gd.row_stride*yn+(ptrdiff_t) N*x;
                     px[0] = m, px[1] = m, px[2] = m;
                     if (stencilOut)
-                        stencilOut[stencilIndex(texel, yn, width, height, cfg.stencil_y_down)] |= (uint8_t) EC_ERROR;
+                        stencilOut[stencilIndex(texel, yn, boxW, boxH, cfg.stencil_y_down)] |= (uint8_t) EC_ERROR;
                 }
             }
         } else {
@@ -1872,8 +1895,8 @@ k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const i
             query.cacheCap = OVERLAP ? (slotCap < slotOffset ? slotCap : slotOffset) : 0;   // (= mergedCap of the launch, msdf_capi.hip: launchEc)
             const size_t texel = cand.texel;
             const int rem = (int) (texel-(size_t) g*texelsPerGlyph);
-            const int yn = rem/width, x = rem%width;
-            const int ys = gd.flip ? height-1-yn : yn;
+            const int yn = rem/boxW, x = rem%boxW;
+            const int ys = gd.flip ? boxH-1-yn : yn;
             const bool artifact = ecEvaluateCandidate(sdf, p, x, ys, cand.t, (cand.dir&3)-1, ((cand.dir>>2)&3)-1, query);
 #if defined(MSDF_PROFILE_QUERY)
             {
@@ -1887,7 +1910,7 @@ k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const i
                 float *px = out+gd.out_offset+(ptrdiff_t) gd.row_stride*yn+(ptrdiff_t) N*x;
                 px[0] = m, px[1] = m, px[2] = m;
                 if (stencilOut)
-                    stencilOut[stencilIndex(texel, yn, width, height, cfg.stencil_y_down)] |= (uint8_t) EC_ERROR;
+                    stencilOut[stencilIndex(texel, yn, boxW, boxH, cfg.stencil_y_down)] |= (uint8_t) EC_ERROR;
             }
         }
         waveSync();                                                 // the next item rewrites the LDS scratch
@@ -1930,14 +1953,23 @@ k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const i
     }
 #endif
 }
+template <int N, bool OVERLAP>
+__global__ void __launch_bounds__(WAVE, MSDF_EC_QUERY_WAVES_PER_SIMD)
+k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const int32_t *__restrict__ contourOffsets, const EdgeRec *__restrict__ recs,
+           const int8_t *__restrict__ windings, const MsdfHipGlyph *__restrict__ glyphs, int width, int height, const float *__restrict__ src, float *__restrict__ out,
+           uint8_t *__restrict__ stencilOut, MsdfHipConfig cfg, const EcGlyphParams *__restrict__ glyphParams, const EcCandidate *__restrict__ cands, unsigned seg,
+           const int *__restrict__ offsets, int *__restrict__ counter, int itemsPerTicket, int slotCap, int slotOffset, EcQueryPolicy lpcMaxContours,
+           unsigned *__restrict__ overflowOut, const int *__restrict__ order, int queryFlags) {   // queryFlags: 1 tickets dealt statically | 4 ... only the first, the others drawn from eight counters
+    extern __shared__ double smemLds[];                             // combiner scratch ([maxContours][64] or [maxContours]) | slotCap PBSlots at slotOffset
+    ecQueryBody<N, OVERLAP>(nGlyphs, glyphContourOffsets, contourOffsets, recs, windings, glyphs, width, height, src, out, stencilOut, cfg, glyphParams, cands, seg, offsets, counter,
+                            itemsPerTicket, slotCap, slotOffset, lpcMaxContours, overflowOut, order, queryFlags, smemLds);
+}
 
 // Full per-texel pipeline incl. the exact shape-distance check (msdf_ec.hpp) for EVERY texel of the batch: used for the stage
 // snapshots of the tests (overflowOnly == 0) and as the safety net when the candidate list overflowed (overflowOnly != 0).
-template <int N, bool OVERLAP, bool GRES = false>
-__global__ void __launch_bounds__(WAVE)
-k_ec_slow(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, const float *src, float *out, uint8_t *stencilOut,
-          MsdfHipConfig cfg, const EcCandidate *cands, unsigned seg, int overflowOnly, double *gres, size_t gresStride) {
-    extern __shared__ double smemLds[];                             // [maxContours][64] combiner scratch (overlap only)
+template <int N, bool OVERLAP, bool GRES, bool SIZED = false>
+__device__ __forceinline__ void ecSlowBody(const BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, const float *src, float *out, uint8_t *stencilOut,
+          const MsdfHipConfig cfg, const EcCandidate *cands, unsigned seg, int overflowOnly, double *gres, size_t gresStride, double *smemLds, const int32_t *dims = NULL) {
     double *smem = GRES ? gres+(size_t) blockIdx.x*gresStride : smemLds;
     const size_t texelsPerGlyph = (size_t) width*height;
     const size_t allTexels = texelsPerGlyph*batch.nGlyphs;
@@ -1950,7 +1982,10 @@ k_ec_slow(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, co
         if (overflowOnly && header[1+g] <= seg)
             continue;                                               // only the glyphs whose segment overflowed are redone
         const int rem = (int) (texel%texelsPerGlyph);
-        const int yn = rem/width, x = rem%width;
+        const int boxW = SIZED ? dims[2*g] : width, boxH = SIZED ? dims[2*g+1] : height;
+        if (SIZED && rem >= boxW*boxH)
+            continue;                                               // the rest of the glyph's slot: no texel
+        const int yn = rem/boxW, x = rem%boxW;
         const int c0 = batch.glyphContourOffsets[g], C = batch.glyphContourOffsets[g+1]-c0;
         const int32_t *coff = batch.contourOffsets+c0;
         const int e0 = coff[0], nE = coff[C]-e0;
@@ -1964,7 +1999,7 @@ k_ec_slow(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, co
         ecDerive(p);
         SdfView sdf;
         sdf.px = src+(size_t) g*texelsPerGlyph*N;
-        sdf.w = width, sdf.h = height, sdf.N = N, sdf.flip = gd.flip;
+        sdf.w = boxW, sdf.h = boxH, sdf.N = N, sdf.flip = gd.flip;
         PsdfQuery<OVERLAP> query;
         query.rec = rec, query.coff = coff, query.windings = batch.windings+c0, query.C = C, query.res = smem+threadIdx.x;
         const int st = ecTexelStencil(sdf, p, rec, nE, x, yn, &query);
@@ -1980,8 +2015,15 @@ k_ec_slow(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, co
         for (int k = 0; k < N; ++k)
             px[k] = v[k];
         if (stencilOut)
-            stencilOut[stencilIndex(texel, yn, width, height, cfg.stencil_y_down)] = (uint8_t) st;
+            stencilOut[stencilIndex(texel, yn, boxW, boxH, cfg.stencil_y_down)] = (uint8_t) st;
     }
+}
+template <int N, bool OVERLAP, bool GRES = false>
+__global__ void __launch_bounds__(WAVE)
+k_ec_slow(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, const float *src, float *out, uint8_t *stencilOut,
+          MsdfHipConfig cfg, const EcCandidate *cands, unsigned seg, int overflowOnly, double *gres, size_t gresStride) {
+    extern __shared__ double smemLds[];                             // [maxContours][64] combiner scratch (overlap only)
+    ecSlowBody<N, OVERLAP, GRES>(batch, glyphs, width, height, src, out, stencilOut, cfg, cands, seg, overflowOnly, gres, gresStride, smemLds);
 }
 
 // ------------------------------------------------------------------------------------------- distance sign correction
@@ -2047,13 +2089,15 @@ __device__ inline void buildRowLists(const RowLists &L, const EdgeRec *rec, int 
     waveSync();
 }
 
-template <int N>
-__global__ void __launch_bounds__(WAVE, 3)
-k_sign_correction(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, int spansX, int span, int spansPerGlyph, int cap,
-                  const float *src, float *out, int dstPacked, float zero, int fillRule, int rasterizeOnly) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
+template <int N, bool SIZED = false>
+__device__ __forceinline__ void signBody(const BatchView &batch, const MsdfHipGlyph *glyphs, const int slotW, const int slotH, int spansX, int span, int spansPerGlyph, int cap,
+                  const float *src, float *out, int dstPacked, float zero, int fillRule, int rasterizeOnly, double *smem, const int32_t *dims = NULL) {
     const GlyphWork wk = decodeBlock(batch.nGlyphs, spansPerGlyph);
     if (!wk.valid)
+        return;
+    // (SIZED: the glyph's own box inside the slotW x slotH slot; a span of tiles wholly outside it leaves here -- wave-uniform)
+    const int width = SIZED ? MSDF_UNIFORM(dims[2*wk.g]) : slotW, height = SIZED ? MSDF_UNIFORM(dims[2*wk.g+1]) : slotH;
+    if (SIZED && ((wk.tile/spansX)*TILE >= height || (wk.tile%spansX)*span*TILE >= width))
         return;
     const int c0 = batch.glyphContourOffsets[wk.g], C = batch.glyphContourOffsets[wk.g+1]-c0;
     const int32_t *coff = batch.contourOffsets+c0;
@@ -2075,7 +2119,7 @@ k_sign_correction(BatchView batch, const MsdfHipGlyph *glyphs, int width, int he
     const int lx = lane&(TILE-1), ly = lane>>3;
     const int ys = ty*TILE+ly;                                           // shape orientation (sdf.reorient, rasterization.cpp:39)
     const int yn = gd.flip ? height-1-ys : ys;
-    const float *tile = src+(size_t) wk.g*height*width*N;
+    const float *tile = src+(size_t) wk.g*slotH*slotW*N;
     const float twice = zero+zero;
     for (int s = 0; s < span; ++s) {                                     // one 8x8 tile per step
         if ((tx0+s)*TILE >= width)
@@ -2134,11 +2178,18 @@ k_sign_correction(BatchView batch, const MsdfHipGlyph *glyphs, int width, int he
                     v[N >= 4 ? 3 : 0] = twice-v[N >= 4 ? 3 : 0];
             }
         }
-        float *px_ = dstPacked ? out+(((size_t) wk.g*height+yn)*width+x)*N
+        float *px_ = dstPacked ? out+(SIZED ? (size_t) wk.g*slotH*slotW+(size_t) yn*width+x : ((size_t) wk.g*height+yn)*width+x)*N
                                : out+gd.out_offset+(ptrdiff_t) gd.row_stride*yn+(ptrdiff_t) N*x;
         for (int i = 0; i < N; ++i)
             px_[i] = v[i];
     }
+}
+template <int N>
+__global__ void __launch_bounds__(WAVE, 3)
+k_sign_correction(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, int spansX, int span, int spansPerGlyph, int cap,
+                  const float *src, float *out, int dstPacked, float zero, int fillRule, int rasterizeOnly) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    signBody<N>(batch, glyphs, width, height, spansX, span, spansPerGlyph, cap, src, out, dstPacked, zero, fillRule, rasterizeOnly, smem);
 }
 
 // ------------------------------------------------------------------------------------------- shape preparation (row f3)
@@ -2431,12 +2482,11 @@ __global__ void k_sdf_error_sum(const double *lines, int nGlyphs, int height, in
 // per-contour distances in a global workspace slice per workgroup. Persistent: a bounded pool of workgroups (the workspace is
 // contours x 1.5 KB per workgroup) draws tiles from one counter. Orders of magnitude slower per edge than the culled path -- it exists so
 // that a valid input is rendered instead of returning MSDFHIP_ERR_TOO_COMPLEX.
-template <int SEL, bool OVERLAP>
-__global__ void __launch_bounds__(WAVE, 2)
-k_distance_unculled(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const int32_t *__restrict__ contourOffsets, const EdgeRec *__restrict__ recs,
-                    const int8_t *__restrict__ windings, const MsdfHipGlyph *__restrict__ glyphs, int width, int height, int tilesX, int tilesPerGlyph,
-                    float *__restrict__ dst, int toScratch, double *__restrict__ gres, size_t gresStride, unsigned *__restrict__ counter, unsigned items,
-                    const int *__restrict__ glyphMap) {
+template <int SEL, bool OVERLAP, bool SIZED = false>
+__device__ __forceinline__ void distanceUnculledBody(int nGlyphs, const int32_t *glyphContourOffsets, const int32_t *contourOffsets, const EdgeRec *recs,
+                    const int8_t *windings, const MsdfHipGlyph *glyphs, int width, int height, int tilesX, int tilesPerGlyph,
+                    float *dst, int toScratch, double *gres, size_t gresStride, unsigned *counter, unsigned items,
+                    const int *glyphMap, const int32_t *dims = NULL) {
     // glyphMap: the launch covers these glyphs of the batch (the oversized ones of a mixed batch: msdf_capi.hip, ensureBuckets), or NULL = all
     enum { NCH = SelTraits<SEL>::NCH };
     const int lane = threadIdx.x;
@@ -2456,7 +2506,8 @@ k_distance_unculled(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets
         const Xform t = loadXform(gd);
         const int tx = tile%tilesX, ty = tile/tilesX;
         const int x = tx*TILE+(lane&(TILE-1)), y = ty*TILE+(lane>>3);
-        if (x >= width || y >= height)
+        const int boxW = SIZED ? dims[2*g] : width, boxH = SIZED ? dims[2*g+1] : height;   // (SIZED: the glyph's own box; a tile outside it has no texel left here)
+        if (x >= boxW || y >= boxH)
             continue;
         const V2 p = unproject(t, mk(x+.5, y+.5));                   // msdfgen.cpp:68
         EdgesAll edges;
@@ -2466,11 +2517,20 @@ k_distance_unculled(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets
             shapeDistanceOverlap<SEL>(rec, edges, windings+c0, C, p, gres+(size_t) blockIdx.x*gresStride+lane, WAVE, d);
         else
             shapeDistanceSimple<SEL>(rec, edges, C, p, d);
-        const int yn = gd.flip ? height-1-y : y;
-        float *px = toScratch ? dst+(((size_t) g*height+yn)*width+x)*NCH : dst+gd.out_offset+(ptrdiff_t) gd.row_stride*yn+(ptrdiff_t) NCH*x;
+        const int yn = gd.flip ? boxH-1-y : y;
+        float *px = toScratch ? dst+(SIZED ? (size_t) g*width*height+(size_t) yn*boxW+x : ((size_t) g*height+yn)*width+x)*NCH : dst+gd.out_offset+(ptrdiff_t) gd.row_stride*yn+(ptrdiff_t) NCH*x;
         for (int ch = 0; ch < NCH; ++ch)
             px[ch] = mapDistance(t, d[ch]);
     }
+}
+template <int SEL, bool OVERLAP>
+__global__ void __launch_bounds__(WAVE, 2)
+k_distance_unculled(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const int32_t *__restrict__ contourOffsets, const EdgeRec *__restrict__ recs,
+                    const int8_t *__restrict__ windings, const MsdfHipGlyph *__restrict__ glyphs, int width, int height, int tilesX, int tilesPerGlyph,
+                    float *__restrict__ dst, int toScratch, double *__restrict__ gres, size_t gresStride, unsigned *__restrict__ counter, unsigned items,
+                    const int *__restrict__ glyphMap) {
+    distanceUnculledBody<SEL, OVERLAP>(nGlyphs, glyphContourOffsets, contourOffsets, recs, windings, glyphs, width, height, tilesX, tilesPerGlyph, dst, toScratch, gres, gresStride,
+                                       counter, items, glyphMap);
 }
 
 // res: the overlapping combiner's per-contour scratch -- LDS (dynamic shared memory sized by the host) or, for shapes with more contours
@@ -2535,6 +2595,90 @@ k_ec_legacy(const float *__restrict__ src, float *__restrict__ dst, int nGlyphs,
     for (size_t i = (size_t) blockIdx.x*blockDim.x+threadIdx.x; i < total; i += (size_t) gridDim.x*blockDim.x) {
         const size_t g = i/texels, rem = i%texels;
         legacyClashTexel<N>(src+g*texels*N, dst+g*texels*N, width, height, (int) (rem%(size_t) width), (int) (rem/(size_t) width), pass, thresholdX, thresholdY);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ per-glyph box sizes
+//
+// The sized twins of the generate kernels (msdfhip_batch_generate_sized): glyph g is rendered as a dims[2g] x dims[2g+1] bitmap. The launches keep the
+// shape of a uniform call at width x height = the LARGEST box of the batch (a padded grid: the host plans grids, LDS and workspaces as for that call) and
+// every per-glyph intermediate buffer keeps slots of width*height texels; glyph g's field is PACKED [h_g][w_g][N] at the start of slot g, its stencil the
+// same. A workgroup whose tiles lie wholly outside its glyph's box leaves after one wave-uniform load of the box. The twins run the bodies of the kernels
+// above with SIZED = true; they are siblings so that the uniform kernels keep their code, and they stay BEHIND everything else in this file (the order of
+// the instantiations in the code object matters, msdf_capi.hip: forDistanceVariant).
+template <int SEL, bool OVERLAP, bool GRES = false, int TPW_ = (GRES ? 1 : (int) QUAD)>
+__global__ void __launch_bounds__(WAVE, OVERLAP ? MSDF_DISTANCE_WAVES_PER_SIMD : GRES ? MSDF_SIMPLE_WAVES_PER_SIMD-1 : MSDF_SIMPLE_WAVES_PER_SIMD)
+k_distance_sized(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const int32_t *__restrict__ contourOffsets, const EdgeRec *__restrict__ recs,
+                 const int8_t *__restrict__ windings, const MsdfHipGlyph *__restrict__ glyphs, int width, int height, int tilesX, int tilesPerGlyph, int maxEdges,
+                 float *__restrict__ dst, int toScratch, unsigned blockBase, double *__restrict__ gres, size_t gresStride, const int *__restrict__ glyphMap, int nMapped,
+                 unsigned *__restrict__ workQueue, unsigned workItems, const int32_t *__restrict__ dims) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    distanceBody<SEL, OVERLAP, GRES, TPW_, 1, true>(nGlyphs, glyphContourOffsets, contourOffsets, recs, windings, glyphs, width, height, tilesX, tilesPerGlyph, maxEdges, dst, toScratch,
+                                                    blockBase, gres, gresStride, glyphMap, nMapped, workQueue, workItems, blockIdx.x, smem, -1, -1, NULL, dims);
+}
+
+template <int SEL, bool OVERLAP>
+__global__ void __launch_bounds__(WAVE, 2)
+k_distance_unculled_sized(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const int32_t *__restrict__ contourOffsets, const EdgeRec *__restrict__ recs,
+                          const int8_t *__restrict__ windings, const MsdfHipGlyph *__restrict__ glyphs, int width, int height, int tilesX, int tilesPerGlyph,
+                          float *__restrict__ dst, int toScratch, double *__restrict__ gres, size_t gresStride, unsigned *__restrict__ counter, unsigned items,
+                          const int *__restrict__ glyphMap, const int32_t *__restrict__ dims) {
+    distanceUnculledBody<SEL, OVERLAP, true>(nGlyphs, glyphContourOffsets, contourOffsets, recs, windings, glyphs, width, height, tilesX, tilesPerGlyph, dst, toScratch, gres,
+                                             gresStride, counter, items, glyphMap, dims);
+}
+
+template <int N, bool LAZY>
+__global__ void __launch_bounds__(WAVE, MSDF_EC_FAST_WAVES_PER_SIMD)
+k_ec_fast_sized(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, int tilesX, int tilesPerGlyph,
+                const float *src, float *out, uint8_t *stencilOut, MsdfHipConfig cfg, const EcGlyphParams *glyphParams, EcCandidate *cands, unsigned seg,
+                int maxEdges, const int *corners, const int32_t *__restrict__ dims) {
+    extern __shared__ int smemFast[];
+    ecFastBody<N, LAZY ? 1 : 0, true>(batch, glyphs, width, height, tilesX, tilesPerGlyph, src, out, stencilOut, cfg, glyphParams, cands, seg, maxEdges, corners, blockIdx.x, smemFast,
+                                      0, 0, dims);
+}
+
+template <int N, bool OVERLAP>
+__global__ void __launch_bounds__(WAVE, MSDF_EC_QUERY_WAVES_PER_SIMD)
+k_ec_query_sized(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const int32_t *__restrict__ contourOffsets, const EdgeRec *__restrict__ recs,
+                 const int8_t *__restrict__ windings, const MsdfHipGlyph *__restrict__ glyphs, int width, int height, const float *__restrict__ src, float *__restrict__ out,
+                 uint8_t *__restrict__ stencilOut, MsdfHipConfig cfg, const EcGlyphParams *__restrict__ glyphParams, const EcCandidate *__restrict__ cands, unsigned seg,
+                 const int *__restrict__ offsets, int *__restrict__ counter, int itemsPerTicket, int slotCap, int slotOffset, EcQueryPolicy lpcMaxContours,
+                 unsigned *__restrict__ overflowOut, const int *__restrict__ order, int queryFlags, const int32_t *__restrict__ dims) {
+    extern __shared__ double smemLds[];
+    ecQueryBody<N, OVERLAP, true>(nGlyphs, glyphContourOffsets, contourOffsets, recs, windings, glyphs, width, height, src, out, stencilOut, cfg, glyphParams, cands, seg, offsets,
+                                  counter, itemsPerTicket, slotCap, slotOffset, lpcMaxContours, overflowOut, order, queryFlags, smemLds, dims);
+}
+
+template <int N, bool OVERLAP, bool GRES = false>
+__global__ void __launch_bounds__(WAVE)
+k_ec_slow_sized(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, const float *src, float *out, uint8_t *stencilOut,
+                MsdfHipConfig cfg, const EcCandidate *cands, unsigned seg, int overflowOnly, double *gres, size_t gresStride, const int32_t *dims) {
+    extern __shared__ double smemLds[];
+    ecSlowBody<N, OVERLAP, GRES, true>(batch, glyphs, width, height, src, out, stencilOut, cfg, cands, seg, overflowOnly, gres, gresStride, smemLds, dims);
+}
+
+template <int N>
+__global__ void __launch_bounds__(WAVE, 3)
+k_sign_correction_sized(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, int spansX, int span, int spansPerGlyph, int cap,
+                        const float *src, float *out, int dstPacked, float zero, int fillRule, int rasterizeOnly, const int32_t *__restrict__ dims) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    signBody<N, true>(batch, glyphs, width, height, spansX, span, spansPerGlyph, cap, src, out, dstPacked, zero, fillRule, rasterizeOnly, smem, dims);
+}
+
+// msdfhip_tiles_to_bytes_sized: glyph g's floats are packed [h_g][w_g][N] at tiles + tileOffsets[g]; the grid's y dimension strides over the glyphs, x over a
+// glyph's texels.
+template <int N>
+__global__ void k_tiles_to_bytes_sized(const float *tiles, const MsdfHipGlyph *glyphs, int nGlyphs, const int32_t *__restrict__ dims, const long long *__restrict__ tileOffsets,
+                                       uint8_t *atlas) {
+    for (int g = blockIdx.y; g < nGlyphs; g += gridDim.y) {
+        const int boxW = dims[2*g], texels = boxW*dims[2*g+1];
+        const float *in = tiles+tileOffsets[g];
+        for (int i = blockIdx.x*blockDim.x+threadIdx.x; i < texels; i += gridDim.x*blockDim.x) {
+            const int y = i/boxW, x = i-y*boxW;
+            uint8_t *o = atlas+glyphs[g].out_offset+(ptrdiff_t) glyphs[g].row_stride*y+(ptrdiff_t) N*x;
+            for (int ch = 0; ch < N; ++ch)
+                o[ch] = pixelFloatToByte(in[(size_t) i*N+ch]);
+        }
     }
 }
 

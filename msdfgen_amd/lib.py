@@ -145,6 +145,8 @@ _PROTOS = {
     "msdfhip_error_correction_legacy": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
     "msdfhip_batch_generate_legacy": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.POINTER(Config), _vp]),
     "msdfhip_batch_error_correction_legacy": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_double, C.c_double, _vp]),
+    "msdfhip_batch_generate_sized": (C.c_int, [_vp, C.c_int, _ip, _vp, _vp, _vp, _vp, C.POINTER(Config), _vp]),
+    "msdfhip_tiles_to_bytes_sized": (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_int64), C.c_int, _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_PROTOS))

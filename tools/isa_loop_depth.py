@@ -2,7 +2,8 @@
 DEPTH (from the compiler's own loop annotations in the assembly), and the instruction mix of the innermost edge loop (the loop holding the hand-placed
 s_load_dwordx16 batches). No GPU needed: hipcc cross-compiles a one-kernel translation unit in a few seconds.
 
-    python tools/isa_loop_depth.py [SEL OVERLAP GRES TPW]        default 3 true false 4 = the LDS class of the msdf bench step
+    python tools/isa_loop_depth.py [SEL OVERLAP GRES TPW [KERNEL]]   default 3 true false 4 k_distance = the LDS class of the msdf bench step;
+                                                                     KERNEL = k_distance_sized: its per-glyph-box twin
 """
 import collections
 import os
@@ -16,13 +17,16 @@ sys.path.insert(0, ROOT)
 from msdfgen_amd import build as B  # noqa: E402
 
 
-def analyse(sel="3", overlap="true", gres="false", tpw="4"):
+KERNEL_EXTRA_ARGS = {"k_distance": "", "k_distance_sized": ", const int32_t *"}   # what a twin's parameter list adds behind k_distance's
+
+
+def analyse(sel="3", overlap="true", gres="false", tpw="4", kernel="k_distance"):
     """-> {"resources": {...}, "instructions": {depth: n}, "lane_moves": {depth: n}, "edge_loop": {class: n} or None}"""
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "probe.hip")
         open(src, "w").write('#include "msdf_kernels.hpp"\nusing namespace msdfhip;\n'
-                             "template __global__ void msdfhip::k_distance<%s, %s, %s, %s>(int, const int32_t *, const int32_t *, const EdgeRec *, const int8_t *, const MsdfHipGlyph *, "
-                             "int, int, int, int, int, float *, int, unsigned, double *, size_t, const int *, int, unsigned *, unsigned);\n" % (sel, overlap, gres, tpw))
+                             "template __global__ void msdfhip::%s<%s, %s, %s, %s>(int, const int32_t *, const int32_t *, const EdgeRec *, const int8_t *, const MsdfHipGlyph *, "
+                             "int, int, int, int, int, float *, int, unsigned, double *, size_t, const int *, int, unsigned *, unsigned%s);\n" % (kernel, sel, overlap, gres, tpw, KERNEL_EXTRA_ARGS[kernel]))
         flags = [f for f in B.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]+os.environ.get("MSDF_ISA_FLAGS", "").split()   # e.g. MSDF_ISA_FLAGS=-DMSDF_DISTANCE_WAVES_PER_SIMD=3
         r = subprocess.run([B.hipcc()] + flags + ["-I", B.CSRC, "-I", os.path.join(ROOT, "include"), "-c", "--cuda-device-only", "-save-temps", "-Rpass-analysis=kernel-resource-usage",
                             src, "-o", os.path.join(d, "probe.o")], capture_output=True, text=True, cwd=d)
@@ -32,9 +36,9 @@ def analyse(sel="3", overlap="true", gres="false", tpw="4"):
         res = {}
         for line in r.stderr.splitlines():
             m = re.search(r"remark: [^ ]+ +([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+) \[-Rpass", line)
-            if m and "k_distance" in r.stderr[:r.stderr.find(line)].rsplit("Function Name:", 1)[-1]:
+            if m and kernel+"I" in r.stderr[:r.stderr.find(line)].rsplit("Function Name:", 1)[-1]:
                 res[m.group(1).strip()] = m.group(2)
-    start = next(i for i, l in enumerate(asm) if re.match(r"_ZN7msdfhip10k_distanceI", l))
+    start = next(i for i, l in enumerate(asm) if re.match(r"_ZN7msdfhip%d%sI" % (len(kernel), kernel), l))
     end = next(i for i in range(start, len(asm)) if "s_endpgm" in asm[i])
     lines = asm[start:end+1]
     depth, d = [], 0
@@ -74,10 +78,10 @@ def analyse(sel="3", overlap="true", gres="false", tpw="4"):
 
 
 def main():
-    sel, overlap, gres, tpw = (sys.argv[1:5] + ["3", "true", "false", "4"][len(sys.argv[1:5]):])
-    a = analyse(sel, overlap, gres, tpw)
+    sel, overlap, gres, tpw, kernel = (sys.argv[1:6] + ["3", "true", "false", "4", "k_distance"][len(sys.argv[1:6]):])
+    a = analyse(sel, overlap, gres, tpw, kernel)
     res = a["resources"]
-    print("k_distance<%s, %s, %s, %s>: %s" % (sel, overlap, gres, tpw, ", ".join("%s %s" % (k, res[k]) for k in ("VGPRs", "TotalSGPRs", "SGPRs Spill", "VGPRs Spill", "Occupancy") if k in res)))
+    print("%s<%s, %s, %s, %s>: %s" % (kernel, sel, overlap, gres, tpw, ", ".join("%s %s" % (k, res[k]) for k in ("VGPRs", "TotalSGPRs", "SGPRs Spill", "VGPRs Spill", "Occupancy") if k in res)))
     print("loop depth   instructions   v_readlane + v_writelane   scratch loads + stores")
     for k in sorted(a["instructions"]):
         print("%10d %14d %10d %22d" % (k, a["instructions"][k], a["lane_moves"].get(k, 0), a["scratch_ops"].get(k, 0)))
