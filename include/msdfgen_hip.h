@@ -150,7 +150,8 @@ int msdfhip_error_correction_shapeless(int channels, float *pixels, int width, i
  * (main.cpp:1223-1298). `stencil`: as msdfhip_generate. Set flip = (shape is Y-downward) xor (bitmap is Y-downward) and cfg->stencil_y_down = (bitmap
  * is Y-downward), as for msdfhip_generate: the two together tell the shape's orientation, and the stencil's memory row r is then the reference's --
  * row r of the SHAPE's rows for a Y-upward shape, row height-1-r for a Y-downward one, whatever the bitmap's own orientation (the legacy generators
- * re-orient the bitmap to the shape before they correct it, core/msdfgen.cpp:223). */
+ * re-orient the bitmap to the shape before they correct it, core/msdfgen.cpp:223). For the same reason the correction without sign_correction
+ * walks the SHAPE's rows, as generateMSDF_legacy's does; with sign_correction it walks the bitmap's, as the CLI flow's does (main.cpp:1260-1294). */
 int msdfhip_generate_legacy(int mode, float *pixels, int width, int height, int row_stride, int flip,
                             const int32_t *contour_offsets, int n_contours, const double *points, const uint8_t *types, const uint8_t *colors,
                             const double *xf, const MsdfHipConfig *cfg, uint8_t *stencil);

@@ -301,6 +301,7 @@ struct GenerateCall {
     hipEvent_t afterDistance = NULL;  // host-output pipeline: recorded on the call's stream between the distance pass and what follows it (NULL: not wanted)
     unsigned *overflowOut = NULL;     // pipeline chunks, single-shape calls: where k_ec_query mirrors the candidate-overflow count (then no k_ec_slow launch)
     bool overflowMirrored = false;    // out: the correction pass did so
+    bool ecShapeRows = false;         // the correction pairs protectEdges' texels along the shape's rows (EcParams::shapeRows): a legacy generator without the sign pass
     const int32_t *boxDims = NULL;    // msdfhip_batch_generate_sized: the device copy of the per-glyph box sizes (w, h below are then the slot's W, H); the sized kernels launch
 };
 
@@ -777,7 +778,20 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
     }
     const size_t gresStride = p.resBytes/sizeof(double);
     const int32_t *dDims = call.boxDims;                         // (a sized call: the twins of the kernels below, same grids, same LDS)
-    rc = dDims ? setLds(ecSlowSizedKernel(N, OVERLAP, GRES), p.slowLds) : setLds(k_ec_slow<N, OVERLAP, GRES>, p.slowLds);
+    // The uniform kernels of this call: those of the modern entry points, or (call.ecShapeRows: a legacy generator, which corrects without overlap support
+    // and without the distance check, hence in the eager order) their instantiations that pair protectEdges' texels along the shape's rows.
+    auto slowKernel = k_ec_slow<N, OVERLAP, GRES>;
+    auto fastKernel = p.lazyProtect ? k_ec_fast<N, true> : k_ec_fast<N, false>;
+    if (call.ecShapeRows) {
+        if constexpr (!OVERLAP && !GRES) {
+            if (dDims || p.lazyProtect)
+                return fail(MSDFHIP_ERR_INVALID, "a correction along the shape's rows takes neither boxes of their own sizes nor the distance check");
+            slowKernel = k_ec_slow<N, false, false, true>;
+            fastKernel = k_ec_fast<N, false, true>;
+        } else
+            return fail(MSDFHIP_ERR_INVALID, "a correction along the shape's rows runs without overlap support");
+    }
+    rc = dDims ? setLds(ecSlowSizedKernel(N, OVERLAP, GRES), p.slowLds) : setLds(slowKernel, p.slowLds);
     if (rc != MSDFHIP_OK)
         return rc;
     ScopedTimer timer(stream, 1, !paramsOnly);
@@ -788,7 +802,7 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
             hipLaunchKernelGGL(ecSlowSizedKernel(N, OVERLAP, GRES), dim3(p.route == EC_ROUTE_SLOW_ALL ? p.slowGrid : p.snapshotBlocks), dim3(WAVE), p.slowLds, stream, viewOf(b),
                                dGlyphs, w, h, src, out, stencil, cfg, (const EcCandidate *) NULL, 0u, 0, gres, gresStride, dDims);
         else
-            hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(p.route == EC_ROUTE_SLOW_ALL ? p.slowGrid : p.snapshotBlocks), dim3(WAVE), p.slowLds, stream, viewOf(b),
+            hipLaunchKernelGGL(slowKernel, dim3(p.route == EC_ROUTE_SLOW_ALL ? p.slowGrid : p.snapshotBlocks), dim3(WAVE), p.slowLds, stream, viewOf(b),
                                dGlyphs, w, h, src, out, stencil, cfg, (const EcCandidate *) NULL, 0u, 0, gres, gresStride);
         HIPCHK(hipGetLastError());
         if (p.route == EC_ROUTE_SLOW_ALL)
@@ -806,7 +820,7 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
     rc = dDims ? setLds(ecQuerySizedKernel(N, OVERLAP), p.queryLds) : setLds(k_ec_query<N, OVERLAP>, p.queryLds);
     if (rc != MSDFHIP_OK)
         return rc;
-    rc = dDims ? setLds(ecFastSizedKernel(N, p.lazyProtect), p.fastLds) : p.lazyProtect ? setLds(k_ec_fast<N, true>, p.fastLds) : setLds(k_ec_fast<N, false>, p.fastLds);
+    rc = dDims ? setLds(ecFastSizedKernel(N, p.lazyProtect), p.fastLds) : setLds(fastKernel, p.fastLds);
     if (rc != MSDFHIP_OK)
         return rc;
     int *offsets = reinterpret_cast<int *>(deferred+candidateRecords(b->nGlyphs, (size_t) w*h));
@@ -828,11 +842,8 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
     if (dDims)
         hipLaunchKernelGGL(ecFastSizedKernel(N, p.lazyProtect), dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
                            (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners, dDims);
-    else if (p.lazyProtect)
-        hipLaunchKernelGGL((k_ec_fast<N, true>), dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
-                           (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
     else
-        hipLaunchKernelGGL((k_ec_fast<N, false>), dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
+        hipLaunchKernelGGL(fastKernel, dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
                            (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
     hipLaunchKernelGGL(k_ec_scan, dim3(1), dim3(1024), 0, stream, b->nGlyphs, reinterpret_cast<const unsigned *>(deferred), seg, offsets, policy, ecOrder);
     if (dDims)
@@ -851,7 +862,7 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         hipLaunchKernelGGL(ecSlowSizedKernel(N, OVERLAP, GRES), dim3(p.slowGrid), dim3(WAVE), p.slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
                            (const EcCandidate *) deferred, seg, 1, gres, gresStride, dDims);
     else
-        hipLaunchKernelGGL((k_ec_slow<N, OVERLAP, GRES>), dim3(p.slowGrid), dim3(WAVE), p.slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
+        hipLaunchKernelGGL(slowKernel, dim3(p.slowGrid), dim3(WAVE), p.slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
                            (const EcCandidate *) deferred, seg, 1, gres, gresStride);
     HIPCHK(hipGetLastError());
     countRoute(ecOrder ? MSDFHIP_ROUTE_EC_QUERY_HEAVIEST : MSDFHIP_ROUTE_EC_QUERY_BATCH);
@@ -1002,7 +1013,9 @@ int launchLegacyCorrection(float *dTiles, float *dScratch, int nGlyphs, int w, i
 }
 
 // One legacy generate call on b (arguments checked, device bound, cfg = legacyConfig): legacy distance pass -> sign correction -> error correction
-// without the distance check. With the sign pass this is the reference CLI's -legacy flow (main.cpp:1223-1298). Nothing of the call stays on the batch:
+// without the distance check. With the sign pass this is the reference CLI's -legacy flow (main.cpp:1223-1298), which corrects the bitmap as it lies.
+// Without it, it is generateMSDF_legacy / generateMTSDF_legacy, which re-orient their bitmap to the shape first (msdfgen.cpp:223, 278) and so pair
+// protectEdges' texels along the shape's rows: call.ecShapeRows. The stencil's rows are the same either way (stencilIndex). Nothing of the call stays on the batch:
 // like runGenerate it carries its state in `call`, and the legacy pass takes no class list, work queue or side stream of the batch.
 int runGenerateLegacy(const MsdfHipBatch *b, int mode, int w, int h, const MsdfHipGlyph *dGlyphs, float *dOut, uint8_t *dStencil, float *dScratch,
                       const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call) {
@@ -1031,6 +1044,7 @@ int runGenerateLegacy(const MsdfHipBatch *b, int mode, int w, int h, const MsdfH
             return rc;
         ecSrc = stageB;
     }
+    call.ecShapeRows = !signPass;
     return runCorrection(b, nch, w, h, dGlyphs, ecSrc, dOut, dStencil, cfg, stream, call);
 }
 

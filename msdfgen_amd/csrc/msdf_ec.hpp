@@ -36,6 +36,9 @@ struct EcParams {
     double hSpan, vSpan, dSpan;       // findErrors spans,   MSDFErrorCorrection.cpp:387-389
     double texelX, texelY;            // unprojectVector(Vector2(1)), :90
     int mode, distanceCheck, overlap, stageLimit;
+    // protectEdges pairs its texels along the SHAPE's rows, not the bitmap's: generateMSDF_legacy / generateMTSDF_legacy re-orient their bitmap to the
+    // shape before they correct it (msdfgen.cpp:223, 278), the modern generators correct the bitmap as it lies. Only a flipped glyph can tell.
+    int shapeRows = 0;
 };
 
 MSDF_HD void ecDerive(EcParams &p) {
@@ -73,7 +76,9 @@ MSDF_HD bool extremeChannelInMask(const float *msd, float m, int mask) {
 }
 
 // Is texel (x, y) [native order] marked by the protectEdges sweeps (:189-250)?  Pair (a, b) = (left,right), (bottom,top),
-// (left-bottom,right-top), (right-bottom,left-top): `a` is always the texel of the lower native row (same row: the left one).
+// (left-bottom,right-top), (right-bottom,left-top): `a` is always the texel of the lower row (same row: the left one) -- of the lower
+// native row, or with p.shapeRows of the lower row of the shape. edgeBetweenTexels(a, b) is not symmetric: t = (a-.5)/(a-b) and
+// mix(a, b, t) round differently from 1-t and mix(b, a, 1-t), and the result is compared for equality.
 MSDF_HD bool protectedByEdges(const SdfView &sdf, const EcParams &p, int x, int y) {
     const float *self = sdf.native(x, y);
     const float sm = medianf(self[0], self[1], self[2]);
@@ -87,7 +92,7 @@ MSDF_HD bool protectedByEdges(const SdfView &sdf, const EcParams &p, int x, int 
             const float radius = dy == 0 ? p.radiusH : dx == 0 ? p.radiusV : p.radiusD;
             const float *other = sdf.native(nx, ny);
             const float om = medianf(other[0], other[1], other[2]);
-            const bool selfIsA = dy > 0 || (dy == 0 && dx > 0);
+            const bool selfIsA = (p.shapeRows && sdf.flip ? dy < 0 : dy > 0) || (dy == 0 && dx > 0);
             const float *a = selfIsA ? self : other, *b = selfIsA ? other : self;
             const float am = selfIsA ? sm : om, bm = selfIsA ? om : sm;
             if (fabsf(am-.5f)+fabsf(bm-.5f) < radius) {

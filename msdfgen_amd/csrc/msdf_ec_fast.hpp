@@ -266,15 +266,16 @@ MSDF_HD void texelProtectPairs(const Neighbourhood &nb, const EcParams &p, Emit 
 }
 
 // Is `self` protected through its pair with neighbour m (`other`)? Pair orientation as the reference's sweeps: `a` is the texel of the
-// lower native row (same row: the left one).
-MSDF_HD bool evaluateProtectPair(const float *self, const float *other, int m) {
+// lower native row (same row: the left one); swapRows: of the higher native row, which is the lower row of a flipped glyph's shape
+// (EcParams::shapeRows).
+MSDF_HD bool evaluateProtectPair(const float *self, const float *other, int m, bool swapRows = false) {
     const int dy = m/3-1, dx = m%3-1;
-    const bool selfIsA = dy > 0 || (dy == 0 && dx > 0);
+    const bool selfIsA = (swapRows ? dy < 0 : dy > 0) || (dy == 0 && dx > 0);
     const int mask = selfIsA ? edgeBetweenTexelsFast(self, other) : edgeBetweenTexelsFast(other, self);
     return extremeChannelInMask(self, medianf(self[0], self[1], self[2]), mask);
 }
 
-MSDF_HD bool protectedByEdgesNb(const Neighbourhood &nb, const EcParams &p) {
+MSDF_HD bool protectedByEdgesNb(const Neighbourhood &nb, const EcParams &p, int flip = 0) {
     struct Items {
         unsigned char m[8];
         int n;
@@ -283,7 +284,7 @@ MSDF_HD bool protectedByEdgesNb(const Neighbourhood &nb, const EcParams &p) {
     items.n = 0;
     texelProtectPairs(nb, p, items);
     for (int i = 0; i < items.n; ++i)
-        if (evaluateProtectPair(nb.v[1][1], nb.v[items.m[i]/3][items.m[i]%3], items.m[i]))
+        if (evaluateProtectPair(nb.v[1][1], nb.v[items.m[i]/3][items.m[i]%3], items.m[i], p.shapeRows && flip))
             return true;
     return false;
 }
@@ -443,14 +444,14 @@ MSDF_HD int ecTexelFast(const SdfView &sdf, const EcParams &p, const int *corner
     if (allowLazy && ecLazyProtect(p)) {
         verdict = texelFindFast(nb, p, true, sdf.flip, sink, EC_ORDER_LAZY);
         if (ecNeedsProtection(verdict)) {
-            if (!(protectedByCornerList(corners, nCorners, x, ys) || protectedByEdgesNb(nb, p)))
+            if (!(protectedByCornerList(corners, nCorners, x, ys) || protectedByEdgesNb(nb, p, sdf.flip)))
                 verdict |= EC_V_ERROR;                       // (a held-back candidate implies a conditional artifact)
             else if (verdict&EC_V_HELD)
                 texelFindFast(nb, p, true, sdf.flip, sink, EC_ORDER_LAZY_HELD);
         }
     } else {
         if (p.mode == EC_MODE_EDGE_PRIORITY) {
-            if (protectedByCornerList(corners, nCorners, x, ys) || protectedByEdgesNb(nb, p))
+            if (protectedByCornerList(corners, nCorners, x, ys) || protectedByEdgesNb(nb, p, sdf.flip))
                 st |= EC_PROTECTED;
         } else if (p.mode == EC_MODE_EDGE_ONLY)
             st |= EC_PROTECTED;

@@ -1264,7 +1264,7 @@ __device__ __forceinline__ bool ecTileCornerTexel(const int *list, int nCorners,
 
 // protectEdges' edgeBetweenTexels tests of the queued pairs (lane | m<<6), densely: lane = pair; a hit protects the owning texel (bit 8 of its word).
 template <int N>
-__device__ __forceinline__ void ecRunProtectQueue(const float *halo, const unsigned short *protectQueue, int nProtect, int *verdictLds, int lane) {
+__device__ __forceinline__ void ecRunProtectQueue(const float *halo, const unsigned short *protectQueue, int nProtect, int *verdictLds, int lane, bool swapRows = false) {
     for (int base = 0; base < nProtect; base += WAVE) {
         const int it = base+lane;
         if (it >= nProtect)
@@ -1273,7 +1273,7 @@ __device__ __forceinline__ void ecRunProtectQueue(const float *halo, const unsig
         const int s = item&63, m = item>>6;
         const int sx = s&(TILE-1), sy = s>>3;
         const float *self = halo+((sy+1)*EC_HALO+sx+1)*N, *other = halo+((sy+m/3)*EC_HALO+sx+m%3)*N;
-        if (evaluateProtectPair(self, other, m))
+        if (evaluateProtectPair(self, other, m, swapRows))
             atomicOr(&verdictLds[s], 0x100);
     }
 }
@@ -1287,7 +1287,9 @@ struct EcPushProtect {
 
 // ORDER: 1 the lazy order, 0 the eager one -- k_ec_fast has an instantiation of each and the host picks by the configuration (67 / 63 VGPRs, 18 / 1 scalar
 // registers parked in vector lanes, all outside the queue loops) -- or -1: decided here, one body for k_single_call.
-template <int N, int ORDER = -1, bool SIZED = false>
+// SHAPE_ROWS: EcParams::shapeRows, the legacy generators' correction (eager order only: it runs without the distance check). An instantiation of its own,
+// so that the kernels of the modern entry points stay what they were.
+template <int N, int ORDER = -1, bool SIZED = false, bool SHAPE_ROWS = false>
 __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHipGlyph *glyphs, int width, int height, int tilesX, int tilesPerGlyph,
           const float *src, float *out, uint8_t *stencilOut, const MsdfHipConfig &cfg, const EcGlyphParams *glyphParams, EcCandidate *cands, unsigned seg,
           int maxEdges, const int *corners, const unsigned blockId, int *smemFast, const int sinkSlots = 0, const int sinkSlot = 0, const int32_t *__restrict__ dims = NULL) {
@@ -1416,7 +1418,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
 
     // ---- phase B (lane = queued pair): protectEdges' edgeBetweenTexels tests, densely; a hit protects the owning texel (eager order; the lazy one has queued none)
     if (!lazy) {
-        ecRunProtectQueue<N>(halo, protectQueue, itemCount[1], verdictLds, lane);
+        ecRunProtectQueue<N>(halo, protectQueue, itemCount[1], verdictLds, lane, SHAPE_ROWS && gd.flip);
         waveSync();
     }
 
@@ -1521,13 +1523,14 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     if (stencilOut)
         stencilOut[stencilIndex(texel, yn, boxW, boxH, cfg.stencil_y_down)] = (uint8_t) st;
 }
-template <int N, bool LAZY>
+template <int N, bool LAZY, bool SHAPE_ROWS = false>
 __global__ void __launch_bounds__(WAVE, MSDF_EC_FAST_WAVES_PER_SIMD)
 k_ec_fast(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, int tilesX, int tilesPerGlyph,
           const float *src, float *out, uint8_t *stencilOut, MsdfHipConfig cfg, const EcGlyphParams *glyphParams, EcCandidate *cands, unsigned seg,
           int maxEdges, const int *corners) {
     extern __shared__ int smemFast[];
-    ecFastBody<N, LAZY ? 1 : 0>(batch, glyphs, width, height, tilesX, tilesPerGlyph, src, out, stencilOut, cfg, glyphParams, cands, seg, maxEdges, corners, blockIdx.x, smemFast);
+    static_assert(!(LAZY && SHAPE_ROWS), "the lazy order's protection round pairs texels along the bitmap's rows");
+    ecFastBody<N, LAZY ? 1 : 0, false, SHAPE_ROWS>(batch, glyphs, width, height, tilesX, tilesPerGlyph, src, out, stencilOut, cfg, glyphParams, cands, seg, maxEdges, corners, blockIdx.x, smemFast);
 }
 
 // Two ways to spend a wavefront on deferred distance checks of a glyph with nE edges:
@@ -1967,7 +1970,7 @@ k_ec_query(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const i
 
 // Full per-texel pipeline incl. the exact shape-distance check (msdf_ec.hpp) for EVERY texel of the batch: used for the stage
 // snapshots of the tests (overflowOnly == 0) and as the safety net when the candidate list overflowed (overflowOnly != 0).
-template <int N, bool OVERLAP, bool GRES, bool SIZED = false>
+template <int N, bool OVERLAP, bool GRES, bool SIZED = false, bool SHAPE_ROWS = false>
 __device__ __forceinline__ void ecSlowBody(const BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, const float *src, float *out, uint8_t *stencilOut,
           const MsdfHipConfig cfg, const EcCandidate *cands, unsigned seg, int overflowOnly, double *gres, size_t gresStride, double *smemLds, const int32_t *dims = NULL) {
     double *smem = GRES ? gres+(size_t) blockIdx.x*gresStride : smemLds;
@@ -1996,6 +1999,7 @@ __device__ __forceinline__ void ecSlowBody(const BatchView batch, const MsdfHipG
         p.minDeviationRatio = cfg.min_deviation_ratio;
         p.minImproveRatio = cfg.min_improve_ratio;
         p.mode = cfg.ec_mode, p.distanceCheck = cfg.ec_distance_check, p.overlap = OVERLAP, p.stageLimit = cfg.ec_stage_limit;
+        p.shapeRows = SHAPE_ROWS;
         ecDerive(p);
         SdfView sdf;
         sdf.px = src+(size_t) g*texelsPerGlyph*N;
@@ -2018,12 +2022,12 @@ __device__ __forceinline__ void ecSlowBody(const BatchView batch, const MsdfHipG
             stencilOut[stencilIndex(texel, yn, boxW, boxH, cfg.stencil_y_down)] = (uint8_t) st;
     }
 }
-template <int N, bool OVERLAP, bool GRES = false>
+template <int N, bool OVERLAP, bool GRES = false, bool SHAPE_ROWS = false>
 __global__ void __launch_bounds__(WAVE)
 k_ec_slow(BatchView batch, const MsdfHipGlyph *glyphs, int width, int height, const float *src, float *out, uint8_t *stencilOut,
           MsdfHipConfig cfg, const EcCandidate *cands, unsigned seg, int overflowOnly, double *gres, size_t gresStride) {
     extern __shared__ double smemLds[];                             // [maxContours][64] combiner scratch (overlap only)
-    ecSlowBody<N, OVERLAP, GRES>(batch, glyphs, width, height, src, out, stencilOut, cfg, cands, seg, overflowOnly, gres, gresStride, smemLds);
+    ecSlowBody<N, OVERLAP, GRES, false, SHAPE_ROWS>(batch, glyphs, width, height, src, out, stencilOut, cfg, cands, seg, overflowOnly, gres, gresStride, smemLds);
 }
 
 // ------------------------------------------------------------------------------------------- distance sign correction

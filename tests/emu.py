@@ -60,7 +60,8 @@ class Emu:
         return out
 
     def generate(self, s, mode, w, h, xf, overlap=True, ec_mode=2, ec_dist=1, stage=0, y_down=False, correct_only=None, stencil=None,
-                 min_dev=1.11111111111111111, min_imp=1.11111111111111111):
+                 min_dev=1.11111111111111111, min_imp=1.11111111111111111, shape_rows=False):
+        """shape_rows: the correction pairs protectEdges' texels along the shape's rows (EcParams::shapeRows), as the legacy generators' does."""
         ms, mt = distance_mapping(xf[4], xf[5])
         x6 = np.array([xf[0], xf[1], xf[2], xf[3], ms, mt], np.float64)
         flip = int(bool(s.inverse_y) != bool(y_down))
@@ -72,7 +73,7 @@ class Emu:
             n = mode = out.shape[2]
         keep, args = self._shape(s)
         self.lib.emu_generate(mode, int(correct_only is not None), _p(out, C.c_float), w, h, w*n, flip, *args, _p(x6, C.c_double), int(overlap),
-                              ec_mode, ec_dist, stage, C.c_double(min_dev), C.c_double(min_imp), _p(stencil, C.c_uint8) if stencil is not None else None)
+                              ec_mode, ec_dist, stage, C.c_double(min_dev), C.c_double(min_imp), _p(stencil, C.c_uint8) if stencil is not None else None, int(shape_rows))
         return out
 
     def sign_correction(self, s, field, xf, zero=.5, rule=0, y_down=False):

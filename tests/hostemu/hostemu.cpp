@@ -323,9 +323,10 @@ void emu_shape_distance(int sel, int overlap, int nC, const int32_t *co, const d
 void emu_set_combiner_form(int form) { g_combinerForm = form; }
 
 // Mirrors msdfhip_generate / msdfhip_error_correction (correctionOnly): xf = {sx, sy, tx, ty, mapScale, mapTranslate}.
+// shapeRows: EcParams::shapeRows, as runGenerateLegacy sets it for a legacy generator without the sign pass.
 void emu_generate(int mode, int correctionOnly, float *pixels, int w, int h, int rowStride, int flip, int nC, const int32_t *co, const double *points,
                   const uint8_t *types, const uint8_t *colors, const double *xf, int overlap, int ecMode, int ecDist, int stageLimit,
-                  double minDev, double minImp, uint8_t *stencil) {
+                  double minDev, double minImp, uint8_t *stencil, int shapeRows) {
     const int N = correctionOnly ? mode : (mode <= 2 ? 1 : mode);
     Digest d = digest(nC, co, points, types, colors);
     const int nE = co[nC];
@@ -353,6 +354,7 @@ void emu_generate(int mode, int correctionOnly, float *pixels, int w, int h, int
     p.t = t;
     p.minDeviationRatio = minDev, p.minImproveRatio = minImp;
     p.mode = ecMode, p.distanceCheck = ecDist, p.overlap = overlap, p.stageLimit = stageLimit;
+    p.shapeRows = shapeRows != 0;
     ecDerive(p);
     SdfView sdf;
     sdf.px = tile.data(), sdf.w = w, sdf.h = h, sdf.N = N, sdf.flip = flip;

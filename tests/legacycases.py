@@ -1,6 +1,8 @@
-"""Shared by the tests of the legacy generators and the legacy correction (test_legacy_host.py, test_gpu_legacy.py) and by tools/make_golden_legacy.py:
-the recorded reference data of tests/golden/legacy.npz, the host build of msdf_legacy.hpp (tests/legacy_host), and a ctypes binding of the compiled
-reference's own legacy functions (oracle/_ref/libmsdfgen_ref.so, by mangled name: its C driver does not cover them)."""
+"""Shared by the tests of the legacy generators and the legacy correction (test_legacy_host.py, test_gpu_legacy.py, test_legacy_cases_host.py,
+test_gpu_legacy_cases.py) and by tools/make_golden_legacy.py / make_golden_legacy_crafted.py: the recorded reference data of tests/golden/legacy.npz and
+legacy_crafted.npz, the host build of msdf_legacy.hpp (tests/legacy_host), what the reference makes of a legacy call from pieces that run anywhere
+(reference_call), and a ctypes binding of the compiled reference's own legacy functions (oracle/_ref/libmsdfgen_ref.so, by mangled name: its C driver
+does not cover them)."""
 import ctypes as C
 import os
 import subprocess
@@ -49,6 +51,21 @@ def xf6(xf):
     """(sx, sy, tx, ty, range lower, range upper) -> the C ABI's (sx, sy, tx, ty, mapScale, mapTranslate)."""
     ms, mt = distance_mapping(xf[4], xf[5])
     return np.array([xf[0], xf[1], xf[2], xf[3], ms, mt], np.float64)
+
+
+def range_of(map_scale, map_translate):
+    """(range lower, range upper) that distance_mapping() turns into exactly (map_scale, map_translate): the inverse of xf6 for transformations that come
+    from the device (GlyphBatch.frame). translate = -lower is exact; the width is searched among the neighbours of 1/scale."""
+    lower = -np.float64(map_translate)
+    span = np.float64(1)/np.float64(map_scale)
+    cands = [span]
+    for _ in range(8):
+        cands = [np.nextafter(cands[0], -np.inf)]+cands+[np.nextafter(cands[-1], np.inf)]
+    for s in sorted(cands, key=lambda s: abs(s-span)):
+        upper = lower+s
+        if distance_mapping(lower, upper) == (float(map_scale), float(map_translate)):
+            return float(lower), float(upper)
+    raise AssertionError("no range maps to (%r, %r)" % (map_scale, map_translate))
 
 
 def shape_arrays(shape):
@@ -102,6 +119,117 @@ def host_correction(lib, field, tx, ty):
     return out
 
 
+# ------------------------------------------------------------------------------------ what the reference makes of a legacy call
+
+DEFAULT_RATIO = 1.11111111111111111
+SignPass = namedtuple("SignPass", "fill_rule zero")                 # the CLI's scanline pass: FillRule 0..3, the SDF's zero level
+
+
+def differing(a, b):
+    """Number of float32 values that differ in their bits, a NaN counting as equal to a NaN only."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    return int(((a.view(np.uint32) != b.view(np.uint32)) & ~(np.isnan(a) & np.isnan(b))).sum())
+
+
+def reference_call(host, oracle, shape, mode, w, h, xf, ec_mode=2, y_down=False, sign=None, min_dev=DEFAULT_RATIO, min_imp=DEFAULT_RATIO, stencil=True):
+    """(bitmap (h, w, N) in memory-row order, stencil uint8 (h, w) as the reference writes it or None) of one legacy call, from pieces that need neither
+    a GPU nor the compiled reference: the host build of msdf_legacy.hpp for the raw field, the plain-C oracle for the rest. Two flows:
+      sign is None   generate*_legacy proper. generateMSDF_legacy / generateMTSDF_legacy re-orient their by-value bitmap to the shape (msdfgen.cpp:223, 278)
+                     and correct THAT section (:273, :332): the correction walks the shape's rows. So the rows are reversed where the bitmap's orientation
+                     is not the shape's, the correction runs on a bitmap of the shape's orientation, and the rows are reversed back. The stencil section
+                     is made upward and re-oriented to the shape's (msdf-error-correction.cpp:19, MSDFErrorCorrection.cpp:122, 192, 385): exactly what the
+                     oracle writes for a bitmap of that orientation.
+      sign           the reference CLI's -legacy flow (main.cpp:1260-1294): field -> distanceSignCorrection -> msdfErrorCorrection, both on the bitmap as
+                     it lies.
+    Either correction runs without overlap support and without the distance check (msdfgen.cpp:272, 331)."""
+    field = host_generate(host, shape, mode, w, h, xf, y_down)
+    correct = mode >= 3 and ec_mode != 0
+    st = np.zeros((h, w), np.uint8) if stencil and correct else None
+    kw = dict(overlap=False, ec_mode=ec_mode, ec_dist=0, min_dev=min_dev, min_imp=min_imp, stencil=st)
+    if sign is not None:
+        field = oracle.sign_correction(shape, field, xf, zero=sign.zero, fill_rule=sign.fill_rule, y_down=y_down)
+        if correct:
+            field = oracle.error_correction(shape, field, xf, y_down=y_down, **kw)
+    elif correct:
+        rev = bool(shape.inverse_y) != bool(y_down)
+        field = oracle.error_correction(shape, np.ascontiguousarray(field[::-1]) if rev else field, xf, y_down=bool(shape.inverse_y), **kw)
+        field = np.ascontiguousarray(field[::-1]) if rev else field
+    return field, st
+
+
+def fuzz_cases(n=60, seed=77):
+    """Seeded random outlines of fuzzlib's kinds 5, 6, 0, 3, 1, 2 in turn, at sizes drawn from 1..40 on each axis; every third is inverse-Y, the bitmap's
+    orientation alternates."""
+    import fuzzlib
+    from msdfgen_amd.shape import autoframe
+    from xformcases import Case
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n):
+        s = fuzzlib._shape(rng, (5, 6, 0, 3, 1, 2)[i % 6], int(rng.integers(0, 2**31)))
+        s.inverse_y = bool(i % 3 == 0)
+        w, h = int(rng.integers(1, 41)), int(rng.integers(1, 41))
+        out.append(Case("fuzz/%d" % i, s, w, h, autoframe(s.bounds(), w, h, min(2., .5*min(w, h))), bool(i & 1)))
+    return out
+
+
+# ---------------------------------------------------------------- crafted fields for the legacy correction (legacyClashTexel, k_ec_legacy)
+
+CRAFTED_SIZES = ((1, 1), (2, 2), (9, 17), (17, 9))                  # (width, height)
+CRAFTED_TX, CRAFTED_TY = .25, .375                                  # exact in float32, and so is their sum: a difference can EQUAL a threshold
+
+
+def _around(v):
+    v = np.float32(v)
+    return [np.nextafter(v, np.float32(0)), v, np.nextafter(v, np.float32(1))]
+
+
+def crafted_fields():
+    """[EcRecord with out=None]: per channel count and size of CRAFTED_SIZES one field of special values. Every channel is drawn from a palette of
+    0, -0, the three thresholds (horizontal, vertical, diagonal) and their float32 neighbours on either side -- next to a 0 they ARE the neighbour
+    difference --, .5, infinities, NaN and +-FLT_MAX (what the float of a mapped -DBL_MAX is where it does not overflow; where it does, -inf). A fifth
+    of the texels is equalized (three equal channels: detectClash's `b0 == b1 && b0 == b2` exit), some are NaN in all channels. On top, planted
+    pairs whose second largest channel difference is exactly a threshold, one ulp less and one ulp more, in each of the three directions."""
+    rng = np.random.default_rng(2024)
+    f32 = np.float32
+    big = np.finfo(np.float32).max
+    palette = np.array([0., 0., 0., -0., .5, .125, 1.]+_around(CRAFTED_TX)+_around(CRAFTED_TY)+_around(CRAFTED_TX+CRAFTED_TY)
+                       + [np.inf, -np.inf, np.nan, big, -big], np.float32)
+    out = []
+    for n in (3, 4):
+        for (w, h) in CRAFTED_SIZES:
+            field = palette[rng.integers(0, len(palette), (h, w, n))]
+            same = rng.uniform(0, 1, (h, w)) < .2
+            field[same, 0:3] = field[same, 0:1]
+            field[rng.uniform(0, 1, (h, w)) < .04] = np.nan
+            if (w, h) == (1, 1):
+                field[0, 0, :3] = np.nan, -np.inf, -0.
+            elif (w, h) == (2, 2):
+                field[0, 0, :3], field[0, 1, :3] = (0., 0., 1.), (CRAFTED_TX, CRAFTED_TX, 0.)
+                field[1, 0, :3], field[1, 1, :3] = (CRAFTED_TY, CRAFTED_TY, 0.), (np.nan, np.inf, -0.)
+            else:
+                for k in range(3):                                  # below, at, above
+                    tx, ty, td = _around(CRAFTED_TX)[k], _around(CRAFTED_TY)[k], _around(CRAFTED_TX+CRAFTED_TY)[k]
+                    field[2*k, 1, :3], field[2*k, 2, :3] = (0., 0., 1.), (tx, tx, 0.)                     # horizontal pair
+                    field[6, 1+3*k, :3], field[7, 1+3*k, :3] = (-0., 0., 1.), (ty, ty, 0.)                 # vertical pair
+                    field[2*k, 5, :3], field[2*k+1, 6, :3] = (0., -0., 1.), (td, td, 0.)                   # diagonal pair
+                field[8, 3, :3], field[8, 4, :3] = (.5, .5, .5), (0., 1., .125)                            # equalized next to unequal
+                field[8, 6, :3], field[8, 7, :3] = (np.nan, 0., 1.), (-np.inf, np.inf, -big)
+            out.append(EcRecord(n, w, h, CRAFTED_TX, CRAFTED_TY, np.ascontiguousarray(field, f32), None))
+    return out
+
+
+def crafted_golden():
+    """[EcRecord]: crafted_fields() as recorded in tests/golden/legacy_crafted.npz with the reference's outputs (tools/make_golden_legacy_crafted.py)."""
+    z = load_npz("legacy_crafted.npz")
+    out = []
+    for k in range(len(z["ec_n"])):
+        n, w, h, o = int(z["ec_n"][k]), int(z["ec_w"][k]), int(z["ec_h"][k]), int(z["ec_off"][k])
+        out.append(EcRecord(n, w, h, float(z["ec_tx"][k]), float(z["ec_ty"][k]), z["ec_in"][o:o+w*h*n].reshape(h, w, n), z["ec_out"][o:o+w*h*n].reshape(h, w, n)))
+    return out
+
+
 # ------------------------------------------------------------------------------- the compiled reference's legacy functions
 
 class _BitmapSection(C.Structure):                                  # BitmapSection<float, N>, core/BitmapRef.hpp:74-81
@@ -126,7 +254,6 @@ _GENERATORS = {1: ("_ZN7msdfgen18generateSDF_legacyE"+_SECTION % 1+_TAIL, False)
                3: ("_ZN7msdfgen19generateMSDF_legacyE"+_SECTION % 3+_TAIL+"NS_21ErrorCorrectionConfigE", True),
                4: ("_ZN7msdfgen20generateMTSDF_legacyE"+_SECTION % 4+_TAIL+"NS_21ErrorCorrectionConfigE", True)}
 _CORRECTION = "_ZN7msdfgen26msdfErrorCorrection_legacyERKNS_13BitmapSectionIfLi%dEEERKNS_7Vector2E"
-DEFAULT_RATIO = 1.11111111111111111
 
 
 class RefLegacy:

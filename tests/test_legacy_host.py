@@ -52,10 +52,11 @@ def test_fixture_covers_what_it_should(gold):
 
 
 def corrected(emu, shape, r, field, stencil=None):
-    """msdfErrorCorrection without the distance check and without overlap support on the legacy field, as generateMSDF_legacy runs it."""
+    """msdfErrorCorrection without the distance check and without overlap support on the legacy field, as generateMSDF_legacy runs it: along the
+    shape's rows (msdfgen.cpp:223)."""
     if r.mode < 3 or r.ec == 0:
         return field
-    return emu.generate(shape, r.mode, r.w, r.h, r.xf, overlap=False, ec_mode=r.ec, ec_dist=0, y_down=r.y_down, correct_only=field, stencil=stencil)
+    return emu.generate(shape, r.mode, r.w, r.h, r.xf, overlap=False, ec_mode=r.ec, ec_dist=0, y_down=r.y_down, correct_only=field, stencil=stencil, shape_rows=True)
 
 
 def test_host_texels_equal_the_recorded_reference(host, gold, emu):
