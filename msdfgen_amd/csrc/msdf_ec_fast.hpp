@@ -15,6 +15,9 @@
 //  * Diagonal pairs: solveQuadratic (sqrt + 2 divisions) is skipped when the quadratic provably has no real root in
 //    [0.005, 0.995] (the reference keeps only roots in (0.01, 0.99); the computed roots are within ~1e-4 of the real ones because
 //    |b| <= 1e12*|a| in that branch).  The extremum parameters tEx (3 divisions) are computed only when a root survives.
+//    A lane visits its in-range roots in the reference's order, but as "first in-range root, second in-range root" rather than by
+//    the solver's index (and the in-range extrema likewise: their flags are OR-ed, any order): same tests per lane, and a wavefront
+//    runs one copy of the body where its lanes' roots sit at different indices (DiagonalRoots).
 //  * Lazy protection (EDGE_PRIORITY with CHECK_DISTANCE_AT_EDGE, the library default): protectAll() precedes the shape pass, so the
 //    stencil byte carries PROTECTED whatever protectCorners / protectEdges found, and the shape classifier never reads their bit.
 //    The base classifier reads it only for a candidate that is no inversion, lies outside the range of its end points and fails the
@@ -132,56 +135,95 @@ MSDF_HD int edgeBetweenTexelsFast(const float *a, const float *b) {
     return 1*(int) edgeBetweenTexelsChannelFast(a, b, 0)+2*(int) edgeBetweenTexelsChannelFast(a, b, 1)+4*(int) edgeBetweenTexelsChannelFast(a, b, 2);
 }
 
+// The roots of a diagonal pair's quadratic that the reference keeps (those in (0.01, 0.99), :296-298), in the order of solveQuadratic's indices, and the
+// extremum parameters of the pair's two channels (:361-365) that lie in (0, 1), likewise in order. Which of x[0] = (-b+sqrt)/(2a) and x[1] = (-b-sqrt)/(2a)
+// is the one in range follows the sign of a: written per index, a wavefront runs both copies of everything behind the test although nearly every lane
+// has one root in range (4.8 % have two) -- hence this compaction: r0 is a lane's first in-range root whatever its index. The same for the extrema.
+struct DiagonalRoots {
+    double r0, r1;      // the m in-range roots
+    double ex0, ex1;    // the ne in-range extremum parameters
+    int m, ne;
+};
+
+// qa, qb, qc: as passed to solveQuadratic. False: no root in range (d.m == 0; the extrema, three divisions, are not computed).
+MSDF_HD bool diagonalRootsInRange(DiagonalRoots &d, double qa, double qb, double qc, float l0, float q0, float l1, float q1) {
+    d.m = 0, d.ne = 0;
+    d.r0 = d.r1 = d.ex0 = d.ex1 = 0;
+    if (!quadraticMayHaveRootInRange(qa, qb, qc))
+        return false;
+    double t[2] = { 0, 0 };
+    const int solutions = solveQuadratic(t, qa, qb, qc);
+    // (no short circuit: all are register values, one branch)
+    const bool in0 = (solutions > 0)&(t[0] > MSDF_ARTIFACT_T_EPSILON)&(t[0] < 1-MSDF_ARTIFACT_T_EPSILON);
+    const bool in1 = (solutions > 1)&(t[1] > MSDF_ARTIFACT_T_EPSILON)&(t[1] < 1-MSDF_ARTIFACT_T_EPSILON);
+    d.m = (int) in0+(int) in1;
+    if (!d.m)
+        return false;
+    d.r0 = in0 ? t[0] : t[1], d.r1 = t[1];
+    const double tEx0 = -.5*l0/q0, tEx1 = -.5*l1/q1;               // :361-365 (l, q of the two channels of the pair)
+    const bool e0 = (tEx0 > 0)&(tEx0 < 1), e1 = (tEx1 > 0)&(tEx1 < 1);
+    d.ne = (int) e0+(int) e1;
+    d.ex0 = e0 ? tEx0 : tEx1, d.ex1 = tEx1;
+    return true;
+}
+
+// One range test of root t (xm: the interpolated median there): over the whole segment, or, for an extremum at tEx, over the part between the
+// extremum and the end point on the root's side (:366-377). The results of a root's tests are OR-ed, so their order is free.
+MSDF_HD int diagonalUnitFlags(const FastCtx &cx, float am, float dm, const float *a, const float *l, const float *q, double t, double tEx, bool extremum, float xm) {
+    if (!extremum)
+        return rangeTest2(cx, 0, 1, t, am, dm, xm);
+    double tEnd0 = 0, tEnd1 = 1;
+    float em0 = am, em1 = dm;
+    const float ex = interpolatedMedianQuad(a, l, q, tEx);
+    if (tEx > t)
+        tEnd1 = tEx, em1 = ex;
+    else
+        tEnd0 = tEx, em0 = ex;
+    return rangeTest2(cx, tEnd0, tEnd1, t, em0, em1, xm);
+}
+
+// What the accumulated flags of root t do to the pair's verdict; true: ERROR, the pair is decided (the reference returns there, :300-326).
+template <class Sink>
+MSDF_HD bool diagonalRootVerdict(const FastCtx &cx, int rangeFlags, double t, int &verdict, Sink &sink) {
+    const int v = judge(rangeFlags);
+    verdict |= v;
+    if (v&EC_V_CHECK) {
+        const bool held = (verdict&EC_V_COND) != 0;
+        if (held)
+            verdict |= EC_V_HELD;
+        if (held == (cx.order == EC_ORDER_LAZY_HELD))
+            sink(t);
+    }
+    return (verdict&EC_V_ERROR) != 0;
+}
+
 // One diagonal channel pair (:291-327) with lazy extremum parameters. Returns judge() of the accumulated flags, OR-ed over roots;
 // candidates that need the distance check are handed to `sink(t)`. Lazy order: a candidate at or after a conditional artifact of this
 // pair is held back (EC_V_HELD) -- were the texel unprotected, the eager order would have returned ERROR at that artifact -- and
 // handed over by the EC_ORDER_LAZY_HELD visit, which hands over nothing else.
+// One pass per in-range root, a lane's roots in index order as before; in a wavefront the first pass is dense and the second runs only if some lane
+// has both roots in range. Inside a pass: the first in-range extremum, then the second if a lane has two.
 template <class Sink>
 MSDF_HD int diagonalPairFast(const FastCtx &cx, float am, float dm, const float *a, const float *l, const float *q,
                              float dA, float dBC, float dD, float l0, float q0, float l1, float q1, Sink &sink) {
     const double qa = dD-dBC+dA, qb = dBC-dA-dA, qc = dA;   // float expressions promoted, exactly as passed at :295
-    if (!quadraticMayHaveRootInRange(qa, qb, qc))
+    DiagonalRoots d;
+    if (!diagonalRootsInRange(d, qa, qb, qc, l0, q0, l1, q1))
         return 0;
-    double t[2];
-    const int solutions = solveQuadratic(t, qa, qb, qc);
     int verdict = 0;
-    for (int i = 0; i < solutions; ++i) {
-        if (t[i] > MSDF_ARTIFACT_T_EPSILON && t[i] < 1-MSDF_ARTIFACT_T_EPSILON) {
-            const float xm = interpolatedMedianQuad(a, l, q, t[i]);
-            int rangeFlags = rangeTest2(cx, 0, 1, t[i], am, dm, xm);
-            const double tEx0 = -.5*l0/q0, tEx1 = -.5*l1/q1;               // :361-365 (l, q of the two channels of the pair)
-            if (tEx0 > 0 && tEx0 < 1) {
-                double tEnd0 = 0, tEnd1 = 1;
-                float em0 = am, em1 = dm;
-                const float ex = interpolatedMedianQuad(a, l, q, tEx0);
-                if (tEx0 > t[i])
-                    tEnd1 = tEx0, em1 = ex;
-                else
-                    tEnd0 = tEx0, em0 = ex;
-                rangeFlags |= rangeTest2(cx, tEnd0, tEnd1, t[i], em0, em1, xm);
-            }
-            if (tEx1 > 0 && tEx1 < 1) {
-                double tEnd0 = 0, tEnd1 = 1;
-                float em0 = am, em1 = dm;
-                const float ex = interpolatedMedianQuad(a, l, q, tEx1);
-                if (tEx1 > t[i])
-                    tEnd1 = tEx1, em1 = ex;
-                else
-                    tEnd0 = tEx1, em0 = ex;
-                rangeFlags |= rangeTest2(cx, tEnd0, tEnd1, t[i], em0, em1, xm);
-            }
-            const int v = judge(rangeFlags);
-            verdict |= v;
-            if (v&EC_V_CHECK) {
-                const bool held = (verdict&EC_V_COND) != 0;
-                if (held)
-                    verdict |= EC_V_HELD;
-                if (held == (cx.order == EC_ORDER_LAZY_HELD))
-                    sink(t[i]);
-            }
-            if (verdict&EC_V_ERROR)
-                return verdict;
-        }
+    MSDF_UNROLL
+    for (int i = 0; i < 2; ++i) {
+        if (i >= d.m)
+            break;
+        const double t = i ? d.r1 : d.r0;
+        const float xm = interpolatedMedianQuad(a, l, q, t);
+        int rangeFlags = diagonalUnitFlags(cx, am, dm, a, l, q, t, 0, false, xm);
+        if (d.ne > 0)
+            rangeFlags |= diagonalUnitFlags(cx, am, dm, a, l, q, t, d.ex0, true, xm);
+        if (d.ne > 1)
+            rangeFlags |= diagonalUnitFlags(cx, am, dm, a, l, q, t, d.ex1, true, xm);
+        if (diagonalRootVerdict(cx, rangeFlags, t, verdict, sink))
+            return verdict;
     }
     return verdict;
 }

@@ -1227,7 +1227,7 @@ k_ec_params(EcGlyphParams *out, BatchView batch, const MsdfHipGlyph *glyphs, Msd
 // the stencil byte [g][h][w] (native rows). Candidates whose verdict needs an exact shape-distance query are appended to `cands`
 // and judged by k_ec_query; a texel with a cheaply decided ERROR never needs them (the flag is an OR).
 #ifndef MSDF_EC_FAST_WAVES_PER_SIMD
-#define MSDF_EC_FAST_WAVES_PER_SIMD 7   // lazy instantiation 67 VGPRs / 18 scalar registers parked in vector lanes, eager 63 / 1; no vector spills, no scratch (tests/test_ec_fast_isa_budget.py); the kernel's 5.6 KB of LDS allow 7 wavefronts per SIMD anyway. Correction pass on the distinct-glyph set: 8 -> 1.94 ms, 7 -> 1.90, 6 -> 1.90
+#define MSDF_EC_FAST_WAVES_PER_SIMD 7   // lazy instantiation 65 VGPRs / 4 scalar registers parked in vector lanes, eager 60 / 0; no vector spills, no scratch (tests/test_ec_fast_isa_budget.py); the kernel's 5.6 KB of LDS allow 7 wavefronts per SIMD anyway. Correction pass on the distinct-glyph set: 8 -> 1.94 ms, 7 -> 1.90, 6 -> 1.90
 #endif
 // LDS of k_ec_fast per wavefront: 10x10 halo tile of the field | per-texel verdict words | item count | item queue (5.6 KB for msdf).
 enum { EC_HALO = TILE+2, EC_QUEUE_CAP = WAVE*24, EC_PROTECT_QUEUE_CAP = WAVE*8 };
@@ -1285,7 +1285,7 @@ struct EcPushProtect {
     __device__ void operator()(int m) { queue[atomicAdd(count, 1)] = (unsigned short) (lane|m<<6); }
 };
 
-// ORDER: 1 the lazy order, 0 the eager one -- k_ec_fast has an instantiation of each and the host picks by the configuration (67 / 63 VGPRs, 18 / 1 scalar
+// ORDER: 1 the lazy order, 0 the eager one -- k_ec_fast has an instantiation of each and the host picks by the configuration (65 / 60 VGPRs, 4 / 0 scalar
 // registers parked in vector lanes, all outside the queue loops) -- or -1: decided here, one body for k_single_call.
 // SHAPE_ROWS: EcParams::shapeRows, the legacy generators' correction (eager order only: it runs without the distance check). An instantiation of its own,
 // so that the kernels of the modern entry points stay what they were.
