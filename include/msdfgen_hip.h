@@ -399,6 +399,33 @@ int msdfhip_generate_stream_csr_prepared_oriented_framed(int device, int mode, i
                                                          const MsdfHipGlyph *glyphs, float *out, size_t out_floats, uint8_t *atlas, size_t atlas_bytes,
                                                          uint8_t *stencil, const MsdfHipConfig *cfg, const MsdfHipPrepConfig *prep, const uint64_t *seeds,
                                                          const MsdfHipOrientConfig *orient, const MsdfHipFrameConfig *frame);
+/* Box sizes on the device: Shape::getBounds(border, miterLimit, polarity) WITH border and miters (core/Shape.cpp:99-115, core/Contour.cpp:39-55), and from
+ * it the box an atlas generator gives every glyph at one common scale -- its size in texels and the transformation that puts the glyph into it -- so that
+ * the field of a sharp corner is not cut off by the box edge and the caller never walks the geometry on the host.
+ * Which arrays the two parts read: the plain bounds are those of msdfhip_batch_bounds (batches made by msdfhip_batch_create_prepared[_oriented]: fixed after
+ * their normalize); the miters are taken over the edges the batch HOLDS (for such a batch the oriented, coloured ones) -- what a caller gets who keeps
+ * getBounds() from load time and calls Shape::boundMiters on the shape it is about to render. For batches made from prepared arrays that is exactly
+ * getBounds(border, miter_limit, polarity) of those arrays, bit for bit. The reference's gates stay: nothing changes unless border > 0, no miter is taken
+ * unless also miter_limit > 0; no argument is invalid. Host double[n_glyphs*4] = l, b, r, t. Synchronous. */
+int msdfhip_batch_bounds_miters(const MsdfHipBatch *batch, double border, double miter_limit, int polarity, double *bounds);
+/* The boxes. With s = scale, (lo, hi) = the range in shape units (a pixel range: range_lower/s, range_upper/s) and l, b, r, t the bounds above with
+ * border = -lo, per axis (l, r -> w, tx; b, t -> h, ty):
+ *   aligned (the texel grid passes through the shape's origin)   sl = floor(s*l - .5), sr = ceil(s*r + .5): w = sr - sl, tx = -sl/s
+ *   otherwise (the glyph is centred)                             d = s*(r - l): w = ceil(d) + 1, tx = -l + (.5*(w - d))/s
+ * and xf[g] = s, s, tx, ty, 1/(hi - lo), -lo: the six doubles of MsdfHipGlyph.xf as they are. A glyph whose PLAIN bounds are empty (l >= r or b >= t: no
+ * edges, a lone horizontal or vertical line) has no box: sizes 0 x 0, tx = ty = 0 -- msdfhip_batch_generate_sized wants at least 1 x 1, so give such a
+ * glyph one texel or leave it out. sizes: host int32[n_glyphs*2] = w, h; xf: host double[n_glyphs*6]; bounds: host double[n_glyphs*4], the extended bounds,
+ * or NULL. Synchronous. A bad field of the config fails with MSDFHIP_ERR_INVALID before the device is touched; so does, after the launch, a box with a side
+ * that is not a number or beyond 2^30 texels (nothing is written then). */
+typedef struct MsdfHipBoxConfig {
+    double scale;                      /* texels per shape unit, both axes; > 0, finite */
+    int32_t range_mode;                /* 0 unit range, 1 pixel range */
+    double range_lower, range_upper;   /* lower < upper, lower <= 0, finite */
+    double miter_limit;                /* <= 0: no miters */
+    int32_t polarity;                  /* as Contour::boundMiters: > 0 / < 0 only the corners turning one way, 0 every corner */
+    int32_t align_x, align_y;          /* 0 or 1: pixel-align the origin per axis */
+} MsdfHipBoxConfig;
+int msdfhip_batch_boxes(const MsdfHipBatch *batch, const MsdfHipBoxConfig *cfg, int32_t *sizes, double *xf, double *bounds);
 /* Diagnostics: after an error-correction pass, counts[0] = 1 if some glyph's candidate segment overflowed (those glyphs were redone by
  * the full per-texel pipeline), counts[1+g] = deferred distance checks pushed for glyph g. counts holds n_glyphs+1 entries. */
 int msdfhip_batch_candidate_counts(const MsdfHipBatch *batch, uint32_t *counts);

@@ -144,6 +144,27 @@ class FrameConfig:
         return _lib.FrameConfig(self.range_mode, int(self.scale is not None), self.range[0], self.range[1], sx, sy)
 
 
+class BoxConfig:
+    """Box sizes on the device (msdfgen_hip.h, MsdfHipBoxConfig): every glyph at ONE scale (texels per shape unit) in a box of its own, as an atlas generator
+    packs a font. Exactly one of px_range and range (in shape units): a width (symmetrical, Range(w) = (-w/2, w/2)) or a (lower, upper) pair with
+    lower <= 0. The box holds Shape::getBounds(border=-lower, miter_limit, polarity) of the glyph (core/Shape.cpp:104-115): miter_limit > 1 pushes it out
+    where a corner is acute, 0 takes no miters; polarity as Contour::boundMiters (core/Contour.cpp:45: the sign a corner's turn must have, 0 takes
+    every corner). align: (x, y) -- put the texel grid through the shape's origin along that axis instead of centring the glyph."""
+
+    def __init__(self, scale, px_range=None, range=None, miter_limit=0., polarity=1, align=(False, False)):
+        if (px_range is None) == (range is None):
+            raise ValueError("BoxConfig takes exactly one of px_range and range")
+        r = px_range if px_range is not None else range
+        self.scale = float(scale)
+        self.range_mode = 1 if px_range is not None else 0
+        self.range = (-.5*float(r), .5*float(r)) if np.isscalar(r) else (float(r[0]), float(r[1]))     # Range.hpp:14
+        self.miter_limit, self.polarity = float(miter_limit), int(polarity)
+        self.align = (bool(align[0]), bool(align[1]))
+
+    def c_struct(self) -> _lib.BoxConfig:
+        return _lib.BoxConfig(self.scale, self.range_mode, self.range[0], self.range[1], self.miter_limit, self.polarity, int(self.align[0]), int(self.align[1]))
+
+
 def _c_config(config, y_orientation=None) -> _lib.Config:
     """y_orientation: the OUTPUT bitmap's orientation; the reference keeps the stencil's rows upward whatever it is
     (core/MSDFErrorCorrection.cpp:122,192,415), which is what MsdfHipConfig.stencil_y_down tells the device -- set on every path that
@@ -525,12 +546,29 @@ class GlyphBatch:
         _lib.check(_lib.load().msdfhip_batch_windings(self._handle, _lib.ptr(out, _lib._ip)))
         return out[:self.shapes.n_contours]
 
-    def bounds(self):
+    def bounds(self, border=0., miter_limit=0., polarity=0):
         """Shape::getBounds (core/Shape.cpp:104-115) of every glyph as the device computes it: (G, 4) float64 rows l, b, r, t; an empty glyph keeps
-        the reference's (1e240, 1e240, -1e240, -1e240). For from_raw batches: of the normalized shape, before the colouring (main.cpp:1125-1132)."""
+        the reference's (1e240, 1e240, -1e240, -1e240). For from_raw batches: of the normalized shape, before the colouring (main.cpp:1125-1132).
+        border, miter_limit, polarity: the reference's getBounds(border, miterLimit, polarity) (msdfhip_batch_bounds_miters) -- with border > 0 the bounds
+        grow by it, and with miter_limit > 0 as well they hold the miter of every corner that passes the polarity test (core/Contour.cpp:39-55; for
+        from_raw batches the miters are those of the edges the batch holds, oriented and coloured). The defaults are the plain bounds."""
         out = np.zeros((max(self.n_glyphs, 1), 4), np.float64)
-        _lib.check(_lib.load().msdfhip_batch_bounds(self._handle, _lib.ptr(out, _lib._dp)))
+        if border == 0 and miter_limit == 0 and polarity == 0:
+            _lib.check(_lib.load().msdfhip_batch_bounds(self._handle, _lib.ptr(out, _lib._dp)))
+        else:
+            _lib.check(_lib.load().msdfhip_batch_bounds_miters(self._handle, float(border), float(miter_limit), int(polarity), _lib.ptr(out, _lib._dp)))
         return out[:self.n_glyphs]
+
+    def boxes(self, cfg: "BoxConfig"):
+        """The box of every glyph at cfg.scale (msdfhip_batch_boxes), computed on the device: (sizes (G, 2) int32 rows w_g, h_g; xf (G, 6) rows sx, sy, tx, ty,
+        mapScale, mapTranslate -- MsdfHipGlyph.xf as it is, for descriptors_sized(raw_xf=xf); bounds (G, 4): getBounds with border and miters, which the
+        box contains). A 0 x 0 box means "no box": the glyph has no edges or is a lone horizontal or vertical line. generate_sized wants every box at
+        least 1 x 1: pass np.maximum(sizes, 1), or a batch without such glyphs."""
+        n = max(self.n_glyphs, 1)
+        sizes, xf, bounds = np.zeros((n, 2), np.int32), np.zeros((n, 6), np.float64), np.zeros((n, 4), np.float64)
+        c = cfg.c_struct()
+        _lib.check(_lib.load().msdfhip_batch_boxes(self._handle, C.byref(c), _lib.ptr(sizes, _lib._ip), _lib.ptr(xf, _lib._dp), _lib.ptr(bounds, _lib._dp)))
+        return sizes[:self.n_glyphs], xf[:self.n_glyphs], bounds[:self.n_glyphs]
 
     def frame(self, width, height, frame: "FrameConfig", descriptors=None, stream=None):
         """The reference CLI's -autoframe per glyph on the device (msdfhip_batch_frame): writes xf of `descriptors` (default: fresh ones for packed
@@ -645,12 +683,15 @@ class GlyphBatch:
         sizes = np.asarray(sizes, np.int64).reshape(-1, 2)
         return np.concatenate([[0], np.cumsum(sizes[:, 0]*sizes[:, 1]*channels)]).astype(np.int64)
 
-    def descriptors_sized(self, xfs, sizes, channels, y_orientation=Y_UPWARD, out_offsets=None, row_strides=None):
+    def descriptors_sized(self, xfs, sizes, channels, y_orientation=Y_UPWARD, out_offsets=None, row_strides=None, raw_xf=None):
         """descriptors() for per-glyph boxes: sizes (G, 2) rows w_g, h_g. Default placement: tiles packed one after another, glyph g [h_g][w_g][N] at
-        packed_offsets(sizes, channels)[g] with row stride w_g*N; or an atlas placement via out_offsets / row_strides (per glyph, in floats, may be negative)."""
+        packed_offsets(sizes, channels)[g] with row stride w_g*N; or an atlas placement via out_offsets / row_strides (per glyph, in floats, may be negative).
+        raw_xf: (G, 6) rows sx, sy, tx, ty, mapScale, mapTranslate stored as they are (what boxes() returns); xfs is then not read."""
         sizes = self._sizes(sizes)
         d = np.zeros(self.n_glyphs, _lib.GLYPH_DTYPE)
-        if xfs is not None:
+        if raw_xf is not None:
+            d["xf"] = np.ascontiguousarray(raw_xf, np.float64).reshape(self.n_glyphs, 6)
+        elif xfs is not None:
             xfs = np.ascontiguousarray(xfs, np.float64).reshape(self.n_glyphs, 6)
             d["xf"][:, :4] = xfs[:, :4]
             d["xf"][:, 4] = np.float64(1)/(xfs[:, 5]-xfs[:, 4])  # DistanceMapping.cpp:13

@@ -288,6 +288,7 @@ struct MsdfHipBatch : ShapeData {
     bool serialClasses = false;       // launch the glyph classes one after the other on the caller's stream (host-output pipeline: its chunks overlap instead)
     mutable WorkBuffer<double> dBounds;   // [nGlyphs][4] l, b, r, t of Shape::getBounds (msdfhip_batch_bounds / _frame; allocated on first need, the batch's own)
     bool boundsFixed = false;         // dBounds were taken at creation from the normalized edges (batches prepared from raw outlines: the arrays they keep are the coloured ones)
+    mutable WorkBuffer<double> dBoxes;    // what k_box writes (msdfhip_batch_bounds_miters / _boxes): ext [n][4], xf [n][6], then wh [n][2] int32; allocated on first need
     mutable Workspace work;
     mutable ClassPlan plan;           // the classes of work.bucket
     void onDevice(int d) { device = work.device = d; }
@@ -1325,6 +1326,19 @@ int checkFrameConfig(const MsdfHipFrameConfig *frame, int w, int h, const char *
     if ((w > 0 && h > 0) && (extent.x <= 0 || extent.y <= 0))
         return fail(MSDFHIP_ERR_INVALID, "%s: cannot fit the specified pixel range (%g to %g) into %d x %d", who, frame->range_lower, frame->range_upper, w, h);
     *out = f, *framed = true;
+    return MSDFHIP_OK;
+}
+
+// The fields of a box configuration (msdf_frame.hpp: planBox), refused like a bad frame: before anything is read or the device is touched.
+int checkBoxConfig(const MsdfHipBoxConfig *cfg, const char *who, BoxParams *out, double *border) {
+    if (!cfg)
+        return fail(MSDFHIP_ERR_INVALID, "%s: NULL config", who);
+    switch (planBox(cfg->scale, cfg->range_mode, cfg->range_lower, cfg->range_upper, cfg->align_x, cfg->align_y, out, border)) {
+        case BOX_CONFIG_SCALE: return fail(MSDFHIP_ERR_INVALID, "%s: scale %g (positive and finite)", who, cfg->scale);
+        case BOX_CONFIG_RANGE_MODE: return fail(MSDFHIP_ERR_INVALID, "%s: range_mode %d (0 unit range, 1 pixel range)", who, cfg->range_mode);
+        case BOX_CONFIG_RANGE: return fail(MSDFHIP_ERR_INVALID, "%s: range %g to %g (finite, range_lower < range_upper, range_lower <= 0)", who, cfg->range_lower, cfg->range_upper);
+        case BOX_CONFIG_ALIGN: return fail(MSDFHIP_ERR_INVALID, "%s: align (%d, %d) (0 or 1 each)", who, cfg->align_x, cfg->align_y);
+    }
     return MSDFHIP_OK;
 }
 
@@ -4073,6 +4087,87 @@ int msdfhip_tiles_to_bytes_sized(const float *dTiles, int nGlyphs, const int32_t
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(stream));                        // (the staging vector and the device buffer of this call go with it)
+    return MSDFHIP_OK;
+}
+
+} // extern "C"
+
+// ---- box sizes on the device: msdfhip_batch_bounds_miters, msdfhip_batch_boxes ----------------------------------------------------------------------
+//
+// One k_box launch (msdf_frame.hpp) and one copy back. The ONLY code that names k_box, behind the sized twins: it is instantiated last (forDistanceVariant).
+
+namespace {
+
+// k_box over the batch on the NULL stream into b->dBoxes, read back into `host` ([n][4] ext, [n][6] xf, [n][2] int32 wh; the last two only with `box`).
+// Synchronous. The plain bounds land in b->dBounds on the way, as msdfhip_batch_bounds leaves them.
+int runBoxes(const MsdfHipBatch *b, double border, double miterLimit, int polarity, const BoxParams *box, std::vector<double> &host) {
+    const size_t n = (size_t) b->nGlyphs;
+    HIPCHK(hipDeviceSynchronize());                              // (the edge arrays may still be written by work the caller queued)
+    HIPCHK(b->dBounds.ensure(4*n));
+    HIPCHK(b->dBoxes.ensure(11*n));
+    const EdgeArrays edges = { b->dPoints.ptr, b->dTypes.ptr, b->dColors.ptr };
+    double *ext = b->dBoxes.ptr, *xf = ext+4*n;
+    int32_t *wh = reinterpret_cast<int32_t *>(xf+6*n);
+    const BoxParams none = { 1., 0., 1., 0, 0 };
+    if (box)
+        hipLaunchKernelGGL(k_box<true>, dim3((unsigned) n), dim3(WAVE), 0, (hipStream_t) NULL, edges, b->dGlyphContourOffsets.ptr, b->dContourOffsets.ptr, b->nGlyphs, b->dBounds.ptr,
+                           b->boundsFixed ? 1 : 0, border, miterLimit, polarity, *box, ext, wh, xf);
+    else
+        hipLaunchKernelGGL(k_box<false>, dim3((unsigned) n), dim3(WAVE), 0, (hipStream_t) NULL, edges, b->dGlyphContourOffsets.ptr, b->dContourOffsets.ptr, b->nGlyphs, b->dBounds.ptr,
+                           b->boundsFixed ? 1 : 0, border, miterLimit, polarity, none, ext, (int32_t *) NULL, (double *) NULL);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(NULL));
+    host.resize(11*n);
+    HIPCHK(hipMemcpy(host.data(), b->dBoxes.ptr, sizeof(double)*(box ? 11 : 4)*n, hipMemcpyDeviceToHost));   // (in stream order behind the kernel)
+    return MSDFHIP_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int msdfhip_batch_bounds_miters(const MsdfHipBatch *b, double border, double miterLimit, int polarity, double *bounds) {
+    if (!b || !bounds)
+        return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_bounds_miters: NULL argument");
+    if (b->nGlyphs == 0)
+        return MSDFHIP_OK;
+    int rc = ensureDevice(b->device);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    std::vector<double> host;
+    rc = runBoxes(b, border, miterLimit, polarity, NULL, host);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    memcpy(bounds, host.data(), sizeof(double)*4*(size_t) b->nGlyphs);
+    return MSDFHIP_OK;
+}
+
+int msdfhip_batch_boxes(const MsdfHipBatch *b, const MsdfHipBoxConfig *cfg, int32_t *sizes, double *xf, double *bounds) {
+    BoxParams box;
+    double border = 0;
+    int rc = checkBoxConfig(cfg, "msdfhip_batch_boxes", &box, &border);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    if (!b || !sizes || !xf)
+        return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_boxes: NULL argument");
+    if (b->nGlyphs == 0)
+        return MSDFHIP_OK;
+    rc = ensureDevice(b->device);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    std::vector<double> host;
+    rc = runBoxes(b, border, cfg->miter_limit, cfg->polarity, &box, host);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    const size_t n = (size_t) b->nGlyphs;
+    const int32_t *wh = reinterpret_cast<const int32_t *>(host.data()+10*n);
+    for (size_t k = 0; k < 2*n; ++k)
+        if (wh[k] < 0)
+            return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_boxes: the box of glyph %zu is not a number or has a side beyond %d texels at scale %g", k/2, (int) BOX_MAX_SIDE, cfg->scale);
+    memcpy(sizes, wh, sizeof(int32_t)*2*n);
+    memcpy(xf, host.data()+4*n, sizeof(double)*6*n);
+    if (bounds)
+        memcpy(bounds, host.data(), sizeof(double)*4*n);
     return MSDFHIP_OK;
 }
 

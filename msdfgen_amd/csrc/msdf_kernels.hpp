@@ -2686,4 +2686,45 @@ __global__ void k_tiles_to_bytes_sized(const float *tiles, const MsdfHipGlyph *g
     }
 }
 
+// Shape::getBounds(border, miterLimit, polarity) of every glyph and the box an atlas gives it (msdf_frame.hpp), one wavefront per glyph, lanes = edges:
+// boundsGlyphWave (with haveBounds the plain bounds are read from bounds[g] instead: a batch prepared from raw outlines took them before its colouring, and
+// `edges` are then its coloured edges), mitersGlyphWave, and with BOX boxGlyph by lane 0. Writes bounds[g][4] (unless haveBounds), ext[g][4] and with BOX
+// wh[g][2], xf[g][6]. A template like the sized twins above and named, like them, only at the end of msdf_capi.hip: it is instantiated behind everything the
+// code object held, so that no other kernel's code moves.
+template <bool BOX>
+__global__ void __launch_bounds__(WAVE) k_box(EdgeArrays edges, const int32_t *gco, const int32_t *co, int nGlyphs, double *bounds, int haveBounds, double border,
+                                              double miterLimit, int polarity, BoxParams box, double *ext, int32_t *wh, double *xf) {
+    __shared__ double part[4*WAVE], run[4], plain[4];
+    const int g = blockIdx.x;
+    if (g >= nGlyphs)
+        return;
+    WaveCtx ctx;
+    ctx.lane = threadIdx.x;
+    const BoundsScratch s = { part, run };
+    if (!haveBounds)
+        boundsGlyphWave(ctx, edges, co, gco[g], gco[g+1], s);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 4; ++k) {
+            if (haveBounds)
+                run[k] = bounds[4*(size_t) g+k];
+            else
+                bounds[4*(size_t) g+k] = run[k];
+            plain[k] = run[k];
+        }
+    ctx.sync();
+    mitersGlyphWave(ctx, edges, co, gco[g], gco[g+1], border, miterLimit, polarity, s);
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 4; ++k)
+            ext[4*(size_t) g+k] = run[k];
+        if (BOX) {
+            int32_t size[2];
+            double t[6];
+            boxGlyph(box, plain, run, size, t);
+            wh[2*(size_t) g] = size[0], wh[2*(size_t) g+1] = size[1];
+            for (int k = 0; k < 6; ++k)
+                xf[6*(size_t) g+k] = t[k];
+        }
+    }
+}
+
 } // namespace msdfhip

@@ -51,6 +51,12 @@ class FrameConfig(C.Structure):
                 ("scale_x", C.c_double), ("scale_y", C.c_double)]
 
 
+class BoxConfig(C.Structure):
+    """MsdfHipBoxConfig."""
+    _fields_ = [("scale", C.c_double), ("range_mode", C.c_int32), ("range_lower", C.c_double), ("range_upper", C.c_double), ("miter_limit", C.c_double),
+                ("polarity", C.c_int32), ("align_x", C.c_int32), ("align_y", C.c_int32)]
+
+
 class Glyph(C.Structure):
     """MsdfHipGlyph."""
     _fields_ = [("xf", C.c_double*6), ("out_offset", C.c_int64), ("row_stride", C.c_int32), ("flip", C.c_int32)]
@@ -147,6 +153,8 @@ _PROTOS = {
     "msdfhip_batch_error_correction_legacy": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_double, C.c_double, _vp]),
     "msdfhip_batch_generate_sized": (C.c_int, [_vp, C.c_int, _ip, _vp, _vp, _vp, _vp, C.POINTER(Config), _vp]),
     "msdfhip_tiles_to_bytes_sized": (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_int64), C.c_int, _vp, _vp, _vp]),
+    "msdfhip_batch_bounds_miters": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, _dp]),
+    "msdfhip_batch_boxes": (C.c_int, [_vp, C.POINTER(BoxConfig), _ip, _dp, _dp]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_PROTOS))
