@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- MSDF glyphs/s (64x64, fp32 tiles) on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--glyphs G] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--glyphs G] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no torchrun environment re-launches itself under torch.distributed.run with N ranks (one per GPU) and fails
@@ -27,10 +27,14 @@ DIR/tiles_nonfinite.npy (-inf, +inf, NaN texels), so that no difference between 
 only, so two builds run with the same arguments can be compared file for file. With --inprocess the sample also holds the 8-bit atlas cells of the same glyphs (atlas_cells.npy,
 as float32).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
-  roofline      dominant pass = the distance field (HIP-event timed inside this process, algorithmic bytes per SURVEY.md 8d)
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the driver's contract fields plus
+  roofline      dominant pass = the distance field (HIP events inside the timed steps, algorithmic bytes per SURVEY.md 8d): arithmetic on what the
+                steps measured and on the committed counter profile, no run of its own
+--full adds everything that takes runs of its own, after the timed steps and outside them (--no-extras / --no-cpu-baseline take parts of it away again):
+  quality       estimateSDFError of the tiles the last timed step wrote
   end_to_end    host CSR arrays -> H2D -> kernels incl. error correction -> D2H into pinned caller-owned tiles (the reference's contract,
                 core/msdfgen.cpp:52-76), and the same with 8-bit output; measured after the timed steps
+  strong_scaling, two_batches_in_flight   config 4 rehearsed on one GPU; the step with two batches on two streams
   secondary     the Basic-Latin set (94 shapes tiled to G glyphs): round 1's workload, for continuity
   cpu_baseline  the compiled reference (or the oracle port) on the host cores, bounded sample
 """
@@ -545,8 +549,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--glyphs", type=int, default=8192, help="glyph tiles per GPU per step")
     ap.add_argument("--size", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip end_to_end / secondary / quality (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure and check everything beyond the headline figure: quality, end_to_end, "
+                                                         "strong_scaling, two_batches_in_flight, secondary, cpu_baseline (a plain run does none of it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without end_to_end / strong_scaling / secondary / quality")
     ap.add_argument("--simple-combiner", action="store_true", help="experiment: overlapSupport=false (NOT the headline config)")
     ap.add_argument("--mock", action="store_true", help="CPU rehearsal of the multi-rank control path (gloo, no kernels); used by the tests")
     ap.add_argument("--same-device", action="store_true", help="rehearsal of the N > 1 path on a ONE-GPU box: every rank uses cuda:0 and the process "
@@ -562,6 +568,7 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    extras, cpu_leg = args.full and not args.no_extras, args.full and not args.no_cpu_baseline   # runs of their own: only under --full
 
     if args.inprocess:
         return inprocess(args)
@@ -662,7 +669,7 @@ def main():
                                    "(%.1f edges, %.2f contours per glyph; tests/golden/dejavu8192.npz, every tile pinned to the compiled reference); "
                                    "overlapSupport=true, error correction EDGE_PRIORITY+CHECK_DISTANCE_AT_EDGE (library defaults); "
                                    "step = digest + distance field + error correction, inputs/outputs resident in HBM -- `value` is this RESIDENT step (bench contract); "
-                                   "SURVEY 8(d)'s end-to-end rate from Shape objects to caller bitmaps is `end_to_end_metric` of this line" % (
+                                   "SURVEY 8(d)'s end-to-end rate from Shape objects to caller bitmaps is `end_to_end_metric` of the --full line" % (
                                        w, h, args.glyphs, batch.n_edges/batch.n_glyphs, batch.n_contours/batch.n_glyphs),
                        "glyphs_per_gpu": batch.n_glyphs if args.strong else args.glyphs, "tile": [w, h], "mode": "msdf",
                        "parallelism": ("glyph-sharded x%d, dealt by modelled cost (msdfgen_amd.shard.partition_dealt), no collective; rank 0 owns %d glyphs of 8192%s" % (
@@ -697,14 +704,14 @@ def main():
         }
         if per_rank is not None:
             res["per_rank"] = per_rank
-        if not args.no_extras:
+        if extras:
             # outside the timed region: the reference-defined quality of what was just rendered (estimateSDFError, core/sdf-error-estimation.h)
             err = gb.estimate_sdf_error(out, xfs)
             res["quality"] = {"metric": "estimateSDFError of the rendered tiles (1 scanline per row, non-zero fill), evaluated on the device",
                               "mean": float(err.mean()), "max": float(err.max())}
     gb.close()
     del out
-    if world > 1 and not args.no_extras:
+    if world > 1 and extras:
         # every rank runs the host-output pipeline of ITS shard at the same time (host CSR -> H2D -> kernels -> D2H into pinned memory): the
         # contention for PCIe / host memory that the resident number cannot show. Aggregate = all glyphs / slowest rank.
         dist.barrier()
@@ -722,9 +729,9 @@ def main():
                                  "note": "all %d ranks run msdfhip_batch_create + msdfhip_batch_generate_host / _bytes_host on their shards SIMULTANEOUSLY "
                                          "(barrier, then each rank its own median of 2 runs); aggregate = all glyphs / slowest rank" % world,
                                  "rank0": mine}
-    if rank == 0 and world == 1 and not args.no_extras and args.strong:
+    if rank == 0 and world == 1 and extras and args.strong:
         res["strong_scaling"] = strong_scaling_one_gpu(M, torch, lib, dev, stream, cfg, steps=max(3, args.steps//4), only=args.strong_set)
-    if rank == 0 and world == 1 and not args.no_extras and not args.strong:
+    if rank == 0 and world == 1 and extras and not args.strong:
         res["end_to_end"] = end_to_end(M, batch, xfs, w, h)
         latin, lxf = load_latin()
         if w != 64:
@@ -763,7 +770,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_leg:
             res["cpu_baseline"] = cpu_baseline(batch, xfs, w, h)
         _restore_stdout(saved_stdout)                                # (everything the runtimes printed meanwhile went to stderr)
         print(json.dumps(res), flush=True)
