@@ -203,6 +203,57 @@ MSDF_HD double median(double a, double b, double c) { return dmax(dmin(a, b), dm
 MSDF_HD float fmin_(float a, float b) { return b < a ? b : a; }
 MSDF_HD float fmax_(float a, float b) { return a < b ? b : a; }
 MSDF_HD float medianf(float a, float b, float c) { return fmax_(fmin_(a, b), fmin_(fmax_(a, b), c)); }
+// The hardware's median, v_med3_f32 (one instruction where medianf is four compares and four selects), for the correction sweep of k_ec_fast.
+//   * Three non-NaN inputs: the ISA returns max(S1, S2) if S0 is the largest, max(S0, S2) if S1 is, else max(S0, S1) -- the middle one of the
+//     three, the value medianf returns (both pick one of the inputs; with ties either pick is the same number). What can differ is the SIGN OF A
+//     ZERO result: the hardware's max orders -0 below +0, medianf's `<` does not tell them apart and keeps the operand its position favours
+//     (medianf(-0, +0, +0) is -0, the instruction gives +0).
+//   * A NaN input: the instruction returns min3 of the inputs (the smallest non-NaN one); medianf returns its first operand for a NaN in the first or
+//     second place, and for a NaN in the third the larger of the other two. They differ as values.
+// So med3f stands for medianf only where no input is a NaN and nothing can tell a zero's sign: k_ec_fast votes on the first per wavefront
+// (msdf_kernels.hpp: EC_MED3_BOUND) and msdf_ec_fast.hpp lists the consumers for the second. The host build runs the ISA's definition, so that
+// tests/test_ec_hw_median_host.py can compare the two spellings and run the sweep's HWMED instantiation without a GPU.
+MSDF_HD float med3Max(float a, float b) {                 // v_max_f32 on non-NaN operands: -0 < +0
+    if (a == 0 && b == 0)
+        return (__builtin_signbit(a) && __builtin_signbit(b)) ? a : 0.f;
+    return a < b ? b : a;
+}
+MSDF_HD float med3Min(float a, float b) {                 // v_min_f32: a NaN operand loses; -0 < +0
+    if (a != a)
+        return b;
+    if (b != b)
+        return a;
+    if (a == 0 && b == 0)
+        return (__builtin_signbit(a) || __builtin_signbit(b)) ? -0.f : 0.f;
+    return b < a ? b : a;
+}
+MSDF_HD float med3Model(float a, float b, float c) {      // V_MED3_F32 as the CDNA ISA guide defines it
+    if (a != a || b != b || c != c)
+        return med3Min(med3Min(a, b), c);
+    const float m = med3Max(med3Max(a, b), c);
+    if (m == a)
+        return med3Max(b, c);
+    if (m == b)
+        return med3Max(a, c);
+    return med3Max(a, b);
+}
+MSDF_HD float med3f(float a, float b, float c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_fmed3f(a, b, c);
+#else
+    return med3Model(a, b, c);
+#endif
+}
+// HWMED: the instantiation of the sweep that a wavefront of k_ec_fast runs once its vote has passed; false: the reference's spelling, everywhere else.
+template <bool HWMED>
+MSDF_HD float medianOf(float a, float b, float c) {
+    if (HWMED)
+        return med3f(a, b, c);
+    return medianf(a, b, c);
+}
+// The smaller / larger of two non-NaN floats as values (zero signs aside), one instruction each: for predicates of the HWMED instantiation only.
+MSDF_HD float med3Lo(float a, float b) { return __builtin_fminf(a, b); }
+MSDF_HD float med3Hi(float a, float b) { return __builtin_fmaxf(a, b); }
 MSDF_HD float mixf(float a, float b, double w) { return (float) ((1.-w)*a+w*b); } // arithmetics.hpp:27-31 (T=float, S=double)
 
 // Correctly rounded quotient a/b from y = RN(1/b) with two FMAs (Markstein, "Computation of elementary functions on the IBM RISC

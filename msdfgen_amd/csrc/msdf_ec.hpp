@@ -180,11 +180,18 @@ MSDF_HD bool evaluate(const Classifier<Query> &c, double t, float m, int flags) 
     return false;
 }
 
+// (HWMED: medianOf, msdf_device.hpp -- only the sweep of k_ec_fast asks for it)
+template <bool HWMED = false>
 MSDF_HD float interpolatedMedianLin(const float *a, const float *b, double t) { // :260-266
-    return medianf(mixf(a[0], b[0], t), mixf(a[1], b[1], t), mixf(a[2], b[2], t));
+    return medianOf<HWMED>(mixf(a[0], b[0], t), mixf(a[1], b[1], t), mixf(a[2], b[2], t));
 }
 
+// HWMED: the fp32 median of the three ROUNDED values for the rounded fp64 median. Rounding to float is monotone, so the middle one of the rounded values
+// is the rounded middle one (an overflow to +-inf keeps the order too); fp64 has no median instruction, the reference's spelling costs four fp64 compares.
+template <bool HWMED = false>
 MSDF_HD float interpolatedMedianQuad(const float *a, const float *l, const float *q, double t) { // :268-275
+    if (HWMED)
+        return med3f((float) (t*(t*q[0]+l[0])+a[0]), (float) (t*(t*q[1]+l[1])+a[1]), (float) (t*(t*q[2]+l[2])+a[2]));
     return (float) median(t*(t*q[0]+l[0])+a[0], t*(t*q[1]+l[1])+a[1], t*(t*q[2]+l[2])+a[2]);
 }
 

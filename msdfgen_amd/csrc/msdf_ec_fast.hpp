@@ -26,6 +26,10 @@
 //    corner test and the protectEdges pairs afterwards.  Where a diagonal pair would hand a distance-check candidate to the sink at or
 //    after a conditional artifact of the same pair (unprotected, the eager order has left the pair by then), the candidate is held
 //    back (fourth bit) and handed over in a second visit of that pair once the texel is known to be protected: same candidate set.
+//  * Three template switches that only k_ec_fast turns on (everything else, the host walk included, runs the defaults = the reference's spelling):
+//    HWMED, the hardware's median where a wavefront's vote has shown that no operand can be a NaN (msdf_device.hpp: med3f; the consumers of a median
+//    and why none sees a zero's sign: at evaluatePair); INDEXED, a test's channels read at computed addresses instead of selected; CORDER, the order
+//    and with it the lazy orders' configuration known at compile time. Same floats, same predicates: tests/test_ec_hw_median_host.py.
 #pragma once
 
 #include "msdf_ec.hpp"
@@ -60,9 +64,12 @@ struct FastCtx {
 
 // rangeTest (:30-40) for both classifiers at once. Returns flags of the base pass in bits 0-1 and of the shape pass in bits 2-3; in the
 // lazy order bit 4: the base pass has an artifact here iff its protectedFlag is false (it exists only through `!p1 && outside`).
+// HWMED (no operand is a NaN): "both end points above .5" is "the smaller one is" -- one v_min_f32 and a compare for two compares and a mask operation.
+template <bool HWMED = false>
 MSDF_HD int rangeTest2(const FastCtx &c, double at, double bt, double xt, float am, float bm, float xm) {
-    const bool inversion = (am > .5f && bm > .5f && xm <= .5f) || (am < .5f && bm < .5f && xm >= .5f);
-    const bool outside = medianf(am, bm, xm) != xm;
+    const bool inversion = HWMED ? (med3Lo(am, bm) > .5f && xm <= .5f) || (med3Hi(am, bm) < .5f && xm >= .5f)
+                                 : (am > .5f && bm > .5f && xm <= .5f) || (am < .5f && bm < .5f && xm >= .5f);
+    const bool outside = medianOf<HWMED>(am, bm, xm) != xm;
     const bool candBase = c.basePass && (inversion || (!c.p1 && outside));
     const bool candShape = c.shapePass && (inversion || (!c.pShape && outside));
     const bool candCond = c.order != EC_ORDER_EAGER && !inversion && outside;
@@ -118,6 +125,7 @@ MSDF_HD bool bernsteinMayHaveRoot(float dA, float dBC, float dD) {
 // edgeBetweenTexelsChannel (MSDFErrorCorrection.cpp:154-168) with the fp64 division skipped when t = (a-.5)/(a-b) cannot lie in
 // (0, 1): numerator n = a-.5 (exact in fp64) and denominator d = fl32(a-b) must have the same sign and |n| < |d|; both are
 // fp32-derived, so n/d < 1 implies n/d <= 1-2^-26 and the rounded quotient is < 1 as well -- the predicate is exact.
+template <bool HWMED = false>
 MSDF_HD bool edgeBetweenTexelsChannelFast(const float *a, const float *b, int channel) {
     const double n = a[channel]-.5;
     const double d = a[channel]-b[channel];
@@ -126,13 +134,14 @@ MSDF_HD bool edgeBetweenTexelsChannelFast(const float *a, const float *b, int ch
     const double t = n/d;
     if (t > 0 && t < 1) {
         float c[3] = { mixf(a[0], b[0], t), mixf(a[1], b[1], t), mixf(a[2], b[2], t) };
-        return medianf(c[0], c[1], c[2]) == c[channel];
+        return medianOf<HWMED>(c[0], c[1], c[2]) == c[channel];
     }
     return false;
 }
 
+template <bool HWMED = false>
 MSDF_HD int edgeBetweenTexelsFast(const float *a, const float *b) {
-    return 1*(int) edgeBetweenTexelsChannelFast(a, b, 0)+2*(int) edgeBetweenTexelsChannelFast(a, b, 1)+4*(int) edgeBetweenTexelsChannelFast(a, b, 2);
+    return 1*(int) edgeBetweenTexelsChannelFast<HWMED>(a, b, 0)+2*(int) edgeBetweenTexelsChannelFast<HWMED>(a, b, 1)+4*(int) edgeBetweenTexelsChannelFast<HWMED>(a, b, 2);
 }
 
 // The roots of a diagonal pair's quadratic that the reference keeps (those in (0.01, 0.99), :296-298), in the order of solveQuadratic's indices, and the
@@ -169,17 +178,18 @@ MSDF_HD bool diagonalRootsInRange(DiagonalRoots &d, double qa, double qb, double
 
 // One range test of root t (xm: the interpolated median there): over the whole segment, or, for an extremum at tEx, over the part between the
 // extremum and the end point on the root's side (:366-377). The results of a root's tests are OR-ed, so their order is free.
+template <bool HWMED = false>
 MSDF_HD int diagonalUnitFlags(const FastCtx &cx, float am, float dm, const float *a, const float *l, const float *q, double t, double tEx, bool extremum, float xm) {
     if (!extremum)
-        return rangeTest2(cx, 0, 1, t, am, dm, xm);
+        return rangeTest2<HWMED>(cx, 0, 1, t, am, dm, xm);
     double tEnd0 = 0, tEnd1 = 1;
     float em0 = am, em1 = dm;
-    const float ex = interpolatedMedianQuad(a, l, q, tEx);
+    const float ex = interpolatedMedianQuad<HWMED>(a, l, q, tEx);
     if (tEx > t)
         tEnd1 = tEx, em1 = ex;
     else
         tEnd0 = tEx, em0 = ex;
-    return rangeTest2(cx, tEnd0, tEnd1, t, em0, em1, xm);
+    return rangeTest2<HWMED>(cx, tEnd0, tEnd1, t, em0, em1, xm);
 }
 
 // What the accumulated flags of root t do to the pair's verdict; true: ERROR, the pair is decided (the reference returns there, :300-326).
@@ -203,7 +213,7 @@ MSDF_HD bool diagonalRootVerdict(const FastCtx &cx, int rangeFlags, double t, in
 // handed over by the EC_ORDER_LAZY_HELD visit, which hands over nothing else.
 // One pass per in-range root, a lane's roots in index order as before; in a wavefront the first pass is dense and the second runs only if some lane
 // has both roots in range. Inside a pass: the first in-range extremum, then the second if a lane has two.
-template <class Sink>
+template <bool HWMED = false, class Sink>
 MSDF_HD int diagonalPairFast(const FastCtx &cx, float am, float dm, const float *a, const float *l, const float *q,
                              float dA, float dBC, float dD, float l0, float q0, float l1, float q1, Sink &sink) {
     const double qa = dD-dBC+dA, qb = dBC-dA-dA, qc = dA;   // float expressions promoted, exactly as passed at :295
@@ -216,12 +226,12 @@ MSDF_HD int diagonalPairFast(const FastCtx &cx, float am, float dm, const float 
         if (i >= d.m)
             break;
         const double t = i ? d.r1 : d.r0;
-        const float xm = interpolatedMedianQuad(a, l, q, t);
-        int rangeFlags = diagonalUnitFlags(cx, am, dm, a, l, q, t, 0, false, xm);
+        const float xm = interpolatedMedianQuad<HWMED>(a, l, q, t);
+        int rangeFlags = diagonalUnitFlags<HWMED>(cx, am, dm, a, l, q, t, 0, false, xm);
         if (d.ne > 0)
-            rangeFlags |= diagonalUnitFlags(cx, am, dm, a, l, q, t, d.ex0, true, xm);
+            rangeFlags |= diagonalUnitFlags<HWMED>(cx, am, dm, a, l, q, t, d.ex0, true, xm);
         if (d.ne > 1)
-            rangeFlags |= diagonalUnitFlags(cx, am, dm, a, l, q, t, d.ex1, true, xm);
+            rangeFlags |= diagonalUnitFlags<HWMED>(cx, am, dm, a, l, q, t, d.ex1, true, xm);
         if (diagonalRootVerdict(cx, rangeFlags, t, verdict, sink))
             return verdict;
     }
@@ -243,7 +253,8 @@ struct Neighbourhood {
     unsigned valid;     // the nine inside bits (host walk; the kernel reads them in cls)
 };
 
-MSDF_HD float ecTexelDeviation(const float *t) { return fabsf(medianf(t[0], t[1], t[2])-.5f); }
+template <bool HWMED = false>
+MSDF_HD float ecTexelDeviation(const float *t) { return fabsf(medianOf<HWMED>(t[0], t[1], t[2])-.5f); }
 
 // Class word of a texel inside the bitmap. With D[j] = t[j+1 mod 3]-t[j] (channel pair j in the reference's minuend / subtrahend order, the float
 // subtraction of hasLinearArtifact / hasDiagonalArtifact): bit j: D[j] > 0, bit 3+j: D[j] < 0, bit 6+j: D[j] == 0 (a NaN sets none of the three),
@@ -310,11 +321,12 @@ MSDF_HD void texelProtectPairs(const Neighbourhood &nb, const EcParams &p, Emit 
 // Is `self` protected through its pair with neighbour m (`other`)? Pair orientation as the reference's sweeps: `a` is the texel of the
 // lower native row (same row: the left one); swapRows: of the higher native row, which is the lower row of a flipped glyph's shape
 // (EcParams::shapeRows).
+template <bool HWMED = false>
 MSDF_HD bool evaluateProtectPair(const float *self, const float *other, int m, bool swapRows = false) {
     const int dy = m/3-1, dx = m%3-1;
     const bool selfIsA = (swapRows ? dy < 0 : dy > 0) || (dy == 0 && dx > 0);
-    const int mask = selfIsA ? edgeBetweenTexelsFast(self, other) : edgeBetweenTexelsFast(other, self);
-    return extremeChannelInMask(self, medianf(self[0], self[1], self[2]), mask);
+    const int mask = selfIsA ? edgeBetweenTexelsFast<HWMED>(self, other) : edgeBetweenTexelsFast<HWMED>(other, self);
+    return extremeChannelInMask(self, medianOf<HWMED>(self[0], self[1], self[2]), mask);
 }
 
 MSDF_HD bool protectedByEdgesNb(const Neighbourhood &nb, const EcParams &p, int flip = 0) {
@@ -393,32 +405,47 @@ MSDF_HD void texelCandidatePairs(const Neighbourhood &nb, Emit &emit) {
 }
 
 MSDF_HD float pick3(const float *v, int i) { return i == 0 ? v[0] : i == 1 ? v[1] : v[2]; }
+// Channel i of a texel. INDEXED: the texel lies in addressable memory (k_ec_fast: the LDS halo; the host), so v[i] is a read at a computed address
+// and costs no compare / select chain; a caller whose texels are register arrays (which an indexed read would send to scratch) keeps pick3. Same float.
+template <bool INDEXED>
+MSDF_HD float pickChannel(const float *v, int i) { return INDEXED ? v[i] : pick3(v, i); }
 
 // Stage 2: one surviving test. c: centre texel, n: the neighbour k, hb / vc: the horizontal / vertical neighbours on the way to a
-// diagonal one (unused for k < 4); any memory (registers, LDS). Returns EC_V_* bits (a candidate that needs the distance check is also
-// reported as sink(t, dx, dyShape)). Same operands and operations as hasLinearArtifact / hasDiagonalArtifact (:330-381).
+// diagonal one (unused for k < 4); any memory (registers, LDS; INDEXED: addressable, see pickChannel). Returns EC_V_* bits (a candidate that needs the
+// distance check is also reported as sink(t, dx, dyShape)). Same operands and operations as hasLinearArtifact / hasDiagonalArtifact (:330-381).
 // order: EC_ORDER_EAGER with the texel's protection in p1, or one of the lazy orders (only where ecLazyProtect(p); p1 is ignored).
-template <class Sink>
+// CORDER >= 0: the order is known where the call is compiled (k_ec_fast's instantiations: `order` must equal it). In a lazy order that settles the
+// classifier's configuration as well -- ecLazyProtect(p) means EDGE_PRIORITY with CHECK_AT_EDGE, so both passes run and both see the texel protected --
+// and rangeTest2 / judge fold: candBase == candShape == inversion, and nothing of the configuration is carried through the item loop as a scalar mask.
+// HWMED: medianOf (msdf_device.hpp). What reads a median here, and why none of it can tell the sign of a zero (values equal the exact spelling's
+// for non-NaN operands, which the caller guarantees): cm, nm, xm and the extremum medians go to rangeTest2, which compares them with .5f, with each
+// other (`!= xm`: +0 == -0) and, promoted to double, with am +- axSpan (x-s and x+s round to the same double for x = +0 and -0 unless s == 0, and then
+// the results are zeros, compared with >= / <=); as operands of the inner median a zero of either sign orders the same. edgeBetweenTexelsChannelFast
+// and evaluateProtectPair compare their median with a channel (==, !=), ecTexelDeviation takes fabsf(m-.5f): -.5f for either zero. No median is stored
+// -- the apply step of ecFastBody, which does store one, keeps medianf.
+template <bool HWMED = false, bool INDEXED = false, int CORDER = -1, class Sink>
 MSDF_HD int evaluatePair(const float *c, const float *n, const float *hb, const float *vc, const EcParams &p, bool p1, int flip, int k, int j, Sink &sink,
-                         int order = EC_ORDER_EAGER) {
+                         int orderArg = EC_ORDER_EAGER) {
+    const int order = CORDER >= 0 ? CORDER : orderArg;
+    constexpr bool LAZY_CT = CORDER == EC_ORDER_LAZY || CORDER == EC_ORDER_LAZY_HELD;
     FastCtx cx;
-    cx.basePass = ecHasBasePass(p);
-    cx.shapePass = ecHasShapePass(p);
+    cx.basePass = LAZY_CT || ecHasBasePass(p);
+    cx.shapePass = LAZY_CT || ecHasShapePass(p);
     cx.order = order;
     cx.p1 = order != EC_ORDER_EAGER || p1;
-    cx.pShape = (p.distanceCheck == EC_CHECK_AT_EDGE) ? true : cx.p1;   // protectAll() precedes the shape pass only in that mode (:38-39, :33)
+    cx.pShape = (LAZY_CT || p.distanceCheck == EC_CHECK_AT_EDGE) ? true : cx.p1;   // protectAll() precedes the shape pass only in that mode (:38-39, :33)
     const int dx = ecNeighbourDx(k), dy = ecNeighbourDy(k);
     const int i0 = j, i1 = j == 2 ? 0 : j+1;
-    const float cm = medianf(c[0], c[1], c[2]), nm = medianf(n[0], n[1], n[2]);
+    const float cm = medianOf<HWMED>(c[0], c[1], c[2]), nm = medianOf<HWMED>(n[0], n[1], n[2]);
     if (k < 4) {
         if (order == EC_ORDER_LAZY_HELD)
             return 0;                                    // one range test per pair: a candidate (inversion) is never conditional as well
         cx.span = dy == 0 ? p.hSpan : p.vSpan;
-        const float dA = pick3(c, i1)-pick3(c, i0), dB = pick3(n, i1)-pick3(n, i0);
+        const float dA = pickChannel<INDEXED>(c, i1)-pickChannel<INDEXED>(c, i0), dB = pickChannel<INDEXED>(n, i1)-pickChannel<INDEXED>(n, i0);
         const double t = (double) dA/(dA-dB);            // :281
         if (t > MSDF_ARTIFACT_T_EPSILON && t < 1-MSDF_ARTIFACT_T_EPSILON) {
-            const float xm = interpolatedMedianLin(c, n, t);
-            const int v = judge(rangeTest2(cx, 0, 1, t, cm, nm, xm));
+            const float xm = interpolatedMedianLin<HWMED>(c, n, t);
+            const int v = judge(rangeTest2<HWMED>(cx, 0, 1, t, cm, nm, xm));
             if (v&EC_V_CHECK)
                 sink(t, dx, flip ? -dy : dy);
             return v;
@@ -436,13 +463,16 @@ MSDF_HD int evaluatePair(const float *c, const float *n, const float *hb, const 
         int dx, dy;
         MSDF_HD void operator()(double t) { sink(t, dx, dy); }
     } dirSink = { sink, dx, flip ? -dy : dy };
-    const float dA = pick3(a, i1)-pick3(a, i0), dBC = pick3(b, i1)-pick3(b, i0)+pick3(cc, i1)-pick3(cc, i0), dD = pick3(d, i1)-pick3(d, i0);
-    return diagonalPairFast(cx, cm, nm, a3, l, q, dA, dBC, dD, pick3(l, i0), pick3(q, i0), pick3(l, i1), pick3(q, i1), dirSink);
+    const float dA = pickChannel<INDEXED>(a, i1)-pickChannel<INDEXED>(a, i0);
+    const float dBC = pickChannel<INDEXED>(b, i1)-pickChannel<INDEXED>(b, i0)+pickChannel<INDEXED>(cc, i1)-pickChannel<INDEXED>(cc, i0);
+    const float dD = pickChannel<INDEXED>(d, i1)-pickChannel<INDEXED>(d, i0);
+    return diagonalPairFast<HWMED>(cx, cm, nm, a3, l, q, dA, dBC, dD, pick3(l, i0), pick3(q, i0), pick3(l, i1), pick3(q, i1), dirSink);   // (l, q: registers)
 }
 
 // Both stages for one texel, test after test (host walk; the kernel queues the items instead). Returns EC_V_* bits OR-ed over the tests;
 // every candidate that needs the distance check is reported as sink(t, dx, dyShape) (MSDFErrorCorrection.cpp:446-453).
-template <class Sink>
+// HWMED: for tests/test_ec_hw_median_host.py, which runs k_ec_fast's second instantiation on the host; the host walk itself never asks for it.
+template <bool HWMED = false, class Sink>
 MSDF_HD int texelFindFast(const Neighbourhood &nb, const EcParams &p, bool p1, int flip, Sink &sink, int order = EC_ORDER_EAGER) {
     struct Items {
         unsigned char k[24], j[24];
@@ -454,7 +484,7 @@ MSDF_HD int texelFindFast(const Neighbourhood &nb, const EcParams &p, bool p1, i
     int verdict = 0;
     for (int i = 0; i < items.n; ++i) {
         const int k = items.k[i], dx = ecNeighbourDx(k), dy = ecNeighbourDy(k);
-        verdict |= evaluatePair(nb.v[1][1], nb.v[dy+1][dx+1], nb.v[1][dx+1], nb.v[dy+1][1], p, p1, flip, k, items.j[i], sink, order);
+        verdict |= evaluatePair<HWMED>(nb.v[1][1], nb.v[dy+1][dx+1], nb.v[1][dx+1], nb.v[dy+1][1], p, p1, flip, k, items.j[i], sink, order);
     }
     return verdict;
 }

@@ -1227,7 +1227,7 @@ k_ec_params(EcGlyphParams *out, BatchView batch, const MsdfHipGlyph *glyphs, Msd
 // the stencil byte [g][h][w] (native rows). Candidates whose verdict needs an exact shape-distance query are appended to `cands`
 // and judged by k_ec_query; a texel with a cheaply decided ERROR never needs them (the flag is an OR).
 #ifndef MSDF_EC_FAST_WAVES_PER_SIMD
-#define MSDF_EC_FAST_WAVES_PER_SIMD 7   // lazy instantiation 65 VGPRs / 4 scalar registers parked in vector lanes, eager 60 / 0; no vector spills, no scratch (tests/test_ec_fast_isa_budget.py); the kernel's 5.6 KB of LDS allow 7 wavefronts per SIMD anyway. Correction pass on the distinct-glyph set: 8 -> 1.94 ms, 7 -> 1.90, 6 -> 1.90
+#define MSDF_EC_FAST_WAVES_PER_SIMD 7   // lazy and eager instantiation 60 VGPRs, no scalar register parked in vector lanes (the lazy one had 65 / 4 until its configuration became compile-time constants); no vector spills, no scratch (tests/test_ec_fast_isa_budget.py); the kernel's 5.6 KB of LDS allow 7 wavefronts per SIMD anyway. Correction pass on the distinct-glyph set: 8 -> 1.94 ms, 7 -> 1.90, 6 -> 1.90
 #endif
 // LDS of k_ec_fast per wavefront: 10x10 halo tile of the field | per-texel verdict words | item count | item queue (5.6 KB for msdf).
 enum { EC_HALO = TILE+2, EC_QUEUE_CAP = WAVE*24, EC_PROTECT_QUEUE_CAP = WAVE*8 };
@@ -1263,7 +1263,7 @@ __device__ __forceinline__ bool ecTileCornerTexel(const int *list, int nCorners,
 }
 
 // protectEdges' edgeBetweenTexels tests of the queued pairs (lane | m<<6), densely: lane = pair; a hit protects the owning texel (bit 8 of its word).
-template <int N>
+template <int N, bool HWMED = false>
 __device__ __forceinline__ void ecRunProtectQueue(const float *halo, const unsigned short *protectQueue, int nProtect, int *verdictLds, int lane, bool swapRows = false) {
     for (int base = 0; base < nProtect; base += WAVE) {
         const int it = base+lane;
@@ -1273,10 +1273,15 @@ __device__ __forceinline__ void ecRunProtectQueue(const float *halo, const unsig
         const int s = item&63, m = item>>6;
         const int sx = s&(TILE-1), sy = s>>3;
         const float *self = halo+((sy+1)*EC_HALO+sx+1)*N, *other = halo+((sy+m/3)*EC_HALO+sx+m%3)*N;
-        if (evaluateProtectPair(self, other, m, swapRows))
+        if (evaluateProtectPair<HWMED>(self, other, m, swapRows))
             atomicOr(&verdictLds[s], 0x100);
     }
 }
+
+template <class T, T V>
+struct EcConstant {
+    static constexpr T value = V;
+};
 
 struct EcPushProtect {
     unsigned short *queue;
@@ -1285,8 +1290,8 @@ struct EcPushProtect {
     __device__ void operator()(int m) { queue[atomicAdd(count, 1)] = (unsigned short) (lane|m<<6); }
 };
 
-// ORDER: 1 the lazy order, 0 the eager one -- k_ec_fast has an instantiation of each and the host picks by the configuration (65 / 60 VGPRs, 4 / 0 scalar
-// registers parked in vector lanes, all outside the queue loops) -- or -1: decided here, one body for k_single_call.
+// ORDER: 1 the lazy order, 0 the eager one -- k_ec_fast has an instantiation of each and the host picks by the configuration (60 VGPRs each, no scalar
+// registers parked in vector lanes) -- or -1: decided here, one body for k_single_call.
 // SHAPE_ROWS: EcParams::shapeRows, the legacy generators' correction (eager order only: it runs without the distance check). An instantiation of its own,
 // so that the kernels of the modern entry points stay what they were.
 template <int N, int ORDER = -1, bool SIZED = false, bool SHAPE_ROWS = false>
@@ -1324,7 +1329,12 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     p.t = loadXform(gd);
     p.minDeviationRatio = cfg.min_deviation_ratio;
     p.minImproveRatio = cfg.min_improve_ratio;
-    p.mode = cfg.ec_mode, p.distanceCheck = cfg.ec_distance_check, p.overlap = cfg.overlap_support, p.stageLimit = 0;
+    // ORDER == 1 (FOLD: in k_ec_fast itself) is launched only where ecLazyProtect(p) holds -- launchEc picks `p.lazyProtect ? k_ec_fast<N, true> : k_ec_fast<N, false>` from the very
+    // predicate (msdf_capi.hip; the sized twins likewise) -- so that instantiation knows its mode and distance check without reading them: nothing below
+    // carries them, or the pass / protection flags derived from them, through the queue loops in scalar registers.
+    constexpr bool FOLD = ORDER == 1 && !SIZED;
+    p.mode = FOLD ? (int) EC_MODE_EDGE_PRIORITY : cfg.ec_mode, p.distanceCheck = FOLD ? (int) EC_CHECK_AT_EDGE : cfg.ec_distance_check;
+    p.overlap = cfg.overlap_support, p.stageLimit = 0;
     const EcGlyphParams gp = glyphParams[wk.g];
     p.hSpan = gp.hSpan, p.vSpan = gp.vSpan, p.dSpan = gp.dSpan, p.texelX = gp.texelX, p.texelY = gp.texelY;
     p.radiusH = gp.radiusH, p.radiusV = gp.radiusV, p.radiusD = gp.radiusD;
@@ -1344,6 +1354,18 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     const ptrdiff_t origin = SIZED ? ((ptrdiff_t) wk.g*width*height+(ptrdiff_t) (ty*TILE-1)*boxW+tx*TILE-1)*N : (((ptrdiff_t) wk.g*height+ty*TILE-1)*width+tx*TILE-1)*N;       // of halo position 0, in floats from src (outside the field where the tile touches a border)
     const int hr0 = lane/EC_HALO, hc0 = lane-hr0*EC_HALO;
     const ptrdiff_t laneStep0 = hr0*rowStep+hc0*N;
+    // The vote for the hardware median (msdf_device.hpp: med3f): a lane objects if a colour channel of a texel it stages is a NaN or has a magnitude of
+    // EC_MED3_BOUND or more; a position outside the bitmap is not read and does not vote. No objection in the wavefront: everything behind the staging
+    // runs its HWMED instantiation. The bound is there for the NaNs that finite texels could make: every median of the sweep is taken over texels,
+    // over mixf(a, b, t) with 0 < t < 1, over t*(t*q+l)+a with 0 < t < 1 (fp64; q = d+(a-b-c), l = -a-(a-b-c) in fp32), or over such medians. With
+    // all channels below 2^100 in magnitude, |a-b-c| < 3*2^100, |l|, |q| < 4*2^100, the quadratic is below 9*2^100 and rounds to a finite float; no
+    // sum overflows (FLT_MAX ~ 2^128), so no inf-inf: no NaN reaches a median. 2^100 is ample -- the fields hold distances mapped to about [0, 1] -- and
+    // what it turns away is the texel the overlapping combiner leaves at -DBL_MAX (-inf as a float), with the eight texels around it.
+    // ORDER < 0 (k_single_call), the sized twins and the legacy generators' instantiation keep the exact spelling throughout.
+    constexpr bool VOTE = ORDER >= 0 && !SIZED && !SHAPE_ROWS;
+    constexpr bool INDEXED = VOTE;          // those instantiations also read a test's channels from the halo at computed addresses (msdf_ec_fast.hpp: pickChannel)
+    constexpr float EC_MED3_BOUND = 0x1p100f;
+    bool objection = false;
     MSDF_UNROLL
     for (int round = 0; round < 2; ++round) {
         const int idx = lane+round*WAVE;
@@ -1358,7 +1380,9 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
                 float tv[N];
                 for (int ch = 0; ch < N; ++ch)
                     tv[ch] = t[ch], halo[idx*N+ch] = tv[ch];
-                classLds[idx].dev = ecTexelDeviation(tv);
+                if (VOTE)
+                    objection = objection || !(fabsf(tv[0]) < EC_MED3_BOUND && fabsf(tv[1]) < EC_MED3_BOUND && fabsf(tv[2]) < EC_MED3_BOUND);
+                classLds[idx].dev = ecTexelDeviation(tv);           // (exact spelling: the vote is not in yet; two medians per lane and tile)
                 cls = ecTexelClassWord(tv);
             }
             classLds[idx].cls = cls;
@@ -1416,16 +1440,23 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     verdictLds[lane] = (st&EC_PROTECTED) ? 0x100 : 0;
     waveSync();
 
+    // Everything from here to the apply step takes medians: compiled twice, and a wavefront runs the HWMED copy iff its vote passed (wave-uniform).
+    const bool hwMedian = VOTE && __ballot(objection) == 0;
+    const auto sweep = [&](auto hwmedTag) {
+    constexpr bool HWMED = decltype(hwmedTag)::value;
     // ---- phase B (lane = queued pair): protectEdges' edgeBetweenTexels tests, densely; a hit protects the owning texel (eager order; the lazy one has queued none)
     if (!lazy) {
-        ecRunProtectQueue<N>(halo, protectQueue, itemCount[1], verdictLds, lane, SHAPE_ROWS && gd.flip);
+        ecRunProtectQueue<N, HWMED>(halo, protectQueue, itemCount[1], verdictLds, lane, SHAPE_ROWS && gd.flip);
         waveSync();
     }
 
     // ---- phase C (lane = queued test): stage 2, densely; verdicts are OR-ed into the owning texel's word. The lazy order comes back once more
     // (EC_ORDER_LAZY_HELD) for the pairs of texels that held a distance-check candidate back and turned out protected.
     const int nItems = itemCount[0];
-    const auto runItems = [&](const int order) {
+    // (the order is a compile-time tag in k_ec_fast's instantiations, which run one order per call site; k_single_call, ORDER < 0, passes it at run time)
+    const auto runItems = [&](auto orderTag, const int orderArg) {
+        constexpr int CORDER = decltype(orderTag)::value;
+        const int order = CORDER >= 0 ? CORDER : orderArg;
         for (int base = 0; base < nItems; base += WAVE) {
             const int it = base+lane;
             if (it >= nItems)
@@ -1444,12 +1475,17 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
             sink.segment = sinkSlots > 0 ? cands+ecHeaderRecords(sinkSlots)+(size_t) sinkSlot*seg : cands+ecHeaderRecords(batch.nGlyphs)+(size_t) wk.g*seg;
             sink.seg = seg, sink.g = sinkSlots > 0 ? sinkSlot : wk.g;
             sink.texel = (unsigned) (SIZED ? (size_t) wk.g*width*height+(size_t) (ty*TILE+sy)*boxW+tx*TILE+sx : ((size_t) wk.g*height+ty*TILE+sy)*width+tx*TILE+sx);
-            const int v = evaluatePair(c, n, hb, vc, p, (word&0x100) != 0, gd.flip, k, jp, sink, order);
+            const int v = evaluatePair<HWMED, INDEXED, (FOLD || CORDER == EC_ORDER_EAGER) ? CORDER : -1>(c, n, hb, vc, p, (word&0x100) != 0, gd.flip, k, jp, sink, order);
             if (v && order != EC_ORDER_LAZY_HELD)
                 atomicOr(&verdictLds[s], v);
         }
     };
-    runItems(lazy ? EC_ORDER_LAZY : EC_ORDER_EAGER);
+    if constexpr (ORDER < 0)
+        runItems(EcConstant<int, -1>(), lazy ? EC_ORDER_LAZY : EC_ORDER_EAGER);
+    else if constexpr (ORDER == 1)
+        runItems(EcConstant<int, EC_ORDER_LAZY>(), EC_ORDER_LAZY);
+    else
+        runItems(EcConstant<int, EC_ORDER_EAGER>(), EC_ORDER_EAGER);
     waveSync();
 
     // ---- lazy protection (lane = texel): only texels whose verdict hinges on it, and only in wavefronts that have one
@@ -1477,7 +1513,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
                     for (int dx = -1; dx <= 1; ++dx) {
                         const int nx = x+dx, ny = yn+dy;
                         const bool in = nx >= 0 && ny >= 0 && nx < boxW && ny < boxH;
-                        nd.dev[dy+1][dx+1] = ecTexelDeviation(halo+((ly+1+(in ? dy : 0))*EC_HALO+lx+1+(in ? dx : 0))*N);
+                        nd.dev[dy+1][dx+1] = ecTexelDeviation<HWMED>(halo+((ly+1+(in ? dy : 0))*EC_HALO+lx+1+(in ? dx : 0))*N);
                         nd.cls[dy+1][dx+1] = in ? (unsigned) EC_CLS_INSIDE : 0u;
                     }
                 }
@@ -1486,7 +1522,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
             }
         }
         waveSync();
-        ecRunProtectQueue<N>(halo, protectQueue, itemCount[1], verdictLds, lane);
+        ecRunProtectQueue<N, HWMED>(halo, protectQueue, itemCount[1], verdictLds, lane);
         waveSync();
         bool revisit = false;
         if (need) {
@@ -1497,9 +1533,17 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
         }
         if (__ballot(revisit)) {                                    // hand over what the protected texels held back
             waveSync();
-            runItems(EC_ORDER_LAZY_HELD);
+            if constexpr (ORDER < 0)
+                runItems(EcConstant<int, -1>(), EC_ORDER_LAZY_HELD);
+            else
+                runItems(EcConstant<int, EC_ORDER_LAZY_HELD>(), EC_ORDER_LAZY_HELD);
         }
     }
+    };
+    if (hwMedian)
+        sweep(EcConstant<bool, true>());
+    else
+        sweep(EcConstant<bool, false>());
 
     if (!inside)
         return;
@@ -1514,7 +1558,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     for (int i = 0; i < N; ++i)
         v[i] = in[i];
     if (st&EC_ERROR) {                                              // apply, MSDFErrorCorrection.cpp:459-479 (alpha untouched)
-        const float m = medianf(v[0], v[1], v[2]);
+        const float m = medianf(v[0], v[1], v[2]);                  // (the one median that is STORED: a zero keeps the sign the reference gives it)
         v[0] = m, v[1] = m, v[2] = m;
     }
     float *px = out+gd.out_offset+(ptrdiff_t) gd.row_stride*yn+(ptrdiff_t) N*x;
