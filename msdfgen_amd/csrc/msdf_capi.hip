@@ -435,39 +435,40 @@ int ensureGres(const MsdfHipBatch *b, size_t bytes, double **out) {
     return MSDFHIP_OK;
 }
 
-// The sized twins of the generate kernels (msdfhip_batch_generate_sized), by the template arguments of their uniform siblings as plain integers. Plain functions
-// defined at the END of this file: nothing in front of them names a twin, so the twins are instantiated behind every kernel the code object has always held
-// (forDistanceVariant: the order of the instantiations matters). All instantiations of one kernel template share a signature, hence one pointer type each.
-typedef void (*DistanceSizedKernel)(int, const int32_t *, const int32_t *, const EdgeRec *, const int8_t *, const MsdfHipGlyph *, int, int, int, int, int, float *, int, unsigned,
-                                    double *, size_t, const int *, int, unsigned *, unsigned, const int32_t *);
-typedef void (*UnculledSizedKernel)(int, const int32_t *, const int32_t *, const EdgeRec *, const int8_t *, const MsdfHipGlyph *, int, int, int, int, float *, int, double *, size_t,
-                                    unsigned *, unsigned, const int *, const int32_t *);
-typedef void (*EcSlowSizedKernel)(BatchView, const MsdfHipGlyph *, int, int, const float *, float *, uint8_t *, MsdfHipConfig, const EcCandidate *, unsigned, int, double *, size_t,
-                                  const int32_t *);
-typedef void (*EcFastSizedKernel)(BatchView, const MsdfHipGlyph *, int, int, int, int, const float *, float *, uint8_t *, MsdfHipConfig, const EcGlyphParams *, EcCandidate *,
-                                  unsigned, int, const int *, const int32_t *);
-typedef void (*EcQuerySizedKernel)(int, const int32_t *, const int32_t *, const EdgeRec *, const int8_t *, const MsdfHipGlyph *, int, int, const float *, float *, uint8_t *,
-                                   MsdfHipConfig, const EcGlyphParams *, const EcCandidate *, unsigned, const int *, int *, int, int, int, EcQueryPolicy, unsigned *, const int *,
-                                   int, const int32_t *);
-typedef void (*SignSizedKernel)(BatchView, const MsdfHipGlyph *, int, int, int, int, int, int, const float *, float *, int, float, int, int, const int32_t *);
-DistanceSizedKernel distanceSizedKernel(int sel, bool overlap, bool gres, int tpw);
-UnculledSizedKernel unculledSizedKernel(int sel, bool overlap);
-EcSlowSizedKernel ecSlowSizedKernel(int n, bool overlap, bool gres);
-EcFastSizedKernel ecFastSizedKernel(int n, bool lazy);
-EcQuerySizedKernel ecQuerySizedKernel(int n, bool overlap);
-SignSizedKernel signSizedKernel(int n);
+// f(integral_constant<int, V>) for the V among VALUES that `value` equals; false if it equals none. f's instantiations are named in the order of VALUES
+// (as with forDistanceVariant below, that order is the order of the kernels in the code object).
+template <int... VALUES, class F>
+bool forOneOf(int value, F &&f) {
+    return (... || (value == VALUES ? (f(std::integral_constant<int, VALUES>()), true) : false));   // (a LEFT fold: the compiler expands a right fold from its last operand)
+}
 
-template <int SEL, bool OVERLAP, bool GRES, int TPW_>
-void launchDistanceKernel(unsigned grid, size_t lds, hipStream_t stream, const DistanceArgs &a, const int32_t *dDims = NULL) {
-    if (dDims) {
-        hipLaunchKernelGGL(distanceSizedKernel(SEL, OVERLAP, GRES, TPW_), dim3(grid), dim3(WAVE), lds, stream, a.batch.nGlyphs, a.batch.glyphContourOffsets, a.batch.contourOffsets,
-                           a.batch.recs, a.batch.windings, a.glyphs, a.width, a.height, a.tilesX, a.tilesPerGlyph, a.maxEdges, a.dst, a.toScratch, a.blockBase, a.gres,
-                           a.gresStride, a.glyphMap, a.nMapped, a.workQueue, a.workItems, dDims);
-        return;
-    }
-    hipLaunchKernelGGL((k_distance<SEL, OVERLAP, GRES, TPW_>), dim3(grid), dim3(WAVE), lds, stream, a.batch.nGlyphs, a.batch.glyphContourOffsets, a.batch.contourOffsets,
-                       a.batch.recs, a.batch.windings, a.glyphs, a.width, a.height, a.tilesX, a.tilesPerGlyph, a.maxEdges, a.dst, a.toScratch, a.blockBase, a.gres,
-                       a.gresStride, a.glyphMap, a.nMapped, a.workQueue, a.workItems);
+// The sized twins of the generate kernels (msdfhip_batch_generate_sized). A twin takes its uniform sibling's arguments and the boxes' sizes behind them: its
+// pointer type is derived from the sibling's (sizedTwinOf, only ever declared), and the two are launched from ONE argument list (launchTwinned). The functions
+// that look a twin up are defined at the END of this file: nothing in front of them names a twin, so the twins are instantiated behind every kernel the code
+// object has always held (the order of the instantiations matters). All instantiations of one kernel template share a signature, hence one pointer type each.
+template <class... A>
+auto sizedTwinOf(void (*)(A...)) -> void (*)(A..., const int32_t *);
+decltype(sizedTwinOf(k_distance<1, false, false, 1>)) distanceSizedKernel(int sel, bool overlap, bool gres, int tpw);
+decltype(sizedTwinOf(k_distance_unculled<1, false>)) unculledSizedKernel(int sel, bool overlap);
+decltype(sizedTwinOf(k_ec_slow<3, false, false>)) ecSlowSizedKernel(int n, bool overlap, bool gres);
+decltype(sizedTwinOf(k_ec_fast<3, false>)) ecFastSizedKernel(int n, bool lazy);
+decltype(sizedTwinOf(k_ec_query<3, false>)) ecQuerySizedKernel(int n, bool overlap);
+decltype(sizedTwinOf(k_sign_correction<1>)) signSizedKernel(int n);
+
+// One launch of a generate kernel (workgroups of one wavefront): of `uniform`, or in a sized call (dDims) of its twin, with dDims behind the same arguments.
+// A... comes from the uniform kernel alone. The twin must be exactly void (*)(A..., const int32_t *): one that drifts from its sibling does not compile.
+// The arguments are not deduced but taken as A..., so NULL, 0u and the like convert as they would in a direct call.
+template <class... A>
+void launchTwinned(void (*uniform)(A...), void (*twin)(A..., const int32_t *), const int32_t *dDims, dim3 grid, size_t lds, hipStream_t stream,
+                   std::enable_if_t<true, A>... args) {
+    if (dDims)
+        hipLaunchKernelGGL(twin, grid, dim3(WAVE), lds, stream, args..., dDims);
+    else
+        hipLaunchKernelGGL(uniform, grid, dim3(WAVE), lds, stream, args...);
+}
+template <class... A>
+int setLdsTwinned(void (*uniform)(A...), void (*twin)(A..., const int32_t *), const int32_t *dDims, size_t bytes) {
+    return dDims ? setLds(twin, bytes) : setLds(uniform, bytes);
 }
 
 // One planned launch of the distance pass (msdf_launchplan.hpp: planDistance); counts its route once it is issued.
@@ -479,7 +480,8 @@ int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
         return MSDFHIP_OK;
     if (blocks > 0x7fffffffull)
         return fail(MSDFHIP_ERR_INVALID, "launch of %zu tile quads exceeds the grid limit; split the batch", blocks);
-    int rc = dDims ? setLds(distanceSizedKernel(SEL, OVERLAP, GRES, TPW_), l.lds.bytes) : setLds(k_distance<SEL, OVERLAP, GRES, TPW_>, l.lds.bytes);
+    const auto twin = distanceSizedKernel(SEL, OVERLAP, GRES, TPW_);
+    int rc = setLdsTwinned(k_distance<SEL, OVERLAP, GRES, TPW_>, twin, dDims, l.lds.bytes);
     if (rc != MSDFHIP_OK)
         return rc;
     const GridPlan grid = gridOf(l, w, h, env);
@@ -493,6 +495,12 @@ int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
             return rc;
         args.gresStride = l.lds.resBytes/sizeof(double);
     }
+    const auto launch = [&](size_t groups) {                     // (args as they stand when it is called)
+        const DistanceArgs &a = args;
+        launchTwinned(k_distance<SEL, OVERLAP, GRES, TPW_>, twin, dDims, dim3((unsigned) groups), l.lds.bytes, stream, a.batch.nGlyphs, a.batch.glyphContourOffsets,
+                      a.batch.contourOffsets, a.batch.recs, a.batch.windings, a.glyphs, a.width, a.height, a.tilesX, a.tilesPerGlyph, a.maxEdges, a.dst, a.toScratch,
+                      a.blockBase, a.gres, a.gresStride, a.glyphMap, a.nMapped, a.workQueue, a.workItems);
+    };
     if (grid.persistent) {
         unsigned *queue = NULL;
         rc = ensureWorkQueue(b, &queue, stream);
@@ -505,13 +513,13 @@ int launchDistance(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
         std::lock_guard<std::mutex> lock(b->work.mutex);
         args.workQueue = queue+(b->work.queueParity ? 16 : 0);    // (the kernel finds the other set at `queue ^ 64 bytes`)
         args.workItems = (unsigned) blocks;
-        launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) grid.chunk, l.lds.bytes, stream, args, dDims);
+        launch(grid.chunk);
         HIPCHK(hipGetLastError());
         b->work.queueParity ^= 1u;
     } else {
         for (size_t base = 0; base < blocks; base += grid.chunk) {
             args.blockBase = (unsigned) base;
-            launchDistanceKernel<SEL, OVERLAP, GRES, TPW_>((unsigned) (blocks-base < grid.chunk ? blocks-base : grid.chunk), l.lds.bytes, stream, args, dDims);
+            launch(blocks-base < grid.chunk ? blocks-base : grid.chunk);
         }
         HIPCHK(hipGetLastError());
     }
@@ -655,12 +663,8 @@ int launchUnculled(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, in
     unsigned *counter = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(gres)+groups*resBytes);
     HIPCHK(hipMemsetAsync(counter, 0, sizeof(unsigned), stream));
     const BatchView v = viewOf(b);
-    if (dDims)
-        hipLaunchKernelGGL(unculledSizedKernel(SEL, OVERLAP), dim3((unsigned) groups), dim3(WAVE), 0, stream, v.nGlyphs, v.glyphContourOffsets, v.contourOffsets, v.recs,
-                           v.windings, dGlyphs, w, h, tilesX, tiles, dst, toScratch, gres, resBytes/sizeof(double), counter, (unsigned) items, dGlyphMap, dDims);
-    else
-        hipLaunchKernelGGL((k_distance_unculled<SEL, OVERLAP>), dim3((unsigned) groups), dim3(WAVE), 0, stream, v.nGlyphs, v.glyphContourOffsets, v.contourOffsets, v.recs,
-                           v.windings, dGlyphs, w, h, tilesX, tiles, dst, toScratch, gres, resBytes/sizeof(double), counter, (unsigned) items, dGlyphMap);
+    launchTwinned(k_distance_unculled<SEL, OVERLAP>, unculledSizedKernel(SEL, OVERLAP), dDims, dim3((unsigned) groups), 0, stream, v.nGlyphs, v.glyphContourOffsets,
+                  v.contourOffsets, v.recs, v.windings, dGlyphs, w, h, tilesX, tiles, dst, toScratch, gres, resBytes/sizeof(double), counter, (unsigned) items, dGlyphMap);
     HIPCHK(hipGetLastError());
     countRoute(MSDFHIP_ROUTE_DIST_UNCULLED);
     return MSDFHIP_OK;
@@ -792,19 +796,19 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         } else
             return fail(MSDFHIP_ERR_INVALID, "a correction along the shape's rows runs without overlap support");
     }
-    rc = dDims ? setLds(ecSlowSizedKernel(N, OVERLAP, GRES), p.slowLds) : setLds(slowKernel, p.slowLds);
+    const auto slowTwin = ecSlowSizedKernel(N, OVERLAP, GRES);   // (the shape-rows instantiations have no twin: refused above)
+    const auto fastTwin = ecFastSizedKernel(N, p.lazyProtect);
+    const auto queryTwin = ecQuerySizedKernel(N, OVERLAP);
+    const BatchView v = viewOf(b);
+    rc = setLdsTwinned(slowKernel, slowTwin, dDims, p.slowLds);
     if (rc != MSDFHIP_OK)
         return rc;
     ScopedTimer timer(stream, 1, !paramsOnly);
     if (p.route == EC_ROUTE_STAGE_SNAPSHOT || p.route == EC_ROUTE_SLOW_ALL) {   // k_ec_slow takes every texel
         if (paramsOnly)
             return MSDFHIP_OK;
-        if (dDims)
-            hipLaunchKernelGGL(ecSlowSizedKernel(N, OVERLAP, GRES), dim3(p.route == EC_ROUTE_SLOW_ALL ? p.slowGrid : p.snapshotBlocks), dim3(WAVE), p.slowLds, stream, viewOf(b),
-                               dGlyphs, w, h, src, out, stencil, cfg, (const EcCandidate *) NULL, 0u, 0, gres, gresStride, dDims);
-        else
-            hipLaunchKernelGGL(slowKernel, dim3(p.route == EC_ROUTE_SLOW_ALL ? p.slowGrid : p.snapshotBlocks), dim3(WAVE), p.slowLds, stream, viewOf(b),
-                               dGlyphs, w, h, src, out, stencil, cfg, (const EcCandidate *) NULL, 0u, 0, gres, gresStride);
+        launchTwinned(slowKernel, slowTwin, dDims, dim3(p.route == EC_ROUTE_SLOW_ALL ? p.slowGrid : p.snapshotBlocks), p.slowLds, stream, v, dGlyphs, w, h, src, out,
+                      stencil, cfg, NULL, 0u, 0, gres, gresStride);
         HIPCHK(hipGetLastError());
         if (p.route == EC_ROUTE_SLOW_ALL)
             countRoute(MSDFHIP_ROUTE_EC_SLOW_ALL);
@@ -818,10 +822,10 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
     if (p.route == EC_ROUTE_TOO_COMPLEX)
         return fail(MSDFHIP_ERR_TOO_COMPLEX, "a glyph has %d contours / %d edges: the error-correction pass needs %zu B of LDS per wavefront, device limit is %d B",
                     b->maxContours, b->maxEdges, p.fastLds > p.queryLds ? p.fastLds : p.queryLds, gLdsLimit.load());
-    rc = dDims ? setLds(ecQuerySizedKernel(N, OVERLAP), p.queryLds) : setLds(k_ec_query<N, OVERLAP>, p.queryLds);
+    rc = setLdsTwinned(k_ec_query<N, OVERLAP>, queryTwin, dDims, p.queryLds);
     if (rc != MSDFHIP_OK)
         return rc;
-    rc = dDims ? setLds(ecFastSizedKernel(N, p.lazyProtect), p.fastLds) : setLds(fastKernel, p.fastLds);
+    rc = setLdsTwinned(fastKernel, fastTwin, dDims, p.fastLds);
     if (rc != MSDFHIP_OK)
         return rc;
     int *offsets = reinterpret_cast<int *>(deferred+candidateRecords(b->nGlyphs, (size_t) w*h));
@@ -840,31 +844,16 @@ int launchEc(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, c
         call.ecParamsQueued = true;
         return MSDFHIP_OK;
     }
-    if (dDims)
-        hipLaunchKernelGGL(ecFastSizedKernel(N, p.lazyProtect), dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
-                           (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners, dDims);
-    else
-        hipLaunchKernelGGL(fastKernel, dim3(blocks), dim3(WAVE), p.fastLds, stream, viewOf(b), dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg,
-                           (const EcGlyphParams *) b->work.ecParams.ptr, deferred, seg, b->maxEdges, (const int *) corners);
+    launchTwinned(fastKernel, fastTwin, dDims, dim3(blocks), p.fastLds, stream, v, dGlyphs, w, h, tilesX, tiles, src, out, stencil, cfg, b->work.ecParams.ptr, deferred,
+                  seg, b->maxEdges, corners);
     hipLaunchKernelGGL(k_ec_scan, dim3(1), dim3(1024), 0, stream, b->nGlyphs, reinterpret_cast<const unsigned *>(deferred), seg, offsets, policy, ecOrder);
-    if (dDims)
-        hipLaunchKernelGGL(ecQuerySizedKernel(N, OVERLAP), dim3(queryBlocks), dim3(WAVE), p.queryLds, stream, b->nGlyphs, (const int32_t *) b->dGlyphContourOffsets.ptr,
-                           (const int32_t *) b->dContourOffsets.ptr, (const EdgeRec *) viewOf(b).recs, viewOf(b).windings, dGlyphs, w, h, src, out, stencil, cfg,
-                           (const EcGlyphParams *) b->work.ecParams.ptr, (const EcCandidate *) deferred, seg, (const int *) offsets, offsets+2*(size_t) b->nGlyphs+2, p.queryBatch,
-                           p.slotCap, p.slotOffset, policy, call.overflowOut, ecOrder, p.queryFlags, dDims);
-    else
-        hipLaunchKernelGGL((k_ec_query<N, OVERLAP>), dim3(queryBlocks), dim3(WAVE), p.queryLds, stream, b->nGlyphs, b->dGlyphContourOffsets.ptr, b->dContourOffsets.ptr,
-                           (const EdgeRec *) viewOf(b).recs, viewOf(b).windings, dGlyphs, w, h, src, out, stencil, cfg,
-                           (const EcGlyphParams *) b->work.ecParams.ptr, (const EcCandidate *) deferred, seg, (const int *) offsets, offsets+2*(size_t) b->nGlyphs+2, p.queryBatch,
-                           p.slotCap, p.slotOffset, policy, call.overflowOut, ecOrder, p.queryFlags);
+    launchTwinned(k_ec_query<N, OVERLAP>, queryTwin, dDims, dim3(queryBlocks), p.queryLds, stream, v.nGlyphs, v.glyphContourOffsets, v.contourOffsets, v.recs, v.windings,
+                  dGlyphs, w, h, src, out, stencil, cfg, b->work.ecParams.ptr, deferred, seg, offsets, offsets+2*(size_t) b->nGlyphs+2, p.queryBatch, p.slotCap,
+                  p.slotOffset, policy, call.overflowOut, ecOrder, p.queryFlags);
     if (call.overflowOut)
         call.overflowMirrored = true;                            // the caller looks at the count after its copy back and reruns with the pass below if needed
-    else if (dDims)
-        hipLaunchKernelGGL(ecSlowSizedKernel(N, OVERLAP, GRES), dim3(p.slowGrid), dim3(WAVE), p.slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
-                           (const EcCandidate *) deferred, seg, 1, gres, gresStride, dDims);
     else
-        hipLaunchKernelGGL(slowKernel, dim3(p.slowGrid), dim3(WAVE), p.slowLds, stream, viewOf(b), dGlyphs, w, h, src, out, stencil, cfg,
-                           (const EcCandidate *) deferred, seg, 1, gres, gresStride);
+        launchTwinned(slowKernel, slowTwin, dDims, dim3(p.slowGrid), p.slowLds, stream, v, dGlyphs, w, h, src, out, stencil, cfg, deferred, seg, 1, gres, gresStride);
     HIPCHK(hipGetLastError());
     countRoute(ecOrder ? MSDFHIP_ROUTE_EC_QUERY_HEAVIEST : MSDFHIP_ROUTE_EC_QUERY_BATCH);
     if (p.wideSlots)
@@ -901,8 +890,9 @@ int ensureScratch(const MsdfHipBatch *b, size_t floats, float **out) {
 // Error correction only: src (packed pre-correction tiles) -> out.
 int runCorrection(const MsdfHipBatch *b, int channels, int w, int h, const MsdfHipGlyph *dGlyphs, const float *src, float *out, uint8_t *stencil,
                   const MsdfHipConfig &cfg, hipStream_t stream, GenerateCall &call, bool paramsOnly) {
-    return channels == 3 ? dispatchEc<3>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly)
-                         : dispatchEc<4>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly);
+    int rc = MSDFHIP_OK;                                         // (channels is 3 or 4: the callers correct in modes 3 and 4 only)
+    forOneOf<3, 4>(channels, [&](auto n) { rc = dispatchEc<decltype(n)::value>(b, dGlyphs, w, h, src, out, stencil, cfg, stream, call, paramsOnly); });
+    return rc;
 }
 
 // What a generate call on `b` will need that does NOT depend on other work of the device: the class lists of the overlapping combiner and the correction
@@ -928,16 +918,13 @@ int launchSign(const MsdfHipBatch *b, int w, int h, const MsdfHipGlyph *dGlyphs,
     const SignPlan p = planSign(planEnv(b->device), b->nGlyphs, b->maxEdges, w, h);
     if (p.blocks > 0x7fffffffull)
         return fail(MSDFHIP_ERR_INVALID, "launch of %zu tile rows exceeds the grid limit; split the batch", p.blocks);
-    int rc = dDims ? setLds(signSizedKernel(N), p.lds) : setLds(k_sign_correction<N>, p.lds);
+    const auto twin = signSizedKernel(N);
+    int rc = setLdsTwinned(k_sign_correction<N>, twin, dDims, p.lds);
     if (rc != MSDFHIP_OK)
         return rc;
     ScopedTimer timer(stream, 2);
-    if (dDims)
-        hipLaunchKernelGGL(signSizedKernel(N), dim3((unsigned) p.blocks), dim3(WAVE), p.lds, stream, viewOf(b), dGlyphs, w, h, p.spansX, p.span, p.spans, (int) p.cap,
-                           src, out, dstPacked, zero, fillRule, rasterizeOnly, dDims);
-    else
-        hipLaunchKernelGGL((k_sign_correction<N>), dim3((unsigned) p.blocks), dim3(WAVE), p.lds, stream, viewOf(b), dGlyphs, w, h, p.spansX, p.span, p.spans, (int) p.cap,
-                           src, out, dstPacked, zero, fillRule, rasterizeOnly);
+    launchTwinned(k_sign_correction<N>, twin, dDims, dim3((unsigned) p.blocks), p.lds, stream, viewOf(b), dGlyphs, w, h, p.spansX, p.span, p.spans, (int) p.cap, src, out,
+                  dstPacked, zero, fillRule, rasterizeOnly);
     HIPCHK(hipGetLastError());
     countRoute(p.wholeRows ? MSDFHIP_ROUTE_SIGN_WHOLE_ROWS : MSDFHIP_ROUTE_SIGN_SPLIT);
     if (p.chunked)
@@ -949,12 +936,13 @@ int runSignCorrection(const MsdfHipBatch *b, int channels, int w, int h, const M
                       float zero, int fillRule, hipStream_t stream, const int32_t *dDims = NULL) {
     if (fillRule < 0 || fillRule > 3)
         return fail(MSDFHIP_ERR_INVALID, "fill rule %d (must be 0..3)", fillRule);
-    switch (channels) {
-        case 1: return launchSign<1>(b, w, h, dGlyphs, src, out, dstPacked, zero, fillRule, src == NULL, stream, dDims);   // no source field: rasterize()
-        case 3: return launchSign<3>(b, w, h, dGlyphs, src, out, dstPacked, zero, fillRule, 0, stream, dDims);
-        case 4: return launchSign<4>(b, w, h, dGlyphs, src, out, dstPacked, zero, fillRule, 0, stream, dDims);
-    }
-    return fail(MSDFHIP_ERR_INVALID, "channels %d (must be 1, 3 or 4)", channels);
+    int rc = MSDFHIP_OK;
+    if (!forOneOf<1, 3, 4>(channels, [&](auto n) {
+            const int rasterizeOnly = decltype(n)::value == 1 && src == NULL;   // one channel and no source field: rasterize()
+            rc = launchSign<decltype(n)::value>(b, w, h, dGlyphs, src, out, dstPacked, zero, fillRule, rasterizeOnly, stream, dDims);
+        }))
+        return fail(MSDFHIP_ERR_INVALID, "channels %d (must be 1, 3 or 4)", channels);
+    return rc;
 }
 
 // ---- the legacy generators and the legacy correction (msdf_legacy.hpp) ----------------------------------------------------------
@@ -988,12 +976,9 @@ int launchLegacyDistanceKernel(const MsdfHipBatch *b, const MsdfHipGlyph *dGlyph
 }
 
 int launchLegacyDistance(int mode, const MsdfHipBatch *b, const MsdfHipGlyph *dGlyphs, int w, int h, float *dst, int toScratch, hipStream_t stream) {
-    switch (mode) {
-        case 1: return launchLegacyDistanceKernel<1>(b, dGlyphs, w, h, dst, toScratch, stream);
-        case 2: return launchLegacyDistanceKernel<2>(b, dGlyphs, w, h, dst, toScratch, stream);
-        case 3: return launchLegacyDistanceKernel<3>(b, dGlyphs, w, h, dst, toScratch, stream);
-    }
-    return launchLegacyDistanceKernel<4>(b, dGlyphs, w, h, dst, toScratch, stream);
+    int rc = MSDFHIP_OK;                                         // (mode is 1..4: checked by the entry points)
+    forOneOf<1, 2, 3, 4>(mode, [&](auto m) { rc = launchLegacyDistanceKernel<decltype(m)::value>(b, dGlyphs, w, h, dst, toScratch, stream); });
+    return rc;
 }
 
 // msdfErrorCorrection_legacy of nGlyphs packed tiles, in place: pass 0 tiles -> scratch, pass 1 scratch -> tiles (planLegacyCorrection).
@@ -1004,10 +989,9 @@ int launchLegacyCorrection(float *dTiles, float *dScratch, int nGlyphs, int w, i
     for (int pass = 0; pass < 2; ++pass) {
         const float *src = pass == 0 ? dTiles : dScratch;
         float *dst = pass == 0 ? dScratch : dTiles;
-        if (channels == 3)
-            hipLaunchKernelGGL(k_ec_legacy<3>, dim3(p.blocks), dim3(PLAN_LEGACY_EC_THREADS), 0, stream, src, dst, nGlyphs, w, h, pass, thresholdX, thresholdY);
-        else
-            hipLaunchKernelGGL(k_ec_legacy<4>, dim3(p.blocks), dim3(PLAN_LEGACY_EC_THREADS), 0, stream, src, dst, nGlyphs, w, h, pass, thresholdX, thresholdY);
+        forOneOf<3, 4>(channels, [&](auto n) {
+            hipLaunchKernelGGL(k_ec_legacy<decltype(n)::value>, dim3(p.blocks), dim3(PLAN_LEGACY_EC_THREADS), 0, stream, src, dst, nGlyphs, w, h, pass, thresholdX, thresholdY);
+        });
         HIPCHK(hipGetLastError());                                   // (a pass that was not queued must not be followed by one that reads its output)
     }
     return MSDFHIP_OK;
@@ -1590,12 +1574,7 @@ static int runGenerate(const MsdfHipBatch *b, int mode, int w, int h, const Msdf
     float *stageA = stages ? dScratch : NULL, *stageB = stages == 2 ? dScratch+tileFloats : NULL;
     float *dst = stages ? stageA : dOut;
     const MsdfHipConfig *ecAhead = correct && !call.ecParamsQueued ? cfg : NULL;   // (taken only where the distance pass forks its classes onto side streams)
-    switch (mode) {
-        case 1: rc = dispatchDistance<1>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream, ecAhead, call); break;
-        case 2: rc = dispatchDistance<2>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream, ecAhead, call); break;
-        case 3: rc = dispatchDistance<3>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream, ecAhead, call); break;
-        default: rc = dispatchDistance<4>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream, ecAhead, call); break;
-    }
+    forOneOf<1, 2, 3, 4>(mode, [&](auto sel) { rc = dispatchDistance<decltype(sel)::value>(b, dGlyphs, w, h, dst, stages != 0, overlap, stream, ecAhead, call); });
     if (rc == MSDFHIP_OK && call.afterDistance)
         HIPCHK(hipEventRecord(call.afterDistance, stream));
     if (rc != MSDFHIP_OK || !stages)
@@ -1666,11 +1645,7 @@ int msdfhip_tiles_to_bytes(const float *dTiles, int nGlyphs, int w, int h, int c
         return rc;
     hipStream_t stream = (hipStream_t) streamPtr;
     const unsigned blocks = (unsigned) ((total+255)/256 < 65536 ? (total+255)/256 : 65536);
-    switch (channels) {
-        case 1: hipLaunchKernelGGL(k_tiles_to_bytes<1>, dim3(blocks), dim3(256), 0, stream, dTiles, dGlyphs, nGlyphs, w, h, dAtlas); break;
-        case 3: hipLaunchKernelGGL(k_tiles_to_bytes<3>, dim3(blocks), dim3(256), 0, stream, dTiles, dGlyphs, nGlyphs, w, h, dAtlas); break;
-        default: hipLaunchKernelGGL(k_tiles_to_bytes<4>, dim3(blocks), dim3(256), 0, stream, dTiles, dGlyphs, nGlyphs, w, h, dAtlas); break;
-    }
+    forOneOf<1, 3, 4>(channels, [&](auto n) { hipLaunchKernelGGL(k_tiles_to_bytes<decltype(n)::value>, dim3(blocks), dim3(256), 0, stream, dTiles, dGlyphs, nGlyphs, w, h, dAtlas); });
     HIPCHK(hipGetLastError());
     return MSDFHIP_OK;
 }
@@ -1708,11 +1683,9 @@ int msdfhip_batch_estimate_sdf_error(const MsdfHipBatch *b, int channels, int w,
     for (size_t base = 0; base < items; base += chunk) {
         const size_t n = items-base < chunk ? items-base : chunk;
         const dim3 grid((unsigned) ((n+63)/64)), block(64);
-        switch (channels) {
-            case 1: hipLaunchKernelGGL(k_sdf_error_lines<1>, grid, block, 0, stream, viewOf(b), dGlyphs, dTiles, w, h, scanlinesPerRow, fillRule, base, n, listX, listDir, refCap, lines); break;
-            case 3: hipLaunchKernelGGL(k_sdf_error_lines<3>, grid, block, 0, stream, viewOf(b), dGlyphs, dTiles, w, h, scanlinesPerRow, fillRule, base, n, listX, listDir, refCap, lines); break;
-            default: hipLaunchKernelGGL(k_sdf_error_lines<4>, grid, block, 0, stream, viewOf(b), dGlyphs, dTiles, w, h, scanlinesPerRow, fillRule, base, n, listX, listDir, refCap, lines); break;
-        }
+        forOneOf<1, 3, 4>(channels, [&](auto c) {
+            hipLaunchKernelGGL(k_sdf_error_lines<decltype(c)::value>, grid, block, 0, stream, viewOf(b), dGlyphs, dTiles, w, h, scanlinesPerRow, fillRule, base, n, listX, listDir, refCap, lines);
+        });
     }
     hipLaunchKernelGGL(k_sdf_error_sum, dim3((b->nGlyphs+63)/64), dim3(64), 0, stream, (const double *) lines, b->nGlyphs, h, scanlinesPerRow, dErrors);
     HIPCHK(hipGetLastError());
@@ -3948,14 +3921,16 @@ extern "C" int msdfhip_debug_wait_profile(unsigned long long *out24, int reset) 
 // ---- per-glyph box sizes: msdfhip_batch_generate_sized, msdfhip_tiles_to_bytes_sized ---------------------------------------------------------------
 //
 // The launch chain is that of a uniform call at W x H = the batch's largest box (msdf_sizedplan.hpp): runGenerate with GenerateCall::boxDims set plans with the
-// same planners, takes the same routes and counts them in the same counters; where it would launch a kernel it launches the kernel's sized twin, which it gets from
-// one of the functions below. They are the ONLY code that names the twins and they come last in this file, so that the twins are instantiated behind every
-// kernel the code object has always held (forDistanceVariant).
+// same planners, takes the same routes and counts them in the same counters; where it would launch a kernel, launchTwinned launches the kernel's sized twin from the
+// same argument list. It gets the twin from one of the functions below, by the sibling's template arguments as plain integers. They are the ONLY code that names the
+// twins and they come last in this file, so that the twins are instantiated behind every kernel the code object has always held. Their return types are derived from
+// the siblings' (sizedTwinOf), so a twin whose signature drifts does not compile here either.
 
 namespace {
 
-DistanceSizedKernel distanceSizedKernel(int sel, bool overlap, bool gres, int tpw) {
-    // (the five variants of forDistanceVariant per selector)
+decltype(sizedTwinOf(k_distance<1, false, false, 1>)) distanceSizedKernel(int sel, bool overlap, bool gres, int tpw) {
+    // (the five variants of forDistanceVariant per selector. Not written with it: the nested conditional instantiates the overlapping three in an order
+    // of its own, which is the order the code object holds them in.)
 #define MSDF_SIZED_VARIANTS(SEL) \
     case SEL: return !overlap ? (gres ? k_distance_sized<SEL, false, true, 1> : k_distance_sized<SEL, false, false, (int) QUAD>) \
                      : gres ? k_distance_sized<SEL, true, true, 1> : tpw != 1 ? k_distance_sized<SEL, true, false, (int) QUAD> : k_distance_sized<SEL, true, false, 1>;
@@ -3968,31 +3943,31 @@ DistanceSizedKernel distanceSizedKernel(int sel, bool overlap, bool gres, int tp
 #undef MSDF_SIZED_VARIANTS
     return NULL;
 }
-UnculledSizedKernel unculledSizedKernel(int sel, bool overlap) {
-    switch (sel) {
-        case 1: return overlap ? k_distance_unculled_sized<1, true> : k_distance_unculled_sized<1, false>;
-        case 2: return overlap ? k_distance_unculled_sized<2, true> : k_distance_unculled_sized<2, false>;
-        case 3: return overlap ? k_distance_unculled_sized<3, true> : k_distance_unculled_sized<3, false>;
-    }
-    return overlap ? k_distance_unculled_sized<4, true> : k_distance_unculled_sized<4, false>;
+decltype(sizedTwinOf(k_distance_unculled<1, false>)) unculledSizedKernel(int sel, bool overlap) {
+    decltype(unculledSizedKernel(sel, overlap)) twin = NULL;
+    forOneOf<1, 2, 3, 4>(sel, [&](auto s) { twin = overlap ? k_distance_unculled_sized<decltype(s)::value, true> : k_distance_unculled_sized<decltype(s)::value, false>; });
+    return twin;
 }
-EcSlowSizedKernel ecSlowSizedKernel(int n, bool overlap, bool gres) {      // (the three of dispatchEc per channel count)
-    if (n == 3)
-        return !overlap ? k_ec_slow_sized<3, false, false> : gres ? k_ec_slow_sized<3, true, true> : k_ec_slow_sized<3, true, false>;
-    return !overlap ? k_ec_slow_sized<4, false, false> : gres ? k_ec_slow_sized<4, true, true> : k_ec_slow_sized<4, true, false>;
+decltype(sizedTwinOf(k_ec_slow<3, false, false>)) ecSlowSizedKernel(int n, bool overlap, bool gres) {      // (the three of dispatchEc per channel count)
+    decltype(ecSlowSizedKernel(n, overlap, gres)) twin = NULL;
+    forOneOf<3, 4>(n, [&](auto c) {
+        enum { N = decltype(c)::value };
+        twin = !overlap ? k_ec_slow_sized<N, false, false> : gres ? k_ec_slow_sized<N, true, true> : k_ec_slow_sized<N, true, false>;
+    });
+    return twin;
 }
-EcFastSizedKernel ecFastSizedKernel(int n, bool lazy) {
-    if (n == 3)
-        return lazy ? k_ec_fast_sized<3, true> : k_ec_fast_sized<3, false>;
-    return lazy ? k_ec_fast_sized<4, true> : k_ec_fast_sized<4, false>;
+decltype(sizedTwinOf(k_ec_fast<3, false>)) ecFastSizedKernel(int n, bool lazy) {
+    decltype(ecFastSizedKernel(n, lazy)) twin = NULL;
+    forOneOf<3, 4>(n, [&](auto c) { twin = lazy ? k_ec_fast_sized<decltype(c)::value, true> : k_ec_fast_sized<decltype(c)::value, false>; });
+    return twin;
 }
-EcQuerySizedKernel ecQuerySizedKernel(int n, bool overlap) {
-    if (n == 3)
-        return overlap ? k_ec_query_sized<3, true> : k_ec_query_sized<3, false>;
-    return overlap ? k_ec_query_sized<4, true> : k_ec_query_sized<4, false>;
+decltype(sizedTwinOf(k_ec_query<3, false>)) ecQuerySizedKernel(int n, bool overlap) {
+    decltype(ecQuerySizedKernel(n, overlap)) twin = NULL;
+    forOneOf<3, 4>(n, [&](auto c) { twin = overlap ? k_ec_query_sized<decltype(c)::value, true> : k_ec_query_sized<decltype(c)::value, false>; });
+    return twin;
 }
-SignSizedKernel signSizedKernel(int n) {
-    return n == 1 ? k_sign_correction_sized<1> : n == 3 ? k_sign_correction_sized<3> : k_sign_correction_sized<4>;
+decltype(sizedTwinOf(k_sign_correction<1>)) signSizedKernel(int n) {
+    return n == 1 ? k_sign_correction_sized<1> : n == 3 ? k_sign_correction_sized<3> : k_sign_correction_sized<4>;   // (likewise: instantiated as 3, 4, 1)
 }
 
 // The sizes of a sized call, validated (msdf_sizedplan.hpp). No device call.
@@ -4080,11 +4055,9 @@ int msdfhip_tiles_to_bytes_sized(const float *dTiles, int nGlyphs, const int32_t
     const unsigned gx = (unsigned) ((layout.slot+255)/256 < 64 ? (layout.slot+255)/256 : 64), gy = (unsigned) (nGlyphs < 65535 ? nGlyphs : 65535);
     const int32_t *dDims = reinterpret_cast<const int32_t *>(dMeta.ptr);
     const long long *dOffsets = dMeta.ptr+nGlyphs;
-    switch (channels) {
-        case 1: hipLaunchKernelGGL(k_tiles_to_bytes_sized<1>, dim3(gx, gy), dim3(256), 0, stream, dTiles, dGlyphs, nGlyphs, dDims, dOffsets, dAtlas); break;
-        case 3: hipLaunchKernelGGL(k_tiles_to_bytes_sized<3>, dim3(gx, gy), dim3(256), 0, stream, dTiles, dGlyphs, nGlyphs, dDims, dOffsets, dAtlas); break;
-        default: hipLaunchKernelGGL(k_tiles_to_bytes_sized<4>, dim3(gx, gy), dim3(256), 0, stream, dTiles, dGlyphs, nGlyphs, dDims, dOffsets, dAtlas); break;
-    }
+    forOneOf<1, 3, 4>(channels, [&](auto n) {
+        hipLaunchKernelGGL(k_tiles_to_bytes_sized<decltype(n)::value>, dim3(gx, gy), dim3(256), 0, stream, dTiles, dGlyphs, nGlyphs, dDims, dOffsets, dAtlas);
+    });
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(stream));                        // (the staging vector and the device buffer of this call go with it)
     return MSDFHIP_OK;
