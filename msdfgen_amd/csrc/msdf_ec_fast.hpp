@@ -26,6 +26,13 @@
 //    corner test and the protectEdges pairs afterwards.  Where a diagonal pair would hand a distance-check candidate to the sink at or
 //    after a conditional artifact of the same pair (unprotected, the eager order has left the pair by then), the candidate is held
 //    back (fourth bit) and handed over in a second visit of that pair once the texel is known to be protected: same candidate set.
+//  * Stage 1 (the sign / radius tests that settle nearly all of a texel's 24 + 8 tests) only SAYS which tests survive: one word per texel, a bit per
+//    test (texelCandidateMask, texelProtectMask), built from the very predicates with selects and ORs. k_ec_fast hands the survivors of a tile's 64
+//    texels to stage 2 in one step (ecAppendItems: popcount, exclusive prefix sum over the wavefront, a walk over the set bits) where every one of the
+//    32 emit sites had been a push of its own, an LDS atomic and a wait each. The items are the same set; their order in the queue changes, and with it
+//    the order in which a glyph's distance-check candidates reach its segment -- nothing reads either order: verdicts are OR-ed into the texel's word,
+//    k_ec_query stores the same median for every candidate that decides a texel, the overflow rule looks at the count. The host walk and every other
+//    caller take the tests from texelCandidatePairs / texelProtectPairs, which walk the bits in the order of the emission they replace.
 //  * Three template switches that only k_ec_fast turns on (everything else, the host walk included, runs the defaults = the reference's spelling):
 //    HWMED, the hardware's median where a wavefront's vote has shown that no operand can be a NaN (msdf_device.hpp: med3f; the consumers of a median
 //    and why none sees a zero's sign: at evaluatePair); INDEXED, a test's channels read at computed addresses instead of selected; CORDER, the order
@@ -115,10 +122,15 @@ MSDF_HD bool quadraticMayHaveRootInRange(double a, double b, double c) {
 // Bernstein coefficients (dA, dBC/2, dD) on [0, 1] (f(0) = dA, f(1) = dD). If all three have the same sign with a margin that
 // dwarfs the rounding of the reference's float coefficients (dD-dBC+dA, dBC-dA-dA: <= 5e-7*M), the quadratic has no real root in
 // [0, 1], so solveQuadratic cannot return one in (0.01, 0.99). False = "cannot have a root".
+// HWMED (no operand is a NaN -- k_ec_fast behind its vote: differences of finite channels below 2^100): "all three above eps" is "the smallest is", "all
+// three below -eps" is "the largest is": v_min3_f32, v_max3_f32 and two compares for six compares and five mask operations. Zeros of either sign compare alike.
+template <bool HWMED = false>
 MSDF_HD bool bernsteinMayHaveRoot(float dA, float dBC, float dD) {
     const float m = fmaxf(fmaxf(fabsf(dA), fabsf(dBC)), fabsf(dD));
     const float eps = 1e-5f*m;
     const float h = .5f*dBC;
+    if (HWMED)
+        return !(med3Lo(med3Lo(dA, h), dD) > eps || med3Hi(med3Hi(dA, h), dD) < -eps);
     return !((dA > eps && h > eps && dD > eps) || (dA < -eps && h < -eps && dD < -eps));
 }
 
@@ -297,25 +309,34 @@ MSDF_HD void loadNeighbourhood(Neighbourhood &nb, const SdfView &sdf, int x, int
 // protectEdges (MSDFErrorCorrection.cpp:189-250) as a gather, from the register neighbourhood; see protectedByEdges in msdf_ec.hpp. Two
 // stages like findErrors below: stage 1 emits the neighbours m = (dy+1)*3+(dx+1) whose pair passes the radius test (:201, :217, :233),
 // stage 2 (evaluateProtectPair) runs edgeBetweenTexels on such a pair -- up to three fp64 divisions -- and is queued by the kernel.
-template <class Emit>
-MSDF_HD void texelProtectPairs(const Neighbourhood &nb, const EcParams &p, Emit &emit) {
+// Stage 1 says WHICH pairs pass, as bit m of one word (texelProtectMask: selects and ORs, no branch per pair); the kernel appends a tile's pairs to its
+// queue in one step (ecAppendItems below), everything else walks the bits in ascending m -- the order of the reference's sweeps, as before.
+enum { EC_PROTECT_TESTS = 8, EC_PROTECT_MASK = 0x1ef };    // bits 0-8 without the centre
+MSDF_HD unsigned texelProtectMask(const Neighbourhood &nb, const EcParams &p) {
     const float sdev = nb.dev[1][1];
+    unsigned mask = 0;
     MSDF_UNROLL
     for (int dy = -1; dy <= 1; ++dy) {
         MSDF_UNROLL
         for (int dx = -1; dx <= 1; ++dx) {
             if (!dx && !dy)
                 continue;
-            if (!(nb.cls[dy+1][dx+1]&EC_CLS_INSIDE))
-                continue;
             const float radius = dy == 0 ? p.radiusH : dx == 0 ? p.radiusV : p.radiusD;
             const float odev = nb.dev[dy+1][dx+1];
             const bool selfIsA = dy > 0 || (dy == 0 && dx > 0);
             const float sum = selfIsA ? sdev+odev : odev+sdev;                     // fabsf(am-.5f)+fabsf(bm-.5f)
-            if (sum < radius)
-                emit((dy+1)*3+(dx+1));
+            mask |= (((nb.cls[dy+1][dx+1]&EC_CLS_INSIDE) != 0)&(sum < radius)) ? 1u<<((dy+1)*3+(dx+1)) : 0u;
         }
     }
+    return mask;
+}
+
+template <class Emit>
+MSDF_HD void texelProtectPairs(const Neighbourhood &nb, const EcParams &p, Emit &emit) {
+    const unsigned mask = texelProtectMask(nb, p);
+    for (int m = 0; m < 9; ++m)
+        if (mask&(1u<<m))
+            emit(m);
 }
 
 // Is `self` protected through its pair with neighbour m (`other`)? Pair orientation as the reference's sweeps: `a` is the texel of the
@@ -362,26 +383,24 @@ MSDF_HD int ecNeighbourDy(int k) { return k < 4 ? (k == 1 ? -1 : k == 3 ? 1 : 0)
 // linear tests of a neighbour are one mask, "positive here and negative there, or the reverse", and one branch on it. The diagonal tests read the
 // channels: dBC belongs to no single texel. They are spelled as the reference spells them (dBC left to right); the class words only tell where
 // dA == 0 && dD == 0, the one case in which dBC == 0 leaves nothing to solve.
-template <class Emit>
-MSDF_HD void texelCandidatePairs(const Neighbourhood &nb, Emit &emit) {
+// The survivors are returned as ONE word, test (k, j) = bit 4*k+j (texelCandidateMask): the three linear tests of a neighbour are their mask shifted into
+// place, a diagonal test is a select and an OR -- one branch per diagonal neighbour (it skips the channel reads), none per test. Handing a survivor over
+// is not stage 1's business: k_ec_fast appends all items of a tile to its queue in one step (ecAppendItems), the host walk and every other caller take
+// them from texelCandidatePairs, which walks the bits in ascending order -- k, then j: the order of the emission it replaces.
+enum { EC_FIND_TESTS = 24, EC_FIND_MASK = 0x77777777, EC_FIND_LINEAR = 0x7777 };     // 8 neighbours x 3 channel pairs, bit 4*k+3 is no test; k < 4: the linear tests
+template <bool HWMED = false>
+MSDF_HD unsigned texelCandidateMask(const Neighbourhood &nb) {
     const float *c = nb.v[1][1];
     const float cdev = nb.dev[1][1];
     const unsigned cw = nb.cls[1][1];
+    unsigned mask = 0;
     MSDF_UNROLL
     for (int k = 0; k < 4; ++k) {
         const int dx = k == 0 ? -1 : k == 2 ? 1 : 0, dy = k == 1 ? -1 : k == 3 ? 1 : 0;
         const unsigned nw = nb.cls[dy+1][dx+1];
         // bit j: D[j] > 0 here and < 0 there, or < 0 here and > 0 there; none for a neighbour outside the bitmap, whose word is 0
         const unsigned opposite = ((cw&(nw>>3))|((cw>>3)&nw))&7u;
-        const unsigned m = cdev >= nb.dev[dy+1][dx+1] ? opposite : 0u;
-        if (m) {
-            if (m&1u)
-                emit(k, 0);
-            if (m&2u)
-                emit(k, 1);
-            if (m&4u)
-                emit(k, 2);
-        }
+        mask |= cdev >= nb.dev[dy+1][dx+1] ? opposite<<(4*k) : 0u;
     }
     MSDF_UNROLL
     for (int k = 4; k < 8; ++k) {
@@ -396,12 +415,51 @@ MSDF_HD void texelCandidatePairs(const Neighbourhood &nb, Emit &emit) {
         for (int j = 0; j < 3; ++j) {
             const int i0 = j, i1 = j == 2 ? 0 : j+1;
             const float dA = c[i1]-c[i0], dBC = b[i1]-b[i0]+cc[i1]-cc[i0], dD = d[i1]-d[i0];
-            if ((zeroAD&(64u<<j)) && dBC == 0)
-                continue;
-            if (bernsteinMayHaveRoot(dA, dBC, dD))
-                emit(k, j);
+            const bool nothingToSolve = ((zeroAD&(64u<<j)) != 0)&(dBC == 0);
+            mask |= ((!nothingToSolve)&bernsteinMayHaveRoot<HWMED>(dA, dBC, dD)) ? 1u<<(4*k+j) : 0u;
         }
     }
+    return mask;
+}
+
+template <class Emit>
+MSDF_HD void texelCandidatePairs(const Neighbourhood &nb, Emit &emit) {
+    const unsigned mask = texelCandidateMask(nb);
+    for (int bit = 0; bit < 32; ++bit)
+        if (mask&(1u<<bit))
+            emit(bit>>2, bit&3);
+}
+
+// ---- one append per tile ---------------------------------------------------------------------------------------------------------------
+// A queued item is 16 bits: lane | bit<<6, `bit` the test's place in its mask (find: 4*k+j, so k and j are shifts; protect: m). A lane hands over all
+// its survivors at once: it reserves popcount(mask) slots that are this lane's alone (reserve, below; k_ec_fast: an exclusive prefix sum over the
+// wavefront; the host test: running counts, lanes in any order) and writes them in a walk over its set bits. Bits outside VALID
+// are dropped BEFORE the count is taken, so whatever the mask, a lane takes n <= TESTS slots (64 lanes: the queue's capacity) and the walk makes exactly
+// n trips, one per slot: the bound is the loop's own condition, a wrong mask can neither make it spin nor write past the lane's slots. Returns n.
+// The order of the items in the queue is free: phase C ORs verdicts into the owning texel's word, and a texel's distance-check candidates reach the
+// glyph's segment in any order (k_ec_query writes one value per texel whichever candidate decides it; the overflow rule looks at the count).
+// What IS worth keeping of the old order (item by item, site after site: the queue sorted by test): linear items (k < 4) and diagonal ones take different
+// paths through stage 2, and a round of 64 items that holds one kind runs one path. So the queue has two parts, the tests of FIRST ahead of the others:
+// reserve(nFirst, nOthers, atFirst, atOthers) gives a lane its slots in each part (measured on the bench workload with the kinds mixed lane by lane:
+// +36 of stage 2's 408 vector instructions per wavefront).
+MSDF_HD int ecItemBit(unsigned item) { return (int) (item>>6); }
+template <unsigned VALID, int TESTS, unsigned FIRST, class Reserve>
+MSDF_HD int ecAppendItems(unsigned short *queue, unsigned mask, int lane, Reserve &reserve) {
+    static_assert(__builtin_popcount(VALID) == TESTS && (FIRST&~VALID) == 0, "a lane's share of the queue is one slot per test");
+    mask &= VALID;
+    const int n = __builtin_popcount(mask);                 // <= TESTS
+    const int nFirst = __builtin_popcount(mask&FIRST);
+    int at = 0, atOthers = 0;
+    reserve(nFirst, n-nFirst, at, atOthers);
+    const int jump = atOthers-(at+nFirst);                  // from the lane's last slot of the first part to its first of the second
+    // (rolled: a wavefront makes as many trips as its fullest lane has items, a handful; unrolled by eight the compiler packs the items into 128-bit
+    // stores at 2-byte-aligned addresses and every tile with one full lane runs a forty-instruction trip)
+    MSDF_NOUNROLL
+    for (int i = 0; i < n; ++i) {                           // at most TESTS trips; the mask has exactly n bits, one goes per trip
+        queue[at+i+(i >= nFirst ? jump : 0)] = (unsigned short) (lane|__builtin_ctz(mask)<<6);
+        mask &= mask-1;
+    }
+    return n;
 }
 
 MSDF_HD float pick3(const float *v, int i) { return i == 0 ? v[0] : i == 1 ? v[1] : v[2]; }

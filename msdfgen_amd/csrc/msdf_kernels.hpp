@@ -1227,7 +1227,7 @@ k_ec_params(EcGlyphParams *out, BatchView batch, const MsdfHipGlyph *glyphs, Msd
 // the stencil byte [g][h][w] (native rows). Candidates whose verdict needs an exact shape-distance query are appended to `cands`
 // and judged by k_ec_query; a texel with a cheaply decided ERROR never needs them (the flag is an OR).
 #ifndef MSDF_EC_FAST_WAVES_PER_SIMD
-#define MSDF_EC_FAST_WAVES_PER_SIMD 7   // lazy and eager instantiation 60 VGPRs, no scalar register parked in vector lanes (the lazy one had 65 / 4 until its configuration became compile-time constants); no vector spills, no scratch (tests/test_ec_fast_isa_budget.py); the kernel's 5.6 KB of LDS allow 7 wavefronts per SIMD anyway. Correction pass on the distinct-glyph set: 8 -> 1.94 ms, 7 -> 1.90, 6 -> 1.90
+#define MSDF_EC_FAST_WAVES_PER_SIMD 7   // lazy instantiation 62 VGPRs, eager 65 (60 each before stage 1 carried its survivors as a mask), no scalar register parked in vector lanes (the lazy one had 65 / 4 until its configuration became compile-time constants); no vector spills, no scratch (tests/test_ec_fast_isa_budget.py); the kernel's 5.6 KB of LDS allow 7 wavefronts per SIMD anyway. Correction pass on the distinct-glyph set: 8 -> 1.94 ms, 7 -> 1.90, 6 -> 1.90
 #endif
 // LDS of k_ec_fast per wavefront: 10x10 halo tile of the field | per-texel verdict words | item count | item queue (5.6 KB for msdf).
 enum { EC_HALO = TILE+2, EC_QUEUE_CAP = WAVE*24, EC_PROTECT_QUEUE_CAP = WAVE*8 };
@@ -1283,14 +1283,40 @@ struct EcConstant {
     static constexpr T value = V;
 };
 
-struct EcPushProtect {
-    unsigned short *queue;
+// Stage 1's survivors of all 64 texels go to their queue in ONE step (msdf_ec_fast.hpp: ecAppendItems): every lane brings its mask, takes the exclusive
+// prefix sum of the popcounts as its offset and writes its items; the sum over the wavefront is the queue's count. All lanes of the wavefront call it
+// together (a lane without a texel brings 0), and the queue must be empty: the count is stored, not added to -- no LDS atomic, no round trip to wait for
+// (pushing item by item had cost a single-lane atomic and a wait at each of the 24 + 8 emit sites). The scan is the usual one over DPP: shifts by 1, 2,
+// 4, 8 inside a row of 16 lanes, then lane 15 of a row to the next row (rows 1 and 3), then lane 31 to rows 2 and 3; a lane without a source adds 0.
+__device__ __forceinline__ int waveInclusiveSum(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);     // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);     // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);     // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);     // row_shr:8
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);     // row_bcast:15 into rows 1 and 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);     // row_bcast:31 into rows 2 and 3
+    return v;
+}
+// The queue's two parts (ecAppendItems: FIRST) take ONE scan: both counts ride in one word, 16 bits each (a part holds at most 64*24 items).
+struct EcWaveReserve {
     int *count;
-    int lane;
-    __device__ void operator()(int m) { queue[atomicAdd(count, 1)] = (unsigned short) (lane|m<<6); }
+    __device__ void operator()(int nFirst, int nOthers, int &atFirst, int &atOthers) {
+        const int n = nFirst|nOthers<<16;
+        const int through = waveInclusiveSum(n);
+        const int total = __builtin_amdgcn_readlane(through, WAVE-1), before = through-n;
+        *count = (total&0xffff)+(total>>16);                            // (every lane stores the same value: no branch around one store)
+        atFirst = before&0xffff, atOthers = (total&0xffff)+(before>>16);
+    }
 };
+template <unsigned VALID, int TESTS, unsigned FIRST>
+__device__ __forceinline__ void ecAppendWave(unsigned short *queue, int *count, unsigned mask, int lane) {
+    if (__ballot(mask != 0) == 0)
+        return;                                                         // nothing survives in this tile (wave-uniform): the count stays 0
+    EcWaveReserve reserve = { count };
+    ecAppendItems<VALID, TESTS, FIRST>(queue, mask, lane, reserve);
+}
 
-// ORDER: 1 the lazy order, 0 the eager one -- k_ec_fast has an instantiation of each and the host picks by the configuration (60 VGPRs each, no scalar
+// ORDER: 1 the lazy order, 0 the eager one -- k_ec_fast has an instantiation of each and the host picks by the configuration (62 and 65 VGPRs, no scalar
 // registers parked in vector lanes) -- or -1: decided here, one body for k_single_call.
 // SHAPE_ROWS: EcParams::shapeRows, the legacy generators' correction (eager order only: it runs without the distance check). An instantiation of its own,
 // so that the kernels of the modern entry points stay what they were.
@@ -1310,7 +1336,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
     float *halo = reinterpret_cast<float *>(smemFast);                                      // [EC_HALO*EC_HALO][N]
     int *verdictLds = reinterpret_cast<int *>(halo+EC_HALO*EC_HALO*N);                      // [WAVE]: bits 0-3 EC_V_*, bit 8 protected
     int *itemCount = verdictLds+WAVE;
-    unsigned short *queue = reinterpret_cast<unsigned short *>(itemCount+4);               // [EC_QUEUE_CAP]: lane | k<<6 | j<<9
+    unsigned short *queue = reinterpret_cast<unsigned short *>(itemCount+4);               // [EC_QUEUE_CAP]: lane | (4*k+j)<<6
     unsigned short *protectQueue = queue+EC_QUEUE_CAP;                                      // [EC_PROTECT_QUEUE_CAP]: lane | m<<6
     // |median - .5| and the class word of every halo texel, computed once while the halo is staged (msdf_ec_fast.hpp: Neighbourhood::dev, ::cls; a position
     // outside the bitmap gets the word 0). The table overlays the TAIL of the item queue: every lane has its nine entries in registers before the wavefront
@@ -1411,6 +1437,9 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
         }
     }
     waveSync();                                                         // classLds is dead from here on: the queue may grow into it
+    unsigned findMask = 0, protectMask = 0;                             // the texel's surviving tests; none for a lane without a texel
+    // The vote is in: the diagonal tests of stage 1 (bernsteinMayHaveRoot) and everything from phase B to the apply step have a copy that relies on it.
+    const bool hwMedian = VOTE && __ballot(objection) == 0;
     if (classify) {
         MSDF_UNROLL
         for (int dy = -1; dy <= 1; ++dy) {
@@ -1423,25 +1452,20 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
         if (p.mode == EC_MODE_EDGE_PRIORITY && !lazy) {
             if (cornerTexel)
                 st |= EC_PROTECTED;
-            if (!(st&EC_PROTECTED)) {
-                EcPushProtect pushProtect = { protectQueue, itemCount+1, lane };
-                texelProtectPairs(nb, p, pushProtect);
-            }
+            if (!(st&EC_PROTECTED))
+                protectMask = texelProtectMask(nb, p);
         } else if (p.mode == EC_MODE_EDGE_ONLY)
             st |= EC_PROTECTED;
-        struct Push {
-            unsigned short *queue;
-            int *count;
-            int lane;
-            __device__ void operator()(int k, int j) { queue[atomicAdd(count, 1)] = (unsigned short) (lane|k<<6|j<<9); }
-        } push = { queue, itemCount, lane };
-        texelCandidatePairs(nb, push);
+        findMask = hwMedian ? texelCandidateMask<VOTE>(nb) : texelCandidateMask<false>(nb);       // (wave-uniform)
     }
+    // (the whole wavefront again: one append per queue, msdf_ec_fast.hpp: ecAppendItems)
+    if (p.mode == EC_MODE_EDGE_PRIORITY && !lazy)
+        ecAppendWave<EC_PROTECT_MASK, EC_PROTECT_TESTS, EC_PROTECT_MASK>(protectQueue, itemCount+1, protectMask, lane);
+    ecAppendWave<EC_FIND_MASK, EC_FIND_TESTS, EC_FIND_LINEAR>(queue, itemCount, findMask, lane);
     verdictLds[lane] = (st&EC_PROTECTED) ? 0x100 : 0;
     waveSync();
 
     // Everything from here to the apply step takes medians: compiled twice, and a wavefront runs the HWMED copy iff its vote passed (wave-uniform).
-    const bool hwMedian = VOTE && __ballot(objection) == 0;
     const auto sweep = [&](auto hwmedTag) {
     constexpr bool HWMED = decltype(hwmedTag)::value;
     // ---- phase B (lane = queued pair): protectEdges' edgeBetweenTexels tests, densely; a hit protects the owning texel (eager order; the lazy one has queued none)
@@ -1462,7 +1486,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
             if (it >= nItems)
                 continue;
             const unsigned item = queue[it];
-            const int s = item&63, k = (item>>6)&7, jp = item>>9;
+            const int s = item&63, k = ecItemBit(item)>>2, jp = ecItemBit(item)&3;
             const int word = verdictLds[s];
             if (order == EC_ORDER_LAZY_HELD && (word&(0x100|EC_V_HELD)) != (0x100|EC_V_HELD))
                 continue;
@@ -1500,6 +1524,7 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
         EcParams pr = p;
         pr.radiusH = gl.radiusH, pr.radiusV = gl.radiusV, pr.radiusD = gl.radiusD;
         cornerTexel = ecTileCornerTexel(corners+2*(size_t) gl.cornerBegin, gl.nCorners, tx, ty, boxH, gd.flip, lane);
+        unsigned roundMask = 0;
         if (need) {
             if (cornerTexel)
                 verdictLds[lane] |= 0x100;
@@ -1517,10 +1542,10 @@ __device__ __forceinline__ void ecFastBody(const BatchView &batch, const MsdfHip
                         nd.cls[dy+1][dx+1] = in ? (unsigned) EC_CLS_INSIDE : 0u;
                     }
                 }
-                EcPushProtect pushProtect = { protectQueue, itemCount+1, lane };
-                texelProtectPairs(nd, pr, pushProtect);
+                roundMask = texelProtectMask(nd, pr);
             }
         }
+        ecAppendWave<EC_PROTECT_MASK, EC_PROTECT_TESTS, EC_PROTECT_MASK>(protectQueue, itemCount+1, roundMask, lane);     // (the lazy order's phase A queued none: the queue is empty)
         waveSync();
         ecRunProtectQueue<N, HWMED>(halo, protectQueue, itemCount[1], verdictLds, lane);
         waveSync();
