@@ -3860,62 +3860,16 @@ int msdfhip_kernel_timing(double *avgDistance, double *avgCorrection, int *launc
 
 } // extern "C"
 
-// Measurement builds only (-DMSDF_BBCOUNT=<counters>, tools/isa_bbcount.py): the execution count of every basic block of the instrumented kernels. The tool
-// compiles this file to gfx950 assembly, inserts a counter bump at the top of every basic block of the chosen kernels (one lane of a few extra VGPRs per
-// block; exec- and SCC-neutral), flushes the lanes into this table with atomics at s_endpgm, and assembles the result back into a library -- the kernels'
-// own instruction stream is the production one. A regular build has no table and reports 0 counters.
-#if defined(MSDF_BBCOUNT)
-extern "C" { __device__ __attribute__((used)) unsigned msdfhip_bbcount[MSDF_BBCOUNT]; }     // (a DEFINITION: the one-line extern "C" form only declares)
-#endif
+// The tables of the measurement builds (msdf_measure.hpp: their readers, which hand out zeros / 0 counters in a regular build).
 extern "C" int msdfhip_debug_bbcount(unsigned *out, int cap, int reset) {
-#if defined(MSDF_BBCOUNT)
-    const int n = cap < (int) MSDF_BBCOUNT ? cap : (int) MSDF_BBCOUNT;
-    HIPCHK(hipDeviceSynchronize());
-    if (out && n > 0)
-        HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(msdfhip_bbcount), sizeof(unsigned)*(size_t) n));
-    if (reset) {
-        static const std::vector<unsigned> zero((size_t) MSDF_BBCOUNT, 0u);
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(msdfhip_bbcount), zero.data(), sizeof(unsigned)*zero.size()));
-    }
+    int n = 0;
+    HIPCHK(msdfhip::readBbcount(out, cap, reset, n));
     return n;
-#else
-    (void) out, (void) cap, (void) reset;
-    return 0;
-#endif
 }
 
-// Measurement builds only (-DMSDF_PROFILE_WAITS, tools/profile_waits.py): reads (and optionally clears) the per-wavefront cycle table of
-// k_distance. A regular build has no such table and reports zeros.
 extern "C" int msdfhip_debug_wait_profile(unsigned long long *out24, int reset) {
-#if defined(MSDF_PROFILE_WAITS)
-    unsigned long long zero[24] = { 0 };
-    if (out24)
-        HIPCHK(hipMemcpyFromSymbol(out24, HIP_SYMBOL(msdfhip::gWaitProfile), sizeof(zero)));
-    if (reset)
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(msdfhip::gWaitProfile), zero, sizeof(zero)));
+    HIPCHK(msdfhip::readWaitProfile(out24, reset));
     return MSDFHIP_OK;
-#elif defined(MSDF_PROFILE_QUERY)                                    // (-DMSDF_PROFILE_QUERY, tools/profile_query.py: the table of k_ec_query instead)
-    unsigned long long zero[24] = { 0 };
-    zero[3] = ~0ull;                                                // first start: an atomic minimum
-    if (out24) {
-        unsigned long long detail[16];
-        HIPCHK(hipMemcpyFromSymbol(out24, HIP_SYMBOL(msdfhip::gQueryProfile), sizeof(zero)));
-        HIPCHK(hipMemcpyFromSymbol(detail, HIP_SYMBOL(msdfhip::gQueryDetail), sizeof(detail)));
-        if (reset == 2)                                             // second page: the cooperative query in detail (tools/profile_query.py)
-            memcpy(out24, detail, sizeof(detail));
-    }
-    if (reset == 1) {
-        unsigned long long zero16[16] = { 0 };
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(msdfhip::gQueryProfile), zero, sizeof(zero)));
-        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(msdfhip::gQueryDetail), zero16, sizeof(zero16)));
-    }
-    return MSDFHIP_OK;
-#else
-    if (out24)
-        memset(out24, 0, 24*sizeof(unsigned long long));
-    (void) reset;
-    return MSDFHIP_OK;
-#endif
 }
 
 // ---- per-glyph box sizes: msdfhip_batch_generate_sized, msdfhip_tiles_to_bytes_sized ---------------------------------------------------------------

@@ -34,6 +34,8 @@
 
 #define MSDF_UNLIKELY(x) __builtin_expect(!!(x), 0)   // a cold path: the register allocator places its spill code by block frequency
 
+#include "msdf_measure.hpp"   // the measurement hooks (profNow, profAdd, ...): empty unless a measurement build fills them
+
 namespace msdfhip {
 
 // Wave vote: does ANY lane of the wavefront need this? Used where skipping work is exact whenever no lane needs it and evaluating more is
@@ -964,10 +966,6 @@ MSDF_HD void selAddContourSerial(Selector<SEL> &sel, const EdgeRec *rec, const E
 template <int SEL> MSDF_HD void selAddContour(Selector<SEL> &sel, const EdgeRec *rec, const EdgesAll &edges, int c, V2 o) { selAddContourSerial(sel, rec, edges, c, o); }
 template <int SEL> MSDF_HD void selAddContour(Selector<SEL> &sel, const EdgeRec *rec, const EdgesCulled &edges, int c, V2 o) { selAddContourSerial(sel, rec, edges, c, o); }
 
-// Measurement hooks (no-ops unless an edge policy overloads them: msdf_kernels.hpp under MSDF_PROFILE_WAITS).
-template <class Edges> MSDF_HD void profAdd(const Edges &, int, unsigned long long) { }
-template <class Edges> MSDF_HD unsigned long long profNow(const Edges &) { return 0; }
-
 // A TEAM of wavefronts may share one texel tile's walk (msdf_kernels.hpp: TeamExchange, k_single_call): every member walks ITS share of a contour's
 // survivors into a partial selector, afterWalk() hands the helpers' partial selectors to the leader, which merges them (selMergePartial) and carries on
 // alone; a helper gets `false` and has nothing else to do for that contour. The default is a team of one.
@@ -1074,7 +1072,7 @@ MSDF_HD void combinerEpilogue(const Edges &edges, const Wind windings, int C, co
     } else {
         for (int ch = 0; ch < NCH; ++ch)
             out[ch] = shapeD[ch];
-        profAdd(edges, 11, profNow(edges)-te0);
+        profAdd(edges, PROF_EPILOGUE, profNow(edges)-te0);
         return;
     }
     for (int c = 0; c < C; ++c)
@@ -1094,7 +1092,7 @@ MSDF_HD void combinerEpilogue(const Edges &edges, const Wind windings, int C, co
             dist[ch] = shapeD[ch];
     for (int ch = 0; ch < NCH; ++ch)
         out[ch] = dist[ch];
-    profAdd(edges, 11, profNow(edges)-te0);
+    profAdd(edges, PROF_EPILOGUE, profNow(edges)-te0);
 }
 
 // OverlappingContourCombiner::distance (contour-combiners.cpp:77-134), restructured around what a lane has to REMEMBER.
@@ -1149,7 +1147,7 @@ MSDF_HD void shapeDistanceOverlap(const EdgeRec *rec, const Edges &edges, const 
             const unsigned long long tw0 = profNow(edges);
             selAddContour(sel, rec, edges, c, o);
             const unsigned long long tw1 = profNow(edges);
-            profAdd(edges, pass == 0 ? 8 : 10, tw1-tw0);
+            profAdd(edges, pass == 0 ? PROF_WALK : PROF_SECOND_WALK, tw1-tw0);
             if (pass == 0 && C == 1) {
                 // One contour: the shape/inner/outer selectors can only ever hold that contour's own state, and every branch of
                 // contour-combiners.cpp:104-133 then returns that contour's distance -- identical to the simple combiner.
@@ -1176,7 +1174,7 @@ MSDF_HD void shapeDistanceOverlap(const EdgeRec *rec, const Edges &edges, const 
                 }
             } else if (member)
                 selMerge(acc, sel);
-            profAdd(edges, 9, profNow(edges)-tw1);
+            profAdd(edges, PROF_BOOKKEEPING, profNow(edges)-tw1);
         }
         if (pass == 0) {
             second = MSDF_WAVE_ANY(nInner >= 2 || nOuter >= 2);
@@ -1223,7 +1221,7 @@ MSDF_HD void shapeDistanceOverlapSplit(const EdgeRec *rec, const Edges &edges, c
         const unsigned long long tw0 = profNow(edges);
         selAddContour(sel, rec, edges, c, o);
         const unsigned long long tw1 = profNow(edges);
-        profAdd(edges, 8, tw1-tw0);
+        profAdd(edges, PROF_WALK, tw1-tw0);
         if (!team.afterWalk(sel))                                // (a helper wavefront of a team: its share of the contour is with the leader now)
             continue;
         if (C == 1) {                                            // (see above: identical to the simple combiner)
@@ -1247,7 +1245,7 @@ MSDF_HD void shapeDistanceOverlapSplit(const EdgeRec *rec, const Edges &edges, c
                 firstOuter = c;
             ++nOuter;
         }
-        profAdd(edges, 9, profNow(edges)-tw1);
+        profAdd(edges, PROF_BOOKKEEPING, profNow(edges)-tw1);
     }
     if (team.isHelper())
         return;
@@ -1280,7 +1278,7 @@ MSDF_HD void shapeDistanceOverlapSplit(const EdgeRec *rec, const Edges &edges, c
                 selInit(sel);
                 const unsigned long long tw0 = profNow(edges);
                 selAddContour(sel, rec, edges2, c, o);
-                profAdd(edges, 10, profNow(edges)-tw0);
+                profAdd(edges, PROF_SECOND_WALK, profNow(edges)-tw0);
                 if (member)
                     selMerge(acc, sel);
             }

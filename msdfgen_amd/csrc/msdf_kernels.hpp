@@ -359,15 +359,6 @@ __device__ inline EdgeRegs loadEdgeRegs(const EdgeRec *rp, int i) {
     return r;
 }
 
-#if defined(MSDF_PROFILE_WAITS)
-// Measurement build only (tools/profile_waits.sh): where a k_distance wavefront's cycles go. s_memtime stamps inside the hand-placed load
-// batches; per-wave sums are added to this table by lane 0 when the wavefront ends. [0] waves [1] wave cycles [2] phase 1 [3] cycles in
-// the R+E0 batch (issue -> landed) [4] batches [5] cycles in the E1+E2 batch [6] batches [7] cycles evaluating edges (selAddEdge) [8]
-// evaluations [9] cycles in relevance tests + vote [10] phase 2 total [11] batches that took > 1000 cycles [12] > 3000 cycles
-__device__ unsigned long long gWaitProfile[24];
-#define MSDF_STAMP(x) const unsigned long long x = __builtin_readcyclecounter()
-#endif
-
 // Contour::winding of a glyph's contours as two bit masks in scalar registers (bit c: winding > 0 / < 0), built once per wavefront from one
 // vector load + two ballots; contours beyond 63 (global-scratch class only) are read from memory.
 struct WindingMasks {
@@ -380,24 +371,17 @@ struct WindingMasks {
     }
 };
 
-struct EdgesCulledPacked {              // survivors of the per-tile cull as packed entries, grouped by contour, nearest-first within a row
+struct PackedSurvivors {                // survivors of the per-tile cull as packed entries, grouped by contour, nearest-first within a row
     const int *cstart;                  // C+1 compacted offsets
     const int *list;                    // packed entries (LDS)
     int total;                          // cstart[C]
     int first, step;                    // this wavefront walks entries first, first+step, ... of every contour's segment (0, 1: all of them; a team of wavefronts: its rank, the team's size)
-#if defined(MSDF_PROFILE_WAITS)
-    mutable unsigned long long prof[16]; // [8] contour walks of pass 0 [9] per-contour bookkeeping after a walk [10] second walks [11] combiner epilogue [12] tile prologue [13] tile stores | [0] batch cycles [1] batches [2] E batch cycles [3] E batches [4] eval cycles [5] evals [6] relevance cycles [7] slow batches (>1000) | (>3000)<<32
-#endif
     // (holding the offsets in lanes 0..C and fetching them with readlane -- no LDS round trip per contour -- was measured: no gain, and
     // one more VGPR in kernels that sit at their register cap)
     __device__ int begin(int c) const { return MSDF_UNIFORM(cstart[c]); }
     __device__ int end(int c) const { return MSDF_UNIFORM(cstart[c+1]); }
 };
-
-#if defined(MSDF_PROFILE_WAITS)
-__device__ inline void profAdd(const EdgesCulledPacked &edges, int i, unsigned long long dt) { edges.prof[i] += dt; }
-__device__ inline unsigned long long profNow(const EdgesCulledPacked &) { return __builtin_readcyclecounter(); }
-#endif
+struct EdgesCulledPacked : PackedSurvivors, WaitCounters { };   // the edge policy: the lists, then the walk's counters (msdf_measure.hpp: an empty base in a regular build)
 
 template <int SEL>
 __device__ inline void selAddContour(Selector<SEL> &sel, const EdgeRec *rec, const EdgesCulledPacked &edges, int c, V2 o) {
@@ -416,17 +400,11 @@ __device__ inline void selAddContour(Selector<SEL> &sel, const EdgeRec *rec, con
         // inside the shared aperture is { src_shared_base (high dword) | LDS offset (low dword) } -- the aperture is 4 GB-aligned, so the
         // truncation is the address-space cast the compiler itself emits for flat -> LDS. This library is built for gfx950 only (build.py).
         const unsigned nextAddr = (unsigned) (size_t) (edges.list+k+edges.step);
-#if defined(MSDF_PROFILE_WAITS)
-        MSDF_STAMP(t0);
-#endif
+        const unsigned long long t0 = profNow(edges);
         asm volatile("ds_read_b32 %0, %4\n\ts_load_dwordx16 %1, %5, 0x0\n\ts_load_dwordx16 %2, %5, 0x40\n\ts_load_dwordx16 %3, %5, 0x80\n\ts_waitcnt lgkmcnt(0)"
                      : "=v"(nextV), "=&s"(r.r0), "=&s"(r.r1), "=&s"(r.e0) : "v"(nextAddr), "s"(rp));
-#if defined(MSDF_PROFILE_WAITS)
-        MSDF_STAMP(t1);
-        edges.prof[0] += t1-t0, edges.prof[1] += 1;
-        if (t1-t0 > 1000) edges.prof[7] += 1;
-        if (t1-t0 > 3000) edges.prof[7] += 1ull<<32;
-#endif
+        const unsigned long long t1 = profNow(edges);
+        profBatch(edges, t1-t0);
         const unsigned next = k+edges.step < edges.total ? (unsigned) __builtin_amdgcn_readfirstlane((int) nextV) : cur;
         // (Requesting the NEXT survivor's lines here without waiting for them -- a scalar-cache warm-up -- was measured: no change, 6.26 vs
         // 6.28 ms per step; a batch lands in 380 cycles on average, 4 % of a wavefront's life. It also cannot be made safe in C++: the
@@ -436,27 +414,17 @@ __device__ inline void selAddContour(Selector<SEL> &sel, const EdgeRec *rec, con
         bool relevant = MSDF_WAVE_ANY(selEdgeRelevantBox(sel, r, o, bound2));      // some lane within reach of the control box: evaluate, whatever the wedges say
         if (SEL >= 2 && !relevant)
             relevant = MSDF_WAVE_ANY(selEdgeRelevantWedges<SEL>(r, o, bound2));
-#if defined(MSDF_PROFILE_WAITS)
-        MSDF_STAMP(t2);
-        edges.prof[6] += t2-t1;
-#endif
+        const unsigned long long t2 = profNow(edges);
+        profAdd(edges, PROF_RELEVANCE, t2-t1);
         if (relevant) {
             if (r.Type() >= 2)                                       // (fetching a curve's E1 + E2 with the first batch: measured, no gain)
                 asm volatile("s_load_dwordx16 %0, %2, 0xc0\n\ts_load_dwordx16 %1, %2, 0x100\n\ts_waitcnt lgkmcnt(0)" : "=&s"(r.e1), "=&s"(r.e2) : "s"(rp));
-#if defined(MSDF_PROFILE_WAITS)
-            MSDF_STAMP(t3);
-            if (r.Type() >= 2) edges.prof[2] += t3-t2, edges.prof[3] += 1;
-#endif
+            const unsigned long long t3 = profNow(edges);
+            if (r.Type() >= 2)
+                profAdd(edges, PROF_CURVE_BATCH, t3-t2), profAdd(edges, PROF_CURVE_BATCH+1, 1);
             selAddEdge(sel, r, (int) (cur&ENTRY_INDEX_MASK), o);
-#if defined(MSDF_PROFILE_WAITS)
-            {
-                double keep = sel.c[0].td;                          // the stamp must not move above the evaluation
-                asm volatile("" : "+v"(keep));
-                sel.c[0].td = keep;
-            }
-            MSDF_STAMP(t4);
-            edges.prof[4] += t4-t3, edges.prof[5] += 1;
-#endif
+            profPin(edges, sel.c[0].td);                            // the stamp must not move above the evaluation
+            profAdd(edges, PROF_EVAL, profNow(edges)-t3), profAdd(edges, PROF_EVAL+1, 1);
         }
         cur = next;
     }
@@ -701,10 +669,9 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
         const int w = lane < C ? (int) wind.mem[lane] : 0;
         wind.pos = __ballot(w > 0), wind.neg = __ballot(w < 0);
     }
-#if defined(MSDF_PROFILE_WAITS)
-    MSDF_STAMP(pStart);
-    unsigned long long pAcc[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-#endif
+    WaitProbe probe;                                                // (msdf_measure.hpp: both empty in a regular build)
+    WaitCounters sums;
+    probe.begin(sums);
 
     // ---- phase 1: cull + compact (row q of 16 lanes = tile q of the quad; lanes of a row = edges)
     // (two divisions per wavefront; texel positions below use divExact. The quotients come out of the VALU in VGPRs although they are wave-uniform, and the
@@ -727,14 +694,7 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
         // needed) and over the whole shape for the simple combiner (a single selector).
         double U[3] = { DBL_MAX, DBL_MAX, DBL_MAX };
         const int nE = knownEdges >= 0 ? knownEdges : coff[C]-e0;
-#if defined(MSDF_PROFILE_WAITS)
-        unsigned long long pHdr;
-        {
-            int sink = MSDF_UNIFORM(nE+(int) gd.flip);              // the header loads have landed when these are usable
-            asm volatile("" : "+s"(sink));
-            pHdr = __builtin_readcyclecounter()+(unsigned long long) (sink&0);
-        }
-#endif
+        probe.headerLanded(nE+(int) gd.flip);
         // Segment-parallel: the lanes of a row take ROW CONSECUTIVE edges of the glyph whatever their contour (a loop per contour left
         // most lanes idle and cost two dependent gathers per contour: 27 rounds for a 14-contour glyph, now 4).
         // Pass A: the bounds. Overlapping combiner: every edge lowers the bound of ITS contour and channels with an LDS atomic minimum
@@ -772,10 +732,7 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
         }
         if (OVERLAP)
             waveSync();
-#if defined(MSDF_PROFILE_WAITS)
-        MSDF_STAMP(pPassA);
-        pAcc[14] = pHdr-pStart, pAcc[15] = pPassA-pHdr;
-#endif
+        probe.passADone(sums);
         // Pass B: the cull test against the bounds; survivors go to the list grouped by contour (edges are stored contour by contour, so
         // list order = lane order does it), within a DPP row nearest-first inside each contour's segment.
         for (int base = 0; base < nE; base += ROW) {
@@ -829,9 +786,7 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
     waveSync();
     if (TEAM > 1)
         __syncthreads();                                            // the leader's lists are the team's
-#if defined(MSDF_PROFILE_WAITS)
-    MSDF_STAMP(pPhase2);
-#endif
+    probe.phase1Done();
 
     // A latency-shaped launch (k_single_call: this wavefront is alone on its SIMD, nothing hides a miss) first pulls the record lines of ALL the
     // tile's survivors into the scalar cache, four records per wait -- the walk below then pays a cache hit per batch instead of an L2 round
@@ -870,11 +825,7 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
                             : unproject(t, mk(x+.5, y+.5));         // msdfgen.cpp:68 (coord/scale-translate, correctly rounded either way)
         EdgesCulledPacked edges;
         edges.total = MSDF_UNIFORM(cstarts[(size_t) q*(C+1)+C]);
-#if defined(MSDF_PROFILE_WAITS)
-        for (int i = 0; i < 16; ++i)
-            edges.prof[i] = 0;
-        MSDF_STAMP(tTile0);
-#endif
+        const unsigned long long tTile0 = profReset(edges);
         edges.cstart = cstarts+(size_t) q*(C+1);
         edges.list = lists+(size_t) q*maxEdges;
         edges.first = teamRank, edges.step = TEAM;
@@ -909,29 +860,9 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
             // FETCH_SIZE 361 -> 160 MB, WRITE_SIZE 2.98 -> 2.80 GB, step 5.47 -> 5.39 ms)
             __builtin_nontemporal_store(mapDistance(t, d[ch]), &px[ch]);   // msdfgen.cpp:20-48
         }
-#if defined(MSDF_PROFILE_WAITS)
-        {
-            MSDF_STAMP(tTile1);
-            edges.prof[13] += tTile1-tTile0;                        // whole tile: prologue + distance + stores
-        }
-        for (int i = 0; i < 16; ++i)
-            pAcc[i] += edges.prof[i];
-#endif
+        probe.tileDone(sums, edges, tTile0);
     }
-#if defined(MSDF_PROFILE_WAITS)
-    {
-        MSDF_STAMP(pEnd);
-        if (lane == 0) {
-            atomicAdd(&gWaitProfile[0], 1ull), atomicAdd(&gWaitProfile[1], pEnd-pStart), atomicAdd(&gWaitProfile[2], pPhase2-pStart);
-            atomicAdd(&gWaitProfile[3], pAcc[0]), atomicAdd(&gWaitProfile[4], pAcc[1]), atomicAdd(&gWaitProfile[5], pAcc[2]), atomicAdd(&gWaitProfile[6], pAcc[3]);
-            atomicAdd(&gWaitProfile[7], pAcc[4]), atomicAdd(&gWaitProfile[8], pAcc[5]), atomicAdd(&gWaitProfile[9], pAcc[6]), atomicAdd(&gWaitProfile[10], pEnd-pPhase2);
-            atomicAdd(&gWaitProfile[11], pAcc[7]&0xffffffffull), atomicAdd(&gWaitProfile[12], pAcc[7]>>32);
-            atomicAdd(&gWaitProfile[13], pAcc[8]), atomicAdd(&gWaitProfile[14], pAcc[9]), atomicAdd(&gWaitProfile[15], pAcc[10]);
-            atomicAdd(&gWaitProfile[16], pAcc[11]), atomicAdd(&gWaitProfile[17], pAcc[13]);
-            atomicAdd(&gWaitProfile[18], pAcc[14]), atomicAdd(&gWaitProfile[19], pAcc[15]);
-        }
-    }
-#endif
+    probe.flush(sums, lane);
     if (!persistent)
         return;
     waveSync();                                                     // the survivor lists in LDS are rebuilt for the next item
@@ -978,7 +909,7 @@ struct PsdfQuery {                                                  // ShapeDist
 // order, so the merged state -- identical in every lane afterwards -- equals the sequential one bit for bit.
 typedef PB PBSlot;                                                  // a single-edge selector state parked in LDS (40 B)
 
-struct EdgesCooperative {
+struct CooperativeState {
     const int32_t *coff;
     int lane;
     PBSlot *slots;                      // LDS: one slot per edge of the glyph, or NULL (glyph too large: per-contour lane merge instead)
@@ -986,23 +917,10 @@ struct EdgesCooperative {
     int nE, C;
     mutable unsigned long long cached;  // (no slots) contours whose merged state already sits in merged[c]: the combiner's second walks do not evaluate a contour's edges again
     int cacheCap;                       // contours merged[] has room for in that case (0: no caching)
-#if defined(MSDF_PROFILE_QUERY)
-    mutable unsigned long long prof[16]; // [8] contour walks of pass 0 [9] bookkeeping [10] second walks [11] epilogue | [0] all-edge evaluation [1] per-contour slot merges
-#endif
     MSDF_HD int begin(int c) const { return coff[c]-coff[0]; }
     MSDF_HD int end(int c) const { return coff[c+1]-coff[0]; }
 };
-#if defined(MSDF_PROFILE_QUERY)
-__device__ inline unsigned long long qNow() {
-#if MSDF_PROFILE_QUERY >= 2
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
-    return __builtin_readcyclecounter();
-}
-__device__ inline void profAdd(const EdgesCooperative &edges, int i, unsigned long long dt) { edges.prof[i] += dt; }
-__device__ inline unsigned long long profNow(const EdgesCooperative &) { return qNow(); }
-__device__ unsigned long long gQueryDetail[16];
-#endif
+struct EdgesCooperative : CooperativeState, QueryCounters { };   // the edge policy: that state, then the query's counters (msdf_measure.hpp: an empty base in a regular build)
 
 __device__ inline void selAddContour(Selector<2> &sel, const EdgeRec *rec, const EdgesCooperative &edges, int c, V2 o) {
     if (edges.slots) {
@@ -1010,9 +928,7 @@ __device__ inline void selAddContour(Selector<2> &sel, const EdgeRec *rec, const
         // own slots in visit order -- a handful of uniform LDS reads per edge instead of a cross-lane reduction per contour.
         // (Slots are filled when contour 0 is walked: the first walk of every query starts there, later walks reuse them.)
         if (c == 0) {
-#if defined(MSDF_PROFILE_QUERY)
-            const unsigned long long qa = qNow();
-#endif
+            const unsigned long long qa = profNow(edges);
             for (int base = 0; base < edges.nE; base += WAVE) {
                 const int i = base+edges.lane;
                 if (i < edges.nE) {
@@ -1024,10 +940,8 @@ __device__ inline void selAddContour(Selector<2> &sel, const EdgeRec *rec, const
                 }
             }
             waveSync();
-#if defined(MSDF_PROFILE_QUERY)
-            const unsigned long long qb = qNow();
-            edges.prof[0] += qb-qa;
-#endif
+            const unsigned long long qb = profNow(edges);
+            profAdd(edges, PROF_QUERY_EDGES, qb-qa);
             // lanes = contours: each merges ITS contour's slots in visit order (the serial part is the longest contour, not the glyph)
             for (int cc = edges.lane; cc < edges.C; cc += WAVE) {
                 PB acc;
@@ -1040,9 +954,7 @@ __device__ inline void selAddContour(Selector<2> &sel, const EdgeRec *rec, const
                 edges.merged[cc] = acc;
             }
             waveSync();
-#if defined(MSDF_PROFILE_QUERY)
-            edges.prof[1] += qNow()-qb;
-#endif
+            profAdd(edges, PROF_QUERY_MERGES, profNow(edges)-qb);
         }
         // merge(sel, merge(...merge(initial, e_first)..., e_last)) == the sequential merges: the earlier state survives ties either way
         const PBSlot whole = edges.merged[c];
@@ -1103,25 +1015,14 @@ struct PsdfQueryCooperative {                                       // same quer
         EdgesCooperative edges;
         edges.coff = coff, edges.lane = lane, edges.slots = slots, edges.merged = merged, edges.nE = coff[C]-coff[0], edges.C = C;
         edges.cached = 0, edges.cacheCap = slots ? 0 : cacheCap;
-#if defined(MSDF_PROFILE_QUERY)
-        for (int i = 0; i < 16; ++i)
-            edges.prof[i] = 0;
-        const unsigned long long qq0 = qNow();
-#endif
+        const unsigned long long qq0 = profReset(edges);
         if (slots)
             waveSync();                                             // the previous query's slot reads are done
         if (OVERLAP)
             shapeDistanceOverlap<2>(rec, edges, windings, C, q, res, 1, out);   // wave-uniform point: every lane holds the same values, one slot per contour
         else
             shapeDistanceSimple<2>(rec, edges, C, q, out);
-#if defined(MSDF_PROFILE_QUERY)
-        if (lane == 0) {
-            atomicAdd(&gQueryDetail[0], 1ull), atomicAdd(&gQueryDetail[1], qNow()-qq0);
-            atomicAdd(&gQueryDetail[2], edges.prof[0]), atomicAdd(&gQueryDetail[3], edges.prof[1]), atomicAdd(&gQueryDetail[4], edges.prof[8]);
-            atomicAdd(&gQueryDetail[5], edges.prof[9]), atomicAdd(&gQueryDetail[6], edges.prof[10]), atomicAdd(&gQueryDetail[7], edges.prof[11]);
-            atomicAdd(&gQueryDetail[8], (unsigned long long) C), atomicAdd(&gQueryDetail[9], (unsigned long long) (slots ? 1 : 0));
-        }
-#endif
+        profQueryDone(edges, qq0, C, slots, lane);
         return out[0];
     }
 };
@@ -1775,20 +1676,6 @@ k_ec_scan(int nGlyphs, const unsigned *__restrict__ header, unsigned seg, int *_
 #ifndef MSDF_EC_QUERY_WAVES_PER_SIMD
 #define MSDF_EC_QUERY_WAVES_PER_SIMD 3   // 168 VGPRs (13 spilled) with the record images of the cooperative path; 2 -> CJK-like set 2.90 ms, 3 -> 2.61, 4 (119 spilled) -> 2.94
 #endif
-#if defined(MSDF_PROFILE_QUERY)
-// Measurement build (tools/profile_query.py): where a wavefront of k_ec_query spends its cycles. [0] waves [1] wave cycles [2] waves with work
-// [3] first start [4] last end (atomic min / max) | chunk items: [5] count [6] cycles | cooperative items: [7] count [8] cycles |
-// [9] ticket wait [10] lookup [11] glyph state [12] evaluation (candidate load, interpolation, distance query, comparison) [13] store + barrier
-// [14] longest item [15] cooperative rounds (64 edges each) [16] end of the last wavefront that still found work
-__device__ unsigned long long gQueryProfile[24];
-// -DMSDF_PROFILE_QUERY=2: every stamp waits for all outstanding memory operations first (attributes the time to the segments, slows the
-// kernel); =1: plain s_memtime stamps -- per-item totals, the longest item and a histogram stay meaningful, the kernel runs at its own pace.
-#if MSDF_PROFILE_QUERY >= 2
-#define MSDF_QSTAMP(x) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long x = __builtin_readcyclecounter()
-#else
-#define MSDF_QSTAMP(x) const unsigned long long x = __builtin_readcyclecounter()
-#endif
-#endif
 // (the body of k_ec_query as a device function, inlined into its one caller per instantiation: k_ec_query, and with SIZED its twin k_ec_query_sized)
 template <int N, bool OVERLAP, bool SIZED = false>
 __device__ __forceinline__ void ecQueryBody(int nGlyphs, const int32_t *__restrict__ glyphContourOffsets, const int32_t *__restrict__ contourOffsets, const EdgeRec *__restrict__ recs,
@@ -1816,10 +1703,10 @@ __device__ __forceinline__ void ecQueryBody(int nGlyphs, const int32_t *__restri
     lpcMaxContours.lpcMaxEdges = offsets[2*batch.nGlyphs+3]&((1<<30)-1);   // as k_ec_scan decided for this launch
     if (offsets[2*batch.nGlyphs+3]&(1<<30))
         lpcMaxContours.gridSteps = 0;
-#if defined(MSDF_PROFILE_QUERY)
-    MSDF_QSTAMP(qStart);
+    // The probe of tools/profile_query.py (msdf_measure.hpp): QueryCounters::clock() is 0 in a regular build, where the q... locals below are dead code.
+    // (Plain locals on purpose: gathered into a state object, in any grouping, they changed the register allocation of the build they measure with.)
+    const unsigned long long qStart = QueryCounters::clock();
     unsigned long long qAcc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, qItems[4] = { 0, 0, 0, 0 }, qLongest = 0, qLastWork = 0, qLongestWho = 0;
-#endif
     // Which tickets a wavefront takes (round 6). They used to be drawn from ONE atomic counter: with the evaluation of every item ablated the launch still took
     // 0.20 of its 0.28 ms (variants/qab3, profiles/r06_ab_notes.md 12) -- ~17 000 device-scope atomics on one address (8 600 tickets + one failing draw per
     // workgroup) serialize at ~12 ns each, across eight XCDs. The list is ordered longest items first (k_ec_scan), so a STATIC deal does nearly as well as
@@ -1827,9 +1714,7 @@ __device__ __forceinline__ void ecQueryBody(int nGlyphs, const int32_t *__restri
     // one round gets the shortest of the next); W is what the device holds of this kernel at once (msdf_capi.hip: queryResidentBlocks).
     const int dealt = (queryFlags&1) ? (int) gridDim.x : 0;
     for (int round = 0;; ++round) {
-#if defined(MSDF_PROFILE_QUERY)
-        MSDF_QSTAMP(q0);
-#endif
+        const unsigned long long q0 = QueryCounters::clock();
         int ticket = 0;
         if (dealt && (queryFlags&4) && round > 0) {
             // (variant: the first ticket dealt, the others drawn from eight counters -- workgroup b from counter b % 8, which hands out the tickets = b (mod 8))
@@ -1852,10 +1737,8 @@ __device__ __forceinline__ void ecQueryBody(int nGlyphs, const int32_t *__restri
             if (ticket >= tickets)
                 break;
         }
-#if defined(MSDF_PROFILE_QUERY)
-        MSDF_QSTAMP(q1);
+        const unsigned long long q1 = QueryCounters::clock();
         qAcc[0] += q1-q0;
-#endif
         const int *part = ticket < chunks ? offsets : offsets+batch.nGlyphs+1;   // heavy first: the lane-per-candidate chunks, then the cooperative items
         const int first = ticket < chunks ? ticket : (ticket-chunks)*itemsPerTicket;
         const int last = ticket < chunks ? first+1 : (first+itemsPerTicket < coopItems ? first+itemsPerTicket : coopItems);
@@ -1870,17 +1753,13 @@ __device__ __forceinline__ void ecQueryBody(int nGlyphs, const int32_t *__restri
         int pos = lo;
         MSDF_NOUNROLL
         for (int i = first; i < last; ++i) {
-#if defined(MSDF_PROFILE_QUERY)
-        MSDF_QSTAMP(q2a);
-#endif
+        const unsigned long long q2a = QueryCounters::clock();
         while (part[pos+1] <= i)                                    // consecutive items: the same position or one of the next few
             ++pos;
         const int item = i-part[pos];
         const int g = order ? order[pos] : pos;                     // positions list the glyphs heaviest first (k_ec_scan)
-#if defined(MSDF_PROFILE_QUERY)
-        MSDF_QSTAMP(q2);
+        const unsigned long long q2 = QueryCounters::clock();
         qAcc[1] += q2-(i == first ? q1 : q2a);
-#endif
         const unsigned count = header[1+g];
         const EcCandidate *segment = cands+ecHeaderRecords(batch.nGlyphs)+(size_t) g*seg;
         const int c0 = batch.glyphContourOffsets[g], C = batch.glyphContourOffsets[g+1]-c0;
@@ -1906,12 +1785,10 @@ __device__ __forceinline__ void ecQueryBody(int nGlyphs, const int32_t *__restri
             const int w = (int) threadIdx.x < C ? (int) wind.mem[threadIdx.x] : 0;
             wind.pos = __ballot(w > 0), wind.neg = __ballot(w < 0);
         }
-#if defined(MSDF_PROFILE_QUERY)
-        MSDF_QSTAMP(q3);
+        const unsigned long long q3 = QueryCounters::clock();
         qAcc[2] += q3-q2;
         unsigned long long q4 = q3;
         const bool qChunk = ecQueryListedFirst(count, nE, C, lpcMaxContours);
-#endif
         const int gridS = ecQueryGridSlices(count, nE, C, lpcMaxContours);
         if (gridS) {                                                // lanes = (candidate, slice): 64 / gridS candidates per item
             PsdfQueryGrid<OVERLAP, WindingMasks> query;
@@ -1970,12 +1847,10 @@ __device__ __forceinline__ void ecQueryBody(int nGlyphs, const int32_t *__restri
             const int yn = rem/boxW, x = rem%boxW;
             const int ys = gd.flip ? boxH-1-yn : yn;
             const bool artifact = ecEvaluateCandidate(sdf, p, x, ys, cand.t, (cand.dir&3)-1, ((cand.dir>>2)&3)-1, query);
-#if defined(MSDF_PROFILE_QUERY)
             {
-                MSDF_QSTAMP(q4c);
+                const unsigned long long q4c = QueryCounters::clock();
                 q4 = q4c;
             }
-#endif
             if (artifact && threadIdx.x == 0) {
                 const float *in = sdf.native(x, yn);
                 const float m = medianf(in[0], in[1], in[2]);
@@ -1986,44 +1861,22 @@ __device__ __forceinline__ void ecQueryBody(int nGlyphs, const int32_t *__restri
             }
         }
         waveSync();                                                 // the next item rewrites the LDS scratch
-#if defined(MSDF_PROFILE_QUERY)
         {
-            MSDF_QSTAMP(q5);
+            const unsigned long long q5 = QueryCounters::clock();
             if (qChunk)
                 q4 = q5;                                            // (chunk: evaluation and stores are not told apart)
             qAcc[3] += q4-q3, qAcc[4] += q5-q4;
             qItems[qChunk ? 0 : 2] += 1, qItems[qChunk ? 1 : 3] += q5-q2a;
-            qItems[2] += 0;
             if (!qChunk)
                 qAcc[5] += (unsigned long long) ((nE+WAVE-1)/WAVE);
             if (q5-q2a > qLongest)
                 qLongest = q5-q2a, qLongestWho = (unsigned long long) g<<1|(qChunk ? 1ull : 0ull);
             qLastWork = q5;
-            if (threadIdx.x == 0) {                                 // histogram of item durations: < 16 k cycles, < 32 k, ... >= 512 k
-                int bucket = 0;
-                for (unsigned long long d = (q5-q2a)>>14; d && bucket < 6; d >>= 1)
-                    ++bucket;
-                atomicAdd(&gQueryDetail[10+(bucket > 5 ? 5 : bucket)], 1ull);
-            }
+            QueryCounters::itemDone(q5-q2a);
         }
-#endif
         }
     }
-#if defined(MSDF_PROFILE_QUERY)
-    {
-        MSDF_QSTAMP(qEnd);
-        if (threadIdx.x == 0) {
-            atomicAdd(&gQueryProfile[0], 1ull), atomicAdd(&gQueryProfile[1], qEnd-qStart);
-            if (qLastWork)
-                atomicAdd(&gQueryProfile[2], 1ull), atomicMax(&gQueryProfile[16], qLastWork);
-            atomicMin(&gQueryProfile[3], qStart), atomicMax(&gQueryProfile[4], qEnd);
-            atomicAdd(&gQueryProfile[5], qItems[0]), atomicAdd(&gQueryProfile[6], qItems[1]), atomicAdd(&gQueryProfile[7], qItems[2]), atomicAdd(&gQueryProfile[8], qItems[3]);
-            atomicAdd(&gQueryProfile[9], qAcc[0]), atomicAdd(&gQueryProfile[10], qAcc[1]), atomicAdd(&gQueryProfile[11], qAcc[2]), atomicAdd(&gQueryProfile[12], qAcc[3]);
-            atomicAdd(&gQueryProfile[13], qAcc[4]), atomicMax(&gQueryProfile[14], qLongest), atomicAdd(&gQueryProfile[15], qAcc[5]);
-            atomicMax(&gQueryProfile[17], (qLongest>>8)<<24|qLongestWho);   // longest item: cycles/256 | glyph<<1 | chunk
-        }
-    }
-#endif
+    QueryCounters::waveDone(qStart, qLastWork, qItems[0], qItems[1], qItems[2], qItems[3], qAcc[0], qAcc[1], qAcc[2], qAcc[3], qAcc[4], qAcc[5], qLongest, qLongestWho);
 }
 template <int N, bool OVERLAP>
 __global__ void __launch_bounds__(WAVE, MSDF_EC_QUERY_WAVES_PER_SIMD)

@@ -16,7 +16,7 @@ def build(lean=False):
     """lean: -DMSDF_LEAN_MATH, i.e. the device's own < 1 ulp cos / cbrt (msdf_device.hpp) instead of libm's in solveCubicNormed -- the host
     rendition then follows the KERNELS bit for bit also where the last ulp of a transcendental decides."""
     so = SO.replace(".so", "_lean.so") if lean else SO
-    srcs = [os.path.join(HERE, "hostemu.cpp")]+[os.path.join(CSRC, f) for f in ("msdf_device.hpp", "msdf_prep.hpp", "msdf_ec.hpp", "msdf_ec_fast.hpp", "msdf_cull.hpp", "msdf_scanline.hpp", "msdf_shapeprep.hpp", "msdf_classplan.hpp", "msdf_hostplan.hpp", "msdf_launchplan.hpp", "msdf_prepplan.hpp")]
+    srcs = [os.path.join(HERE, "hostemu.cpp")]+[os.path.join(CSRC, f) for f in ("msdf_device.hpp", "msdf_measure.hpp", "msdf_prep.hpp", "msdf_ec.hpp", "msdf_ec_fast.hpp", "msdf_cull.hpp", "msdf_scanline.hpp", "msdf_shapeprep.hpp", "msdf_classplan.hpp", "msdf_hostplan.hpp", "msdf_launchplan.hpp", "msdf_prepplan.hpp")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]+(["-DMSDF_LEAN_MATH"] if lean else [])+["-o", so, srcs[0]], check=True)
     return so

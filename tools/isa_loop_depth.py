@@ -20,24 +20,30 @@ from msdfgen_amd import build as B  # noqa: E402
 KERNEL_EXTRA_ARGS = {"k_distance": "", "k_distance_sized": ", const int32_t *"}   # what a twin's parameter list adds behind k_distance's
 
 
-def analyse(sel="3", overlap="true", gres="false", tpw="4", kernel="k_distance"):
-    """-> {"resources": {...}, "instructions": {depth: n}, "lane_moves": {depth: n}, "edge_loop": {class: n} or None}"""
+def compile_kernel(instantiation, extra_flags=()):
+    """-> (lines of gfx950 assembly, the compiler's remarks) of a translation unit that holds ONE kernel: `instantiation` is its explicit instantiation without
+    the leading `template __global__ void msdfhip::`; compiled with the project's flags plus extra_flags (e.g. the -D of a measurement build)."""
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "probe.hip")
-        open(src, "w").write('#include "msdf_kernels.hpp"\nusing namespace msdfhip;\n'
-                             "template __global__ void msdfhip::%s<%s, %s, %s, %s>(int, const int32_t *, const int32_t *, const EdgeRec *, const int8_t *, const MsdfHipGlyph *, "
-                             "int, int, int, int, int, float *, int, unsigned, double *, size_t, const int *, int, unsigned *, unsigned%s);\n" % (kernel, sel, overlap, gres, tpw, KERNEL_EXTRA_ARGS[kernel]))
-        flags = [f for f in B.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]+os.environ.get("MSDF_ISA_FLAGS", "").split()   # e.g. MSDF_ISA_FLAGS=-DMSDF_DISTANCE_WAVES_PER_SIMD=3
+        open(src, "w").write('#include "msdf_kernels.hpp"\nusing namespace msdfhip;\ntemplate __global__ void msdfhip::%s;\n' % instantiation)
+        flags = [f for f in B.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]+list(extra_flags)
         r = subprocess.run([B.hipcc()] + flags + ["-I", B.CSRC, "-I", os.path.join(ROOT, "include"), "-c", "--cuda-device-only", "-save-temps", "-Rpass-analysis=kernel-resource-usage",
                             src, "-o", os.path.join(d, "probe.o")], capture_output=True, text=True, cwd=d)
         if r.returncode != 0:
             raise RuntimeError(r.stderr[-2000:])
-        asm = open(os.path.join(d, "probe-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines()
-        res = {}
-        for line in r.stderr.splitlines():
-            m = re.search(r"remark: [^ ]+ +([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+) \[-Rpass", line)
-            if m and kernel+"I" in r.stderr[:r.stderr.find(line)].rsplit("Function Name:", 1)[-1]:
-                res[m.group(1).strip()] = m.group(2)
+        return open(os.path.join(d, "probe-hip-amdgcn-amd-amdhsa-gfx950.s")).read().splitlines(), r.stderr
+
+
+def analyse(sel="3", overlap="true", gres="false", tpw="4", kernel="k_distance"):
+    """-> {"resources": {...}, "instructions": {depth: n}, "lane_moves": {depth: n}, "edge_loop": {class: n} or None}"""
+    asm, remarks = compile_kernel("%s<%s, %s, %s, %s>(int, const int32_t *, const int32_t *, const EdgeRec *, const int8_t *, const MsdfHipGlyph *, int, int, int, int, int, float *, int, "
+                                  "unsigned, double *, size_t, const int *, int, unsigned *, unsigned%s)" % (kernel, sel, overlap, gres, tpw, KERNEL_EXTRA_ARGS[kernel]),
+                                  os.environ.get("MSDF_ISA_FLAGS", "").split())   # e.g. MSDF_ISA_FLAGS=-DMSDF_DISTANCE_WAVES_PER_SIMD=3
+    res = {}
+    for line in remarks.splitlines():
+        m = re.search(r"remark: [^ ]+ +([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+) \[-Rpass", line)
+        if m and kernel+"I" in remarks[:remarks.find(line)].rsplit("Function Name:", 1)[-1]:
+            res[m.group(1).strip()] = m.group(2)
     start = next(i for i, l in enumerate(asm) if re.match(r"_ZN7msdfhip%d%sI" % (len(kernel), kernel), l))
     end = next(i for i in range(start, len(asm)) if "s_endpgm" in asm[i])
     lines = asm[start:end+1]
