@@ -54,9 +54,34 @@ MSDF_HD double cullLowerDistance2(const EdgeRec &e, V2 c) {
     return dx*dx+dy*dy;
 }
 
-// Can edge e matter for some texel of the tile (c, r), given Umax (see header)? PERP: the selector uses perpendicular distances.
+// Is the WHOLE tile (c, r) outside the wedge { add > 0, ts > 0 } (end A) / { bdd > 0, ts > 0 } (end B) in which the reference lets that end of
+// edge e contribute a perpendicular distance (edge-selectors.cpp:199-224, :42-52)? Two bits. They decide (2) of the header for cullEdgeSurvives, and a
+// survivor carries them into the per-texel walk (msdf_kernels.hpp: packEntry), which then leaves out that end's block of selAddEdge and that end's
+// test of selEdgeRelevantWedges for every texel of the tile. That is exact, not merely conservative:
+//   * every texel centre P of the tile has |P-c| <= r, and na, nb, aDirN, bDirN are unit vectors or zero (normalize(true); their rounding puts the
+//     norm within a few 2^-53 of 1), so  dot(P-p0, na) <= dot(c-p0, na)+r*|na|  and likewise for the other three fields;
+//   * a bit is set only if  dot(c-p0, na)+r*(1+1e-6) <= 0  (resp. the tangent's ts): the spare 1e-6*r is many orders above the fp64 rounding of
+//     the two dot products, of c itself (the kernel's tile centre against its texel centres) and of the norm -- so add <= 0 (or ts <= 0) holds
+//     in the per-texel arithmetic of selAddEdge at every texel;
+//   * then the reference's own branch -- `if (add > 0)` resp. `if (ts > 0)` inside getPerpendicularDistance -- is not taken: the block changes nothing;
+//   * a zero tangent (REC_A_ZERO / REC_B_ZERO: aDirN = 0, na possibly 0 as well) gives dot = 0 and 0+R <= 0 is false for R > 0: the bit stays clear
+//     unless the bisector says "outside" by itself. Were R = 0 (a degenerate transform), 0 <= 0 sets the bit and ts = 0 > 0 is false at every texel
+//     as well. A NaN anywhere compares false: bit clear, the old path.
+// Not covered by the bits: distanceToPerpendicular of the NEAREST edge (param < 0 && ts < 0 / param > 1 && ts > 0) -- another region; it stays as it is.
+enum { CULL_OUTSIDE_A = 1, CULL_OUTSIDE_B = 2 };
+MSDF_HD int cullWedgeOutside(const EdgeRec &e, V2 c, double r) {
+    const double R = r*MSDF_CULL_SLACK;
+    const V2 ap = c-ld(e.p0), aDir = ld(e.aDirN);
+    const bool outsideA = dot(ap, ld(e.na))+R <= 0 || -dot(ap, aDir)+R <= 0;       // add <= 0 or ts <= 0 on the whole tile
+    const V2 bp = c-ld(e.pe), bDir = ld(e.bDirN);
+    const bool outsideB = -dot(bp, ld(e.nb))+R <= 0 || dot(bp, bDir)+R <= 0;        // bdd <= 0 or ts <= 0 on the whole tile
+    return (outsideA ? (int) CULL_OUTSIDE_A : 0)|(outsideB ? (int) CULL_OUTSIDE_B : 0);
+}
+
+// Can edge e matter for some texel of the tile (c, r), given Umax (see header)? PERP: the selector uses perpendicular distances;
+// outside = cullWedgeOutside(e, c, r) then (the caller keeps the bits for the survivor's list entry).
 template <bool PERP>
-MSDF_HD bool cullEdgeSurvives(const EdgeRec &e, V2 c, double r, double Umax) {
+MSDF_HD bool cullEdgeSurvives(const EdgeRec &e, V2 c, double r, double Umax, int outside) {
     const double R = r*MSDF_CULL_SLACK;
     const double reach = (Umax+R)*MSDF_CULL_SLACK;               // >= final minimum true distance of the contour-channel at any texel
     const double beyond = reach+R;
@@ -64,15 +89,17 @@ MSDF_HD bool cullEdgeSurvives(const EdgeRec &e, V2 c, double r, double Umax) {
         return true;
     if (PERP) {
         const V2 ap = c-ld(e.p0), aDir = ld(e.aDirN);
-        const bool outsideA = dot(ap, ld(e.na))+R <= 0 || -dot(ap, aDir)+R <= 0;   // add <= 0 or ts <= 0 on the whole tile
-        if (!outsideA && !(fabs(cross(ap, aDir))-R > reach))
+        if (!(outside&CULL_OUTSIDE_A) && !(fabs(cross(ap, aDir))-R > reach))
             return true;
         const V2 bp = c-ld(e.pe), bDir = ld(e.bDirN);
-        const bool outsideB = -dot(bp, ld(e.nb))+R <= 0 || dot(bp, bDir)+R <= 0;    // bdd <= 0 or ts <= 0 on the whole tile
-        if (!outsideB && !(fabs(cross(bp, bDir))-R > reach))
+        if (!(outside&CULL_OUTSIDE_B) && !(fabs(cross(bp, bDir))-R > reach))
             return true;
     }
     return false;
+}
+template <bool PERP>
+MSDF_HD bool cullEdgeSurvives(const EdgeRec &e, V2 c, double r, double Umax) {
+    return cullEdgeSurvives<PERP>(e, c, r, Umax, PERP ? cullWedgeOutside(e, c, r) : 0);
 }
 
 // Walk order of a contour's survivors: nearest first (ascending key), so that the per-texel relevance test (selEdgeRelevant) can

@@ -112,6 +112,10 @@ struct alignas(128) EdgeRec {
     MSDF_HD int Type() const { return type; }
     MSDF_HD int Color() const { return color; }
     MSDF_HD int Flags() const { return flags; }
+    // "The whole tile lies outside end A's / end B's wedge" (msdf_cull.hpp: cullWedgeOutside) travels in a survivor's packed list entry
+    // (msdf_kernels.hpp: EdgeRegs). A record in memory belongs to no tile: not known, every end is looked at.
+    MSDF_HD bool OutsideA() const { return false; }
+    MSDF_HD bool OutsideB() const { return false; }
 };
 static_assert(sizeof(EdgeRec) == 384, "EdgeRec layout");
 static_assert(offsetof(EdgeRec, na) == 0x40 && offsetof(EdgeRec, ab) == 0x80 && offsetof(EdgeRec, br) == 0xc0 && offsetof(EdgeRec, rcp) == 0x100 &&
@@ -814,23 +818,29 @@ MSDF_HD void selAddEdge(Selector<SEL> &s, const Rec &e, int idx, V2 o) {
             if (nearer[i])
                 s.c[i].td = sd.d, s.c[i].tdot = sd.dot, s.c[i].perp = conv.d, s.idx[i] = idx;
     }
-    V2 ap = o-e.P0();
-    V2 bp = o-e.PE();
-    double add = dot(ap, e.NA());
-    double bdd = -dot(bp, e.NB());
-    if (add > 0) {
-        double pd = sd.d;
-        if (getPerpendicularDistance(pd, ap, -e.ADirN())) {
-            pd = -pd;
-            for (int i = 0; i < (int) SelTraits<SEL>::NPB; ++i)
-                pbAddPerpIf(s.c[i], pd, (mask&(1<<i)) != 0);
+    // An end whose wedge the whole tile lies outside of (OutsideA / OutsideB: wave-uniform bits of the survivor's list entry, a scalar branch) has
+    // add <= 0 or ts <= 0 at every texel: its block below would change nothing (msdf_cull.hpp: cullWedgeOutside has the argument), so it is not run.
+    if (!e.OutsideA()) {
+        V2 ap = o-e.P0();
+        double add = dot(ap, e.NA());
+        if (add > 0) {
+            double pd = sd.d;
+            if (getPerpendicularDistance(pd, ap, -e.ADirN())) {
+                pd = -pd;
+                for (int i = 0; i < (int) SelTraits<SEL>::NPB; ++i)
+                    pbAddPerpIf(s.c[i], pd, (mask&(1<<i)) != 0);
+            }
         }
     }
-    if (bdd > 0) {
-        double pd = sd.d;
-        if (getPerpendicularDistance(pd, bp, e.BDirN())) {
-            for (int i = 0; i < (int) SelTraits<SEL>::NPB; ++i)
-                pbAddPerpIf(s.c[i], pd, (mask&(1<<i)) != 0);
+    if (!e.OutsideB()) {
+        V2 bp = o-e.PE();
+        double bdd = -dot(bp, e.NB());
+        if (bdd > 0) {
+            double pd = sd.d;
+            if (getPerpendicularDistance(pd, bp, e.BDirN())) {
+                for (int i = 0; i < (int) SelTraits<SEL>::NPB; ++i)
+                    pbAddPerpIf(s.c[i], pd, (mask&(1<<i)) != 0);
+            }
         }
     }
 }
@@ -871,17 +881,22 @@ MSDF_HD bool selEdgeRelevantBox(const Selector<SEL> &s, const Rec &e, V2 o, doub
 template <int SEL, class Rec>
 MSDF_HD bool selEdgeRelevantWedges(const Rec &e, V2 o, double bound2) {
     if (SEL >= 2) {
-        const V2 ap = o-e.P0(), aDir = e.ADirN();
-        if (dot(ap, e.NA()) > 0 && dot(ap, -aDir) > 0) {             // add > 0 && ts > 0 (edge-selectors.cpp:199-202, :43-44)
-            const double perp = cross(ap, aDir);
-            if (!(perp*perp > bound2))
-                return true;
+        // (an end that phase 1 found outside its wedge on the whole tile fails its domain test at every texel: not looked at)
+        if (!e.OutsideA()) {
+            const V2 ap = o-e.P0(), aDir = e.ADirN();
+            if (dot(ap, e.NA()) > 0 && dot(ap, -aDir) > 0) {         // add > 0 && ts > 0 (edge-selectors.cpp:199-202, :43-44)
+                const double perp = cross(ap, aDir);
+                if (!(perp*perp > bound2))
+                    return true;
+            }
         }
-        const V2 bp = o-e.PE(), bDir = e.BDirN();
-        if (-dot(bp, e.NB()) > 0 && dot(bp, bDir) > 0) {             // bdd > 0 && ts > 0 (:212-215)
-            const double perp = cross(bp, bDir);
-            if (!(perp*perp > bound2))
-                return true;
+        if (!e.OutsideB()) {
+            const V2 bp = o-e.PE(), bDir = e.BDirN();
+            if (-dot(bp, e.NB()) > 0 && dot(bp, bDir) > 0) {         // bdd > 0 && ts > 0 (:212-215)
+                const double perp = cross(bp, bDir);
+                if (!(perp*perp > bound2))
+                    return true;
+            }
         }
     }
     return false;

@@ -307,7 +307,8 @@ __device__ inline int rowRank(unsigned key) {
 // is first used: one DEPENDENT scalar-cache round trip per field group -- flags, control box, p0 + bisector, tangent, type, ... about ten
 // per evaluated edge, a third of them missing the 16 KB scalar cache (profiles/r02_scalar_cache.txt) -- and a wavefront spent 44 % of its
 // life in s_waitcnt. Here the walk is laid out by hand instead:
-//   * the survivor list holds PACKED entries (record index | type | colour | flags): nothing has to be loaded to know what an edge is;
+//   * the survivor list holds PACKED entries (record index | type | colour | flags | phase 1's two wedge verdicts for this tile): nothing has to be
+//     loaded to know what an edge is, nor tested per texel to know that an end's wedge misses the tile;
 //   * EdgeRec is stored in 64-byte blocks in the order of use (msdf_device.hpp); the relevance test + a whole linear evaluation need
 //     R + E0 = three s_load_dwordx16, issued together with the LDS read of the NEXT list entry and waited for ONCE;
 //   * a curve fetches E1 + E2 after the wave vote said the edge matters (second round trip).
@@ -316,8 +317,12 @@ __device__ inline int rowRank(unsigned key) {
 typedef double d8 __attribute__((ext_vector_type(8)));
 
 enum { ENTRY_INDEX_BITS = 20, ENTRY_INDEX_MASK = (1<<ENTRY_INDEX_BITS)-1 };   // 1 M edges per glyph (the LDS lists hold far fewer)
-__device__ inline unsigned packEntry(int i, const EdgeRec &e) {
-    return (unsigned) (i&ENTRY_INDEX_MASK)|(unsigned) e.type<<20|(unsigned) (e.color&7)<<22|(unsigned) (e.flags&7)<<25|(unsigned) ((e.flags>>4)&1)<<28;   // (index bits: k_distance's lists only; k_ec_query passes the index separately)
+// Bits 29 / 30 (k_distance's lists only): the tile of this list lies outside end A's / end B's wedge, CULL_OUTSIDE_A / _B of msdf_cull.hpp's
+// cullWedgeOutside -- wave-uniform in the walk, which then skips that end's work (EdgeRegs::OutsideA / OutsideB). 0: not known, the end is looked at.
+enum { ENTRY_OUTSIDE_SHIFT = 29 };
+__device__ inline unsigned packEntry(int i, const EdgeRec &e, int outside = 0) {
+    return (unsigned) (i&ENTRY_INDEX_MASK)|(unsigned) e.type<<20|(unsigned) (e.color&7)<<22|(unsigned) (e.flags&7)<<25|(unsigned) ((e.flags>>4)&1)<<28|   // (index bits: k_distance's lists only; k_ec_query passes the index separately)
+           (unsigned) (outside&3)<<ENTRY_OUTSIDE_SHIFT;
 }
 
 struct EdgeRegs {
@@ -344,7 +349,10 @@ struct EdgeRegs {
     __device__ int Type() const { return (int) (meta>>20)&3; }
     __device__ int Color() const { return (int) (meta>>22)&7; }
     __device__ int Flags() const { return (int) ((meta>>25)&7)|(int) ((meta>>28)&1)<<4; }
+    __device__ bool OutsideA() const { return ((meta>>ENTRY_OUTSIDE_SHIFT)&CULL_OUTSIDE_A) != 0; }
+    __device__ bool OutsideB() const { return ((meta>>ENTRY_OUTSIDE_SHIFT)&CULL_OUTSIDE_B) != 0; }
 };
+static_assert(CULL_OUTSIDE_A == 1 && CULL_OUTSIDE_B == 2 && ENTRY_OUTSIDE_SHIFT+2 <= 31 && ENTRY_OUTSIDE_SHIFT > 28, "packEntry / EdgeRegs::OutsideA, OutsideB");
 static_assert(REC_A_ZERO == 1 && REC_B_ZERO == 2 && REC_NORMED == 4 && REC_FASTDIV == 16, "packEntry / EdgeRegs::Flags");
 
 // The same register image of a record for a lane that evaluates ITS OWN edge (k_ec_query: lanes = edges): the five blocks and the packed
@@ -412,7 +420,7 @@ __device__ inline void selAddContour(Selector<SEL> &sel, const EdgeRec *rec, con
         // load is still in flight. Gone.)
         double bound2;
         bool relevant = MSDF_WAVE_ANY(selEdgeRelevantBox(sel, r, o, bound2));      // some lane within reach of the control box: evaluate, whatever the wedges say
-        if (SEL >= 2 && !relevant)
+        if (SEL >= 2 && !relevant && !(r.OutsideA() && r.OutsideB()))             // (the tile outside both wedges: no lane can pass the second test, no vote)
             relevant = MSDF_WAVE_ANY(selEdgeRelevantWedges<SEL>(r, o, bound2));
         const unsigned long long t2 = profNow(edges);
         profAdd(edges, PROF_RELEVANCE, t2-t1);
@@ -738,7 +746,7 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
         for (int base = 0; base < nE; base += ROW) {
             const int i = base+col;
             bool keep = false;
-            int c = 0;
+            int c = 0, outside = 0;                                 // outside: the tile against the edge's two wedges (SEL >= 2), kept in the survivor's entry
             float sample2 = 0;
             if (i < nE) {
                 if (tileValid)
@@ -750,7 +758,9 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
                     for (int ch = 0; ch < (SEL <= 2 ? 1 : 3); ++ch)
                         if ((mask>>ch)&1)
                             umax = dmax(umax, OVERLAP ? (double) __int_as_float((int) bounds[(size_t) c*3+ch]) : U[ch]);
-                    keep = cullEdgeSurvives<(SEL >= 2)>(rec[i], tc, tr, umax);
+                    if (SEL >= 2)
+                        outside = cullWedgeOutside(rec[i], tc, tr);
+                    keep = cullEdgeSurvives<(SEL >= 2)>(rec[i], tc, tr, umax, outside);
                 }
             }
             // key = (contour segment within the 16-lane row | distance | slot): contours stay grouped, nearest first inside each. The
@@ -768,7 +778,7 @@ __device__ __forceinline__ void distanceBody(int nGlyphs, const int32_t *__restr
             const unsigned long long rowBallot = TPW == 1 ? ballot : (ballot>>(ROW*q))&0xffffull;
             const int before = TPW == 1 ? __popcll(ballot&((1ull<<(col&~15))-1ull)) : 0;     // survivors in the earlier rows of a 64-lane chunk
             if (keep)
-                list[nSurv+before+rank] = (int) packEntry(i, rec[i]);
+                list[nSurv+before+rank] = (int) packEntry(i, rec[i], outside);
             if (i < nE && coff[c]-e0 == i) {                        // first edge of its contour: the contour's list starts here ...
                 const int at = nSurv+__popcll(rowBallot&((1ull<<col)-1ull));
                 cstart[c] = at;
