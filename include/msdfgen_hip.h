@@ -452,6 +452,16 @@ int msdfhip_tiles_to_bytes_sized(const float *d_tiles, int n_glyphs, const int32
  * (sdf-error-estimation.cpp:146; for Y-upward bitmaps that is the flip flag the tiles were generated with). Asynchronous on `stream`. */
 int msdfhip_batch_estimate_sdf_error(const MsdfHipBatch *batch, int channels, int width, int height, const MsdfHipGlyph *d_glyphs, const float *d_tiles,
                                      int scanlines_per_row, int fill_rule, double *d_errors, void *stream);
+/* msdfhip_batch_estimate_sdf_error for boxes: glyph g's field is w_g x h_g, packed [h_g][w_g][channels] at float offset tile_offsets[g] of d_tiles (HOST
+ * int64[n_glyphs]; what msdfhip_batch_generate_sized writes by default), sizes as that call takes them (HOST int32[n_glyphs*2] = w_g, h_g, validated the same
+ * way, with the same texts, before the device is touched). d_errors[g] is what msdfhip_batch_estimate_sdf_error writes for glyph g alone at width = w_g,
+ * height = h_g, bit for bit: (h_g-1)*scanlines_per_row scanlines, and 0 without any where w_g <= 1 or h_g <= 1 (core/sdf-error-estimation.cpp:136);
+ * scanlines_per_row < 1 zeroes all errors. d_glyphs[g].xf[0..3] and .flip are read as there. channels outside {1, 3, 4}, fill_rule outside 0..3 or more than
+ * 2^48 scanlines fail with MSDFHIP_ERR_INVALID. The work is ordered on `stream`; the call returns when it has run: the two host arrays are read before it
+ * returns, and their device copy lives for the call, in the batch's list workspace beside the lists (calls on one batch are ordered by the caller, as ever).
+ * MSDFHIP_ERROR_WORKSPACE_MB ("environment") caps the lists of one launch, of this call and of the uniform one. */
+int msdfhip_batch_estimate_sdf_error_sized(const MsdfHipBatch *batch, int channels, const int32_t *sizes, const int64_t *tile_offsets,
+                                           const MsdfHipGlyph *d_glyphs, const float *d_tiles, int scanlines_per_row, int fill_rule, double *d_errors, void *stream);
 
 /* renderSDF(output, sdf, sdfPxRange, sdThreshold) for n_glyphs packed tiles: d_out[g][oh][ow][out_channels] from
  * d_sdf[g][sh][sw][sdf_channels], memory rows as they are.
@@ -461,6 +471,16 @@ int msdfhip_batch_estimate_sdf_error(const MsdfHipBatch *batch, int channels, in
 int msdfhip_render_sdf(const float *d_sdf, int n_glyphs, int sdf_width, int sdf_height, int sdf_channels, float *d_out, int out_width, int out_height,
                        int out_channels, double range_lower, double range_upper, float sd_threshold, void *stream);
 int msdfhip_simulate_8bit(float *d_pixels, size_t n, void *stream);
+/* msdfhip_render_sdf for boxes: glyph g's sw_g x sh_g field, packed [sh_g][sw_g][sdf_channels] at float offset sdf_offsets[g] of d_sdf, is rendered into an
+ * ow_g x oh_g bitmap packed [oh_g][ow_g][out_channels] at float offset out_offsets[g] of d_out -- renderSDF of that field into a bitmap of that size, bit for
+ * bit: scale = (sw_g/ow_g, sh_g/oh_g) and the range times (ow_g+oh_g)/(sw_g+sh_g) PER GLYPH (core/render-sdf.cpp:16, 26), computed on the host in fp64 in the
+ * order msdfhip_render_sdf computes them. sdf_sizes: HOST int32[n_glyphs*2] = sw_g, sh_g, validated as the sizes of msdfhip_tiles_to_bytes_sized are (same
+ * texts, before the device is touched); out_sizes: HOST int32[n_glyphs*2] = ow_g, oh_g, where either side may be 0: that glyph writes nothing and its field is
+ * not read; the two offset arrays: HOST int64[n_glyphs]. Channel pairs, range and threshold as msdfhip_render_sdf. The rendering is ordered on `stream`; the
+ * call returns when it has run: the four host arrays are read before it returns (their device copy lives for the call: there is no batch to keep it). */
+int msdfhip_render_sdf_sized(const float *d_sdf, int n_glyphs, const int32_t *sdf_sizes, const int64_t *sdf_offsets, int sdf_channels, float *d_out,
+                             const int32_t *out_sizes, const int64_t *out_offsets, int out_channels, double range_lower, double range_upper, float sd_threshold,
+                             void *stream);
 /* The same two on HOST bitmaps (what the C++ shim's renderSDF / simulate8bit overloads call; synchronous). Strides in floats. */
 int msdfhip_render_sdf_host(float *out, int out_width, int out_height, int out_row_stride, int out_channels,
                             const float *sdf, int sdf_width, int sdf_height, int sdf_row_stride, int sdf_channels,

@@ -9,6 +9,7 @@ on top of the C ABI.  Same names, argument meaning and defaults as the reference
     distance_sign_correction(sdf, shape, projection, sdf_zero_value, fill_rule)
     rasterize(output, shape, projection, fill_rule)
     render_sdf(sdf_tiles, out_width, out_height, out_channels, sdf_px_range, sd_threshold) / simulate_8bit(tiles)   -- device tensors
+    render_sdf_sized(sdf, sdf_sizes, sdf_channels, out_sizes, out_channels, sdf_px_range, sd_threshold)             -- boxes of different sizes, one call
     shape_distance(shape, selector, overlap_support, points)      -- ShapeDistanceFinder::oneShotDistance
 
 `GlyphBatch` is the batched, device-resident front door (one launch for thousands of glyph tiles); it uses torch only to own
@@ -408,6 +409,44 @@ def render_sdf(sdf_tiles, out_width, out_height, out_channels, sdf_px_range=(0.,
     return out
 
 
+def render_sdf_sized(sdf, sdf_sizes, sdf_channels, out_sizes, out_channels, sdf_px_range=(0., 0.), sd_threshold=.5, sdf_offsets=None, out=None, stream=None):
+    """render_sdf() for boxes (msdfhip_render_sdf_sized): `sdf` is the flat float32 device tensor of GlyphBatch.generate_sized -- glyph g's field packed
+    [sh_g][sw_g][sdf_channels] at sdf_offsets[g] (default: GlyphBatch.packed_offsets(sdf_sizes, sdf_channels)) --, sdf_sizes (G, 2) rows sw_g, sh_g. Glyph g is
+    rendered as renderSDF renders its field into an ow_g x oh_g bitmap: out_sizes (G, 2) rows ow_g, oh_g (a 0 on either side: nothing is written for that
+    glyph), or a scalar factor k for k*sw_g x k*sh_g. Returns (out, out_offsets): the flat float32 device tensor and the (G+1,) packed float offsets of the
+    outputs in it -- glyph g is out[out_offsets[g]:out_offsets[g+1]] viewed (oh_g, ow_g, out_channels). Returns when the rendering has run."""
+    import torch
+    lo, hi = (-.5*sdf_px_range, .5*sdf_px_range) if np.isscalar(sdf_px_range) else sdf_px_range
+    sdf_sizes = np.ascontiguousarray(sdf_sizes, np.int32).reshape(-1, 2)
+    g = len(sdf_sizes)
+    if g and sdf_sizes.min() < 1:
+        raise ValueError("every box must be at least 1 x 1")
+    if np.isscalar(out_sizes):
+        scaled = sdf_sizes.astype(np.int64)*int(out_sizes)
+        if g and (scaled.min() < 0 or scaled.max() > 0x7fffffff):
+            raise ValueError("the factor gives an output side outside 0 .. 2^31-1")
+        out_sizes = scaled
+    out_sizes = np.ascontiguousarray(out_sizes, np.int32).reshape(g, 2)
+    if g and out_sizes.min() < 0:
+        raise ValueError("an output side may be 0, not negative")
+    assert sdf.dtype == torch.float32 and sdf.is_contiguous()
+    soff = np.ascontiguousarray(GlyphBatch.packed_offsets(sdf_sizes, sdf_channels)[:-1] if sdf_offsets is None else sdf_offsets, np.int64).reshape(g)
+    out_offsets = GlyphBatch.packed_offsets(out_sizes, out_channels)
+    if g and (int(soff.min()) < 0 or int((soff+sdf_sizes[:, 0].astype(np.int64)*sdf_sizes[:, 1]*sdf_channels).max()) > sdf.numel()):
+        raise ValueError("a glyph's field lies outside `sdf`")
+    if out is None:
+        out = torch.empty(int(out_offsets[-1]), dtype=torch.float32, device=sdf.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < int(out_offsets[-1]):
+        raise ValueError("`out` must be a contiguous float32 tensor of at least out_offsets[-1] floats")
+    s = (stream or torch.cuda.current_stream(sdf.device)).cuda_stream
+    i64 = C.POINTER(C.c_int64)
+    ooff = np.ascontiguousarray(out_offsets[:-1])
+    _lib.check(_lib.load().msdfhip_render_sdf_sized(sdf.data_ptr(), g, _lib.ptr(sdf_sizes, _lib._ip), soff.ctypes.data_as(i64), int(sdf_channels), out.data_ptr(),
+                                                    _lib.ptr(out_sizes, _lib._ip), ooff.ctypes.data_as(i64), int(out_channels), float(lo), float(hi),
+                                                    float(sd_threshold), s))
+    return out, out_offsets
+
+
 def simulate_8bit(tiles, stream=None):
     """simulate8bit (core/render-sdf.h:20-22), in place on a contiguous float32 device tensor."""
     import torch
@@ -759,6 +798,38 @@ class GlyphBatch:
         _lib.check(_lib.load().msdfhip_tiles_to_bytes_sized(tiles.data_ptr(), g, _lib.ptr(sizes, _lib._ip), toff.ctypes.data_as(C.POINTER(C.c_int64)), int(channels),
                                                             desc.data_ptr(), atlas.data_ptr(), s))
         return atlas
+
+    def estimate_sdf_error_sized(self, tiles, sizes, xfs=None, scanlines_per_row=1, fill_rule=FILL_NONZERO, tile_offsets=None, raw_xf=None, stream=None,
+                                 channels=None):
+        """estimate_sdf_error() for boxes (msdfhip_batch_estimate_sdf_error_sized): `tiles` is the flat float32 device tensor generate_sized returns, sizes
+        (G, 2) rows w_g, h_g; glyph g's field is packed [h_g][w_g][N] at tile_offsets[g] (default: packed_offsets(sizes, N)). Returns a float64 device tensor
+        (G,): estimateSDFError of every glyph at its own size (0 for a box of one texel column or row). xfs: the (G, 6) rows the tiles were generated with, or
+        raw_xf: (G, 6) rows as boxes() returns them (only sx, sy, tx, ty are read of either). channels: N; by default tiles.numel() / sum of w_g*h_g, which
+        must then be 1, 3 or 4 -- pass it where `tiles` holds more than the packed fields. Returns when the estimate has run.
+        simulate_8bit works on the flat tensor, so estimate_sdf_error_sized(simulate_8bit(tiles.clone()), ...) is the error of the 8-bit atlas."""
+        torch = self.torch
+        sizes = self._sizes(sizes)
+        g = self.n_glyphs
+        assert tiles.dtype == torch.float32 and tiles.is_contiguous()
+        w, h = sizes[:, 0].astype(np.int64), sizes[:, 1].astype(np.int64)
+        if channels is None:
+            texels = int((w*h).sum())
+            channels = tiles.numel()//texels if texels and tiles.numel() % texels == 0 else 0
+            if g and channels not in (1, 3, 4):
+                raise ValueError("cannot infer the channels: `tiles` has %d floats for %d texels; pass channels" % (tiles.numel(), texels))
+            channels = channels or 1
+        toff = np.ascontiguousarray(self.packed_offsets(sizes, channels)[:-1] if tile_offsets is None else tile_offsets, np.int64).reshape(g)
+        if g and (int(toff.min()) < 0 or int((toff+w*h*channels).max()) > tiles.numel()):
+            raise ValueError("a glyph's tile lies outside `tiles`")
+        d = np.zeros(g, _lib.GLYPH_DTYPE)
+        d["xf"][:, :4] = np.ascontiguousarray(raw_xf if raw_xf is not None else xfs, np.float64).reshape(g, 6)[:, :4]
+        d["flip"] = self.shapes.inverse_y.astype(bool).astype(np.int32)      # shape.getYAxisOrientation() == Y_DOWNWARD
+        desc = torch.from_numpy(d.view(np.uint8).reshape(g, 64)).to(self.device)
+        out = torch.empty(g, dtype=torch.float64, device=self.device)
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        _lib.check(_lib.load().msdfhip_batch_estimate_sdf_error_sized(self._handle, int(channels), _lib.ptr(sizes, _lib._ip), toff.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                                      desc.data_ptr(), tiles.data_ptr(), int(scanlines_per_row), int(fill_rule), out.data_ptr(), s))
+        return out
 
     def generate_legacy(self, mode, width, height, xfs=None, config=None, out=None, stencil=None, descriptors=None, stream=None, y_orientation=Y_UPWARD,
                         scanline_pass=False, fill_rule=FILL_NONZERO, sdf_zero_value=.5, frame: Optional["FrameConfig"] = None):

@@ -29,6 +29,7 @@
 #include "msdf_kernels.hpp"
 #include "msdf_launchplan.hpp"
 #include "msdf_prepplan.hpp"
+#include "msdf_qualityplan.hpp"
 #include "msdf_resources.hpp"
 #include "msdf_single.hpp"
 #include "msdf_sizedplan.hpp"
@@ -76,6 +77,7 @@ struct Tuning {
     int hostThreads;                 // MSDFHIP_HOST_THREADS        host threads of the streamed generator's flatten pool (0 = the usable cores, at most 32); read when the pool is created
     long singleSpinLimit;            // MSDFHIP_SINGLE_SPIN_LIMIT   tests: iterations k_single_call's grid barrier waits before it gives up (0 = scaled with the shape)
     bool singleVerbose;              // MSDFHIP_SINGLE_VERBOSE      report abandoned fused launches on stderr
+    size_t errorWorkspaceBytes;      // MSDFHIP_ERROR_WORKSPACE_MB  list workspace of one launch of the error estimate, in MB (512; fractions allowed: tests put the chunk boundary at small sizes)
 };
 // Published through an atomic pointer: msdfhip_reload_tuning() builds a fresh table and swaps it in while launch paths on other threads keep
 // reading the one they loaded. Superseded tables stay alive -- a thread may still hold a reference -- in gTuningTables (a few hundred bytes per
@@ -124,6 +126,7 @@ void readTuning() {
     t.hostThreads = (env = getenv("MSDFHIP_HOST_THREADS")) && atoi(env) > 0 ? atoi(env) : 0;
     t.singleSpinLimit = (env = getenv("MSDFHIP_SINGLE_SPIN_LIMIT")) && atol(env) > 0 ? atol(env) : 0;
     t.singleVerbose = getenv("MSDFHIP_SINGLE_VERBOSE") != NULL;
+    t.errorWorkspaceBytes = (env = getenv("MSDFHIP_ERROR_WORKSPACE_MB")) && atof(env) > 0 && atof(env) <= 65536 ? (size_t) (atof(env)*(double) (1u<<20)) : (size_t) 512u<<20;
     gTuningTables.push_back(&t);                                 // (callers hold gTuningMutex)
     gTuning.store(&t, std::memory_order_release);
 }
@@ -454,6 +457,10 @@ decltype(sizedTwinOf(k_ec_slow<3, false, false>)) ecSlowSizedKernel(int n, bool 
 decltype(sizedTwinOf(k_ec_fast<3, false>)) ecFastSizedKernel(int n, bool lazy);
 decltype(sizedTwinOf(k_ec_query<3, false>)) ecQuerySizedKernel(int n, bool overlap);
 decltype(sizedTwinOf(k_sign_correction<1>)) signSizedKernel(int n);
+// (the quality calls: msdfhip_batch_estimate_sdf_error_sized, msdfhip_render_sdf_sized. Their twins take the call's device table in the place of the sizes.)
+decltype(sizedTwinOf(k_sdf_error_lines<1>)) errorLinesSizedKernel(int n);
+decltype(sizedTwinOf(k_sdf_error_sum)) errorSumSizedKernel();
+decltype(sizedTwinOf(k_render_sdf<1, 1>)) renderSizedKernel(int no, int ns);
 
 // One launch of a generate kernel (workgroups of one wavefront): of `uniform`, or in a sized call (dDims) of its twin, with dDims behind the same arguments.
 // A... comes from the uniform kernel alone. The twin must be exactly void (*)(A..., const int32_t *): one that drifts from its sibling does not compile.
@@ -465,6 +472,15 @@ void launchTwinned(void (*uniform)(A...), void (*twin)(A..., const int32_t *), c
         hipLaunchKernelGGL(twin, grid, dim3(WAVE), lds, stream, args..., dDims);
     else
         hipLaunchKernelGGL(uniform, grid, dim3(WAVE), lds, stream, args...);
+}
+// (the same for a kernel of `block` threads per workgroup and no LDS: k_render_sdf)
+template <class... A>
+void launchTwinnedBlock(void (*uniform)(A...), void (*twin)(A..., const int32_t *), const int32_t *dDims, dim3 grid, dim3 block, hipStream_t stream,
+                        std::enable_if_t<true, A>... args) {
+    if (dDims)
+        hipLaunchKernelGGL(twin, grid, block, 0, stream, args..., dDims);
+    else
+        hipLaunchKernelGGL(uniform, grid, block, 0, stream, args...);
 }
 template <class... A>
 int setLdsTwinned(void (*uniform)(A...), void (*twin)(A..., const int32_t *), const int32_t *dDims, size_t bytes) {
@@ -1650,6 +1666,66 @@ int msdfhip_tiles_to_bytes(const float *dTiles, int nGlyphs, int w, int h, int c
     return MSDFHIP_OK;
 }
 
+namespace {
+
+// The launches of an error estimate over `items` scanlines (> 0), planned by msdf_qualityplan.hpp: k_sdf_error_lines over chunks of lanes whose lists fit the
+// workspace cap (MSDFHIP_ERROR_WORKSPACE_MB), then k_sdf_error_sum. w x h: the fields of a uniform call; in a sized call (`table`: the host copy of the device
+// table of k_sdf_error_lines_sized) the largest width and height, and the twins run from the same argument lists with the table, which is uploaded on `stream`
+// into the workspace, behind them. The workspace (ensureGres): lines[items] | the table | the lists of one chunk.
+int runEstimate(const MsdfHipBatch *b, int channels, int w, int h, const MsdfHipGlyph *dGlyphs, const float *dTiles, int scanlinesPerRow, int fillRule, double *dErrors,
+                hipStream_t stream, size_t items, const std::vector<int64_t> *table) {
+    const size_t refCap = errorRefCap(b->maxEdges), sdfCap = errorSdfCap(w);
+    const size_t perLane = errorLaneBytes(refCap, sdfCap);
+    const size_t chunk = errorChunkLanes((int64_t) items, perLane, tuning().errorWorkspaceBytes);   // lanes per launch
+    const size_t tableWords = table ? table->size() : 0;
+    double *work = NULL;
+    int rc = ensureGres(b, chunk*perLane+(items+tableWords)*sizeof(double), &work);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    double *lines = work;                                            // [items]
+    double *listX = work+items+tableWords;                           // [refCap+sdfCap][chunk]
+    int *listDir = reinterpret_cast<int *>(listX+(refCap+sdfCap)*chunk);
+    const int32_t *dDims = NULL;
+    if (table) {
+        HIPCHK(hipMemcpyAsync(work+items, table->data(), sizeof(int64_t)*tableWords, hipMemcpyHostToDevice, stream));
+        dDims = reinterpret_cast<const int32_t *>(work+items);
+    }
+    for (size_t base = 0; base < items; base += chunk) {
+        const size_t n = items-base < chunk ? items-base : chunk;
+        const dim3 grid((unsigned) ((n+63)/64));
+        forOneOf<1, 3, 4>(channels, [&](auto c) {
+            launchTwinned(k_sdf_error_lines<decltype(c)::value>, errorLinesSizedKernel(decltype(c)::value), dDims, grid, 0, stream, viewOf(b), dGlyphs, dTiles, w, h,
+                          scanlinesPerRow, fillRule, base, n, listX, listDir, (int) refCap, lines);
+        });
+    }
+    launchTwinned(k_sdf_error_sum, errorSumSizedKernel(), dDims, dim3((b->nGlyphs+63)/64), 0, stream, (const double *) lines, b->nGlyphs, h, scanlinesPerRow, dErrors);
+    HIPCHK(hipGetLastError());
+    return MSDFHIP_OK;
+}
+
+// The launch of a rendering of `total` output texels (> 0) with the range mapping `m` (msdf_qualityplan.hpp): k_render_sdf, or with dDims (the device table
+// of a sized call) its twin from the same argument list.
+int launchRender(int no, int ns, const int32_t *dDims, size_t total, hipStream_t stream, const float *dSdf, int nGlyphs, int sw, int sh, float *dOut, int ow, int oh,
+                 const RenderMapping &m, int threshold, float sdThreshold) {
+    const float sdBias = threshold ? 0.f : .5f-sdThreshold;
+    const unsigned blocks = (unsigned) ((total+255)/256 < 65536 ? (total+255)/256 : 65536);
+    #define RENDER(NO, NS) launchTwinnedBlock(k_render_sdf<NO, NS>, renderSizedKernel(NO, NS), dDims, dim3(blocks), dim3(256), stream, dSdf, nGlyphs, sw, sh, dOut, ow, oh, \
+                                              m.scaleX, m.scaleY, threshold, m.mapScale, m.mapTranslate, sdThreshold, sdBias)
+    if (no == 1 && ns == 1) RENDER(1, 1);
+    else if (no == 3 && ns == 1) RENDER(3, 1);
+    else if (no == 1 && ns == 3) RENDER(1, 3);
+    else if (no == 3 && ns == 3) RENDER(3, 3);
+    else if (no == 1 && ns == 4) RENDER(1, 4);
+    else RENDER(4, 4);
+    #undef RENDER
+    HIPCHK(hipGetLastError());
+    return MSDFHIP_OK;
+}
+
+bool renderChannelsOk(int no, int ns) { return (no == 1 && (ns == 1 || ns == 3 || ns == 4)) || (no == 3 && (ns == 1 || ns == 3)) || (no == 4 && ns == 4); }
+
+} // namespace
+
 int msdfhip_batch_estimate_sdf_error(const MsdfHipBatch *b, int channels, int w, int h, const MsdfHipGlyph *dGlyphs, const float *dTiles,
                                      int scanlinesPerRow, int fillRule, double *dErrors, void *streamPtr) {
     if (!b || !dGlyphs || !dTiles || !dErrors || w < 0 || h < 0 || (channels != 1 && channels != 3 && channels != 4))
@@ -1667,36 +1743,14 @@ int msdfhip_batch_estimate_sdf_error(const MsdfHipBatch *b, int channels, int w,
         return MSDFHIP_OK;
     }
     const size_t perGlyph = (size_t) (h-1)*scanlinesPerRow, items = perGlyph*b->nGlyphs;
-    const int refCap = 3*(b->maxEdges > 0 ? b->maxEdges : 1), sdfCap = 3*w+2;
-    const size_t perLane = (size_t) (refCap+sdfCap)*(sizeof(double)+sizeof(int));
-    size_t chunk = (512u<<20)/perLane;                               // lanes per launch: at most 512 MB of list workspace
-    chunk = chunk < 64 ? 64 : chunk/64*64;
-    if (chunk > items)
-        chunk = (items+63)/64*64;
-    double *work = NULL;
-    rc = ensureGres(b, chunk*perLane+items*sizeof(double), &work);
-    if (rc != MSDFHIP_OK)
-        return rc;
-    double *lines = work;                                            // [items]
-    double *listX = work+items;                                      // [refCap+sdfCap][chunk]
-    int *listDir = reinterpret_cast<int *>(listX+(size_t) (refCap+sdfCap)*chunk);
-    for (size_t base = 0; base < items; base += chunk) {
-        const size_t n = items-base < chunk ? items-base : chunk;
-        const dim3 grid((unsigned) ((n+63)/64)), block(64);
-        forOneOf<1, 3, 4>(channels, [&](auto c) {
-            hipLaunchKernelGGL(k_sdf_error_lines<decltype(c)::value>, grid, block, 0, stream, viewOf(b), dGlyphs, dTiles, w, h, scanlinesPerRow, fillRule, base, n, listX, listDir, refCap, lines);
-        });
-    }
-    hipLaunchKernelGGL(k_sdf_error_sum, dim3((b->nGlyphs+63)/64), dim3(64), 0, stream, (const double *) lines, b->nGlyphs, h, scanlinesPerRow, dErrors);
-    HIPCHK(hipGetLastError());
-    return MSDFHIP_OK;
+    return runEstimate(b, channels, w, h, dGlyphs, dTiles, scanlinesPerRow, fillRule, dErrors, stream, items, NULL);
 }
 
 int msdfhip_render_sdf(const float *dSdf, int nGlyphs, int sw, int sh, int ns, float *dOut, int ow, int oh, int no, double rangeLower, double rangeUpper,
                        float sdThreshold, void *streamPtr) {
     if (nGlyphs < 0 || sw < 0 || sh < 0 || ow < 0 || oh < 0)
         return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_render_sdf");
-    if (!((no == 1 && (ns == 1 || ns == 3 || ns == 4)) || (no == 3 && (ns == 1 || ns == 3)) || (no == 4 && ns == 4)))
+    if (!renderChannelsOk(no, ns))
         return fail(MSDFHIP_ERR_INVALID, "renderSDF has no overload for %d <- %d channels (core/render-sdf.h:12-17)", no, ns);
     const size_t total = (size_t) nGlyphs*ow*oh;
     if (!total)
@@ -1706,30 +1760,8 @@ int msdfhip_render_sdf(const float *dSdf, int nGlyphs, int sw, int sh, int ns, f
     int rc = ensureDeviceOf(dSdf);
     if (rc != MSDFHIP_OK)
         return rc;
-    const double scaleX = (double) sw/ow, scaleY = (double) sh/oh;       // render-sdf.cpp:15
-    const int threshold = rangeLower == rangeUpper;
-    double mapScale = 1, mapTranslate = 0;
-    float sdBias = 0;
-    if (!threshold) {
-        const double f = (double) (ow+oh)/(sw+sh);                       // render-sdf.cpp:24: sdfPxRange *= ...
-        rangeLower *= f, rangeUpper *= f;
-        const double rangeWidth = rangeUpper-rangeLower;                 // DistanceMapping::inverse(Range), DistanceMapping.cpp:6-9
-        mapScale = rangeWidth, mapTranslate = rangeLower/(rangeWidth ? rangeWidth : 1);
-        sdBias = .5f-sdThreshold;
-    }
-    hipStream_t stream = (hipStream_t) streamPtr;
-    const unsigned blocks = (unsigned) ((total+255)/256 < 65536 ? (total+255)/256 : 65536);
-    #define RENDER(NO, NS) hipLaunchKernelGGL((k_render_sdf<NO, NS>), dim3(blocks), dim3(256), 0, stream, dSdf, nGlyphs, sw, sh, dOut, ow, oh, scaleX, scaleY, \
-                                              threshold, mapScale, mapTranslate, sdThreshold, sdBias)
-    if (no == 1 && ns == 1) RENDER(1, 1);
-    else if (no == 3 && ns == 1) RENDER(3, 1);
-    else if (no == 1 && ns == 3) RENDER(1, 3);
-    else if (no == 3 && ns == 3) RENDER(3, 3);
-    else if (no == 1 && ns == 4) RENDER(1, 4);
-    else RENDER(4, 4);
-    #undef RENDER
-    HIPCHK(hipGetLastError());
-    return MSDFHIP_OK;
+    return launchRender(no, ns, NULL, total, (hipStream_t) streamPtr, dSdf, nGlyphs, sw, sh, dOut, ow, oh, renderMapping(sw, sh, ow, oh, rangeLower, rangeUpper),
+                        rangeLower == rangeUpper, sdThreshold);
 }
 
 int msdfhip_simulate_8bit(float *dPixels, size_t n, void *streamPtr) {
@@ -4095,6 +4127,125 @@ int msdfhip_batch_boxes(const MsdfHipBatch *b, const MsdfHipBoxConfig *cfg, int3
     memcpy(xf, host.data()+4*n, sizeof(double)*6*n);
     if (bounds)
         memcpy(bounds, host.data(), sizeof(double)*4*n);
+    return MSDFHIP_OK;
+}
+
+} // extern "C"
+
+// ---- quality calls for boxes: msdfhip_batch_estimate_sdf_error_sized, msdfhip_render_sdf_sized -----------------------------------------------------
+//
+// The launches are those of the uniform calls (runEstimate, launchRender) with the twins in the kernels' places. The ONLY code that names the twins, behind k_box:
+// they are instantiated last. What the launches depend on -- the item and texel prefixes, their refusals, the chunks, the range mapping per glyph -- is host code
+// of msdf_qualityplan.hpp.
+
+namespace {
+
+decltype(sizedTwinOf(k_sdf_error_lines<1>)) errorLinesSizedKernel(int n) {
+    return n == 1 ? k_sdf_error_lines_sized<1> : n == 3 ? k_sdf_error_lines_sized<3> : k_sdf_error_lines_sized<4>;
+}
+decltype(sizedTwinOf(k_sdf_error_sum)) errorSumSizedKernel() { return k_sdf_error_sum_sized<>; }
+decltype(sizedTwinOf(k_render_sdf<1, 1>)) renderSizedKernel(int no, int ns) {
+    return no == 1 ? (ns == 1 ? k_render_sdf_sized<1, 1> : ns == 3 ? k_render_sdf_sized<1, 3> : k_render_sdf_sized<1, 4>)
+         : no == 3 ? (ns == 1 ? k_render_sdf_sized<3, 1> : k_render_sdf_sized<3, 3>) : k_render_sdf_sized<4, 4>;
+}
+
+} // namespace
+
+extern "C" {
+
+int msdfhip_batch_estimate_sdf_error_sized(const MsdfHipBatch *b, int channels, const int32_t *sizes, const int64_t *tileOffsets, const MsdfHipGlyph *dGlyphs,
+                                           const float *dTiles, int scanlinesPerRow, int fillRule, double *dErrors, void *streamPtr) {
+    if (!b || (channels != 1 && channels != 3 && channels != 4))
+        return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_batch_estimate_sdf_error_sized");
+    if (fillRule < 0 || fillRule > 3)
+        return fail(MSDFHIP_ERR_INVALID, "fill rule %d (must be 0..3)", fillRule);
+    SizedLayout layout;
+    int rc = checkSizes("msdfhip_batch_estimate_sdf_error_sized", b->nGlyphs, sizes, layout);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    if (b->nGlyphs == 0)
+        return MSDFHIP_OK;
+    if (!tileOffsets || !dGlyphs || !dTiles || !dErrors)
+        return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_estimate_sdf_error_sized: NULL argument");
+    // The device table of k_sdf_error_lines_sized, in 8-byte words: the sizes | the item prefix | the tile offsets.
+    const size_t n = (size_t) b->nGlyphs;
+    std::vector<int64_t> table(3*n+1);
+    size_t items = 0;
+    if (scanlinesPerRow >= 1) {
+        if (errorItemPrefix(b->nGlyphs, sizes, scanlinesPerRow, table.data()+n) != QUALITY_OK)
+            return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_estimate_sdf_error_sized: more than 2^48 scanlines; split the batch");
+        items = (size_t) table[2*n];
+    }
+    rc = ensureDevice(b->device);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    hipStream_t stream = (hipStream_t) streamPtr;
+    if (!items) {                                                    // sdf-error-estimation.cpp:136-137: every estimate is 0
+        HIPCHK(hipMemsetAsync(dErrors, 0, sizeof(double)*n, stream));
+        return MSDFHIP_OK;
+    }
+    memcpy(table.data(), sizes, sizeof(int32_t)*2*n);
+    for (size_t g = 0; g < n; ++g)
+        table[2*n+1+g] = tileOffsets[g];
+    rc = runEstimate(b, channels, layout.W, layout.H, dGlyphs, dTiles, scanlinesPerRow, fillRule, dErrors, stream, items, &table);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    HIPCHK(hipStreamSynchronize(stream));                            // (the host table has been read, and the device copy in the batch's workspace is done with)
+    return MSDFHIP_OK;
+}
+
+int msdfhip_render_sdf_sized(const float *dSdf, int nGlyphs, const int32_t *sdfSizes, const int64_t *sdfOffsets, int ns, float *dOut, const int32_t *outSizes,
+                             const int64_t *outOffsets, int no, double rangeLower, double rangeUpper, float sdThreshold, void *streamPtr) {
+    if (nGlyphs < 0)
+        return fail(MSDFHIP_ERR_INVALID, "bad arguments to msdfhip_render_sdf_sized");
+    if (!renderChannelsOk(no, ns))
+        return fail(MSDFHIP_ERR_INVALID, "renderSDF has no overload for %d <- %d channels (core/render-sdf.h:12-17)", no, ns);
+    SizedLayout layout;
+    int rc = checkSizes("msdfhip_render_sdf_sized", nGlyphs, sdfSizes, layout);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    if (nGlyphs == 0)
+        return MSDFHIP_OK;
+    if (!outSizes)
+        return fail(MSDFHIP_ERR_INVALID, "msdfhip_render_sdf_sized: out_sizes is NULL");
+    // The device table of k_render_sdf_sized, in 8-byte words: field sizes | output sizes | the output texel prefix | field offsets | output offsets | the mappings.
+    const size_t n = (size_t) nGlyphs;
+    std::vector<int64_t> table(9*n+1);
+    int bad = -1;
+    switch (renderTexelPrefix(nGlyphs, outSizes, table.data()+2*n, &bad)) {
+        case QUALITY_BAD_OUTPUT: return fail(MSDFHIP_ERR_INVALID, "msdfhip_render_sdf_sized: glyph %d has a %d x %d output (a side may be 0, not negative)", bad, (int) outSizes[2*(size_t) bad],
+                                             (int) outSizes[2*(size_t) bad+1]);
+        case QUALITY_TOO_MANY: return fail(MSDFHIP_ERR_INVALID, "msdfhip_render_sdf_sized: more than 2^48 output texels; split the batch");
+    }
+    const size_t total = (size_t) table[3*n];
+    if (!total)
+        return MSDFHIP_OK;
+    if (!dSdf || !dOut || !sdfOffsets || !outOffsets)
+        return fail(MSDFHIP_ERR_INVALID, "msdfhip_render_sdf_sized: NULL argument");
+    rc = ensureDeviceOf(dSdf);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    memcpy(table.data(), sdfSizes, sizeof(int32_t)*2*n);
+    memcpy(table.data()+n, outSizes, sizeof(int32_t)*2*n);
+    double *params = reinterpret_cast<double *>(table.data()+5*n+1);
+    for (size_t g = 0; g < n; ++g) {
+        table[3*n+1+g] = sdfOffsets[g], table[4*n+1+g] = outOffsets[g];
+        const int ow = outSizes[2*g], oh = outSizes[2*g+1];
+        if (ow > 0 && oh > 0) {
+            const RenderMapping m = renderMapping(sdfSizes[2*g], sdfSizes[2*g+1], ow, oh, rangeLower, rangeUpper);
+            params[4*g] = m.scaleX, params[4*g+1] = m.scaleY, params[4*g+2] = m.mapScale, params[4*g+3] = m.mapTranslate;
+        }
+    }
+    hipStream_t stream = (hipStream_t) streamPtr;
+    // The table goes to a device buffer of this call, freed once the rendering has run: no batch whose workspace could hold it.
+    WorkBuffer<long long> dTable;
+    HIPCHK(dTable.ensure(table.size()));
+    HIPCHK(hipMemcpyAsync(dTable.ptr, table.data(), sizeof(int64_t)*table.size(), hipMemcpyHostToDevice, stream));
+    const RenderMapping none = { 0, 0, 0, 0 };
+    rc = launchRender(no, ns, reinterpret_cast<const int32_t *>(dTable.ptr), total, stream, dSdf, nGlyphs, 0, 0, dOut, 0, 0, none, rangeLower == rangeUpper, sdThreshold);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    HIPCHK(hipStreamSynchronize(stream));                            // (the host table and the device buffer of this call go with it)
     return MSDFHIP_OK;
 }
 

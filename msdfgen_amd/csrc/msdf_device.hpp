@@ -421,8 +421,109 @@ MSDF_HD double powThird(double x) {
 #endif
 }
 
+// acos ROUNDED TO NEAREST, for the error estimate (msdf_scanline.hpp: sdfErrorOfLine). The estimate sums interval lengths that reach the last bit of a root of
+// the cubic solver, so the last bit of its acos reaches the result: OCML's acos (< 1 ulp, what the generators call) and the reference's C library differ there
+// on some 5 % of the arguments, by one ulp. glibc's acos returns the correctly rounded value but for very rare arguments (its error stays below 0.53 ulp), so
+// the rounded value is what meets the reference; the same operations run on the host (tests/hostemu). Evaluated in double-double (~2^-100):
+//   |x| <= .5:  acos x = pi/2 - asin x                         with asin z = z P(z^2), P the Taylor series (terms below 2^-88 dropped: z^2 <= .25)
+//   |x| >  .5:  acos |x| = 2 asin sqrt((1-|x|)/2), acos(-|x|) = pi - acos |x|          ((1-|x|)/2 is exact, and IS z^2)
+// Some 45 double-double multiply-adds: for a diagnostics kernel, not for the per-texel walk.
+struct DD { double h, l; };
+MSDF_HD DD ddFast(double a, double b) { DD r; r.h = a+b; r.l = b-(r.h-a); return r; }                    // |a| >= |b|
+MSDF_HD DD ddSum(double a, double b) { DD r; r.h = a+b; const double t = r.h-a; r.l = (a-(r.h-t))+(b-t); return r; }
+MSDF_HD DD ddAdd(DD a, DD b) { DD s = ddSum(a.h, b.h); s.l += a.l+b.l; return ddFast(s.h, s.l); }
+MSDF_HD DD ddMul(DD a, DD b) { const double p = a.h*b.h; return ddFast(p, fma(a.h, b.h, -p)+(a.h*b.l+a.l*b.h)); }
+MSDF_HD double acosRounded(double x) {
+    const double C[45][2] = {
+        { 1.0, 0.0 },
+        { 0.16666666666666666, 9.25185853854297e-18 },
+        { 0.075, 2.7755575615628915e-18 },
+        { 0.044642857142857144, -9.912705577010326e-19 },
+        { 0.030381944444444444, 3.854941057726238e-19 },
+        { 0.022372159090909092, -9.462128050782583e-19 },
+        { 0.017352764423076924, -8.006416042969879e-19 },
+        { 0.01396484375, -6.938893903907229e-19 },
+        { 0.011551800896139705, 8.163404592832033e-19 },
+        { 0.009761609529194078, 5.478074134663601e-19 },
+        { 0.008390335809616815, 4.130293990420969e-19 },
+        { 0.0073125258735988454, -3.394024192128536e-19 },
+        { 0.006447210311889649, -3.1225022567582527e-19 },
+        { 0.005740037670841924, -1.2849803525754126e-19 },
+        { 0.005153309682319905, -3.888173308223878e-19 },
+        { 0.004660143486915096, -2.7979410902851727e-20 },
+        { 0.004240907093679363, -1.5770213417970974e-19 },
+        { 0.003880964558837669, 1.858632295689436e-19 },
+        { 0.0035692053938259347, -1.992587776459846e-19 },
+        { 0.003297059503473485, -1.3344026738283132e-19 },
+        { 0.0030578216492580306, 2.1155164341180575e-20 },
+        { 0.002846178401108942, 1.1094161764967953e-19 },
+        { 0.00265787063820729, -1.4456028966473392e-19 },
+        { 0.0024894486782468836, -8.304527278612374e-20 },
+        { 0.002338091892111975, 1.4161007967157608e-19 },
+        { 0.0022014739737101384, -1.5306383611560064e-19 },
+        { 0.0020776610325181676, -1.4728784229991757e-19 },
+        { 0.0019650336162772837, -7.096596038086938e-20 },
+        { 0.0018622264064031275, -5.325905408700723e-20 },
+        { 0.0017680811205154183, -5.880418562633244e-20 },
+        { 0.0016816093935831068, 1.4219044885055797e-20 },
+        { 0.001601963275351444, 4.818676322157797e-20 },
+        { 0.0015284115961225677, -3.8364076872564005e-20 },
+        { 0.0014603208940791154, -1.375480368078625e-20 },
+        { 0.0013971399176302534, 1.11955659115351e-20 },
+        { 0.0013383869512751784, -5.506907161304015e-20 },
+        { 0.0012836393876290285, 3.621355929288591e-20 },
+        { 0.001232525098500017, -9.357455312634007e-20 },
+        { 0.0011847152561624392, 8.758128167121453e-20 },
+        { 0.0011399183307022236, 8.194708704184068e-20 },
+        { 0.0010978750465914472, 4.854022464579631e-20 },
+        { 0.0010583541258722428, 9.018646571938304e-20 },
+        { 0.0010211486797106276, 8.391832465295875e-20 },
+        { 0.0009860731369833312, 7.622485745671054e-20 },
+        { 0.0009529606197429564, 3.077887041034637e-20 }
+    };                                               // (2k)! / (4^k k!^2 (2k+1)) as double-doubles
+    const double ax = fabs(x);
+    if (!(ax < 1))
+        return acos(x);                              // +-1 (exact: 0, pi), NaN, out of range
+    const bool small = ax <= .5;
+    DD z, u;                                         // asin's argument and its square
+    if (small) {
+        z.h = x, z.l = 0;
+        u.h = x*x, u.l = fma(x, x, -u.h);
+    } else {
+        u.h = .5*(1-ax), u.l = 0;                    // exact
+        const double s = sqrt(u.h);
+        const double p = s*s;
+        z = ddFast(s, ((u.h-p)-fma(s, s, -p))/(2*s));    // sqrt(u) to ~2^-104
+    }
+    DD P = { C[44][0], C[44][1] };
+    for (int k = 43; k >= 0; --k) {
+        const DD c = { C[k][0], C[k][1] };
+        P = ddAdd(ddMul(P, u), c);
+    }
+    const DD as = ddMul(z, P);                       // asin z
+    const DD halfPi = { 1.5707963267948966, 6.123233995736766e-17 }, pi = { 3.141592653589793, 1.2246467991473532e-16 };
+    DD r;
+    if (small) {
+        const DD n = { -as.h, -as.l };
+        r = ddAdd(halfPi, n);
+    } else {
+        DD t = { 2*as.h, 2*as.l };
+        if (x < 0) {
+            t.h = -t.h, t.l = -t.l;
+            r = ddAdd(pi, t);
+        } else
+            r = t;
+    }
+    return r.h+r.l;
+}
+
 // solveCubicNormed (equation-solver.cpp:34-61) with the pixel-independent a, a*a and a*(1/3.) taken from the edge record.
-MSDF_HD int solveCubicNormedPre(double x[3], double a, double a2, double a3, double b, double c) {
+// ROUNDED_ACOS: the trigonometric branch takes acosRounded in the place of the math library's acos (the error estimate; the generators keep theirs).
+template <bool ROUNDED_ACOS>
+MSDF_HD int solveCubicNormedPreT(double x[3], double a, double a2, double a3, double b, double c);
+MSDF_HD int solveCubicNormedPre(double x[3], double a, double a2, double a3, double b, double c) { return solveCubicNormedPreT<false>(x, a, a2, a3, b, c); }
+template <bool ROUNDED_ACOS>
+MSDF_HD int solveCubicNormedPreT(double x[3], double a, double a2, double a3, double b, double c) {
     double q = 1/9.*(a2-3*b);
     double r = 1/54.*(a*(2*a2-9*b)+27*c);
     double r2 = r*r;
@@ -431,7 +532,7 @@ MSDF_HD int solveCubicNormedPre(double x[3], double a, double a2, double a3, dou
         double t = r/sqrt(q3);
         if (t < -1) t = -1;
         if (t > 1) t = 1;
-        t = acos(t);
+        t = ROUNDED_ACOS ? acosRounded(t) : acos(t);
         q = -2*sqrt(q);
         double c0, c1, c2;
         cosThirds(t, c0, c1, c2);

@@ -23,6 +23,8 @@
 #include "msdf_ec_fast.hpp"
 #include "msdf_cull.hpp"
 #include "msdf_scanline.hpp"
+#include "msdf_render.hpp"
+#include "msdf_qualityplan.hpp"
 #include "msdf_shapeprep.hpp"
 #include "msdf_frame.hpp"
 #include "msdf_legacy.hpp"
@@ -2325,46 +2327,45 @@ __global__ void k_tiles_to_bytes(const float *tiles, const MsdfHipGlyph *glyphs,
 
 // ------------------------------------------------------------------------------------------- renderSDF / simulate8bit (row f4)
 
-// renderSDF (core/render-sdf.cpp:14-170) of G tiles: out[g][oh][ow][NO] from sdf[g][sh][sw][NS]; one thread per output texel.
+// renderSDF (core/render-sdf.cpp:14-170) of G tiles: out[g][oh][ow][NO] from sdf[g][sh][sw][NS]; one thread per output texel (msdf_render.hpp: renderSdfTexel).
 // threshold != 0: sdfPxRange.lower == upper (binary output); else mapScale/mapTranslate = DistanceMapping::inverse(range scaled to
-// the output size), computed by the host in fp64 exactly as render-sdf.cpp:24-25. Rows are memory rows (the reference does not reorient).
-template <int NO, int NS>
-__global__ void k_render_sdf(const float *sdf, int nGlyphs, int sw, int sh, float *out, int ow, int oh, double scaleX, double scaleY, int threshold,
-                             double mapScale, double mapTranslate, float sdThreshold, float sdBias) {
+// the output size), computed by the host in fp64 exactly as the reference does (msdf_qualityplan.hpp: renderMapping). Rows are memory rows (the reference
+// does not reorient).
+// SIZED (k_render_sdf_sized, msdfhip_render_sdf_sized): every glyph has a field size, an output size and with them a scale and a range mapping of its own.
+// `dims` is then the call's device table, in 8-byte words with n = nGlyphs (the host fills it: msdf_capi.hip, msdfhip_render_sdf_sized):
+//   [0, n) sw_g, sh_g as int32 pairs | [n, 2n) ow_g, oh_g as int32 pairs | [2n, 3n+1) the output texel prefix | [3n+1, 4n+1) float offset of the field |
+//   [4n+1, 5n+1) float offset of the output | [5n+1, 9n+1) scaleX, scaleY, mapScale, mapTranslate as doubles
+// and a thread finds its glyph by a search over the prefix (msdf_qualityplan.hpp: renderTexelOf), which steps over the glyphs without output.
+template <int NO, int NS, bool SIZED = false>
+__device__ __forceinline__ void renderSdfBody(const float *sdf, int nGlyphs, int sw, int sh, float *out, int ow, int oh, double scaleX, double scaleY, int threshold,
+                                              double mapScale, double mapTranslate, float sdThreshold, float sdBias, const int32_t *dims = NULL) {
+    if (SIZED) {
+        const int64_t *words = reinterpret_cast<const int64_t *>(dims);
+        const int64_t *outStart = words+2*(size_t) nGlyphs, *sdfOffsets = outStart+nGlyphs+1, *outOffsets = sdfOffsets+nGlyphs;
+        const double *params = reinterpret_cast<const double *>(outOffsets+nGlyphs);
+        const int32_t *outDims = dims+2*(size_t) nGlyphs;
+        const int64_t total = outStart[nGlyphs];
+        for (int64_t i = (int64_t) blockIdx.x*blockDim.x+threadIdx.x; i < total; i += (int64_t) gridDim.x*blockDim.x) {
+            const RenderTexel t = renderTexelOf(outStart, nGlyphs, outDims, i);
+            const double *m = params+4*(size_t) t.g;
+            renderSdfTexel<NO, NS>(out+outOffsets[t.g]+(i-outStart[t.g])*NO, sdf+sdfOffsets[t.g], dims[2*t.g], dims[2*t.g+1], t.x, t.y, m[0], m[1], threshold, m[2], m[3],
+                                   sdThreshold, sdBias);
+        }
+        return;
+    }
     const size_t perGlyph = (size_t) ow*oh, total = perGlyph*nGlyphs;
     for (size_t i = (size_t) blockIdx.x*blockDim.x+threadIdx.x; i < total; i += (size_t) gridDim.x*blockDim.x) {
         const int g = (int) (i/perGlyph);
         const int rem = (int) (i-(size_t) g*perGlyph);
         const int y = rem/ow, x = rem-y*ow;
-        const float *px = sdf+(size_t) g*sw*sh*NS;
-        V2 pos = mk(scaleX*(x+.5), scaleY*(y+.5));                  // scale*Point2(x+.5, y+.5)
-        pos.x = clampd(pos.x, (double) sw);                         // interpolate, bitmap-interpolation.hpp:10-25
-        pos.y = clampd(pos.y, (double) sh);
-        pos.x -= .5, pos.y -= .5;
-        int l = (int) floor(pos.x), b = (int) floor(pos.y);
-        int r = l+1, t = b+1;
-        const double lr = pos.x-l, bt = pos.y-b;
-        l = clampi(l, sw-1), r = clampi(r, sw-1);
-        b = clampi(b, sh-1), t = clampi(t, sh-1);
-        float sd[NS];
-        for (int c = 0; c < NS; ++c)
-            sd[c] = mixf(mixf(px[((size_t) b*sw+l)*NS+c], px[((size_t) b*sw+r)*NS+c], lr), mixf(px[((size_t) t*sw+l)*NS+c], px[((size_t) t*sw+r)*NS+c], lr), bt);
-        float in[NO];
-        if (NO == 1 && NS >= 3)
-            in[0] = medianf(sd[0], sd[NS >= 3 ? 1 : 0], sd[NS >= 3 ? 2 : 0]);
-        else
-            for (int c = 0; c < NO; ++c)
-                in[c] = sd[c < NS ? c : 0];
-        float *o = out+i*NO;
-        for (int c = 0; c < NO; ++c) {
-            if (threshold)
-                o[c] = (float) (in[c] >= sdThreshold);
-            else {                                                  // distVal, render-sdf.cpp:10-12
-                const double v = mapScale*((double) (in[c]+sdBias)+mapTranslate)+.5;
-                o[c] = (float) (v >= 0 && v <= 1 ? v : (double) (v > 0));
-            }
-        }
+        renderSdfTexel<NO, NS>(out+i*NO, sdf+(size_t) g*sw*sh*NS, sw, sh, x, y, scaleX, scaleY, threshold, mapScale, mapTranslate, sdThreshold, sdBias);
     }
+}
+
+template <int NO, int NS>
+__global__ void k_render_sdf(const float *sdf, int nGlyphs, int sw, int sh, float *out, int ow, int oh, double scaleX, double scaleY, int threshold,
+                             double mapScale, double mapTranslate, float sdThreshold, float sdBias) {
+    renderSdfBody<NO, NS>(sdf, nGlyphs, sw, sh, out, ow, oh, scaleX, scaleY, threshold, mapScale, mapTranslate, sdThreshold, sdBias);
 }
 
 // simulate8bit (core/render-sdf.cpp:172-188): p = pixelByteToFloat(pixelFloatToByte(p)).
@@ -2376,17 +2377,33 @@ __global__ void k_simulate_8bit(float *px, size_t n) {
 // estimateSDFError (core/sdf-error-estimation.cpp:134-154), one lane per scanline (glyph, row, subRow). items: scanlines of this
 // launch chunk [itemBase, itemBase+nItems) in (glyph, row, subRow) order; lists: workspace, lane-strided (msdf_scanline.hpp).
 // lines[item] = 1 - overlapFactor*overlap. glyphs[g].flip is read as "the shape's Y axis points down" (shape.getYAxisOrientation()).
-template <int N>
-__global__ void k_sdf_error_lines(BatchView batch, const MsdfHipGlyph *glyphs, const float *tiles, int width, int height, int scanlinesPerRow, int fillRule,
-                                  size_t itemBase, size_t nItems, double *listX, int *listDir, int refCap, double *lines) {
+// SIZED (k_sdf_error_lines_sized, msdfhip_batch_estimate_sdf_error_sized): glyph g is a w_g x h_g field packed at a float offset of its own and has
+// (h_g-1)*scanlinesPerRow items, none where w_g <= 1 or h_g <= 1 (:136). `dims` is then the call's device table, in 8-byte words with n = batch.nGlyphs:
+//   [0, n) w_g, h_g as int32 pairs | [n, 2n+1) the item prefix | [2n+1, 3n+1) float offset of the tile
+// and a lane finds its glyph by a search over the prefix (msdf_qualityplan.hpp: errorItemOf), which steps over the glyphs without items. width and height
+// are not read.
+template <int N, bool SIZED = false>
+__device__ __forceinline__ void sdfErrorLinesBody(BatchView batch, const MsdfHipGlyph *glyphs, const float *tiles, int width, int height, int scanlinesPerRow, int fillRule,
+                                                  size_t itemBase, size_t nItems, double *listX, int *listDir, int refCap, double *lines, const int32_t *dims = NULL) {
     const size_t local = (size_t) blockIdx.x*blockDim.x+threadIdx.x;
     if (local >= nItems)
         return;
     const size_t item = itemBase+local;
-    const size_t perGlyph = (size_t) (height-1)*scanlinesPerRow;
-    const int g = (int) (item/perGlyph);
-    const int rem = (int) (item-(size_t) g*perGlyph);
-    const int row = rem/scanlinesPerRow, subRow = rem-row*scanlinesPerRow;
+    int g, row, subRow, boxW = width, boxH = height;
+    const float *px;
+    if (SIZED) {
+        const int64_t *itemStart = reinterpret_cast<const int64_t *>(dims)+batch.nGlyphs, *tileOffsets = itemStart+batch.nGlyphs+1;
+        const ErrorItem it = errorItemOf(itemStart, batch.nGlyphs, scanlinesPerRow, (int64_t) item);
+        g = it.g, row = it.row, subRow = it.subRow;
+        boxW = dims[2*g], boxH = dims[2*g+1];
+        px = tiles+tileOffsets[g];
+    } else {
+        const size_t perGlyph = (size_t) (height-1)*scanlinesPerRow;
+        g = (int) (item/perGlyph);
+        const int rem = (int) (item-(size_t) g*perGlyph);
+        row = rem/scanlinesPerRow, subRow = rem-row*scanlinesPerRow;
+        px = tiles+(size_t) g*width*height*N;
+    }
     const int c0 = batch.glyphContourOffsets[g], C = batch.glyphContourOffsets[g+1]-c0;
     const int32_t *coff = batch.contourOffsets+c0;
     const int e0 = coff[0], nE = coff[C]-e0;
@@ -2394,20 +2411,42 @@ __global__ void k_sdf_error_lines(BatchView batch, const MsdfHipGlyph *glyphs, c
     StridedList refList, sdfList;
     refList.x = listX+local, refList.dir = listDir+local, refList.stride = nItems, refList.n = 0;
     sdfList.x = listX+(size_t) refCap*nItems+local, sdfList.dir = listDir+(size_t) refCap*nItems+local, sdfList.stride = nItems, sdfList.n = 0;
-    lines[item] = sdfErrorOfLine<N>(batch.recs+e0, nE, tiles+(size_t) g*width*height*N, width, height, gd.xf[0], gd.xf[1], gd.xf[2], gd.xf[3], gd.flip != 0,
+    lines[item] = sdfErrorOfLine<N>(batch.recs+e0, nE, px, boxW, boxH, gd.xf[0], gd.xf[1], gd.xf[2], gd.xf[3], gd.flip != 0,
                                     row, subRow, scanlinesPerRow, fillRule, refList, sdfList);
 }
 
+template <int N>
+__global__ void k_sdf_error_lines(BatchView batch, const MsdfHipGlyph *glyphs, const float *tiles, int width, int height, int scanlinesPerRow, int fillRule,
+                                  size_t itemBase, size_t nItems, double *listX, int *listDir, int refCap, double *lines) {
+    sdfErrorLinesBody<N>(batch, glyphs, tiles, width, height, scanlinesPerRow, fillRule, itemBase, nItems, listX, listDir, refCap, lines);
+}
+
 // The reference sums the scanlines of a glyph in (row, subRow) order and divides (:141-153): one thread per glyph, same order.
-__global__ void k_sdf_error_sum(const double *lines, int nGlyphs, int height, int scanlinesPerRow, double *errors) {
+// SIZED (k_sdf_error_sum_sized): the glyph's lines are those of its stretch of the item prefix (`dims`: the table of k_sdf_error_lines_sized); a glyph
+// without items gets 0 (:136). height is not read.
+template <bool SIZED = false>
+__device__ __forceinline__ void sdfErrorSumBody(const double *lines, int nGlyphs, int height, int scanlinesPerRow, double *errors, const int32_t *dims = NULL) {
     const int g = blockIdx.x*blockDim.x+threadIdx.x;
     if (g >= nGlyphs)
         return;
+    if (SIZED) {
+        const int64_t *itemStart = reinterpret_cast<const int64_t *>(dims)+nGlyphs;
+        const int64_t from = itemStart[g], to = itemStart[g+1];
+        double error = 0;
+        for (int64_t i = from; i < to; ++i)
+            error += lines[i];
+        errors[g] = to > from ? error/(double) (to-from) : 0;       // (to-from = (h_g-1)*scanlinesPerRow)
+        return;
+    }
     const size_t perGlyph = (size_t) (height-1)*scanlinesPerRow;
     double error = 0;
     for (size_t i = 0; i < perGlyph; ++i)
         error += lines[(size_t) g*perGlyph+i];
     errors[g] = error/((height-1)*scanlinesPerRow);
+}
+
+__global__ void k_sdf_error_sum(const double *lines, int nGlyphs, int height, int scanlinesPerRow, double *errors) {
+    sdfErrorSumBody(lines, nGlyphs, height, scanlinesPerRow, errors);
 }
 
 // ------------------------------------------------------------------------------------------------- distance queries
@@ -2657,6 +2696,26 @@ __global__ void __launch_bounds__(WAVE) k_box(EdgeArrays edges, const int32_t *g
                 xf[6*(size_t) g+k] = t[k];
         }
     }
+}
+
+// The sized twins of the quality kernels (msdfhip_batch_estimate_sdf_error_sized, msdfhip_render_sdf_sized): the bodies of k_sdf_error_lines, k_sdf_error_sum
+// and k_render_sdf with SIZED = true and the call's device table behind their siblings' arguments. Named, like the twins above, only at the end of
+// msdf_capi.hip: they are instantiated behind everything the code object held.
+template <int N>
+__global__ void k_sdf_error_lines_sized(BatchView batch, const MsdfHipGlyph *glyphs, const float *tiles, int width, int height, int scanlinesPerRow, int fillRule,
+                                        size_t itemBase, size_t nItems, double *listX, int *listDir, int refCap, double *lines, const int32_t *dims) {
+    sdfErrorLinesBody<N, true>(batch, glyphs, tiles, width, height, scanlinesPerRow, fillRule, itemBase, nItems, listX, listDir, refCap, lines, dims);
+}
+
+template <bool SIZED = true>     // (a template only to be instantiated where it is named, like k_box)
+__global__ void k_sdf_error_sum_sized(const double *lines, int nGlyphs, int height, int scanlinesPerRow, double *errors, const int32_t *dims) {
+    sdfErrorSumBody<SIZED>(lines, nGlyphs, height, scanlinesPerRow, errors, dims);
+}
+
+template <int NO, int NS>
+__global__ void k_render_sdf_sized(const float *sdf, int nGlyphs, int sw, int sh, float *out, int ow, int oh, double scaleX, double scaleY, int threshold,
+                                   double mapScale, double mapTranslate, float sdThreshold, float sdBias, const int32_t *dims) {
+    renderSdfBody<NO, NS, true>(sdf, nGlyphs, sw, sh, out, ow, oh, scaleX, scaleY, threshold, mapScale, mapTranslate, sdThreshold, sdBias, dims);
 }
 
 } // namespace msdfhip

@@ -17,7 +17,10 @@ namespace msdfhip {
 MSDF_HD int isign(double n) { return (0 < n)-(n < 0); }                      // arithmetics.hpp:53-55
 
 // EdgeSegment::scanlineIntersections from the digested record (control points, ab, br, as). Returns the count; x[3], dy[3].
-MSDF_HD int scanlineIntersections(const EdgeRec &e, double x[3], int dy[3], double y) {
+// ROUNDED_ACOS: a cubic's roots with the acos rounded to nearest (msdf_device.hpp: acosRounded) -- the error estimate; the sign pass and the rasterizer
+// keep the math library's (scanlineIntersections).
+template <bool ROUNDED_ACOS>
+MSDF_HD int scanlineIntersectionsT(const EdgeRec &e, double x[3], int dy[3], double y) {
     const V2 p0 = ld(e.p0), p1 = e.type == 1 ? ld(e.pe) : ld(e.p1), p2 = e.type == 2 ? ld(e.pe) : ld(e.p2), p3 = ld(e.pe);   // control points as stored (EdgeRec blocks)
     if (e.type == 1) {                                                        // edge-segments.cpp:279-287
         if ((y >= p0.y && y < p1.y) || (y >= p1.y && y < p0.y)) {
@@ -56,7 +59,7 @@ MSDF_HD int scanlineIntersections(const EdgeRec &e, double x[3], int dy[3], doub
             if (a != 0) {
                 const double bn = b/a;
                 if (fabs(bn) < 1e6)
-                    solutions = solveCubicNormedPre(t, bn, bn*bn, bn*(1/3.), c/a, d/a);
+                    solutions = solveCubicNormedPreT<ROUNDED_ACOS>(t, bn, bn*bn, bn*(1/3.), c/a, d/a);
             }
             if (solutions == -2)
                 solutions = solveQuadratic(t, b, c, d);
@@ -120,6 +123,8 @@ MSDF_HD int scanlineIntersections(const EdgeRec &e, double x[3], int dy[3], doub
     return total;
 }
 
+MSDF_HD int scanlineIntersections(const EdgeRec &e, double x[3], int dy[3], double y) { return scanlineIntersectionsT<false>(e, x, dy, y); }
+
 // Can edge e intersect row y at all? A Bezier lies in the hull of its control points; rows more than a rounding margin outside the
 // control box yield no intersection in any branch of scanlineIntersections (the end-point fix-ups need p.y == y or a sign change).
 MSDF_HD bool rowMayIntersect(const EdgeRec &e, double y) {
@@ -172,14 +177,14 @@ MSDF_HD void listPreprocess(StridedList &l) {                                 //
     }
 }
 
-MSDF_HD void shapeScanline(StridedList &l, const EdgeRec *rec, int nE, double y) { // Shape::scanline, Shape.cpp:117-135
+MSDF_HD void shapeScanline(StridedList &l, const EdgeRec *rec, int nE, double y) { // Shape::scanline, Shape.cpp:117-135 (for the estimate: acos rounded to nearest)
     l.n = 0;
     for (int e = 0; e < nE; ++e) {
         if (!rowMayIntersect(rec[e], y))
             continue;
         double x[3];
         int dy[3];
-        const int n = scanlineIntersections(rec[e], x, dy, y);
+        const int n = scanlineIntersectionsT<true>(rec[e], x, dy, y);
         for (int k = 0; k < 3; ++k)
             if (k < n)
                 l.push(x[k], dy[k]);

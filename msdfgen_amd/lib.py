@@ -155,6 +155,9 @@ _PROTOS = {
     "msdfhip_tiles_to_bytes_sized": (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_int64), C.c_int, _vp, _vp, _vp]),
     "msdfhip_batch_bounds_miters": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, _dp]),
     "msdfhip_batch_boxes": (C.c_int, [_vp, C.POINTER(BoxConfig), _ip, _dp, _dp]),
+    "msdfhip_batch_estimate_sdf_error_sized": (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_int64), _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "msdfhip_render_sdf_sized": (C.c_int, [_vp, C.c_int, _ip, C.POINTER(C.c_int64), C.c_int, _vp, _ip, C.POINTER(C.c_int64), C.c_int, C.c_double, C.c_double,
+                                           C.c_float, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_PROTOS))
