@@ -431,6 +431,25 @@ int msdfhip_batch_boxes(const MsdfHipBatch *batch, const MsdfHipBoxConfig *cfg, 
 int msdfhip_batch_candidate_counts(const MsdfHipBatch *batch, uint32_t *counts);
 int msdfhip_batch_info(const MsdfHipBatch *batch, int *n_glyphs, int *n_contours, int *n_edges, int *max_contours, int *max_edges);
 int msdfhip_batch_download(const MsdfHipBatch *batch, int32_t *contour_offsets, double *points, uint8_t *types, uint8_t *colors);
+/* A new batch out of glyphs that are already resident (a dynamic atlas taking some glyphs of a font, several fonts in one atlas, one glyph under several
+ * transformations, the glyphs of one box-size class): glyph k of the result is glyph indices[k] of sources[source_of[k]].
+ *   sources    HOST array of n_sources batches on one device; source_of, indices: HOST int32[n_glyphs], read before the call returns.
+ *              source_of == NULL: every glyph comes from sources[0] (n_sources must then be 1). Indices may repeat, come in any order and leave glyphs
+ *              out; n_glyphs == 0 gives an empty batch.
+ * The result's arrays are those msdfhip_batch_create would hold for the chosen shapes in that order (offsets rebased; points, types, colours edge for
+ * edge), copied on the device and digested like any new batch; msdfhip_batch_info reports the counts and per-glyph maxima of the SELECTION. It owns all
+ * of them: a source may be destroyed, digested again or rewritten as soon as the call has returned (destroying it frees device memory, which waits for
+ * the device). Bounds: if a source has the bounds it took at creation (msdfhip_batch_create_prepared*), the result keeps, per glyph, the bounds of the
+ * glyph's source (computed on `stream` for a source that has none fixed); otherwise the result computes them on demand from its own arrays.
+ * Asynchronous on `stream`: the upload of the copy plan (from pinned memory the result keeps), the copies and the digestion are ordered on it, so the
+ * points, types and colours of a source may still be pending there; its OFFSETS are read when the call is made (first need of the per-glyph counts of
+ * a msdfhip_batch_create_device batch: one synchronous read-back), and allocations may wait for the device. Caller's arrays under such a source stay
+ * valid until `stream` has passed the call.
+ * Fails with MSDFHIP_ERR_INVALID, naming the position, before anything is allocated or launched: batch, sources or an entry of it NULL; n_sources < 1;
+ * n_glyphs < 0; indices NULL with n_glyphs > 0; source_of NULL with n_sources > 1; a source_of[k] outside 0..n_sources-1; an index outside its
+ * source's glyphs; sources on different devices; more than INT32_MAX contours or edges in all (summed in 64 bits: instancing reaches that). */
+int msdfhip_batch_gather(MsdfHipBatch **batch, const MsdfHipBatch *const *sources, int n_sources, int n_glyphs, const int32_t *source_of,
+                         const int32_t *indices, void *stream);
 
 /* 8-bit atlas output: converts packed fp32 tiles [g][h][w][channels] (msdfhip_batch_generate's output with out_offset =
  * g*h*w*channels, row_stride = w*channels) with pixelFloatToByte (core/pixel-conversion.hpp:8-10, what the reference's savers

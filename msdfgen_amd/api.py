@@ -563,6 +563,61 @@ class GlyphBatch:
         self._glyph_cache = {}
         return self
 
+    # ---- new batches out of resident glyphs (msdfhip_batch_gather): no host flatten, no upload of the outlines
+
+    @classmethod
+    def gather(cls, sources, source_of, indices, stream=None):
+        """A new batch on the device out of glyphs of resident ones: glyph k is glyph indices[k] of sources[source_of[k]] (source_of None: all of
+        sources[0], which must then be the only one). Indices may repeat, come in any order and leave glyphs out. The arrays are copied on the device and
+        digested on `stream` (torch's current stream by default); the result is a library-owned batch like from_raw's that borrows nothing: the sources
+        may be closed or rewritten right away. `.shapes` is the host mirror of the same selection."""
+        sources = list(sources)
+        if not sources:
+            raise ValueError("gather needs at least one source batch")
+        first = sources[0]
+        torch = first.torch
+        idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        src = None if source_of is None else np.ascontiguousarray(source_of, np.int32).reshape(-1)
+        if src is not None and len(src) != len(idx):
+            raise ValueError("source_of and indices differ in length")
+        self = object.__new__(cls)
+        self.torch, self.device = torch, first.device
+        lib = _lib.load()
+        s = stream or torch.cuda.current_stream(self.device)
+        handles = (C.c_void_p*len(sources))(*[b._handle for b in sources])
+        self._handle = C.c_void_p()
+        _lib.check(lib.msdfhip_batch_gather(C.byref(self._handle), handles, len(sources), len(idx), None if src is None else _lib.ptr(src, _lib._ip),
+                                            _lib.ptr(idx, _lib._ip), s.cuda_stream))
+        if s != torch.cuda.current_stream(self.device):                # torch-owned arrays of the sources are read on a stream torch did not allocate them on
+            for b in sources:
+                for t in (getattr(b, name, None) for name in ("_gco", "_co", "_pts", "_types", "_colors")):
+                    if t is not None:
+                        t.record_stream(s)
+        pick = [(0 if src is None else int(src[k]), int(idx[k])) for k in range(len(idx))]
+        if len(sources) == 1:
+            self.shapes = first.shapes.select([i for _, i in pick])
+        else:
+            names = [sources[j].shapes.names[i] for j, i in pick] if all(b.shapes.names for b in sources) else []
+            self.shapes = ShapeBatch.from_shapes([sources[j].shapes.shape(i) for j, i in pick], names)
+        ng, mc, me = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(lib.msdfhip_batch_info(self._handle, C.byref(ng), None, None, C.byref(mc), C.byref(me)))
+        self.n_glyphs, self.max_contours, self.max_edges = ng.value, mc.value, me.value
+        self._scratch = None
+        self._glyph_cache = {}
+        return self
+
+    def select(self, indices, stream=None):
+        """The glyphs `indices` of this batch as a new batch (GlyphBatch.gather with this batch as the only source)."""
+        return type(self).gather([self], None, indices, stream)
+
+    @classmethod
+    def concat(cls, batches, stream=None):
+        """All glyphs of `batches`, one batch after the other, as one new batch (fonts loaded at different times in one atlas)."""
+        batches = list(batches)
+        source_of = np.concatenate([np.full(b.n_glyphs, k, np.int32) for k, b in enumerate(batches)]) if batches else np.zeros(0, np.int32)
+        indices = np.concatenate([np.arange(b.n_glyphs, dtype=np.int32) for b in batches]) if batches else np.zeros(0, np.int32)
+        return cls.gather(batches, source_of, indices, stream)
+
     def close(self):
         if getattr(self, "_handle", None) is not None and self._handle:
             self.torch.cuda.synchronize(self.device)

@@ -25,6 +25,8 @@
 #include <sched.h>
 
 #include "msdf_classplan.hpp"
+#include "msdf_gather.hpp"
+#include "msdf_gatherplan.hpp"
 #include "msdf_hostplan.hpp"
 #include "msdf_kernels.hpp"
 #include "msdf_launchplan.hpp"
@@ -294,6 +296,8 @@ struct MsdfHipBatch : ShapeData {
     mutable WorkBuffer<double> dBoxes;    // what k_box writes (msdfhip_batch_bounds_miters / _boxes): ext [n][4], xf [n][6], then wh [n][2] int32; allocated on first need
     mutable Workspace work;
     mutable ClassPlan plan;           // the classes of work.bucket
+    WorkBuffer<int32_t> gatherTable;  // a batch gathered from others (msdfhip_batch_gather): the table its copy kernels read (msdf_gatherplan.hpp) ...
+    WorkBuffer<int32_t, true> hGatherTable;   // ... and the pinned copy it is uploaded from on the call's stream; both go with the batch, so nobody waits for the upload
     void onDevice(int d) { device = work.device = d; }
 };
 
@@ -4250,3 +4254,125 @@ int msdfhip_render_sdf_sized(const float *dSdf, int nGlyphs, const int32_t *sdfS
 }
 
 } // extern "C"
+
+// ---- a new batch out of glyphs of resident ones: msdfhip_batch_gather ----------------------------------------------------------------------------------
+//
+// The plan is host code of msdf_gatherplan.hpp; the copies are the three kernels of msdf_gather.hpp, templates that ONLY this code names, behind the quality
+// twins: they are instantiated last. Records and windings come from digest(), like every new batch's.
+
+namespace {
+
+int failGather(int code, const GatherRefusal &bad) {
+    switch (code) {
+        case GATHER_NO_SOURCES: return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_gather: no sources (n_sources must be at least 1)");
+        case GATHER_BAD_COUNT: return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_gather: n_glyphs is negative");
+        case GATHER_NO_INDICES: return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_gather: indices is NULL");
+        case GATHER_NO_SOURCE_OF: return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_gather: source_of is NULL with more than one source");
+        case GATHER_BAD_SOURCE: return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_gather: source_of[%d] = %lld is outside 0..%d", bad.position, bad.value, bad.limit-1);
+        case GATHER_BAD_INDEX: return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_gather: indices[%d] = %lld is outside its source's %d glyphs", bad.position, bad.value, bad.limit);
+        case GATHER_MIXED_DEVICES: return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_gather: sources[%d] lives on device %lld, sources[0] on device %d", bad.position, bad.value, bad.limit);
+        case GATHER_TOO_MANY_CONTOURS: return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_gather: %lld contours up to indices[%d] exceed INT32_MAX; split the selection", bad.value, bad.position);
+        case GATHER_TOO_MANY_EDGES: return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_gather: %lld edges up to indices[%d] exceed INT32_MAX; split the selection", bad.value, bad.position);
+    }
+    return MSDFHIP_OK;
+}
+
+// Everything of the call behind its checks, on the new batch b (destroyed by the caller on failure).
+int runGather(MsdfHipBatch *b, const MsdfHipBatch *const *sources, const std::vector<GatherSource> &src, int n, const int32_t *sourceOf, const int32_t *indices,
+              const GatherTotals &totals, hipStream_t stream) {
+    const int nSources = (int) src.size();
+    b->nGlyphs = n, b->nContours = (int) totals.contours, b->nEdges = (int) totals.edges;
+    b->maxContours = totals.maxContours, b->maxEdges = totals.maxEdges;
+    b->hContours.resize((size_t) n), b->hEdges.resize((size_t) n);
+    bool fixed = false;
+    for (int s = 0; s < nSources; ++s)
+        fixed = fixed || sources[s]->boundsFixed;
+    // the table: the plan's int32 block, then one row of pointers per source
+    const GatherColumns col = gatherColumns(n);
+    const size_t tableInts = col.ints+sizeof(GatherSourceArrays)/sizeof(int32_t)*(size_t) nSources;
+    const size_t eAlloc = b->nEdges > 0 ? (size_t) b->nEdges : 1;
+    HIPCHK(b->hGatherTable.ensure(tableInts));
+    HIPCHK(b->gatherTable.ensure(tableInts));
+    HIPCHK(b->dGlyphContourOffsets.ensure((size_t) n+1));
+    HIPCHK(b->dContourOffsets.ensure((size_t) b->nContours+1));
+    HIPCHK(b->dPoints.ensure(8*eAlloc));
+    HIPCHK(b->dTypes.ensure(eAlloc));
+    HIPCHK(b->dColors.ensure(eAlloc));
+    if (fixed)
+        HIPCHK(b->dBounds.ensure(4*(size_t) (n > 0 ? n : 1)));
+    gatherFill(src.data(), nSources, n, sourceOf, indices, b->hGatherTable.ptr, b->hContours.data(), b->hEdges.data());
+    GatherSourceArrays *rows = reinterpret_cast<GatherSourceArrays *>(b->hGatherTable.ptr+col.ints);
+    for (int s = 0; s < nSources; ++s) {
+        const MsdfHipBatch *from = sources[s];
+        if (fixed && !from->boundsFixed) {                       // its bounds as msdfhip_batch_bounds would compute them, on the call's stream
+            const int rc = frameBatch(from, NULL, 0, 0, NULL, stream);
+            if (rc != MSDFHIP_OK)
+                return rc;
+        }
+        const GatherSourceArrays row = { from->dContourOffsets.ptr, from->dPoints.ptr, from->dTypes.ptr, from->dColors.ptr, fixed ? from->dBounds.ptr : NULL };
+        rows[s] = row;
+    }
+    // glyph_contour_offsets IS the plan's first column; the rest of the block goes to the table
+    int rc = uploadSmall(b->dGlyphContourOffsets.ptr, b->hGatherTable.ptr+col.dstContour0, sizeof(int32_t)*((size_t) n+1), stream);
+    if (rc == MSDFHIP_OK)
+        rc = uploadSmall(b->gatherTable.ptr+col.source, b->hGatherTable.ptr+col.source, sizeof(int32_t)*(tableInts-col.source), stream);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    const int32_t *t = b->gatherTable.ptr;
+    const GatherSourceArrays *dRows = reinterpret_cast<const GatherSourceArrays *>(t+col.ints);
+    hipLaunchKernelGGL(k_gather_contours<>, dim3((unsigned) (((size_t) b->nContours+1+255)/256)), dim3(256), 0, stream, b->dContourOffsets.ptr, n, b->nContours, b->nEdges,
+                       t+col.source, t+col.srcContour0, t+col.srcEdge0, (const int32_t *) b->dGlyphContourOffsets.ptr, t+col.dstEdge0, dRows);
+    if (b->nEdges > 0)
+        hipLaunchKernelGGL(k_gather_edges<>, dim3((unsigned) ((4*(size_t) b->nEdges+255)/256)), dim3(256), 0, stream, b->dPoints.ptr, b->dTypes.ptr, b->dColors.ptr, n, b->nEdges,
+                           t+col.source, t+col.srcEdge0, t+col.dstEdge0, dRows);
+    if (fixed && n > 0)
+        hipLaunchKernelGGL(k_gather_bounds<>, dim3((unsigned) ((2*(size_t) n+255)/256)), dim3(256), 0, stream, b->dBounds.ptr, n, t+col.source, t+col.srcGlyph, dRows);
+    HIPCHK(hipGetLastError());
+    b->boundsFixed = fixed;
+    return digest(b, stream);
+}
+
+} // namespace
+
+extern "C" int msdfhip_batch_gather(MsdfHipBatch **batch, const MsdfHipBatch *const *sources, int n_sources, int n_glyphs, const int32_t *source_of,
+                                    const int32_t *indices, void *stream) {
+    if (!batch)
+        return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_gather: batch is NULL");
+    GatherRefusal bad = { -1, 0, 0 };
+    int code = gatherCheckCounts(sources != NULL, n_sources, n_glyphs, source_of, indices);
+    if (code != GATHER_OK)
+        return failGather(code, bad);
+    std::vector<GatherSource> src((size_t) n_sources);
+    for (int s = 0; s < n_sources; ++s)
+        if (!sources[s])
+            return fail(MSDFHIP_ERR_INVALID, "msdfhip_batch_gather: sources[%d] is NULL", s);
+    for (int s = 0; s < n_sources; ++s) {
+        const GatherSource one = { sources[s]->nGlyphs, sources[s]->device, NULL, NULL };
+        src[(size_t) s] = one;
+    }
+    code = gatherCheckArgs(src.data(), n_sources, n_glyphs, source_of, indices, bad);
+    if (code != GATHER_OK)
+        return failGather(code, bad);
+    int rc = ensureDevice(sources[0]->device);
+    if (rc != MSDFHIP_OK)
+        return rc;
+    for (int s = 0; s < n_sources; ++s) {
+        rc = fetchGlyphCounts(sources[s]);                       // (batches of device arrays: read back once, the first time anybody needs them)
+        if (rc != MSDFHIP_OK)
+            return rc;
+        src[(size_t) s].contours = sources[s]->hContours.data(), src[(size_t) s].edges = sources[s]->hEdges.data();
+    }
+    GatherTotals totals;
+    code = gatherTotals(src.data(), n_glyphs, source_of, indices, totals, bad);
+    if (code != GATHER_OK)
+        return failGather(code, bad);
+    MsdfHipBatch *b = new MsdfHipBatch();
+    b->onDevice(currentDevice());
+    rc = runGather(b, sources, src, n_glyphs, source_of, indices, totals, (hipStream_t) stream);
+    if (rc != MSDFHIP_OK) {
+        msdfhip_batch_destroy(b);
+        return rc;
+    }
+    *batch = b;
+    return MSDFHIP_OK;
+}

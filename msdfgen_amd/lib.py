@@ -93,6 +93,7 @@ _PROTOS = {
     "msdfhip_batch_candidate_counts": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "msdfhip_batch_info": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "msdfhip_batch_download": (C.c_int, [_vp, _ip, _dp, _bp, _bp]),
+    "msdfhip_batch_gather": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_int, _ip, _ip, _vp]),
     "msdfhip_batch_digest": (C.c_int, [_vp, _vp]),
     "msdfhip_batch_destroy": (None, [_vp]),
     "msdfhip_batch_windings": (C.c_int, [_vp, _ip]),
