@@ -175,11 +175,23 @@ int msdfhip_rasterize(float *pixels, int width, int height, int row_stride, int 
 
 /* Transparent micro-batching of the single-shape entry points above. Host threads that call them concurrently
  * (msdf-atlas-gen's workers) are combined group-commit style into one device batch per set of calls with equal launch parameters
- * (mode, size, config); a lone caller never waits. On by default (groups of up to 256 calls, 4 concurrent leaders); the
- * environment variable MSDFHIP_MICROBATCH=0 or max_group <= 1 turns it off (every call then runs on its own stream).
+ * (mode, config); sizes may differ within MSDFHIP_MICROBATCH_MAX_PAD: a leader takes queued calls in arrival order while the
+ * group's padded grid n*W*H (W, H: the largest width and height taken) stays within that factor of the sum of the calls' own
+ * w*h and the slot W*H within that factor of every member's own w*h, and runs them as one sized batch; below 1 (also 0) only calls of equal size share a group. The legacy generators
+ * (msdfhip_generate_legacy) always group by equal size. A lone caller never waits. On by default (groups of up to 256 calls,
+ * 4 concurrent leaders); the environment variable MSDFHIP_MICROBATCH=0 or max_group <= 1 turns it off (every call then runs on
+ * its own stream).
  * msdfhip_microbatch_stats: calls served / device batches run / largest group since the last reset. */
 int msdfhip_set_microbatch(int max_group, int max_leaders);
 int msdfhip_microbatch_stats(long long *calls, long long *batches, long long *largest, int reset);
+/* The groups among them that held bitmaps of different sizes, since the last reset: such groups / their calls / the sum of their
+ * padded grids n*W*H / the sum of their calls' own w*h (texels). Any pointer may be NULL. */
+int msdfhip_microbatch_mixed_stats(long long *mixed_batches, long long *mixed_calls, long long *padded_texels, long long *box_texels, int reset);
+/* Makes grouping deterministic for tests and A/B scripts. hold_ms > 0: single-shape calls that arrive queue up and no new group
+ * starts until the hold is released or hold_ms milliseconds have passed since this call (the wait is bounded: a hold that nobody
+ * releases ends by itself); groups already running finish. hold_ms == 0: releases the hold. Returns the number of queued calls
+ * that no group has taken yet (negative: an error code). Host state only: no device is touched. */
+int msdfhip_microbatch_hold(int hold_ms);
 /* Where the host-pointer calls spend their wall time, summed over device batches since the last reset (milliseconds):
  * staging the inputs, H2D + kernels + D2H + stream sync, scattering the tiles into the callers' bitmaps. */
 int msdfhip_microbatch_times(double *stage_ms, double *device_ms, double *scatter_ms, int reset);

@@ -24,9 +24,11 @@
 
 #include <sched.h>
 
+#include "msdf_boxslots.hpp"
 #include "msdf_classplan.hpp"
 #include "msdf_gather.hpp"
 #include "msdf_gatherplan.hpp"
+#include "msdf_groupplan.hpp"
 #include "msdf_hostplan.hpp"
 #include "msdf_kernels.hpp"
 #include "msdf_launchplan.hpp"
@@ -70,6 +72,7 @@ struct Tuning {
     PlanTuning plan;                 // what the launch plans read (msdf_launchplan.hpp)
     bool pipelineTrace;              // MSDFHIP_PIPELINE_TRACE      host-output pipeline prints per chunk when its kernels / its copy back finished (stderr)
     int microbatch;                  // MSDFHIP_MICROBATCH          0 / 1 disables the grouping of concurrent single-shape calls; N caps the group
+    double microbatchMaxPad;         // MSDFHIP_MICROBATCH_MAX_PAD  calls of different bitmap sizes share a group while n*W*H <= this * sum of w*h (msdf_groupplan.hpp); below 1: equal sizes only
     bool noArgPayloadSingle;         // MSDFHIP_NO_ARG_PAYLOAD_SINGLE k_single_call reads small shapes from the staging area instead of its kernel arguments (A/B)
     bool noZeroCopySingle;           // MSDFHIP_NO_ZERO_COPY_SINGLE k_single_call on uploaded inputs / device outputs + one copy back (A/B)
     bool noFusedSingle;              // MSDFHIP_NO_FUSED_SINGLE     single-shape calls through the batched launch sequence instead of k_single_call (A/B)
@@ -108,6 +111,10 @@ void readTuning() {
     t.microbatch = (env = getenv("MSDFHIP_MICROBATCH")) ? atoi(env) : 256;
     if (t.microbatch < 1)
         t.microbatch = 1;
+    // 5 is the padding of a real font's boxes, 1/0.202, not a fitted value: the one crossover sweep there is (profiles/microbatch_sizes.md (c):
+    // one L x L call with 63 8 x 8 calls, driven from Python threads) has a group winning up to a padding of 51 and level from 58, half of which would be
+    // 25-29. The sweep's baseline is too loose to raise the default on; at 5 a font's calls group already (97 % of them from 64 threads).
+    t.microbatchMaxPad = (env = getenv("MSDFHIP_MICROBATCH_MAX_PAD")) ? atof(env) : 5.;
     t.devices[0] = 0;
     p.queryStatic = (env = getenv("MSDFHIP_QUERY_STATIC")) ? atoi(env) : p.queryStatic;
     p.queryGridSteps = (env = getenv("MSDFHIP_QUERY_GRID")) ? atoi(env) : p.queryGridSteps;
@@ -2867,7 +2874,7 @@ static int arenaReserve(ThreadArena &a, size_t devBytes, size_t pinnedBytes) {
     return MSDFHIP_OK;
 }
 
-enum SingleOp { OP_GENERATE = 0, OP_ERROR_CORRECTION = 1, OP_SIGN_CORRECTION = 2, OP_RASTERIZE = 3, OP_GENERATE_LEGACY = 4 };   // what the single-shape call does to `pixels`
+// (SingleOp, what the single-shape call does to `pixels`: msdf_groupplan.hpp)
 
 // One host-pointer call (generate* / msdfErrorCorrection / distanceSignCorrection / rasterize on one shape and one bitmap).
 struct ShapeCall {
@@ -2886,9 +2893,14 @@ struct ShapeCall {
     std::condition_variable cv;
 };
 
-// Calls can share one launch sequence when everything that is a launch parameter agrees.
+// Calls can share one launch sequence when everything that is a launch parameter agrees; the sizes of their bitmaps may differ where the operation has
+// sized kernels (groupCompatible, msdf_groupplan.hpp: the rule is written there).
+static GroupKey keyOf(const ShapeCall &c) {
+    const GroupKey k = { c.mode, c.channels, c.op, c.w, c.h, &c.cfg, sizeof(MsdfHipConfig) };
+    return k;
+}
 static bool sameLaunch(const ShapeCall &a, const ShapeCall &b) {
-    return a.mode == b.mode && a.channels == b.channels && a.op == b.op && a.w == b.w && a.h == b.h && memcmp(&a.cfg, &b.cfg, sizeof(MsdfHipConfig)) == 0;
+    return groupCompatible(keyOf(a), keyOf(b));
 }
 
 static std::atomic<long long> gNsStage(0), gNsDevice(0), gNsScatter(0);
@@ -3006,14 +3018,32 @@ struct GroupPlan {
     // device-only work buffers behind the mirror
     size_t dRecs, dWind, dScratch, dCands, dParams, gresNeed, dGres, dPriv, devBytes;
     size_t pvWind, pvOff, pvGco, pvGlyph, pvStride;   // k_single_call: offsets inside one workgroup's private digest area, and the areas' stride (msdf_single.hpp)
+    // A group of bitmaps of different sizes (msdf_groupplan.hpp): one sized call at w x h = the largest width x the largest height. texels / tileBytes are then
+    // those of a SLOT, hSrc / hOut hold the boxes packed at `offsets`, hDims (in the input region: it travels with the one upload) the n*2 box sizes, and
+    // dSlots is the device-only source region of the in-place operations, which k_boxes_to_slots fills from the packed upload.
+    bool mixed;
+    int w, h;
+    size_t hDims, dSlots, outBytes;   // outBytes: the results without the stencils
+    std::vector<int64_t> offsets;     // mixed: n+1 float offsets (groupPackedOffsets)
 };
 
-static GroupPlan planGroup(ShapeCall *const *calls, int n) {
+static GroupPlan planGroup(ShapeCall *const *calls, int n, const GroupSelection *sel = NULL) {
     const ShapeCall &c0 = *calls[0];
-    const int channels = c0.channels, op = c0.op, w = c0.w, h = c0.h;
+    const int channels = c0.channels, op = c0.op;
     const MsdfHipConfig *cfg = &c0.cfg;
     GroupPlan p;
     p.n = n;
+    p.mixed = sel && !sel->uniform && n > 1;
+    const int w = p.w = p.mixed ? sel->W : c0.w, h = p.h = p.mixed ? sel->H : c0.h;
+    size_t packedBytes = 0;
+    if (p.mixed) {
+        std::vector<int32_t> sizes(2*(size_t) n);
+        for (int g = 0; g < n; ++g)
+            sizes[2*(size_t) g] = calls[g]->w, sizes[2*(size_t) g+1] = calls[g]->h;
+        p.offsets.resize((size_t) n+1);
+        groupPackedOffsets(n, sizes.data(), channels, p.offsets.data());
+        packedBytes = (size_t) p.offsets[(size_t) n]*sizeof(float);
+    }
     p.bitmapIsInput = op == OP_ERROR_CORRECTION || op == OP_SIGN_CORRECTION;
     const bool generates = op == OP_GENERATE || op == OP_GENERATE_LEGACY;
     p.correct = (generates || op == OP_ERROR_CORRECTION) && channels >= 3 && cfg->ec_mode != MSDFHIP_EC_DISABLED;
@@ -3037,11 +3067,13 @@ static GroupPlan planGroup(ShapeCall *const *calls, int n) {
     Carver hc;
     p.hGco = hc.take((n+1)*sizeof(int32_t)), p.hCo = hc.take((p.sumC+1)*sizeof(int32_t)), p.hPts = hc.take(eAlloc*8*sizeof(double));
     p.hTypes = hc.take(eAlloc), p.hColors = hc.take(eAlloc), p.hGlyph = hc.take(n*sizeof(MsdfHipGlyph));
-    p.hSrc = p.bitmapIsInput ? hc.take(n*tileBytes) : hc.off;
+    p.hSrc = p.bitmapIsInput ? hc.take(p.mixed ? packedBytes : n*tileBytes) : hc.off;
+    p.hDims = p.mixed ? hc.take(n*2*sizeof(int32_t)) : hc.off;
     p.inputBytes = hc.off;
     p.hBucket = hc.take(n*sizeof(int));                          // class lists of the overlapping combiner (uploaded on the stream by the launch code)
     p.hStatus = hc.take(256);                                    // [0]: candidate-overflow count of the correction pass, copied back with the results
-    p.hOut = hc.take(n*tileBytes), p.hStencil = hc.take(n*texels);
+    p.outBytes = p.mixed ? packedBytes : n*tileBytes;
+    p.hOut = hc.take(p.outBytes), p.hStencil = hc.take(n*texels);
     p.resultBytes = hc.off-p.hOut;
     p.pinnedBytes = hc.off;
     // device layout: mirror of the staging area, then device-only work buffers
@@ -3049,6 +3081,7 @@ static GroupPlan planGroup(ShapeCall *const *calls, int n) {
     dc.off = hc.off;
     p.dRecs = dc.take(eAlloc*sizeof(EdgeRec)), p.dWind = dc.take(cAlloc), p.dScratch = dc.take(n*tileBytes*p.stages);
     p.dCands = dc.take(p.correct ? p.candCap*sizeof(EcCandidate) : 0), p.dParams = dc.take(n*sizeof(EcGlyphParams));
+    p.dSlots = dc.take(p.mixed && p.bitmapIsInput ? n*tileBytes : 0);
     // combiner scratch of the small-launch distance kernels (one tile per wavefront), see dispatchDistance
     p.gresNeed = op == OP_GENERATE && cfg->overlap_support && p.maxC > 1 && (size_t) n*tilesAll <= 8192 ? (size_t) n*tilesAll*p.maxC*channels*WAVE*sizeof(double) : 0;
     if (p.gresNeed > ((size_t) 64<<20))
@@ -3065,9 +3098,9 @@ static GroupPlan planGroup(ShapeCall *const *calls, int n) {
 
 // Flattens the calls' shapes (and, for the in-place operations, their bitmaps) into the arena's pinned staging as one CSR batch.
 static void stageGroup(const GroupPlan &p, ThreadArena &a, ShapeCall *const *calls, int n) {
-    const ShapeCall &c0 = *calls[0];
-    const int channels = c0.channels, w = c0.w, h = c0.h;
+    const int channels = calls[0]->channels;
     int32_t *gco = reinterpret_cast<int32_t *>(a.pinned.ptr+p.hGco), *co = reinterpret_cast<int32_t *>(a.pinned.ptr+p.hCo);
+    int32_t *dims = reinterpret_cast<int32_t *>(a.pinned.ptr+p.hDims);
     MsdfHipGlyph *gd = reinterpret_cast<MsdfHipGlyph *>(a.pinned.ptr+p.hGlyph);
     size_t cAt = 0, eAt = 0;
     co[0] = 0;
@@ -3084,12 +3117,18 @@ static void stageGroup(const GroupPlan &p, ThreadArena &a, ShapeCall *const *cal
         }
         cAt += c.nC, eAt += nE;
         memcpy(gd[g].xf, c.xf, sizeof(gd[g].xf));
-        gd[g].out_offset = (int64_t) ((size_t) g*p.texels*channels);   // the device tiles are tightly packed in memory-row order
+        const int w = c.w, h = c.h;                              // (of every call of a group that is not mixed: p.w, p.h)
+        // the device tiles are tightly packed in memory-row order: one after the other, or (mixed) each box at its packed offset; an in-place operation's
+        // bitmaps are staged the same way
+        const size_t at = p.mixed ? (size_t) p.offsets[(size_t) g] : (size_t) g*p.texels*channels;
+        gd[g].out_offset = (int64_t) at;
         gd[g].row_stride = w*channels;
         gd[g].flip = c.flip ? 1 : 0;
+        if (p.mixed)
+            dims[2*(size_t) g] = w, dims[2*(size_t) g+1] = h;
         if (p.bitmapIsInput)
             for (int y = 0; y < h; ++y)
-                memcpy(a.pinned.ptr+p.hSrc+((size_t) g*p.texels+(size_t) y*w)*channels*sizeof(float), c.pixels+(ptrdiff_t) c.rowStride*y, sizeof(float)*(size_t) w*channels);
+                memcpy(a.pinned.ptr+p.hSrc+(at+(size_t) y*w*channels)*sizeof(float), c.pixels+(ptrdiff_t) c.rowStride*y, sizeof(float)*(size_t) w*channels);
     }
     gco[n] = (int32_t) cAt;
 }
@@ -3122,7 +3161,7 @@ static void buildView(const GroupPlan &p, ThreadArena &a, ShapeCall *const *call
 
 // The status words and the results (with the stencils only where one is wanted) -> pinned staging, and the end of everything queued on the arena's stream.
 static int copyBackAndWait(const GroupPlan &p, ThreadArena &a) {
-    HIPCHK(hipMemcpyAsync(a.pinned.ptr+p.hStatus, a.dev.ptr+p.hStatus, 256+(p.anyStencil ? p.resultBytes : p.n*p.tileBytes), hipMemcpyDeviceToHost, a.stream));
+    HIPCHK(hipMemcpyAsync(a.pinned.ptr+p.hStatus, a.dev.ptr+p.hStatus, 256+(p.anyStencil ? p.resultBytes : p.outBytes), hipMemcpyDeviceToHost, a.stream));
     HIPCHK(waitStream(a.stream));
     return MSDFHIP_OK;
 }
@@ -3261,25 +3300,35 @@ static int runFused(const GroupPlan &p, const SinglePlan &single, ThreadArena &a
 // next to the results instead of a launch of the overflow pass per call; where a glyph's candidate segment did overflow (more than 1/16 of its texels needed
 // a distance check: pathological inputs only) the operation runs once more, with the per-texel overflow pass in its launch sequence -- an in-place correction
 // too: the input copy on the device is intact.
+static int launchBoxesToSlots(float *dSlots, const float *dPacked, const MsdfHipGlyph *dGlyphs, const int32_t *dDims, int n, int channels, size_t slot, hipStream_t stream);   // (at the end of this file: it names k_boxes_to_slots)
+
 static int runBatched(const GroupPlan &p, ThreadArena &a, MsdfHipBatch &b, const ShapeCall &c) {
     const MsdfHipGlyph *dGlyph = reinterpret_cast<const MsdfHipGlyph *>(a.dev.ptr+p.hGlyph);
     const float *dSrc = reinterpret_cast<const float *>(a.dev.ptr+p.hSrc);
     float *dOut = reinterpret_cast<float *>(a.dev.ptr+p.hOut);
     uint8_t *dStencil = p.anyStencil ? reinterpret_cast<uint8_t *>(a.dev.ptr+p.hStencil) : NULL;
+    // A mixed group: the sized twins at the launches of a p.w x p.h call. Their sizes came with the inputs; the sized passes read a source field at the start
+    // of its slot, so an in-place operation's packed bitmaps are spread into slots on the device first (what crossed PCIe is the packed region only).
+    const int32_t *dDims = p.mixed ? reinterpret_cast<const int32_t *>(a.dev.ptr+p.hDims) : NULL;
     int rc = digest(&b, a.stream);
+    if (rc == MSDFHIP_OK && p.mixed && p.bitmapIsInput) {
+        rc = launchBoxesToSlots(reinterpret_cast<float *>(a.dev.ptr+p.dSlots), dSrc, dGlyph, dDims, p.n, c.channels, p.texels, a.stream);
+        dSrc = reinterpret_cast<const float *>(a.dev.ptr+p.dSlots);
+    }
     for (int attempt = 0; rc == MSDFHIP_OK && attempt < 2; ++attempt) {   // mirrored, then with the overflow pass
         GenerateCall call;
         call.overflowOut = attempt == 0 ? reinterpret_cast<unsigned *>(a.dev.ptr+p.hStatus) : NULL;
+        call.boxDims = dDims;
         if (c.op == OP_ERROR_CORRECTION)
-            rc = runCorrection(&b, c.channels, c.w, c.h, dGlyph, dSrc, dOut, dStencil, c.cfg, a.stream, call);
+            rc = runCorrection(&b, c.channels, p.w, p.h, dGlyph, dSrc, dOut, dStencil, c.cfg, a.stream, call);
         else if (c.op == OP_SIGN_CORRECTION)
-            rc = runSignCorrection(&b, c.channels, c.w, c.h, dGlyph, dSrc, dOut, 0, c.cfg.sdf_zero_value, c.cfg.fill_rule, a.stream);
+            rc = runSignCorrection(&b, c.channels, p.w, p.h, dGlyph, dSrc, dOut, 0, c.cfg.sdf_zero_value, c.cfg.fill_rule, a.stream, dDims);
         else if (c.op == OP_RASTERIZE)
-            rc = runSignCorrection(&b, 1, c.w, c.h, dGlyph, NULL, dOut, 0, 0.f, c.cfg.fill_rule, a.stream);
-        else if (c.op == OP_GENERATE_LEGACY)                     // (c.cfg is a legacyConfig: msdfhip_generate_legacy)
-            rc = runGenerateLegacy(&b, c.mode, c.w, c.h, dGlyph, dOut, dStencil, p.stages ? reinterpret_cast<float *>(a.dev.ptr+p.dScratch) : NULL, c.cfg, a.stream, call);
+            rc = runSignCorrection(&b, 1, p.w, p.h, dGlyph, NULL, dOut, 0, 0.f, c.cfg.fill_rule, a.stream, dDims);
+        else if (c.op == OP_GENERATE_LEGACY)                     // (c.cfg is a legacyConfig: msdfhip_generate_legacy; never mixed: groupOpTakesSizes)
+            rc = runGenerateLegacy(&b, c.mode, p.w, p.h, dGlyph, dOut, dStencil, p.stages ? reinterpret_cast<float *>(a.dev.ptr+p.dScratch) : NULL, c.cfg, a.stream, call);
         else
-            rc = runGenerate(&b, c.mode, c.w, c.h, dGlyph, dOut, dStencil, p.stages ? reinterpret_cast<float *>(a.dev.ptr+p.dScratch) : NULL, &c.cfg, a.stream, call);
+            rc = runGenerate(&b, c.mode, p.w, p.h, dGlyph, dOut, dStencil, p.stages ? reinterpret_cast<float *>(a.dev.ptr+p.dScratch) : NULL, &c.cfg, a.stream, call);
         if (rc == MSDFHIP_OK)
             rc = copyBackAndWait(p, a);
         if (!(call.overflowMirrored && *reinterpret_cast<const unsigned *>(a.pinned.ptr+p.hStatus) != 0))
@@ -3290,24 +3339,27 @@ static int runBatched(const GroupPlan &p, ThreadArena &a, MsdfHipBatch &b, const
 
 // The tiles in the pinned staging -> the callers' bitmaps (any row stride) and stencils.
 static void scatterGroup(const GroupPlan &p, ThreadArena &a, ShapeCall *const *calls, int n) {
-    const int channels = calls[0]->channels, w = calls[0]->w, h = calls[0]->h;
+    const int channels = calls[0]->channels;
     for (int g = 0; g < n; ++g) {
         const ShapeCall &c = *calls[g];
-        const float *tile = reinterpret_cast<const float *>(a.pinned.ptr+p.hOut)+(size_t) g*p.texels*channels;
+        const int w = c.w, h = c.h;                              // (mixed: the call's own box at its packed offset, its stencil packed at the start of slot g)
+        const float *tile = reinterpret_cast<const float *>(a.pinned.ptr+p.hOut)+(p.mixed ? (size_t) p.offsets[(size_t) g] : (size_t) g*p.texels*channels);
         for (int y = 0; y < h; ++y)
             memcpy(c.pixels+(ptrdiff_t) c.rowStride*y, tile+(size_t) y*w*channels, sizeof(float)*(size_t) w*channels);
         if (c.stencil && p.anyStencil)
-            memcpy(c.stencil, a.pinned.ptr+p.hStencil+(size_t) g*p.texels, p.texels);
+            memcpy(c.stencil, a.pinned.ptr+p.hStencil+(size_t) g*p.texels, (size_t) w*h);
     }
 }
 
-static int runGroup(ShapeCall *const *calls, int n) {
+// sel: what the leader's selection found (NULL: one call, or calls of one size). A group of different sizes takes the batched sequence with sizes; every other
+// group runs exactly as it did before sizes could differ.
+static int runGroup(ShapeCall *const *calls, int n, const GroupSelection *sel = NULL) {
     const ShapeCall &c0 = *calls[0];
     const MsdfHipConfig *cfg = &c0.cfg;
     int rc = ensureDevice(frontDoorDevice());
     if (rc != MSDFHIP_OK)
         return rc;
-    const GroupPlan plan = planGroup(calls, n);
+    const GroupPlan plan = planGroup(calls, n, sel);
     ArenaHold lease;
     rc = takeArena(lease);
     if (rc != MSDFHIP_OK)
@@ -3370,6 +3422,8 @@ static std::mutex gQueueMutex;
 static std::vector<ShapeCall *> gQueue;                          // arrival order; claimed entries belong to a running leader
 static int gActiveLeaders = 0;
 static std::atomic<long long> gStatCalls(0), gStatBatches(0), gStatLargest(0);
+static std::atomic<long long> gStatMixedBatches(0), gStatMixedCalls(0), gStatPaddedTexels(0), gStatBoxTexels(0);   // groups run with sizes (msdfhip_microbatch_mixed_stats)
+static long long gHoldUntilNs = 0;                               // msdfhip_microbatch_hold: no new leader starts before this time (guarded by gQueueMutex; 0: no hold)
 static const size_t GROUP_BYTES_LIMIT = 256u<<20;                // tiles of one group (bounds the per-thread arena)
 
 static int maxGroup() {
@@ -3396,33 +3450,56 @@ static int submitCall(ShapeCall &c) {
         return runGroup(&one, 1);
     }
     std::vector<ShapeCall *> group;
+    GroupSelection selection;
     {
         std::unique_lock<std::mutex> lock(gQueueMutex);
         c.claimed = c.done = false;
         gQueue.push_back(&c);
-        while (!c.done && !(gActiveLeaders < gMaxLeaders.load() && firstUnclaimed() == &c))
-            c.cv.wait(lock);
+        for (;;) {                                               // (under a hold the wait is bounded: the hold ends by itself, and nobody is there to notify then)
+            const long long holdLeft = gHoldUntilNs-nowNs();
+            if (c.done || (holdLeft <= 0 && gActiveLeaders < gMaxLeaders.load() && firstUnclaimed() == &c))
+                break;
+            if (holdLeft > 0)
+                c.cv.wait_for(lock, std::chrono::nanoseconds(holdLeft));
+            else
+                c.cv.wait(lock);
+        }
         if (c.done) {
             if (c.rc != MSDFHIP_OK)
                 tlsError = c.error;
             return c.rc;
         }
-        const size_t tileBytes = (size_t) c.w*c.h*c.channels*sizeof(float);
-        for (size_t i = 0; i < gQueue.size() && (int) group.size() < cap; ++i) {
+        // The leader's own call, then every queued call that may share its launch sequence, in arrival order; the selection (msdf_groupplan.hpp) says which of
+        // them it takes. What it passes over stays queued for the next leader, like the calls of another launch.
+        std::vector<ShapeCall *> compatible(1, &c);
+        for (size_t i = 0; i < gQueue.size(); ++i) {
             ShapeCall *q = gQueue[i];
-            if (!q->claimed && (q == &c || (sameLaunch(*q, c) && (group.size()+1)*tileBytes <= GROUP_BYTES_LIMIT))) {
-                q->claimed = true;
-                group.push_back(q);
-            }
+            if (!q->claimed && q != &c && sameLaunch(*q, c))
+                compatible.push_back(q);
         }
+        std::vector<int32_t> sizes(2*compatible.size()), scratch(2*compatible.size());
+        std::vector<uint8_t> taken(compatible.size());
+        for (size_t i = 0; i < compatible.size(); ++i)
+            sizes[2*i] = compatible[i]->w, sizes[2*i+1] = compatible[i]->h;
+        groupSelect((int) compatible.size(), sizes.data(), c.channels, cap, GROUP_BYTES_LIMIT, tuning().microbatchMaxPad, taken.data(), scratch.data(), selection);
+        for (size_t i = 0; i < compatible.size(); ++i)
+            if (taken[i]) {
+                compatible[i]->claimed = true;
+                group.push_back(compatible[i]);
+            }
         ++gActiveLeaders;
         if (gActiveLeaders < gMaxLeaders.load())
             if (ShapeCall *next = firstUnclaimed())
                 next->cv.notify_one();                           // a second leader may start on what is left
     }
-    int rc = runGroup(group.data(), (int) group.size());
+    int rc = runGroup(group.data(), (int) group.size(), &selection);
     gStatCalls += (long long) group.size();
     ++gStatBatches;
+    if (!selection.uniform && group.size() > 1) {
+        ++gStatMixedBatches;
+        gStatMixedCalls += (long long) group.size();
+        gStatPaddedTexels += (long long) (group.size()*selection.slot), gStatBoxTexels += (long long) selection.boxTexels;
+    }
     for (long long seen = gStatLargest.load(); (long long) group.size() > seen && !gStatLargest.compare_exchange_weak(seen, (long long) group.size()); ) { }
     std::string error = rc != MSDFHIP_OK ? tlsError : std::string();
     std::vector<int> rcs(group.size(), rc);
@@ -3696,6 +3773,32 @@ int msdfhip_microbatch_stats(long long *calls, long long *batches, long long *la
     if (reset)
         gStatCalls = 0, gStatBatches = 0, gStatLargest = 0;
     return MSDFHIP_OK;
+}
+
+int msdfhip_microbatch_mixed_stats(long long *mixedBatches, long long *mixedCalls, long long *paddedTexels, long long *boxTexels, int reset) {
+    if (mixedBatches) *mixedBatches = gStatMixedBatches.load();
+    if (mixedCalls) *mixedCalls = gStatMixedCalls.load();
+    if (paddedTexels) *paddedTexels = gStatPaddedTexels.load();
+    if (boxTexels) *boxTexels = gStatBoxTexels.load();
+    if (reset)
+        gStatMixedBatches = 0, gStatMixedCalls = 0, gStatPaddedTexels = 0, gStatBoxTexels = 0;
+    return MSDFHIP_OK;
+}
+
+// Host state only: no device is touched. hold_ms > 0: calls that arrive queue up and no new leader starts until the hold is released or hold_ms have passed
+// (every waiting call bounds its own wait by the hold's end, so a hold nobody releases cannot park callers); running leaders finish. 0: release.
+int msdfhip_microbatch_hold(int holdMs) {
+    if (holdMs < 0)
+        return fail(MSDFHIP_ERR_INVALID, "msdfhip_microbatch_hold(%d)", holdMs);
+    std::unique_lock<std::mutex> lock(gQueueMutex);
+    int unclaimed = 0;
+    for (size_t i = 0; i < gQueue.size(); ++i)
+        unclaimed += gQueue[i]->claimed ? 0 : 1;
+    gHoldUntilNs = holdMs > 0 ? nowNs()+(long long) holdMs*1000000 : 0;
+    if (holdMs == 0)
+        if (ShapeCall *next = firstUnclaimed())
+            next->cv.notify_one();
+    return unclaimed;
 }
 
 int msdfhip_microbatch_times(double *stageMs, double *deviceMs, double *scatterMs, int reset) {
@@ -4374,5 +4477,17 @@ extern "C" int msdfhip_batch_gather(MsdfHipBatch **batch, const MsdfHipBatch *co
         return rc;
     }
     *batch = b;
+    return MSDFHIP_OK;
+}
+
+// ---- groups of single-shape calls of different sizes: the packed bitmaps of an in-place operation into slots ------------------------------------------
+//
+// The ONLY code that names k_boxes_to_slots (msdf_boxslots.hpp), behind the gather kernels: it is instantiated last. runBatched calls it for a mixed group of
+// msdfhip_error_correction / msdfhip_distance_sign_correction calls, whose sized passes read box g's source field at the start of slot g.
+
+static int launchBoxesToSlots(float *dSlots, const float *dPacked, const MsdfHipGlyph *dGlyphs, const int32_t *dDims, int n, int channels, size_t slot, hipStream_t stream) {
+    const size_t slotFloats = slot*(size_t) channels, chunks = (slotFloats+3)/4;
+    hipLaunchKernelGGL(k_boxes_to_slots<>, dim3((unsigned) ((chunks+255)/256), (unsigned) n), dim3(256), 0, stream, dSlots, dPacked, dGlyphs, dDims, (long long) slotFloats, channels);
+    HIPCHK(hipGetLastError());
     return MSDFHIP_OK;
 }

@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI (include/msdfgen_hip.h).  Loading never falls back to anything: if libmsdfgen_hip.so is
 missing it is built with hipcc, and if no gfx950 device is usable every compute entry point raises MsdfHipError."""
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -84,6 +85,8 @@ _PROTOS = {
     "msdfhip_set_microbatch": (C.c_int, [C.c_int, C.c_int]),
     "msdfhip_microbatch_stats": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_int]),
     "msdfhip_microbatch_times": (C.c_int, [_dp, _dp, _dp, C.c_int]),
+    "msdfhip_microbatch_mixed_stats": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_int]),
+    "msdfhip_microbatch_hold": (C.c_int, [C.c_int]),
     "msdfhip_shape_distance": (C.c_int, [C.c_int, C.c_int] + _SHAPE_ARGS + [C.c_int, _dp, _dp]),
     "msdfhip_batch_create": (C.c_int, [C.POINTER(_vp), C.c_int, _ip, _ip, _dp, _bp, _bp]),
     "msdfhip_batch_create_device": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -244,9 +247,42 @@ def set_microbatch(max_group=256, max_leaders=2):
 def microbatch_stats(reset=False):
     a, b, c = C.c_longlong(), C.c_longlong(), C.c_longlong()
     x, y, z = C.c_double(), C.c_double(), C.c_double()
+    m = [C.c_longlong() for _ in range(4)]
     check(load().msdfhip_microbatch_times(C.byref(x), C.byref(y), C.byref(z), int(reset)))
     check(load().msdfhip_microbatch_stats(C.byref(a), C.byref(b), C.byref(c), int(reset)))
-    return {"calls": a.value, "batches": b.value, "largest": c.value, "stage_ms": round(x.value, 3), "device_ms": round(y.value, 3), "scatter_ms": round(z.value, 3)}
+    check(load().msdfhip_microbatch_mixed_stats(*[C.byref(v) for v in m], int(reset)))
+    return {"calls": a.value, "batches": b.value, "largest": c.value, "stage_ms": round(x.value, 3), "device_ms": round(y.value, 3), "scatter_ms": round(z.value, 3),
+            "mixed_batches": m[0].value, "mixed_calls": m[1].value, "padded_texels": m[2].value, "box_texels": m[3].value}
+
+
+class _MicrobatchHold(contextlib.AbstractContextManager):
+    """What microbatch_hold returns: the hold is set on creation and released on exit; queued() = the calls waiting for a group."""
+
+    def __init__(self, ms):
+        self.ms = int(ms)
+        self.queued()
+
+    def queued(self):
+        n = load().msdfhip_microbatch_hold(self.ms)
+        if n < 0:
+            check(n)
+        return n
+
+    def release(self):
+        n = load().msdfhip_microbatch_hold(0)
+        if n < 0:
+            check(n)
+        return n
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
+
+
+def microbatch_hold(ms):
+    """Context manager: while it is open (and for at most `ms` milliseconds) concurrent single-shape calls queue up and no new group starts
+    (msdfhip_microbatch_hold); released on exit. Tests and A/B scripts make grouping deterministic with it."""
+    return _MicrobatchHold(ms)
 
 
 def route_counts(reset=False):
